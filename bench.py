@@ -12,7 +12,9 @@ use): every rank rolls out its own independent scenes (weak scaling, no data-pat
 all-gathered once at the end (RCCL) inside the timed region.  Weights are random-init (PyTorch-default-like) of the
 UMGen_Large architecture and inputs are synthetic tokenized_origin_scenes-shaped tokens: no checkpoint/dataset offline.
 
-Rank 0 prints ONE JSON line with the contract fields plus ``roofline`` (dominant kernel) and ``cpu_baseline``.
+Rank 0 prints ONE JSON line with the contract fields (``ms_per_step`` = one timed frame), the per-phase times of the timed frames
+and the engine's decode path.  ``--full`` adds ``roofline`` (dominant kernel, from one extra profiled frame), ``roofline_gemm`` /
+``roofline_attn``, ``closed_loop`` and ``cpu_baseline``; ``--dump-outputs DIR`` writes the tokens of the last timed frame.
 """
 import argparse
 import json
@@ -122,6 +124,89 @@ def cpu_baseline(cfg_name: str, threads: int):
     return res
 
 
+def dump_outputs(path: str, out, cap_bytes: int = 64 << 20):
+    """--dump-outputs: the tokens the timed path sampled in its last step (one frame per scene), one float64 [scenes, tokens]
+    array per modality as <path>/tokens_<modality>.npy.  Past cap_bytes in all, a fixed seeded sample of the scenes is kept."""
+    os.makedirs(path, exist_ok=True)
+    last = {m: np.asarray(out[m])[:, -1].astype(np.float64) for m in MOD_ORDER}
+    n = last["pose"].shape[0]
+    per_scene = sum(a[0].nbytes for a in last.values()) if n else 0
+    if n and n * per_scene > cap_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(n, cap_bytes // per_scene, replace=False))
+        last = {m: a[keep] for m, a in last.items()}
+    for m, a in last.items():
+        np.save(os.path.join(path, f"tokens_{m}.npy"), a)
+
+
+def full_figures(eng, args, cfg, tm, profiled_frame, world):
+    """--full: everything the line carries beside the headline figure -- kernel-level rooflines from one extra profiled frame,
+    the committed PMC traffic and closed-loop records, and the CPU-baseline sample."""
+    B = args.batch
+    # kernel-level rooflines of the prefill side: one extra frame with per-launch HIP events (the engine runs the whole
+    # window in the foreground then, on all its CUs, so the launches are timed alone)
+    eng.set_profiling(True)
+    profiled_frame()
+    tp = eng.timings()
+    eng.set_profiling(False)
+    for k in ("gemm_ms", "gemm_flops", "gemm_launches", "attn_ms", "attn_flops", "attn_launches", "layers_ms", "layers_launches"):
+        tm[k] = tp[k]
+    gemm_tfs = (tm["gemm_flops"] / (tm["gemm_ms"] * 1e-3) / 1e12) if tm["gemm_ms"] > 0 else 0.0
+    attn_tfs = (tm["attn_flops"] / (tm["attn_ms"] * 1e-3) / 1e12) if tm["attn_ms"] > 0 else 0.0
+    steps_total = max(1, tm["oar_steps"])
+    step_us = tm["oar_ms"] * 1e3 / steps_total
+    engine_on = bool(tm["decode_engine"])
+    # dominant kernel: the decode step's layer kernel(s).  Algorithmic bytes per step = the OAR weights once + the KV rows of
+    # every scene (DESIGN.md section 5; the head / sampler launches of the step are not part of this kernel).  Its duration is
+    # measured per launch with HIP events on the decode stream in the extra profiled frame (eager launches, nothing else runs).
+    wsz = 4 if args.precision == "fp32" else 2
+    # AR heads: one GEMV per sampled step; head_tar_bbox3d: ONE GEMM per frame (tar_head_logits) -- per step, frame average
+    head_bytes = (cfg.map_vocab_size * 1024 + cfg.bbox3d_vocab_size * (660 + 1) + cfg.img_vocab_size * 512) * cfg.n_embd * wsz / 2206.0
+    bytes_per_step = tm["oar_bytes"] / steps_total        # whole batch
+    layer_bytes = bytes_per_step - head_bytes
+    layers_us = tp["layers_ms"] * 1e3 / max(1, tp["layers_launches"])
+    ach = layer_bytes / (layers_us * 1e-6) / 1e9 if layers_us > 0 else 0.0
+    oar_gbs = (tm["oar_bytes"] / (tm["oar_ms"] * 1e-3) / 1e9) if tm["oar_ms"] > 0 else 0.0
+    traffic, traffic_src = pmc_traffic_per_launch(engine_on and (B == 1 or B in PMC_FILES_BATCH) and args.config == "large", PMC_FILES_BATCH.get(B))
+    lanes = int(tm.get("decode_lanes", 0))
+    if int(tm["decode_engine"]) == 3:
+        kname = ("umgen::oar_engine_wide_kernel (chip-wide decode engine of the 2x-width layers: the 36 BlockOAR layers of a decode step of one scene "
+                 "in one launch of 256 workgroups)")
+        if B == 1 and args.config == "wide2x":
+            traffic, traffic_src = pmc_traffic_per_launch(True, ["r05_pmc_fetch_size_wide_engine.csv"], "oar_engine_wide_kernel")
+    elif engine_on:
+        kname = "umgen::oar_engine_kernel (XCD-resident decode engine: the 36 BlockOAR layers of a decode step in one launch)"
+    elif tm.get("decode_batched"):
+        kname = ("batched decode layer (rows_mfma_kernel x144 + attn_decode_batched_kernel x36 per step and lane; scenes as the MFMA's B-columns)" +
+                 (f", {lanes} decode lanes on their own streams: avg_launch_us = lane 0's whole step (layers + head + sampler) in the profiled frame, "
+                  "all lanes running" if lanes > 1 else ""))
+    else:
+        kname = "OAR decode layers as launches (gemv_ln_kernel x72, attn_partial_kernel x36, gemv_resid_kernel x72 per step)"
+    res = {
+        "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                     "traffic": traffic, "traffic_source": traffic_src, "kernel": kname,
+                     "avg_launch_us": layers_us, "launches_timed": tp["layers_launches"],
+                     "algorithmic_bytes_per_launch": layer_bytes, "scenes_per_launch": B,
+                     # the whole decode step (layer kernel + head GEMV + sampler, replayed from a hipGraph), timed region:
+                     "step": {"avg_step_us": step_us, "algorithmic_bytes_per_step": bytes_per_step, "achieved": oar_gbs,
+                              "frac": oar_gbs / HBM_PEAK_GBS, "kernels_per_step": tm["oar_kernels"] / steps_total}},
+        "roofline_gemm": {"bound": "mfma", "achieved": gemm_tfs, "peak": MFMA_BF16_PEAK_TFS, "unit": "TFLOP/s",
+                          "frac": gemm_tfs / MFMA_BF16_PEAK_TFS, "kernel": ("gemm16_256_kernel (256 x 256 tiles; launches under 300 tiles: gemm_bf16_pers_kernel / gemm_bf16_glds_kernel), TAR / ego stacks"
+                                     if args.precision != "fp32" else "gemm_f32_mfma_kernel (v_mfma_f32_32x32x2_f32), TAR / ego stacks"),
+                          "launches": tm["gemm_launches"], "avg_launch_ms": tm["gemm_ms"] / max(1, tm["gemm_launches"]),
+                          "clock_note": "peak is the nominal 2.4 GHz figure; inside these kernels' k-loops the chip sustains 1.46-1.71 GHz "
+                                        "(profiles/r04_gemm_stamps_clock.txt, measurement build; not measured in this run)"},
+        "roofline_attn": {"bound": "mfma", "achieved": attn_tfs, "peak": MFMA_BF16_PEAK_TFS, "unit": "TFLOP/s",
+                          "frac": attn_tfs / MFMA_BF16_PEAK_TFS, "kernel": "attn_spatial_mfma_kernel",
+                          "launches": tm["attn_launches"], "avg_launch_ms": tm["attn_ms"] / max(1, tm["attn_launches"])},
+        "prefill_ms_unoverlapped": {"ego": tp["ego_ms"], "tar": tp["tar_ms"]},
+        "closed_loop": closed_loop_record(args.precision) if args.config == "large" else None,
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        # 32 threads is the measured optimum on a 2x64-core host (more threads are slower): "cores" = threads actually used
+        res["cpu_baseline"] = cpu_baseline(args.config, threads=min(32, os.cpu_count() or 1))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -147,7 +232,12 @@ def main():
                     help="world size 1 only: still create the RCCL process group (backend nccl, device_id = this GPU) and run the path's "
                          "barrier, device all-gather and max all-reduce on it -- the hardware execution of the N > 1 communication code a "
                          "one-GPU box allows (the line carries rccl_exercised)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: one extra profiled frame for the kernel rooflines, the committed PMC / closed-loop "
+                         "records and the CPU-baseline sample (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tokens of their last step as DIR/tokens_<modality>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline sample")
     ap.add_argument("--no-graphs", action="store_true")
     args = ap.parse_args()
 
@@ -235,48 +325,11 @@ def main():
     tm = eng.timings()
 
     if rank == 0:
-        # kernel-level rooflines of the prefill side: one extra frame with per-launch HIP events (the engine runs the whole
-        # window in the foreground then, on all its CUs, so the launches are timed alone)
-        eng.set_profiling(True)
-        eng.rollout(tokens, 1, cond_frames=T, input_cond_frames=T, seeds=seeds, **control_of(mine, 1))
-        tp = eng.timings()
-        eng.set_profiling(False)
-        for k in ("gemm_ms", "gemm_flops", "gemm_launches", "attn_ms", "attn_flops", "attn_launches", "layers_ms", "layers_launches"):
-            tm[k] = tp[k]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
         total_scenes = B * world
         value = total_scenes * args.steps * SEQ_LEN / dt
         frames = max(1, tm["frames"])
-        gemm_tfs = (tm["gemm_flops"] / (tm["gemm_ms"] * 1e-3) / 1e12) if tm["gemm_ms"] > 0 else 0.0
-        attn_tfs = (tm["attn_flops"] / (tm["attn_ms"] * 1e-3) / 1e12) if tm["attn_ms"] > 0 else 0.0
-        steps_total = max(1, tm["oar_steps"])
-        step_us = tm["oar_ms"] * 1e3 / steps_total
-        engine_on = bool(tm["decode_engine"])
-        # dominant kernel: the decode step's layer kernel(s).  Algorithmic bytes per step = the OAR weights once + the KV rows of
-        # every scene (the head / sampler launches of the step are not part of this kernel).  Its duration is
-        # measured per launch with HIP events on the decode stream in the extra profiled frame (eager launches, nothing else runs).
-        wsz = 4 if args.precision == "fp32" else 2
-        # AR heads: one GEMV per sampled step; head_tar_bbox3d: ONE GEMM per frame (tar_head_logits) -- per step, frame average
-        head_bytes = (cfg.map_vocab_size * 1024 + cfg.bbox3d_vocab_size * (660 + 1) + cfg.img_vocab_size * 512) * cfg.n_embd * wsz / 2206.0
-        bytes_per_step = tm["oar_bytes"] / steps_total        # whole batch
-        layer_bytes = bytes_per_step - head_bytes
-        layers_us = tp["layers_ms"] * 1e3 / max(1, tp["layers_launches"])
-        ach = layer_bytes / (layers_us * 1e-6) / 1e9 if layers_us > 0 else 0.0
-        oar_gbs = (tm["oar_bytes"] / (tm["oar_ms"] * 1e-3) / 1e9) if tm["oar_ms"] > 0 else 0.0
-        traffic, traffic_src = pmc_traffic_per_launch(engine_on and (B == 1 or B in PMC_FILES_BATCH) and args.config == "large", PMC_FILES_BATCH.get(B))
-        lanes = int(tm.get("decode_lanes", 0))
-        if int(tm["decode_engine"]) == 3:
-            kname = ("umgen::oar_engine_wide_kernel (chip-wide decode engine of the 2x-width layers: the 36 BlockOAR layers of a decode step of one scene "
-                     "in one launch of 256 workgroups)")
-            if B == 1 and args.config == "wide2x":
-                traffic, traffic_src = pmc_traffic_per_launch(True, ["r05_pmc_fetch_size_wide_engine.csv"], "oar_engine_wide_kernel")
-        elif engine_on:
-            kname = "umgen::oar_engine_kernel (XCD-resident decode engine: the 36 BlockOAR layers of a decode step in one launch)"
-        elif tm.get("decode_batched"):
-            kname = ("batched decode layer (rows_mfma_kernel x144 + attn_decode_batched_kernel x36 per step and lane; scenes as the MFMA's B-columns)" +
-                     (f", {lanes} decode lanes on their own streams: avg_launch_us = lane 0's whole step (layers + head + sampler) in the profiled frame, "
-                      "all lanes running" if lanes > 1 else ""))
-        else:
-            kname = "OAR decode layers as launches (gemv_ln_kernel x72, attn_partial_kernel x36, gemv_resid_kernel x72 per step)"
         res = {
             "metric": "scene_tokens_per_sec", "value": value, "unit": "scene-tokens/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3 / args.steps,
@@ -286,22 +339,6 @@ def main():
                                    f"{B} scene(s)/GPU, T={T} history frames" + (f" (starting from {T_in})" if T_in != T else "") +
                                    ", top-k 5/5/16 sampling, rule_constrain",
                        "scenes_per_gpu": B, "history_frames": T, "input_history_frames": T_in, "sec_per_frame": dt / args.steps},
-            "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src, "kernel": kname,
-                         "avg_launch_us": layers_us, "launches_timed": tp["layers_launches"],
-                         "algorithmic_bytes_per_launch": layer_bytes, "scenes_per_launch": B,
-                         # the whole decode step (layer kernel + head GEMV + sampler, replayed from a hipGraph), timed region:
-                         "step": {"avg_step_us": step_us, "algorithmic_bytes_per_step": bytes_per_step, "achieved": oar_gbs,
-                                  "frac": oar_gbs / HBM_PEAK_GBS, "kernels_per_step": tm["oar_kernels"] / steps_total}},
-            "roofline_gemm": {"bound": "mfma", "achieved": gemm_tfs, "peak": MFMA_BF16_PEAK_TFS, "unit": "TFLOP/s",
-                              "frac": gemm_tfs / MFMA_BF16_PEAK_TFS, "kernel": ("gemm16_256_kernel (256 x 256 tiles; launches under 300 tiles: gemm_bf16_pers_kernel / gemm_bf16_glds_kernel), TAR / ego stacks"
-                                         if args.precision != "fp32" else "gemm_f32_mfma_kernel (v_mfma_f32_32x32x2_f32), TAR / ego stacks"),
-                              "launches": tm["gemm_launches"], "avg_launch_ms": tm["gemm_ms"] / max(1, tm["gemm_launches"]),
-                              "clock_note": "peak is the nominal 2.4 GHz figure; inside these kernels' k-loops the chip sustains 1.46-1.71 GHz "
-                                            "(profiles/r04_gemm_stamps_clock.txt, measurement build; not measured in this run)"},
-            "roofline_attn": {"bound": "mfma", "achieved": attn_tfs, "peak": MFMA_BF16_PEAK_TFS, "unit": "TFLOP/s",
-                              "frac": attn_tfs / MFMA_BF16_PEAK_TFS, "kernel": "attn_spatial_mfma_kernel",
-                              "launches": tm["attn_launches"], "avg_launch_ms": tm["attn_ms"] / max(1, tm["attn_launches"])},
             # foreground stream per frame; "background" = the next frame's history slots pushed through the stacks on the CU-masked
             # second stream while the decode loop runs (only with UMGEN_OVERLAP=1, i.e. without the engine)
             "phases_ms_per_frame": {"ego": tm["ego_ms"] / frames, "tar": tm["tar_ms"] / frames, "oar": tm["oar_ms"] / frames,
@@ -309,12 +346,14 @@ def main():
                                     "overlapped_frames": tm["overlapped_frames"],
                                     # frames that pushed only their new last slot through the stacks (growing window, slot caches: f-3)
                                     "frames_reusing_slot_caches": tm["overlapped_frames"]},
-            "prefill_ms_unoverlapped": {"ego": tp["ego_ms"], "tar": tp["tar_ms"]},
             "weight_load_s": t_load,
-            "closed_loop": closed_loop_record(args.precision) if args.config == "large" else None,
             "decode_engine": int(tm["decode_engine"]), "engine_fallback": int(tm["engine_fallback"]), "decode_batched": int(tm.get("decode_batched", 0)),
-            "decode_lanes": lanes,
+            "decode_lanes": int(tm.get("decode_lanes", 0)),
         }
+        if args.full:
+            # one extra profiled frame, the rooflines and the CPU baseline: none of them is part of the headline figure
+            res.update(full_figures(eng, args, cfg, tm, lambda: eng.rollout(tokens, 1, cond_frames=T, input_cond_frames=T, seeds=seeds,
+                                                                            **control_of(mine, 1)), world))
         if force_dist:
             res["rccl_exercised"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "collective_device": gdev,
                                      "calls": "init_process_group(nccl, device_id), barrier, all_reduce(MAX) x2, all_gather of the int32 token buffer -- inside the timed region"}
@@ -323,9 +362,6 @@ def main():
         if tm["engine_fallback"]:
             print("bench.py: WARNING -- the XCD-resident decode engine was NOT used (census failed at umgen_create): this line measures the "
                   "five-launch decode layer, not the production path", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
-            # 32 threads is the measured optimum on the 2x64-core host (more threads are slower): "cores" = threads actually used
-            res["cpu_baseline"] = cpu_baseline(args.config, threads=min(32, os.cpu_count() or 1))
         print(json.dumps(res))
     eng.close()
     if dist_on:

@@ -85,18 +85,19 @@ def test_token_pickle_writer_skips_existing(tmp_path):
     assert scene_io.save_tokens(out, str(tmp_path), "clip_a") is None          # model_pl.py:215-216
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/projects"), reason="reference checkout not present")
 def test_live_against_reference_dataset_on_a_fresh_seed(tmp_path):
+    """A seed outside scene_reader.npz: the reference dataset's tokens of it are in reference_checks.npz (make_reference_checks.py)."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_scene_golden
-    ref = make_scene_golden.reference_tokens(11, 150, 30, 120)
-    path = tmp_path / "scene_11_synthetic_clip_000.pkl"
+    import make_reference_checks as rc
+    ref = np.load(rc.OUT)
+    seed, n_frames, block, n_tracks = rc.SCENE_CASE
+    path = tmp_path / f"scene_{seed}_synthetic_clip_000.pkl"
     with open(path, "wb") as f:
-        pickle.dump(scene_io.synthetic_raw_scene(11, 150, 120), f)
-    item = scene_io.SceneReader(str(path), block_size=30)[0]
+        pickle.dump(scene_io.synthetic_raw_scene(seed, n_frames, n_tracks), f)
+    item = scene_io.SceneReader(str(path), block_size=block)[0]
     for m in MOD_ORDER:
-        np.testing.assert_array_equal(item[m], ref[m], err_msg=m)
+        np.testing.assert_array_equal(item[m], ref[f"scene11_{m}"], err_msg=m)
 
 
 def test_evaluate_loads_raw_clips_through_the_reader(tmp_path, gold):
