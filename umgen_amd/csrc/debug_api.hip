@@ -2,6 +2,7 @@
 // HIP kernel against the CPU oracle at production width; never called by the product path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -19,6 +20,45 @@ struct DevBuf {
 };
 inline int up(void* d, const void* h, size_t n) { return hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess ? 0 : UMGEN_E_HIP; }
 inline int down(void* h, const void* d, size_t n) { return hipMemcpy(h, d, n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : UMGEN_E_HIP; }
+
+// Output buffer of the batched-decode and sampler hooks: `bytes` the kernel may write, then a band of `guard` bytes filled with a sentinel.
+// A kernel that writes past N, M or the row changes the band; the hook then returns UMGEN_E_STATE.
+constexpr unsigned char kGuardByte = 0xA7;
+constexpr size_t kGuardBytes = (size_t)64 << 10;
+struct GuardedBuf : DevBuf {
+    size_t bytes, guard;
+    explicit GuardedBuf(size_t b, size_t g = kGuardBytes) : DevBuf(b + g), bytes(b), guard(g) {
+        if (p && hipMemset((char*)p + bytes, kGuardByte, guard) != hipSuccess) { (void)hipFree(p); p = nullptr; }
+    }
+    bool intact() const {
+        std::vector<unsigned char> h(guard);
+        if (hipMemcpy(h.data(), (const char*)p + bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (unsigned char c : h)
+            if (c != kGuardByte) return false;
+        return true;
+    }
+};
+// band behind a buffer of M per-scene rows: the rows scenes M .. kRowsMaxM - 1 would take (at least 64 KB, at most 64 MB)
+inline size_t scene_band(size_t row_bytes, int M) {
+    return std::min(std::max(kGuardBytes, row_bytes * (size_t)(kRowsMaxM - M)), (size_t)64 << 20);
+}
+constexpr unsigned kNaN32 = 0x7fc00000u;
+inline unsigned short nan16(int prec) { return prec == 2 ? 0x7e00 : 0x7fc0; }
+// floats of a fragment-major buffer of kRowsMaxM scenes x C columns (frag_index, kernels.h)
+inline size_t frag_floats(int C) { return (size_t)((C + 31) / 32) * 32 * kRowsMaxM; }
+// fragment-major [kRowsMaxM][C] on the device -> row-major [M][C] on the host; UMGEN_E_STATE if a column m >= M or a pad column >= C was written
+int frag_down(const void* d, int M, int C, float* rows) {
+    std::vector<unsigned> h(frag_floats(C));
+    if (int rc = down(h.data(), d, h.size() * 4)) return rc;
+    bool clean = true;
+    for (int m = 0; m < kRowsMaxM; ++m)
+        for (int c = 0; c < (C + 31) / 32 * 32; ++c) {
+            const unsigned v = h[frag_index(m, c)];
+            if (m < M && c < C) memcpy(rows + (size_t)m * C + c, &v, 4);
+            else clean = clean && v == kNaN32;
+        }
+    return clean ? UMGEN_OK : UMGEN_E_STATE;
+}
 }  // namespace
 
 extern "C" {
@@ -307,6 +347,110 @@ int umgen_dbg_batched_layer_bench(int prec, int M, int L, int iters, float* us) 
     hipEventDestroy(e1);
     hipStreamDestroy(st);
     return UMGEN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Kernel-level hooks of the batched decode layer (decode_batched.hip) and of the sampler (frame.hip).  Each launches what the decode step
+// launches, through the same launchers and argument layout as oar_layers / sample_token_kernel (engine.hip, frame.hip).  Every output
+// buffer carries a guard band (GuardedBuf); every location the kernel must not write holds NaN and is checked where it comes back.
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// launch_rows_to_frag + launch_rows_mfma on x [M][K] (row-major fp32) and W [N][K] (16-bit bits of precision code prec: 1 bf16, 2 fp16).
+//   ROWS_QKV   out [M][ldo]: q columns 0 .. E-1; cache [M][2][H][Lmax][48] (16-bit, H = E / 48, output only: NaN before the launch) gets its
+//              K / V rows at position pos
+//   ROWS_GELU  out_rows [M][N]: gelu(LN(x) W^T + bias), converted from the fragment-major output
+//   ROWS_RESID out [M][ldo] (in/out): out + x W^T + bias; out_rows [M][N]: the fragment-major copy, un-permuted
+//   ROWS_F32   out [M][ldo]: LN(x) W^T + bias
+// The fragment columns m >= M of the input, the row-major output columns the mode does not write (up to ldo) and the whole cache hold NaN
+// at the launch; out and cache come back whole, so that the caller sees whether any of them changed.
+int umgen_dbg_rows(int prec, int mode, const float* x, const float* ln_w, const void* W, const float* bias, int M, int N, int K, int E, float* out,
+                   long ldo, float* out_rows, void* cache, int Lmax, int pos) {
+    if ((prec != 1 && prec != 2) || mode < ROWS_F32 || mode > ROWS_RESID) return UMGEN_E_INVALID;
+    if (M < 1 || M > kRowsMaxM || N < 1 || K < 32 || K % 32 || !x || !W) return UMGEN_E_INVALID;
+    const bool ln = mode != ROWS_RESID, has_out = mode != ROWS_GELU, has_frag = mode == ROWS_GELU || mode == ROWS_RESID;
+    if (ln && (!ln_w || K > 768)) return UMGEN_E_INVALID;        // the LayerNorm prologue keeps every k-step of a wave in registers
+    const long ncol = mode == ROWS_QKV ? E : N;                   // row-major columns the kernel writes
+    if (has_out && (!out || ldo < ncol)) return UMGEN_E_INVALID;
+    if (has_frag && !out_rows) return UMGEN_E_INVALID;
+    if (mode == ROWS_QKV && (E < kHeadDim || E % kHeadDim || N != 3 * E || !cache || Lmax < 1 || pos < 0 || pos >= Lmax)) return UMGEN_E_INVALID;
+    const size_t cstride = mode == ROWS_QKV ? (size_t)2 * (E / kHeadDim) * Lmax * kHeadDim : 0;   // 16-bit elements per scene
+    const size_t osz = has_out ? (size_t)M * ldo * 4 : 0, csz = (size_t)M * cstride * 2;
+    DevBuf dX((size_t)M * K * 4), dXf(frag_floats(K) * 4), dL((size_t)K * 4), dW((size_t)N * K * 2), dB((size_t)N * 4), dlen(4);
+    GuardedBuf dO(osz, scene_band((size_t)ldo * 4, M)), dF(has_frag ? frag_floats(N) * 4 : 0), dC(csz, scene_band(cstride * 2, M));
+    if (!dX.p || !dXf.p || !dL.p || !dW.p || !dB.p || !dlen.p || !dO.p || !dF.p || !dC.p) return UMGEN_E_NOMEM;
+    if (up(dX.p, x, (size_t)M * K * 4) || up(dW.p, W, (size_t)N * K * 2) || up(dlen.p, &pos, 4)) return UMGEN_E_HIP;
+    if ((ln && up(dL.p, ln_w, (size_t)K * 4)) || (bias && up(dB.p, bias, (size_t)N * 4))) return UMGEN_E_HIP;
+    if (hipMemsetD32((hipDeviceptr_t)dXf.p, (int)kNaN32, frag_floats(K)) != hipSuccess) return UMGEN_E_HIP;
+    if (has_frag && hipMemsetD32((hipDeviceptr_t)dF.p, (int)kNaN32, frag_floats(N)) != hipSuccess) return UMGEN_E_HIP;
+    if (csz && hipMemsetD16((hipDeviceptr_t)dC.p, nan16(prec), csz / 2) != hipSuccess) return UMGEN_E_HIP;
+    if (has_out) {
+        std::vector<float> ho((size_t)M * ldo);
+        const float qnan = __builtin_bit_cast(float, kNaN32);
+        for (int m = 0; m < M; ++m)
+            for (long n = 0; n < ldo; ++n) ho[(size_t)m * ldo + n] = (mode == ROWS_RESID && n < ncol) ? out[(size_t)m * ldo + n] : qnan;
+        if (up(dO.p, ho.data(), osz)) return UMGEN_E_HIP;
+    }
+    launch_rows_to_frag(nullptr, (const float*)dX.p, K, M, K, (float*)dXf.p);
+    RowsArgs r{};
+    r.x = (const float*)dXf.p; r.M = M; r.ln_w = ln ? (const float*)dL.p : nullptr; r.W = dW.p; r.bias = bias ? (const float*)dB.p : nullptr;
+    r.N = N; r.K = K; r.mode = mode; r.out = has_out ? (float*)dO.p : nullptr; r.ldo = ldo; r.out_frag = has_frag ? (float*)dF.p : nullptr;
+    r.cache = csz ? dC.p : nullptr; r.scene_stride = (long)cstride; r.d_len = (const int*)dlen.p; r.Lmax = Lmax; r.E = E;
+    if (prec == 2) launch_rows_mfma<f16_t>(nullptr, r); else launch_rows_mfma<bf16_t>(nullptr, r);
+    if (hipDeviceSynchronize() != hipSuccess) return UMGEN_E_HIP;
+    if (!dO.intact() || !dF.intact() || !dC.intact()) return UMGEN_E_STATE;
+    if (has_out && down(out, dO.p, osz)) return UMGEN_E_HIP;
+    if (csz && down(cache, dC.p, csz)) return UMGEN_E_HIP;
+    return has_frag ? frag_down(dF.p, M, N, out_rows) : UMGEN_OK;
+}
+
+// launch_attn_decode_batched on q [M][H * 48] (fp32) against the cache image [M][2][H][Lmax][48] (16-bit bits of prec) with *d_len = len, i.e.
+// keys 0 .. len; y [M][H * 48] row-major (converted from the kernel's fragment-major output)
+int umgen_dbg_attn_decode_batched(int prec, const float* q, const void* cache, int M, int H, int Lmax, int len, float* y) {
+    if ((prec != 1 && prec != 2) || M < 1 || M > kRowsMaxM || H < 1 || len < 0 || len >= Lmax || !q || !cache || !y) return UMGEN_E_INVALID;
+    const int E = H * kHeadDim;
+    const size_t cstride = (size_t)2 * H * Lmax * kHeadDim, csz = (size_t)M * cstride * 2;
+    DevBuf dQ((size_t)M * E * 4), dC(csz), dlen(4);
+    GuardedBuf dY(frag_floats(E) * 4);
+    if (!dQ.p || !dC.p || !dlen.p || !dY.p) return UMGEN_E_NOMEM;
+    if (up(dQ.p, q, (size_t)M * E * 4) || up(dC.p, cache, csz) || up(dlen.p, &len, 4)) return UMGEN_E_HIP;
+    if (hipMemsetD32((hipDeviceptr_t)dY.p, (int)kNaN32, frag_floats(E)) != hipSuccess) return UMGEN_E_HIP;
+    if (prec == 2) launch_attn_decode_batched<f16_t>(nullptr, (const float*)dQ.p, (const f16_t*)dC.p, (long)cstride, M, H, Lmax, (const int*)dlen.p, (float*)dY.p);
+    else launch_attn_decode_batched<bf16_t>(nullptr, (const float*)dQ.p, (const bf16_t*)dC.p, (long)cstride, M, H, Lmax, (const int*)dlen.p, (float*)dY.p);
+    if (hipDeviceSynchronize() != hipSuccess) return UMGEN_E_HIP;
+    if (!dY.intact()) return UMGEN_E_STATE;
+    return frag_down(dY.p, M, E, y);
+}
+
+// block_sample (frame.hip; method 0 top-k with k, 1 top-p with p; temperature temp) on n rows of V <= 8192 logits, one block per row, with the
+// uniforms u[n] and the masked index mask_idx (-1: none) -> tokens[n]
+int umgen_dbg_sample(int method, const float* logits, int n, int V, int k, float p, float temp, int mask_idx, const float* u, int32_t* tokens) {
+    if ((method != 0 && method != 1) || V < 1 || V > 8192 || n < 1 || k < 1 || mask_idx < -1 || mask_idx >= V) return UMGEN_E_INVALID;
+    DevBuf dL((size_t)n * V * 4), dU((size_t)n * 4), dO(4);
+    GuardedBuf dT((size_t)n * 4);
+    if (!dL.p || !dU.p || !dO.p || !dT.p) return UMGEN_E_NOMEM;
+    if (up(dL.p, logits, (size_t)n * V * 4) || up(dU.p, u, (size_t)n * 4) || hipMemset(dO.p, 0, 4) != hipSuccess) return UMGEN_E_HIP;
+    SamplerParams sp{};
+    sp.method = method; sp.top_k = sp.top_k_map = sp.topk_image = k; sp.p = sp.p_map = p; sp.temperature = temp;
+    launch_sample_dbg(nullptr, (const float*)dL.p, V, sp, k, p, (const float*)dU.p, mask_idx, (int*)dT.p, (int*)dO.p, n);
+    if (hipDeviceSynchronize() != hipSuccess) return UMGEN_E_HIP;
+    if (!dT.intact()) return UMGEN_E_STATE;
+    return down(tokens, dT.p, (size_t)n * 4);
+}
+
+// check_collision_dev (frame.hip) on n_sets box sets: boxes [n_sets][max_n][10] fp64, set i = its first counts[i] boxes -> out[i] 0 / 1
+int umgen_dbg_collision(const double* boxes, const int32_t* counts, int n_sets, int max_n, int32_t* out) {
+    if (n_sets < 1 || max_n < 1 || max_n > 64 || !boxes || !counts || !out) return UMGEN_E_INVALID;     // the sampler's corner table holds 64 boxes
+    for (int i = 0; i < n_sets; ++i)
+        if (counts[i] < 1 || counts[i] > max_n) return UMGEN_E_INVALID;
+    const size_t bsz = (size_t)n_sets * max_n * 10 * 8;
+    DevBuf dB(bsz), dN((size_t)n_sets * 4);
+    GuardedBuf dO((size_t)n_sets * 4);
+    if (!dB.p || !dN.p || !dO.p) return UMGEN_E_NOMEM;
+    if (up(dB.p, boxes, bsz) || up(dN.p, counts, (size_t)n_sets * 4)) return UMGEN_E_HIP;
+    launch_collision_rows(nullptr, (const double*)dB.p, (const int*)dN.p, max_n, (int*)dO.p, n_sets);
+    if (hipDeviceSynchronize() != hipSuccess) return UMGEN_E_HIP;
+    if (!dO.intact()) return UMGEN_E_STATE;
+    return down(out, dO.p, (size_t)n_sets * 4);
 }
 
 }  // extern "C"

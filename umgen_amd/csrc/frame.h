@@ -96,6 +96,10 @@ void launch_prefix_kv_to_cache(hipStream_t s, const T* qk, const T* vt, int B, i
 void launch_sample_token(hipStream_t s, const SampleArgs& a, int B);            // sampled steps
 // ego head: sample 3 pose tokens per scene from logits [B*3][vocab]
 void launch_sample_rows(hipStream_t s, const float* logits, int V, int k, float temp, const float* u, int* out, int* overflow, int n);   // test hook
+// test hooks: block_sample (top-k or top-p by sp.method) with a masked index; check_collision_dev on sets of <= 64 boxes [n_sets][max_n][10]
+void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerParams& sp, int k, float p, const float* u, int mask_idx, int* out,
+                       int* overflow, int n);
+void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts, int max_n, int* out, int n_sets);
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
                        const int* forced, int* out_tokens, int B, int* overflow);
 // ego query rows: egoe[j] + spe[j] + tpe[T-1]

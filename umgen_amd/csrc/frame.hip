@@ -260,15 +260,15 @@ __device__ int block_sample_topk(const float* __restrict__ logits, int V, int k,
             int last = 0;
             for (int idx = 0; idx < V; ++idx) {
                 const float l = idx != mask_idx ? logits[idx] : -INFINITY;
-                if (l >= kth && l > -INFINITY) { total = __fadd_rn(total, exp_det(__fsub_rn(l / temp, zmax))); last = idx; }
+                if (l >= kth && l > -INFINITY) { total = add_rn(total, exp_det(sub_rn(l / temp, zmax))); last = idx; }
             }
-            const float target = __fmul_rn(u, total);
+            const float target = mul_rn(u, total);
             float c = 0.f;
             int res = last;
             for (int idx = 0; idx < V; ++idx) {
                 const float l = idx != mask_idx ? logits[idx] : -INFINITY;
                 if (l >= kth && l > -INFINITY) {
-                    c = __fadd_rn(c, exp_det(__fsub_rn(l / temp, zmax)));
+                    c = add_rn(c, exp_det(sub_rn(l / temp, zmax)));
                     if (c > target) { res = idx; break; }
                 }
             }
@@ -286,14 +286,14 @@ __device__ int block_sample_topk(const float* __restrict__ logits, int V, int k,
         const int si = lane < n ? sh.cand_i[lane] : 0;
         const float z = lane < n ? sh.cand_v[lane] / temp : -INFINITY;
         const float zmax = wave_max(z);
-        const float ev = lane < n ? exp_det(__fsub_rn(z, zmax)) : 0.f;
+        const float ev = lane < n ? exp_det(sub_rn(z, zmax)) : 0.f;
         float total = 0.f;
-        for (int a = 0; a < n; ++a) total = __fadd_rn(total, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev), a)));
-        const float target = __fmul_rn(u, total);
+        for (int a = 0; a < n; ++a) total = add_rn(total, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev), a)));
+        const float target = mul_rn(u, total);
         float c = 0.f;
         int res = __builtin_amdgcn_readlane(si, n - 1);
         for (int a = 0; a < n; ++a) {
-            c = __fadd_rn(c, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev), a)));
+            c = add_rn(c, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev), a)));
             if (c > target) { res = __builtin_amdgcn_readlane(si, a); break; }
         }
         if (lane == 0) sh.result = res;
@@ -331,11 +331,11 @@ __device__ int block_sample_topp(const float* __restrict__ logits, int V, float 
     if (lane == 0) sh.red[wave] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(sh.red[0], sh.red[1]), fmaxf(sh.red[2], sh.red[3]));
-    for (int i = tid; i < kTopPMax; i += 256) sh.pr[i] = exp_det(__fsub_rn(sh.pr[i], mx));   // exp(-inf) = 0 for padding / masked
+    for (int i = tid; i < kTopPMax; i += 256) sh.pr[i] = exp_det(sub_rn(sh.pr[i], mx));   // exp(-inf) = 0 for padding / masked
     __syncthreads();
     if (tid == 0) {
         float t = 0.f;
-        for (int i = 0; i < V; ++i) t = __fadd_rn(t, sh.pr[i]);
+        for (int i = 0; i < V; ++i) t = add_rn(t, sh.pr[i]);
         sh.total = t;
     }
     __syncthreads();
@@ -361,14 +361,14 @@ __device__ int block_sample_topp(const float* __restrict__ logits, int V, float 
     if (tid == 0) {
         float c = 0.f;
         int n = 0;
-        while (n < V && !(c > p)) { c = __fadd_rn(c, sh.pr[n]); ++n; }      // (cumsum - p_j) > p masks entry j
+        while (n < V && !(c > p)) { c = add_rn(c, sh.pr[n]); ++n; }      // (cumsum - p_j) > p masks entry j
         float t2 = 0.f;
-        for (int i = 0; i < n; ++i) t2 = __fadd_rn(t2, sh.pr[i]);
-        const float target = __fmul_rn(u, t2);
+        for (int i = 0; i < n; ++i) t2 = add_rn(t2, sh.pr[i]);
+        const float target = mul_rn(u, t2);
         float cc = 0.f;
         int res = sh.ix[n - 1];
         for (int i = 0; i < n; ++i) {
-            cc = __fadd_rn(cc, sh.pr[i]);
+            cc = add_rn(cc, sh.pr[i]);
             if (cc > target) { res = sh.ix[i]; break; }
         }
         sh.result = res;
@@ -394,16 +394,17 @@ __device__ inline int block_sample(const SamplerParams& sp, const float* logits,
 // rule-based constraint (UMGen.py:1275-1383) and its helpers, evaluated by one thread
 //   decode: BBox3DTokenizer.decode_single_objects (tokenizer.py:679-687) + Normalize.unnormalize_bbox3d (normalize.py:136-229)
 //   collision: BoxOverlap.check_collision(fliter=True) (misc.py:591-630), bbox3d2bevcorners (143-177), box_collision_test (203-311)
-// fp64 / fp32 operations are issued unfused (__dmul_rn, __fsub_rn ...) to follow numpy's evaluation order.
+// fp64 / fp32 operations are issued unfused (mul_rn, sub_rn ..., common.h: hipcc would fuse plain * and + into FMAs) to follow numpy's
+// evaluation order.
 // ---------------------------------------------------------------------------------------------------------
 __device__ inline double box_bin(int i) {   // np.linspace(0, 1, 1024)[i]
-    return (i >= 1023) ? 1.0 : __dadd_rn(__dmul_rn((double)i, 1.0 / 1023.0), 0.0);
+    return (i >= 1023) ? 1.0 : add_rn(mul_rn((double)i, 1.0 / 1023.0), 0.0);
 }
 __constant__ double kBoxLo[10] = {-64, -64, -5, 0, 0, 0, -3.14, -20, -15, -0.3};
 __constant__ double kBoxHi[10] = {64, 64, 5, 15, 4, 5, 3.14, 20, 15, 0.3};
 
 __device__ inline bool gt_cross(float a1, float a0, float b1, float b0) {   // a1*a0 > b1*b0 in fp32
-    return __fmul_rn(a1, a0) > __fmul_rn(b1, b0);
+    return mul_rn(a1, a0) > mul_rn(b1, b0);
 }
 
 __device__ bool check_collision_dev(const double* boxes, int n, float (*cor)[8]) {
@@ -416,11 +417,11 @@ __device__ bool check_collision_dev(const double* boxes, int n, float (*cor)[8])
         const double sn = sin(ang), cs = cos(ang);
         const double tx[4] = {-0.5, -0.5, 0.5, 0.5}, ty[4] = {-0.5, 0.5, 0.5, -0.5};
         for (int k = 0; k < 4; ++k) {
-            const double x = __dmul_rn(tx[k], l), y = __dmul_rn(ty[k], w);
-            const double rx = __dadd_rn(__dmul_rn(x, cs), __dmul_rn(y, -sn));
-            const double ry = __dadd_rn(__dmul_rn(x, sn), __dmul_rn(y, cs));
-            cor[m][2 * k] = (float)__dadd_rn(rx, bx[0]);
-            cor[m][2 * k + 1] = (float)__dadd_rn(ry, bx[1]);
+            const double x = mul_rn(tx[k], l), y = mul_rn(ty[k], w);
+            const double rx = add_rn(mul_rn(x, cs), mul_rn(y, -sn));
+            const double ry = add_rn(mul_rn(x, sn), mul_rn(y, cs));
+            cor[m][2 * k] = (float)add_rn(rx, bx[0]);
+            cor[m][2 * k + 1] = (float)add_rn(ry, bx[1]);
         }
         ++m;
     }
@@ -432,19 +433,19 @@ __device__ bool check_collision_dev(const double* boxes, int n, float (*cor)[8])
         const float* bq = cor[i];
         float bx0 = bq[0], bx1 = bq[0], by0 = bq[1], by1 = bq[1];
         for (int k = 1; k < 4; ++k) { bx0 = fminf(bx0, bq[2 * k]); bx1 = fmaxf(bx1, bq[2 * k]); by0 = fminf(by0, bq[2 * k + 1]); by1 = fmaxf(by1, bq[2 * k + 1]); }
-        const float iw = __fsub_rn(fminf(bx1, qx1), fmaxf(bx0, qx0));
+        const float iw = sub_rn(fminf(bx1, qx1), fmaxf(bx0, qx0));
         if (!(iw > 0.f)) continue;
-        const float ih = __fsub_rn(fminf(by1, qy1), fmaxf(by0, qy0));
+        const float ih = sub_rn(fminf(by1, qy1), fmaxf(by0, qy0));
         if (!(ih > 0.f)) continue;
         for (int k = 0; k < 4; ++k) {
             const float A0 = bq[2 * k], A1 = bq[2 * k + 1], B0 = bq[2 * ((k + 1) & 3)], B1 = bq[2 * ((k + 1) & 3) + 1];
             for (int l2 = 0; l2 < 4; ++l2) {
                 const float C0 = q[2 * l2], C1 = q[2 * l2 + 1], D0 = q[2 * ((l2 + 1) & 3)], D1 = q[2 * ((l2 + 1) & 3) + 1];
-                const bool acd = gt_cross(__fsub_rn(D1, A1), __fsub_rn(C0, A0), __fsub_rn(C1, A1), __fsub_rn(D0, A0));
-                const bool bcd = gt_cross(__fsub_rn(D1, B1), __fsub_rn(C0, B0), __fsub_rn(C1, B1), __fsub_rn(D0, B0));
+                const bool acd = gt_cross(sub_rn(D1, A1), sub_rn(C0, A0), sub_rn(C1, A1), sub_rn(D0, A0));
+                const bool bcd = gt_cross(sub_rn(D1, B1), sub_rn(C0, B0), sub_rn(C1, B1), sub_rn(D0, B0));
                 if (acd != bcd) {
-                    const bool abc = gt_cross(__fsub_rn(C1, A1), __fsub_rn(B0, A0), __fsub_rn(B1, A1), __fsub_rn(C0, A0));
-                    const bool abd = gt_cross(__fsub_rn(D1, A1), __fsub_rn(B0, A0), __fsub_rn(B1, A1), __fsub_rn(D0, A0));
+                    const bool abc = gt_cross(sub_rn(C1, A1), sub_rn(B0, A0), sub_rn(B1, A1), sub_rn(C0, A0));
+                    const bool abd = gt_cross(sub_rn(D1, A1), sub_rn(B0, A0), sub_rn(B1, A1), sub_rn(D0, A0));
                     if (abc != abd) return true;
                 }
             }
@@ -588,8 +589,8 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
                 for (int q = 0; q < 10; ++q) {
                     const int t = toks[off + k - 10 + q];
                     const int right = min(max(t, 0), 1023), left = min(max(t - 1, 0), 1023);
-                    const double v = __dadd_rn(box_bin(left), box_bin(right)) / 2.0;
-                    nb[q] = __dadd_rn(__dmul_rn(v, kBoxHi[q] - kBoxLo[q]), kBoxLo[q]);
+                    const double v = add_rn(box_bin(left), box_bin(right)) / 2.0;
+                    nb[q] = add_rn(mul_rn(v, kBoxHi[q] - kBoxLo[q]), kBoxLo[q]);
                 }
                 ++n;
                 const bool collision = check_collision_dev(boxes, n, cor);
@@ -646,6 +647,30 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
 }
 void launch_sample_rows(hipStream_t s, const float* logits, int V, int k, float temp, const float* u, int* out, int* overflow, int n) {
     hipLaunchKernelGGL(sample_rows_kernel, dim3(n), dim3(256), 0, s, logits, V, k, temp, u, out, overflow);
+}
+
+// test hook (debug_api.hip): block_sample -- the decode step's dispatch on SamplerParams.method -- on n independent rows with given
+// uniforms and one masked index (sample_token_kernel's control resample masks vocab - 1)
+__global__ __launch_bounds__(256) void sample_dbg_kernel(const float* __restrict__ logits, int V, SamplerParams sp, int k, float p,
+                                                         const float* __restrict__ u, int mask_idx, int* __restrict__ out, int* overflow) {
+    __shared__ SamplerLds sh;
+    const int tok = block_sample(sp, logits + (long)blockIdx.x * V, V, k, p, u[blockIdx.x], mask_idx, sh, overflow);
+    if (threadIdx.x == 0) out[blockIdx.x] = tok;
+}
+void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerParams& sp, int k, float p, const float* u, int mask_idx, int* out,
+                       int* overflow, int n) {
+    hipLaunchKernelGGL(sample_dbg_kernel, dim3(n), dim3(256), 0, s, logits, V, sp, k, p, u, mask_idx, out, overflow);
+}
+
+// test hook (debug_api.hip): check_collision_dev on box set b = boxes[b][0 .. counts[b]), one block per set; thread 0 evaluates it with
+// the same LDS corner table sample_token_kernel gives it
+__global__ __launch_bounds__(64) void collision_rows_kernel(const double* __restrict__ boxes, const int* __restrict__ counts, int max_n,
+                                                            int* __restrict__ out) {
+    __shared__ float cor[64][8];
+    if (threadIdx.x == 0) out[blockIdx.x] = check_collision_dev(boxes + (long)blockIdx.x * max_n * 10, counts[blockIdx.x], cor) ? 1 : 0;
+}
+void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts, int max_n, int* out, int n_sets) {
+    hipLaunchKernelGGL(collision_rows_kernel, dim3(n_sets), dim3(64), 0, s, boxes, counts, max_n, out);
 }
 
 }  // namespace umgen
