@@ -20,7 +20,8 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
            "umgen_dbg_linear", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_oar_step", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
-           "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision"]
+           "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
+           "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer"]
 
 HEADERS = ("common.h", "kernels.h", "frame.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h")
 
@@ -244,6 +245,10 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_attn_decode_batched.argtypes = [i32, fp, vp, i32, i32, i32, i32, fp]
     lib.umgen_dbg_sample.argtypes = [i32, fp, i32, i32, i32, C.c_float, C.c_float, i32, fp, i32p]
     lib.umgen_dbg_collision.argtypes = [f64p, i32p, i32, i32, i32p]
+    lib.umgen_dbg_gemv_modes.argtypes = [i32, i32, i32, fp, i32, fp, vp, fp, i32, i32, i32, i32, fp, C.c_long, vp, i32, i32]
+    lib.umgen_dbg_gemv_resid.argtypes = [i32, i32, fp, C.c_long, vp, fp, i32, i32, i32, fp]
+    lib.umgen_dbg_attn_partial.argtypes = [i32, i32, i32, fp, vp, i32, i32, i32, i32, i32, vp, fp, fp]
+    lib.umgen_dbg_decode_layer.argtypes = [i32, i32, i32, i32, i32, i32, fp, vp, fp, vp, fp, fp, vp, vp, fp, fp, vp]
     lib.umgen_vq_create.argtypes = [C.POINTER(VQConfig), C.POINTER(vp)]
     lib.umgen_vq_load_tensor.argtypes = [vp, C.c_char_p, fp, i64p, i32]
     lib.umgen_vq_finalize.argtypes = [vp]

@@ -59,6 +59,17 @@ int frag_down(const void* d, int M, int C, float* rows) {
         }
     return clean ? UMGEN_OK : UMGEN_E_STATE;
 }
+// f(T{}) with T the operand type of precision code prec (0 fp32, 1 bf16, 2 fp16)
+template <typename F>
+void by_prec(int prec, F&& f) {
+    if (prec == 2) f(f16_t{}); else if (prec == 1) f(bf16_t{}); else f(float{});
+}
+// launch errors first (a launch the runtime refused writes nothing), then the work itself
+inline int finish() {
+    if (hipGetLastError() != hipSuccess) return UMGEN_E_HIP;
+    return hipDeviceSynchronize() == hipSuccess ? UMGEN_OK : UMGEN_E_HIP;
+}
+constexpr float kStalePartial = 1000.f;   // never-written slots of the attention partials: finite garbage, like the product's stale values
 }  // namespace
 
 extern "C" {
@@ -451,6 +462,144 @@ int umgen_dbg_collision(const double* boxes, const int32_t* counts, int n_sets, 
     if (hipDeviceSynchronize() != hipSuccess) return UMGEN_E_HIP;
     if (!dO.intact()) return UMGEN_E_STATE;
     return down(out, dO.p, (size_t)n_sets * 4);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Kernel-level hooks of the five-launch decode layer and the ego decoder's attention (gemv.hip).  Operands of type T by precision code prec
+// (0 fp32, 1 bf16 bits, 2 fp16 bits); activations, biases and LayerNorm weights fp32.  Outputs carry guard bands (GuardedBuf).
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// launch_gemv in output mode `mode` (GEMV_OUT_F32 / _GELU / _QKV) with rows_per_block rpb (0: row loop, 1, 2) on W [N][K]; ln_w nullable.
+//   x: xoff < 0: the rows [M][K]; xoff >= 0: [xoff + M][K], the input rows addressed through the device-side offset d_xoff (= xoff rows)
+//   out [M][ldo]: returned whole; NaN at the launch, the kernel writes columns < N (QKV: < E)
+//   cache (QKV only) [M][2][H][Lmax][48] of T, in / out: the kernel may change row pos of every (scene, K / V, head) only
+int umgen_dbg_gemv_modes(int prec, int mode, int rpb, const float* x, int xoff, const float* ln_w, const void* W, const float* bias, int M, int N,
+                         int K, int E, float* out, long ldo, void* cache, int Lmax, int pos) {
+    if (prec < 0 || prec > 2 || mode < GEMV_OUT_F32 || mode > GEMV_OUT_QKV || rpb < 0 || rpb > 2) return UMGEN_E_INVALID;
+    if (M < 1 || N < 1 || K < 8 || K % 8 || K > 1536 || !x || !W || !out) return UMGEN_E_INVALID;
+    const bool qkv = mode == GEMV_OUT_QKV;
+    if (ldo < (qkv ? E : N)) return UMGEN_E_INVALID;
+    if (qkv && (E < kHeadDim || E % kHeadDim || N != 3 * E || !cache || Lmax < 1 || pos < 0 || pos >= Lmax)) return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, rows = (size_t)M + std::max(xoff, 0);
+    const size_t cstride = qkv ? (size_t)2 * (E / kHeadDim) * Lmax * kHeadDim : 0, csz = (size_t)M * cstride * es, osz = (size_t)M * ldo * 4;
+    DevBuf dX(rows * K * 4), dL((size_t)K * 4), dW((size_t)N * K * es), dB((size_t)N * 4), dOff(4), dlen(4);
+    GuardedBuf dO(osz, scene_band((size_t)ldo * 4, M)), dC(csz, scene_band(cstride * es, M));
+    if (!dX.p || !dL.p || !dW.p || !dB.p || !dOff.p || !dlen.p || !dO.p || !dC.p) return UMGEN_E_NOMEM;
+    if (up(dX.p, x, rows * K * 4) || up(dW.p, W, (size_t)N * K * es) || up(dOff.p, &xoff, 4) || up(dlen.p, &pos, 4)) return UMGEN_E_HIP;
+    if ((ln_w && up(dL.p, ln_w, (size_t)K * 4)) || (bias && up(dB.p, bias, (size_t)N * 4)) || (csz && up(dC.p, cache, csz))) return UMGEN_E_HIP;
+    if (hipMemsetD32((hipDeviceptr_t)dO.p, (int)kNaN32, osz / 4) != hipSuccess) return UMGEN_E_HIP;
+    GemvArgs a{};
+    a.x = (const float*)dX.p; a.ldx = K;
+    if (xoff >= 0) { a.d_xoff = (const int*)dOff.p; a.xoff_mul = K; }
+    a.ln_w = ln_w ? (const float*)dL.p : nullptr; a.W = dW.p; a.bias = bias ? (const float*)dB.p : nullptr; a.N = N; a.K = K; a.M = M;
+    a.out_mode = mode; a.out = (float*)dO.p; a.ldo = ldo; a.cache = csz ? dC.p : nullptr; a.scene_stride = (long)cstride;
+    a.d_len = qkv ? (const int*)dlen.p : nullptr; a.Lmax = Lmax; a.E = qkv ? E : K; a.rows_per_block = rpb;
+    by_prec(prec, [&](auto t) { launch_gemv<decltype(t)>(nullptr, a); });
+    if (int rc = finish()) return rc;
+    if (!dO.intact() || !dC.intact()) return UMGEN_E_STATE;
+    if (down(out, dO.p, osz)) return UMGEN_E_HIP;
+    return csz ? down(cache, dC.p, csz) : UMGEN_OK;
+}
+
+// The plain form of launch_gemv_resid (MLP down-projection): x [M][N] (in / out) += a[:, :K] . W[N][K]^T + bias, a [M][lda]; rpb as above.
+int umgen_dbg_gemv_resid(int prec, int rpb, const float* a_in, long lda, const void* W, const float* bias, int M, int N, int K, float* x) {
+    if (prec < 0 || prec > 2 || rpb < 0 || rpb > 2 || M < 1 || N < 1 || K < 8 || K % 8 || K > 12 * 512 || lda < K || lda % 4 || !a_in || !W || !x)
+        return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, xsz = (size_t)M * N * 4;
+    DevBuf dA((size_t)M * lda * 4), dW((size_t)N * K * es), dB((size_t)N * 4);
+    GuardedBuf dX(xsz, scene_band((size_t)N * 4, M));
+    if (!dA.p || !dW.p || !dB.p || !dX.p) return UMGEN_E_NOMEM;
+    if (up(dA.p, a_in, (size_t)M * lda * 4) || up(dW.p, W, (size_t)N * K * es) || up(dX.p, x, xsz) || (bias && up(dB.p, bias, (size_t)N * 4)))
+        return UMGEN_E_HIP;
+    GemvResidArgs r{};
+    r.rows_per_block = rpb; r.a = (const float*)dA.p; r.lda = lda; r.H = 1; r.ns = 1; r.W = dW.p; r.bias = bias ? (const float*)dB.p : nullptr;
+    r.N = N; r.K = K; r.M = M; r.x = (float*)dX.p; r.ldx = N;
+    by_prec(prec, [&](auto t) { launch_gemv_resid<decltype(t)>(nullptr, r); });
+    if (int rc = finish()) return rc;
+    if (!dX.intact()) return UMGEN_E_STATE;
+    return down(x, dX.p, xsz);
+}
+
+// One attention site -- launch_attn_partial with the product's geometry -- and its projection with the split merge (launch_gemv_resid,
+// part != nullptr, rows_per_block rpb): x [M][E] (in / out) += merge(partials) . Wo[E][E]^T + bo.  E = H * 48.  geom:
+//   0  decode step (launch_decode_layer): M = B; q [B][E]; kv = cache [B][2][H][Lmax][48] of T, keys 0 .. pos (*d_len = pos); ns splits
+//   1  ego self-attention (launch_ego_self_attn): M = 3B; q = the packed q|k|v rows qkv3 [3B][3E] (fp32 in every mode); kv unused
+//   2  ego cross-attention (launch_ego_cross_attn): M = 3B; q [3B][E]; kv [B * kSeq][2E] of T
+// The partials start as finite garbage (the product's buffer keeps the values of earlier launches): slots >= ns must weigh 0.
+int umgen_dbg_attn_partial(int prec, int geom, int rpb, const float* q, const void* kv, int B, int H, int Lmax, int pos, int ns, const void* Wo,
+                           const float* bo, float* x) {
+    if (prec < 0 || prec > 2 || geom < 0 || geom > 2 || rpb < 0 || rpb > 2 || B < 1 || H < 1 || H > 32 || !q || !Wo || !x) return UMGEN_E_INVALID;
+    if (geom != 1 && !kv) return UMGEN_E_INVALID;
+    if (geom == 0 && (Lmax < kAttnSplit * kAttnChunk || pos < 0 || pos >= kAttnSplit * kAttnChunk || ns < attn_nsplit(pos + 1) || ns > kAttnSplit))
+        return UMGEN_E_INVALID;                    // the loads are clamped to kAttnSplit * kAttnChunk rows per (scene, head)
+    const int E = H * kHeadDim, M = geom == 0 ? B : 3 * B;
+    const size_t es = prec ? 2 : 4, xsz = (size_t)M * E * 4, psz = (size_t)M * H * kAttnRec;
+    const size_t qsz = (size_t)M * (geom == 1 ? 3 : 1) * E * 4;
+    const size_t kvsz = geom == 0 ? (size_t)B * 2 * H * Lmax * kHeadDim * es : (geom == 2 ? (size_t)B * kSeq * 2 * E * es : 0);
+    DevBuf dQin(qsz), dQ((size_t)M * E * 4), dKV(kvsz), dP(psz * 4), dW((size_t)E * E * es), dB((size_t)E * 4), dlen(4);
+    GuardedBuf dX(xsz, scene_band((size_t)E * 4, M));
+    if (!dQin.p || !dQ.p || !dKV.p || !dP.p || !dW.p || !dB.p || !dlen.p || !dX.p) return UMGEN_E_NOMEM;
+    if (up(dQin.p, q, qsz) || (kvsz && up(dKV.p, kv, kvsz)) || up(dW.p, Wo, (size_t)E * E * es) || up(dX.p, x, xsz) || up(dlen.p, &pos, 4))
+        return UMGEN_E_HIP;
+    if ((bo && up(dB.p, bo, (size_t)E * 4)) || hipMemsetD32((hipDeviceptr_t)dP.p, (int)__builtin_bit_cast(unsigned, kStalePartial), psz) != hipSuccess)
+        return UMGEN_E_HIP;
+    const float* dq = (const float*)dQin.p;
+    int nsplit = ns;
+    by_prec(prec, [&](auto t) {
+        typedef decltype(t) T;
+        if (geom == 0) {
+            launch_attn_partial<T>(nullptr, dq, (const T*)dKV.p, (long)2 * H * Lmax * kHeadDim, (long)Lmax * kHeadDim, kHeadDim,
+                                   (long)H * Lmax * kHeadDim, B, 1, H, (const int*)dlen.p, 1, ns, (float*)dP.p);
+        } else if (geom == 1) {                    // run_ego: the q rows gathered out of the packed q|k|v rows first
+            (void)hipMemcpy2DAsync(dQ.p, (size_t)E * 4, dQin.p, (size_t)3 * E * 4, (size_t)E * 4, M, hipMemcpyDeviceToDevice, nullptr);
+            launch_ego_self_attn(nullptr, (const float*)dQ.p, dq, M, H, (float*)dP.p);
+            nsplit = 1;
+        } else {
+            launch_ego_cross_attn<T>(nullptr, dq, (const T*)dKV.p, M, H, (float*)dP.p);
+            nsplit = ego_cross_nsplit();
+        }
+        GemvResidArgs r{};
+        r.rows_per_block = rpb; r.part = (const float*)dP.p; r.H = H; r.ns = nsplit; r.W = dW.p; r.bias = bo ? (const float*)dB.p : nullptr;
+        r.N = E; r.K = E; r.M = M; r.x = (float*)dX.p; r.ldx = E;
+        launch_gemv_resid<T>(nullptr, r);
+    });
+    if (int rc = finish()) return rc;
+    if (!dX.intact()) return UMGEN_E_STATE;
+    return down(x, dX.p, xsz);
+}
+
+// One whole BlockOAR layer of the decode step through launch_decode_layer (what oar_layers launches per layer) for B scenes at position pos:
+// x [B][E] (in / out), q [B][E] (out: the q rows), cache [B][2][H][kAttnSplit * kAttnChunk][48] of T (in / out; the layer writes row pos).
+// Weights Wqkv [3E][E], Wo [E][E], Wfc [4E][E], Wproj [E][4E] of T; bqkv [3E], bo [E], ln_a, ln_b [E].
+int umgen_dbg_decode_layer(int prec, int rpb, int B, int E, int pos, int ns, const float* ln_a, const void* Wqkv, const float* bqkv, const void* Wo,
+                           const float* bo, const float* ln_b, const void* Wfc, const void* Wproj, float* x, float* q, void* cache) {
+    const int Lmax = kAttnSplit * kAttnChunk, H = E / kHeadDim;
+    if (prec < 0 || prec > 2 || rpb < 0 || rpb > 2 || B < 1 || E < kHeadDim || E % kHeadDim || E > 1536 || pos < 0 || pos >= Lmax) return UMGEN_E_INVALID;
+    if (ns < attn_nsplit(pos + 1) || ns > kAttnSplit || !ln_a || !Wqkv || !bqkv || !Wo || !bo || !ln_b || !Wfc || !Wproj || !x || !q || !cache)
+        return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, EE = (size_t)E * E, xsz = (size_t)B * E * 4, cstride = (size_t)2 * H * Lmax * kHeadDim, csz = B * cstride * es;
+    const size_t psz = (size_t)B * H * kAttnRec;
+    DevBuf dLa((size_t)E * 4), dLb((size_t)E * 4), dWqkv(3 * EE * es), dbqkv((size_t)3 * E * 4), dWo(EE * es), dbo((size_t)E * 4), dWfc(4 * EE * es),
+        dWproj(4 * EE * es), dH((size_t)B * 4 * E * 4), dP(psz * 4), dlen(4);
+    GuardedBuf dX(xsz, scene_band((size_t)E * 4, B)), dQ(xsz, scene_band((size_t)E * 4, B)), dC(csz, scene_band(cstride * es, B));
+    if (!dLa.p || !dLb.p || !dWqkv.p || !dbqkv.p || !dWo.p || !dbo.p || !dWfc.p || !dWproj.p || !dH.p || !dP.p || !dlen.p || !dX.p || !dQ.p || !dC.p)
+        return UMGEN_E_NOMEM;
+    if (up(dLa.p, ln_a, (size_t)E * 4) || up(dLb.p, ln_b, (size_t)E * 4) || up(dWqkv.p, Wqkv, 3 * EE * es) || up(dbqkv.p, bqkv, (size_t)3 * E * 4) ||
+        up(dWo.p, Wo, EE * es) || up(dbo.p, bo, (size_t)E * 4) || up(dWfc.p, Wfc, 4 * EE * es) || up(dWproj.p, Wproj, 4 * EE * es) || up(dX.p, x, xsz) ||
+        up(dC.p, cache, csz) || up(dlen.p, &pos, 4))
+        return UMGEN_E_HIP;
+    if (hipMemsetD32((hipDeviceptr_t)dQ.p, (int)kNaN32, xsz / 4) != hipSuccess ||
+        hipMemsetD32((hipDeviceptr_t)dP.p, (int)__builtin_bit_cast(unsigned, kStalePartial), psz) != hipSuccess)
+        return UMGEN_E_HIP;
+    DecodeLayerArgs d{};
+    d.ln_a = (const float*)dLa.p; d.Wqkv = dWqkv.p; d.bqkv = (const float*)dbqkv.p; d.Wo = dWo.p; d.bo = (const float*)dbo.p; d.ln_b = (const float*)dLb.p;
+    d.Wfc = dWfc.p; d.Wproj = dWproj.p; d.x = (float*)dX.p; d.q = (float*)dQ.p; d.h = (float*)dH.p; d.part = (float*)dP.p;
+    d.cache = dC.p; d.scene_stride = (long)cstride; d.Lmax = Lmax; d.d_len = (const int*)dlen.p; d.B = B; d.E = E; d.H = H; d.ns = ns; d.rows_per_block = rpb;
+    by_prec(prec, [&](auto t) { launch_decode_layer<decltype(t)>(nullptr, d); });
+    if (int rc = finish()) return rc;
+    if (!dX.intact() || !dQ.intact() || !dC.intact()) return UMGEN_E_STATE;
+    if (down(x, dX.p, xsz) || down(q, dQ.p, xsz)) return UMGEN_E_HIP;
+    return down(cache, dC.p, csz);
 }
 
 }  // extern "C"

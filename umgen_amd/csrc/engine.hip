@@ -534,14 +534,14 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
         gemv<T>(e, x, E, d.ln1, d.self.Wqkv, d.self.bqkv, 3 * E, E, M, GEMV_OUT_F32, e->qkv3, 3L * E);
         // self-attention among the 3 ego queries of a scene (non-causal); q rows gathered out of the packed q|k|v rows
         hipMemcpy2DAsync(e->qdec, (size_t)E * 4, e->qkv3, (size_t)3 * E * 4, (size_t)E * 4, M, hipMemcpyDeviceToDevice, e->stream);
-        launch_attn_partial<float>(e->stream, e->qdec, e->qkv3 + E, 3L * 3 * E, kHeadDim, 3L * E, E, M, 3, H, nullptr, 3, 1, e->part);
+        launch_ego_self_attn(e->stream, e->qdec, e->qkv3, M, H, e->part);
         gemv_resid<T>(e, nullptr, 0, e->part, d.self.Wo, d.self.bo, E, E, M, x, E, 1);
         // cross attention to the frame's 2207 scene tokens (FlashCrossAttention.forward, module.py:482-509)
         gemv<T>(e, x, E, d.ln2, d.Wq, d.bq, E, E, M, GEMV_OUT_F32, e->qdec, E);
         launch_layernorm<T>(e->stream, e->pego, E, (long)B * kSeq, E, d.ln3, PN);
         linear_store<T>(e, d.Wkv, d.bkv, 2 * E, E, PN, (long)B * kSeq, KV, 2L * E, 0);
-        launch_attn_partial<T>(e->stream, e->qdec, KV, (long)kSeq * 2 * E, kHeadDim, 2L * E, E, M, 3, H, nullptr, kSeq, attn_nsplit(kSeq), e->part);
-        gemv_resid<T>(e, nullptr, 0, e->part, d.Wco, d.bco, E, E, M, x, E, attn_nsplit(kSeq));
+        launch_ego_cross_attn<T>(e->stream, e->qdec, KV, M, H, e->part);
+        gemv_resid<T>(e, nullptr, 0, e->part, d.Wco, d.bco, E, E, M, x, E, ego_cross_nsplit());
         gemv<T>(e, x, E, d.ln4, d.mlp.Wfc, nullptr, 4 * E, E, M, GEMV_OUT_GELU, e->hdec, 4L * E);
         gemv_resid<T>(e, e->hdec, 4L * E, nullptr, d.mlp.Wproj, nullptr, E, 4 * E, M, x, E);
     }
@@ -637,19 +637,12 @@ int oar_layers(umgen_engine* e, int B, int ns) {
     }
     for (size_t li = 0; li < e->oar.size(); ++li) {
         const SubW& w = e->oar[e->dbg_same_layer ? 0 : li];
-        T* cache = reinterpret_cast<T*>(e->kvcache) + (long)li * e->kv_layer_stride;
-        {
-            GemvArgs a{};
-            a.x = e->xdec; a.ldx = E; a.ln_w = w.ln_a; a.W = w.attn.Wqkv; a.bias = w.attn.bqkv; a.N = 3 * E; a.K = E; a.M = B;
-            a.out_mode = GEMV_OUT_QKV; a.out = e->qdec; a.ldo = E; a.cache = cache; a.scene_stride = e->kv_scene_stride; a.d_len = d_len;
-            a.Lmax = e->Lmax; a.E = E; a.rows_per_block = rows_per_block_for(e, B);
-            launch_gemv<T>(e->stream, a);
-            launch_attn_partial<T>(e->stream, e->qdec, cache, e->kv_scene_stride, (long)e->Lmax * kHeadDim, kHeadDim,
-                                   (long)H * e->Lmax * kHeadDim, B, 1, H, d_len, 1, ns, e->part);
-            gemv_resid<T>(e, nullptr, 0, e->part, w.attn.Wo, w.attn.bo, E, E, B, e->xdec, E, ns);
-        }
-        gemv<T>(e, e->xdec, E, w.ln_b, w.mlp.Wfc, nullptr, 4 * E, E, B, GEMV_OUT_GELU, e->hdec, 4L * E);
-        gemv_resid<T>(e, e->hdec, 4L * E, nullptr, w.mlp.Wproj, nullptr, E, 4 * E, B, e->xdec, E);
+        DecodeLayerArgs d{};
+        d.ln_a = w.ln_a; d.Wqkv = w.attn.Wqkv; d.bqkv = w.attn.bqkv; d.Wo = w.attn.Wo; d.bo = w.attn.bo; d.ln_b = w.ln_b; d.Wfc = w.mlp.Wfc;
+        d.Wproj = w.mlp.Wproj; d.x = e->xdec; d.q = e->qdec; d.h = e->hdec; d.part = e->part;
+        d.cache = reinterpret_cast<T*>(e->kvcache) + (long)li * e->kv_layer_stride; d.scene_stride = e->kv_scene_stride; d.Lmax = e->Lmax;
+        d.d_len = d_len; d.B = B; d.E = E; d.H = H; d.ns = ns; d.rows_per_block = rows_per_block_for(e, B);
+        launch_decode_layer<T>(e->stream, d);
     }
     return 0;
 }

@@ -564,4 +564,31 @@ template void launch_attn_partial<float>(hipStream_t, const float*, const float*
 template void launch_attn_partial<bf16_t>(hipStream_t, const float*, const bf16_t*, long, long, long, long, int, int, int, const int*, int, int, float*);
 template void launch_attn_partial<f16_t>(hipStream_t, const float*, const f16_t*, long, long, long, long, int, int, int, const int*, int, int, float*);
 
+template <typename T>
+void launch_decode_layer(hipStream_t s, const DecodeLayerArgs& d) {
+    const int E = d.E, H = d.H;
+    GemvArgs a{};
+    a.x = d.x; a.ldx = E; a.ln_w = d.ln_a; a.W = d.Wqkv; a.bias = d.bqkv; a.N = 3 * E; a.K = E; a.M = d.B;
+    a.out_mode = GEMV_OUT_QKV; a.out = d.q; a.ldo = E; a.cache = d.cache; a.scene_stride = d.scene_stride; a.d_len = d.d_len;
+    a.Lmax = d.Lmax; a.E = E; a.rows_per_block = d.rows_per_block;
+    launch_gemv<T>(s, a);
+    launch_attn_partial<T>(s, d.q, static_cast<const T*>(d.cache), d.scene_stride, (long)d.Lmax * kHeadDim, kHeadDim, (long)H * d.Lmax * kHeadDim,
+                           d.B, 1, H, d.d_len, 1, d.ns, d.part);
+    GemvResidArgs p{};
+    p.rows_per_block = d.rows_per_block; p.part = d.part; p.H = H; p.ns = d.ns; p.W = d.Wo; p.bias = d.bo; p.N = E; p.K = E; p.M = d.B;
+    p.x = d.x; p.ldx = E;
+    launch_gemv_resid<T>(s, p);
+    GemvArgs f{};
+    f.rows_per_block = d.rows_per_block; f.x = d.x; f.ldx = E; f.ln_w = d.ln_b; f.W = d.Wfc; f.N = 4 * E; f.K = E; f.M = d.B;
+    f.out_mode = GEMV_OUT_GELU; f.out = d.h; f.ldo = 4L * E; f.E = E;
+    launch_gemv<T>(s, f);
+    GemvResidArgs r{};
+    r.rows_per_block = d.rows_per_block; r.a = d.h; r.lda = 4L * E; r.H = H; r.ns = 1; r.W = d.Wproj; r.N = E; r.K = 4 * E; r.M = d.B;
+    r.x = d.x; r.ldx = E;
+    launch_gemv_resid<T>(s, r);
+}
+template void launch_decode_layer<float>(hipStream_t, const DecodeLayerArgs&);
+template void launch_decode_layer<bf16_t>(hipStream_t, const DecodeLayerArgs&);
+template void launch_decode_layer<f16_t>(hipStream_t, const DecodeLayerArgs&);
+
 }  // namespace umgen

@@ -112,6 +112,33 @@ struct GemvResidArgs {
 };
 template <typename T> void launch_gemv_resid(hipStream_t s, const GemvResidArgs& a);
 
+// One BlockOAR layer of the decode step as five launches (gemv.hip): LN + q|k|v (K/V rows into the head-major cache at *d_len),
+// attention partials over keys 0 .. *d_len, c_proj with the split merge (+x), LN + c_fc + GELU, mlp c_proj (+x).  oar_layers
+// (engine.hip) and the test hook umgen_dbg_decode_layer both launch through it.
+struct DecodeLayerArgs {
+    const float *ln_a, *bqkv, *bo, *ln_b;
+    const void *Wqkv, *Wo, *Wfc, *Wproj;
+    float* x;                          // [B][E] residual stream (in / out)
+    float *q, *h, *part;               // scratch: q rows [B][E], gelu(c_fc) [B][4E], attention partials [B][H][kAttnRec]
+    void* cache; long scene_stride; int Lmax; const int* d_len;   // [B][2][H][Lmax][48] of T (Lmax >= kAttnSplit * kAttnChunk)
+    int B, E, H, ns, rows_per_block;
+};
+template <typename T> void launch_decode_layer(hipStream_t s, const DecodeLayerArgs& a);
+
+// The ego decoder's two attentions (engine.hip run_ego, shared with the test hook umgen_dbg_attn_partial): 3 queries q [3B][E] per scene
+//   self:  over the scene's own 3 packed q|k|v rows qkv3 [3B][3E] (fp32 in every precision mode), one split
+//   cross: over the scene's kSeq k|v rows kv [B * kSeq][2E] of T, attn_nsplit(kSeq) splits
+inline int ego_cross_nsplit() { return attn_nsplit(kSeq); }
+inline void launch_ego_self_attn(hipStream_t s, const float* q, const float* qkv3, int M, int H, float* part) {
+    const int E = H * kHeadDim;
+    launch_attn_partial<float>(s, q, qkv3 + E, 3L * 3 * E, kHeadDim, 3L * E, E, M, 3, H, nullptr, 3, 1, part);
+}
+template <typename T>
+void launch_ego_cross_attn(hipStream_t s, const float* q, const T* kv, int M, int H, float* part) {
+    const int E = H * kHeadDim;
+    launch_attn_partial<T>(s, q, kv, (long)kSeq * 2 * E, kHeadDim, 2L * E, E, M, 3, H, nullptr, kSeq, ego_cross_nsplit(), part);
+}
+
 // ------------------------------------------------------------------------------------------------
 // batched decode layer for many scenes per GPU (decode_batched.hip): the scenes are the B-columns of the matrix-core instruction
 // ------------------------------------------------------------------------------------------------
