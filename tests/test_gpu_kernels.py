@@ -202,6 +202,32 @@ def test_attn_spatial_fp32_matrix_core_kernel(F, S, H):
         np.testing.assert_allclose(y, ref, atol=2e-5, rtol=0, err_msg=f"flag {flag}")
 
 
+# 1030 and 1692 are the prefixes the product passes (a given map, a given map + boxes)
+@pytest.mark.parametrize("S", [1, 2, 5, 127, 128, 129, 257, 1030, 1692])
+@pytest.mark.parametrize("H", [2, 16])
+@pytest.mark.parametrize("F", [1, 3])
+@pytest.mark.parametrize("bf16", PREC)
+def test_attn_causal(bf16, F, S, H):
+    """The causal S x S attention of the OAR prefix pass (launch_attn_causal_mfma<T> / launch_attn_causal_f32, hook flag 64) with the bars of
+    test_attn_spatial / test_attn_spatial_fp32_matrix_core_kernel (the same arithmetic on fewer keys).  Query 0 sees one key: its output is
+    v[0] up to the output type's rounding."""
+    E = H * 48
+    rng = np.random.default_rng(S + H + F)
+    q = rng.standard_normal((F, S, E), dtype=np.float32) * 1.5
+    k = rng.standard_normal((F, S, E), dtype=np.float32) * 1.5
+    v = rng.standard_normal((F, S, E), dtype=np.float32)
+    if bf16:
+        q, k, v = round16(q, bf16), round16(k, bf16), round16(v, bf16)
+    qk = np.ascontiguousarray(np.concatenate([q, k], axis=-1))
+    y = np.zeros((F, S, E), dtype=np.uint16 if bf16 else np.float32)       # (the hook's device buffer starts as NaN: an unwritten row stays NaN)
+    check(lib().umgen_dbg_attn_spatial(bf16 | 64, vp(bits16(qk, bf16) if bf16 else qk), vp(bits16(v, bf16) if bf16 else v), F, S, H, vp(y)))
+    got = from_bits16(y, bf16) if bf16 else y
+    ref = np.concatenate([ref_attention(q[f:f + 1], k[f:f + 1], v[f:f + 1], H, True) for f in range(F)])   # per frame: H * S * S doubles at a time
+    np.testing.assert_allclose(got, ref, atol=(2e-2 * EPS16[bf16] if bf16 else 2e-5), rtol=0)
+    ulp = np.abs(v[:, 0]) * 2.0 ** -(23 if not bf16 else (7 if bf16 == 1 else 10))     # one unit in the last place of the output type (at most)
+    assert np.all(np.abs(got[:, 0] - v[:, 0]) <= ulp), "query 0 (one key) is not v[0] up to the output rounding"
+
+
 @pytest.mark.parametrize("B,T,S,H", [(1, 20, 333, 16), (2, 3, 100, 2), (1, 40, 77, 4), (1, 64, 31, 2)])
 @pytest.mark.parametrize("bf16", PREC)
 def test_attn_temporal(bf16, B, T, S, H):

@@ -21,7 +21,9 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
            "umgen_dbg_linear", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_oar_step", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
            "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
-           "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer"]
+           "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer",
+           "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
+           "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego"]
 
 HEADERS = ("common.h", "kernels.h", "frame.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h")
 
@@ -59,6 +61,30 @@ class Trace(C.Structure):
                 ("forced_bbox3d", C.POINTER(C.c_int64)), ("forced_image", C.POINTER(C.c_int64)),
                 ("counters", C.POINTER(C.c_int32)),
                 ("given_map", C.POINTER(C.c_int64)), ("given_bbox3d", C.POINTER(C.c_int64))]
+
+
+class DbgTables(C.Structure):
+    """umgen_dbg_tables (csrc/debug_api.hip): the embedding tables of a kernel-level hook as host arrays, with their row counts"""
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in ("egoe", "axe", "be", "tpe", "spe", "gmap", "gimg")] + \
+        [(n, C.POINTER(C.c_uint16)) for n in ("fouier_pe", "posi", "grid_posi")] + \
+        [(n, C.c_int32) for n in ("E", "n_tpe", "n_pose", "n_map", "n_box", "n_img", "n_posi")]
+
+
+class DbgSamplerParams(C.Structure):
+    """SamplerParams (csrc/frame.h)"""
+    _fields_ = [("method", C.c_int32), ("top_k", C.c_int32), ("top_k_map", C.c_int32), ("topk_image", C.c_int32),
+                ("p", C.c_float), ("p_map", C.c_float), ("temperature", C.c_float),
+                ("rule_constrain", C.c_int32), ("merge_ar_tar", C.c_int32), ("only_ar", C.c_int32)]
+
+
+class DbgSteps(C.Structure):
+    """umgen_dbg_steps (csrc/debug_api.hip): inputs and outputs of umgen_dbg_token_steps"""
+    _fields_ = [("cond", C.POINTER(C.c_float)), ("logits", C.POINTER(C.c_float)), ("logits_tar", C.POINTER(C.c_float)),
+                ("prev_box", C.POINTER(C.c_int32)), ("control_slot", C.POINTER(C.c_ubyte)), ("forced", C.POINTER(C.c_int32)),
+                ("seeds", C.POINTER(C.c_uint64)), ("tokens", C.POINTER(C.c_int32)), ("x_next", C.POINTER(C.c_float)),
+                ("counters", C.POINTER(C.c_int32)), ("n_boxes", C.POINTER(C.c_int32)), ("boxes", C.POINTER(C.c_double)),
+                ("state_log", C.POINTER(C.c_uint32)), ("sp", DbgSamplerParams)] + \
+        [(n, C.c_int32) for n in ("B", "j0", "j1", "given_end", "ld_logits", "use_forced", "use_control", "frame_idx")] + [("epoch0", C.c_uint32)]
 
 
 class Timings(C.Structure):
@@ -249,6 +275,16 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_gemv_resid.argtypes = [i32, i32, fp, C.c_long, vp, fp, i32, i32, i32, fp]
     lib.umgen_dbg_attn_partial.argtypes = [i32, i32, i32, fp, vp, i32, i32, i32, i32, i32, vp, fp, fp]
     lib.umgen_dbg_decode_layer.argtypes = [i32, i32, i32, i32, i32, i32, fp, vp, fp, vp, fp, fp, vp, vp, fp, fp, vp]
+    tp = C.POINTER(DbgTables)
+    lib.umgen_dbg_embed_warp.argtypes = [i32, tp, i32p, i32p, i32p, i32p, i32, i32, i32, i32, fp, i32, fp, fp, fp]
+    lib.umgen_dbg_layernorm.argtypes = [i32, fp, C.c_long, C.c_long, i32, fp, vp, C.c_long]
+    lib.umgen_dbg_cond_rows.argtypes = [i32, i32, i32, i32, fp, fp, fp, fp]
+    lib.umgen_dbg_first_input.argtypes = [i32, i32, fp, fp, fp]
+    lib.umgen_dbg_ego_queries.argtypes = [tp, i32, i32, fp]
+    lib.umgen_dbg_prefix_rows.argtypes = [tp, fp, fp, i32p, i32, i32, fp, fp]
+    lib.umgen_dbg_prefix_kv_to_cache.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.umgen_dbg_token_steps.argtypes = [tp, C.POINTER(DbgSteps)]
+    lib.umgen_dbg_sample_ego.argtypes = [fp, i32, C.POINTER(DbgSamplerParams), C.POINTER(C.c_uint64), i32, i32p, i32, i32p]
     lib.umgen_vq_create.argtypes = [C.POINTER(VQConfig), C.POINTER(vp)]
     lib.umgen_vq_load_tensor.argtypes = [vp, C.c_char_p, fp, i64p, i32]
     lib.umgen_vq_finalize.argtypes = [vp]

@@ -116,7 +116,7 @@ int umgen_dbg_linear_vt(int flags, const void* act, const void* W, const float* 
 }
 
 // spatial attention on q|k rows [F*S][2E] and v rows [F*S][E] (both row-major on the host; V is transposed on the device
-// through the same GEMM_VT-layout the engine uses).  y [F*S][E].
+// through the same GEMM_VT-layout the engine uses).  y [F*S][E].  flag 64: causal (query i sees keys 0 .. i), else every key.
 int umgen_dbg_attn_spatial(int flags, const void* qk, const void* v, int F, int S, int H, void* y) {
     const int bf16 = flags & 3;                 // precision code; flag 32 (fp32 only): the VALU kernel instead of the matrix-core one
     const int E = H * kHeadDim, S_pad = ((S + 63) / 64) * 64;
@@ -129,14 +129,24 @@ int umgen_dbg_attn_spatial(int flags, const void* qk, const void* v, int F, int 
         for (int s = 0; s < S; ++s)
             for (int c = 0; c < E; ++c)
                 memcpy(&vt[(((size_t)f * E + c) * S_pad + s) * es], &vs[(((size_t)f * S + s) * E + c) * es], es);
-    DevBuf dQK(R * 2 * E * es), dVT(vt.size()), dY(R * E * es);
+    if ((flags & 64) && (flags & 32)) return UMGEN_E_UNSUPPORTED;   // the causal launchers have no kernel choice
+    DevBuf dQK(R * 2 * E * es), dVT(vt.size());
+    GuardedBuf dY(R * E * es);                  // NaN at the launch: a row the kernel leaves out comes back as NaN
     if (!dQK.p || !dVT.p || !dY.p) return UMGEN_E_NOMEM;
     if (up(dQK.p, qk, R * 2 * E * es) || up(dVT.p, vt.data(), vt.size())) return UMGEN_E_HIP;
-    if (bf16 == 2) launch_attn_spatial_mfma<f16_t>(nullptr, (const f16_t*)dQK.p, (const f16_t*)dVT.p, (f16_t*)dY.p, F, S, S_pad, H);
+    if (bf16 ? hipMemsetD16((hipDeviceptr_t)dY.p, nan16(bf16), R * E) != hipSuccess : hipMemsetD32((hipDeviceptr_t)dY.p, (int)kNaN32, R * E) != hipSuccess)
+        return UMGEN_E_HIP;
+    if (flags & 64) {                           // flag 64: the causal S x S form of the OAR prefix pass (run_prefix_prefill)
+        if (bf16 == 2) launch_attn_causal_mfma<f16_t>(nullptr, (const f16_t*)dQK.p, (const f16_t*)dVT.p, (f16_t*)dY.p, F, S, S_pad, H);
+        else if (bf16) launch_attn_causal_mfma<bf16_t>(nullptr, (const bf16_t*)dQK.p, (const bf16_t*)dVT.p, (bf16_t*)dY.p, F, S, S_pad, H);
+        else launch_attn_causal_f32(nullptr, (const float*)dQK.p, (const float*)dVT.p, (float*)dY.p, F, S, S_pad, H);
+    }
+    else if (bf16 == 2) launch_attn_spatial_mfma<f16_t>(nullptr, (const f16_t*)dQK.p, (const f16_t*)dVT.p, (f16_t*)dY.p, F, S, S_pad, H);
     else if (bf16) launch_attn_spatial_mfma<bf16_t>(nullptr, (const bf16_t*)dQK.p, (const bf16_t*)dVT.p, (bf16_t*)dY.p, F, S, S_pad, H);
     else if (flags & 32) launch_attn_spatial_valu<float>(nullptr, (const float*)dQK.p, (const float*)dVT.p, (float*)dY.p, F, S, S_pad, H);   // flag 32: the VALU kernel
     else launch_attn_spatial_f32_mfma(nullptr, (const float*)dQK.p, (const float*)dVT.p, (float*)dY.p, F, S, S_pad, H);
-    if (hipDeviceSynchronize() != hipSuccess) return UMGEN_E_HIP;
+    if (int rc = finish()) return rc;
+    if (!dY.intact()) return UMGEN_E_STATE;
     return down(y, dY.p, R * E * es);
 }
 
@@ -600,6 +610,310 @@ int umgen_dbg_decode_layer(int prec, int rpb, int B, int E, int pos, int ns, con
     if (!dX.intact() || !dQ.intact() || !dC.intact()) return UMGEN_E_STATE;
     if (down(x, dX.p, xsz) || down(q, dQ.p, xsz)) return UMGEN_E_HIP;
     return down(cache, dC.p, csz);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Kernel-level hooks of frame assembly (frame.hip, rowops.hip): token embedding + map warp, LayerNorm, conditioning rows, first input, ego
+// queries, the given-token prefix rows and their K/V move, the per-token step (fixed / sampled token with the bbox3d control flow) and the
+// ego sampler.  Each goes through the product's launcher.  Outputs start as NaN (or as the caller's buffer where they are in / out) and
+// carry guard bands; every token a launch may use as a table index is checked against the table's size on the host first.
+// ---------------------------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+// host image of EmbedTables: fp32 tables and raw bf16 bits, with their row counts (spe has kSeq rows, egoe 3, axe 8, grid_posi 1024)
+struct umgen_dbg_tables {
+    const float *egoe, *axe, *be, *tpe, *spe, *gmap, *gimg;
+    const uint16_t *fouier_pe, *posi, *grid_posi;
+    int32_t E, n_tpe, n_pose, n_map, n_box, n_img, n_posi;
+};
+
+// everything umgen_dbg_token_steps reads and writes (see there)
+struct umgen_dbg_steps {
+    const float *cond, *logits, *logits_tar;
+    const int32_t* prev_box;
+    const unsigned char* control_slot;
+    const int32_t* forced;
+    const uint64_t* seeds;
+    int32_t* tokens;
+    float* x_next;
+    int32_t *counters, *n_boxes;
+    double* boxes;
+    uint32_t* state_log;
+    SamplerParams sp;
+    int32_t B, j0, j1, given_end, ld_logits, use_forced, use_control, frame_idx;
+    uint32_t epoch0;
+};
+
+namespace {
+struct TablesDev {
+    std::vector<DevBuf*> bufs;
+    EmbedTables tb{};
+    bool ok = true;
+    const void* put(const void* h, size_t bytes) {
+        if (!h) return nullptr;
+        bufs.push_back(new DevBuf(bytes));
+        if (!bufs.back()->p || up(bufs.back()->p, h, bytes)) { ok = false; return nullptr; }
+        return bufs.back()->p;
+    }
+    explicit TablesDev(const umgen_dbg_tables& t) {
+        const size_t E = (size_t)t.E;
+        tb.E = t.E;
+        tb.egoe = (const float*)put(t.egoe, 3 * E * 4);
+        tb.axe = (const float*)put(t.axe, 8 * E * 4);
+        tb.be = (const float*)put(t.be, (size_t)t.n_box * E * 4);
+        tb.tpe = (const float*)put(t.tpe, (size_t)t.n_tpe * E * 4);
+        tb.spe = (const float*)put(t.spe, (size_t)kSeq * E * 4);
+        tb.gmap = (const float*)put(t.gmap, (size_t)t.n_map * E * 4);
+        tb.gimg = (const float*)put(t.gimg, (size_t)t.n_img * E * 4);
+        tb.fouier_pe = (const bf16_t*)put(t.fouier_pe, (size_t)t.n_pose * E * 2);
+        tb.posi = (const bf16_t*)put(t.posi, (size_t)t.n_posi * E * 2);
+        tb.grid_posi = (const bf16_t*)put(t.grid_posi, (size_t)kNMap * E * 2);
+    }
+    ~TablesDev() { for (DevBuf* b : bufs) delete b; }
+    TablesDev(const TablesDev&) = delete;
+};
+inline bool tables_sane(const umgen_dbg_tables* t) {
+    return t && t->E >= 1 && t->n_tpe >= 0 && t->n_pose >= 0 && t->n_map >= 0 && t->n_box >= 0 && t->n_img >= 0 && t->n_posi >= 0;
+}
+inline bool in_range(const int32_t* t, size_t n, int hi) {
+    for (size_t i = 0; i < n; ++i)
+        if (t[i] < 0 || t[i] >= hi) return false;
+    return true;
+}
+inline int fill_nan32(void* d, size_t n) { return hipMemsetD32((hipDeviceptr_t)d, (int)kNaN32, n) == hipSuccess ? 0 : UMGEN_E_HIP; }
+inline int kind_of_pos(int j, int given_end) {    // engine.hip umgen_frame: 0 fixed token, 1 map, 2 bbox3d, 3 image
+    if (j < given_end) return 0;
+    return (j >= kMapC0 && j < kMapEos) ? 1 : (j >= kBoxC0 && j < kBoxEos) ? 2 : (j >= kImgC0 && j < kImgEos) ? 3 : 0;
+}
+}  // namespace
+
+extern "C" {
+
+// run_stack's first two launches (engine.hip): launch_embed_stack, then for every stack but STACK_EGO launch_warp_map.  Token arrays
+// [B][Tf][3 | 1024 | 660 | 512] and pose_diff [B][Tf][3] with Tf = Tfull (0: T); the pass covers slots t0 .. t0 + T - 1.
+// -> X [B][T][stack_len][E], mapfeat [B][T][1024][E], warped_last [B][1024][E] (handed to the launcher only when want_last != 0).
+int umgen_dbg_embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B,
+                         int T, int Tfull, int t0, const float* pose_diff, int want_last, float* X, float* mapfeat, float* warped_last) {
+    if (stack < STACK_EGO || stack > STACK_TAR || !tables_sane(t) || B < 1 || T < 1 || Tfull < 0 || t0 < 0) return UMGEN_E_INVALID;
+    const int Tf = Tfull ? Tfull : T;
+    if (t0 + T > Tf || Tf > t->n_tpe || !pose || !map || !box || !img || !pose_diff || !X || !mapfeat || !warped_last) return UMGEN_E_INVALID;
+    if (!t->axe || !t->be || !t->tpe || !t->spe || !t->gmap || !t->gimg || !t->fouier_pe || !t->posi || !t->grid_posi) return UMGEN_E_INVALID;
+    const size_t F = (size_t)B * Tf, E = (size_t)t->E;
+    if (!in_range(pose, F * kNPose, t->n_pose) || !in_range(map, F * kNMap, t->n_map) || !in_range(box, F * kNBox, t->n_box) ||
+        !in_range(img, F * kNImg, t->n_img))
+        return UMGEN_E_INVALID;
+    for (size_t f = 0; f < F; ++f)
+        for (int sl = 0; sl < kSlots; ++sl)
+            if (box[f * kNBox + sl * kSlotLen] >= t->n_posi || box[f * kNBox + sl * kSlotLen + 1] >= t->n_posi) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * T * stack_len(stack) * E, mn = (size_t)B * T * kNMap * E, wn = (size_t)B * kNMap * E;
+    TablesDev td(*t);
+    DevBuf dP(F * kNPose * 4), dM(F * kNMap * 4), dB(F * kNBox * 4), dI(F * kNImg * 4), dPD(F * 3 * 4);
+    GuardedBuf dX(xn * 4), dMF(mn * 4), dWL(wn * 4);
+    if (!td.ok || !dP.p || !dM.p || !dB.p || !dI.p || !dPD.p || !dX.p || !dMF.p || !dWL.p) return UMGEN_E_NOMEM;
+    if (up(dP.p, pose, F * kNPose * 4) || up(dM.p, map, F * kNMap * 4) || up(dB.p, box, F * kNBox * 4) || up(dI.p, img, F * kNImg * 4) ||
+        up(dPD.p, pose_diff, F * 3 * 4) || fill_nan32(dX.p, xn) || fill_nan32(dMF.p, mn) || fill_nan32(dWL.p, wn))
+        return UMGEN_E_HIP;
+    WindowTokens w{};
+    w.pose = (const int*)dP.p; w.map = (const int*)dM.p; w.box = (const int*)dB.p; w.img = (const int*)dI.p; w.B = B; w.T = T; w.Tfull = Tfull; w.t0 = t0;
+    launch_embed_stack(nullptr, stack, td.tb, w, (float*)dX.p, (float*)dMF.p);
+    if (stack != STACK_EGO)
+        launch_warp_map(nullptr, stack, td.tb, B, T, (const float*)dMF.p, (const float*)dPD.p, (float*)dX.p, want_last ? (float*)dWL.p : nullptr, Tfull, t0);
+    if (int rc = finish()) return rc;
+    if (!dX.intact() || !dMF.intact() || !dWL.intact()) return UMGEN_E_STATE;
+    if (down(X, dX.p, xn * 4) || down(mapfeat, dMF.p, mn * 4)) return UMGEN_E_HIP;
+    return down(warped_last, dWL.p, wn * 4);
+}
+
+// launch_layernorm<T> (T by prec) on n_rows rows of x (row r at x + r * row_stride, E <= 1536 columns) -> out [out_rows][E] of T, out_rows >= n_rows:
+// NaN at the launch, so rows >= n_rows come back as NaN
+int umgen_dbg_layernorm(int prec, const float* x, long row_stride, long n_rows, int E, const float* w, void* out, long out_rows) {
+    if (prec < 0 || prec > 2 || !x || !w || !out || E < 1 || E > 64 * 24 || row_stride < E || n_rows < 1 || out_rows < n_rows) return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, xsz = (size_t)n_rows * row_stride * 4, on = (size_t)out_rows * E;
+    DevBuf dXi(xsz), dW((size_t)E * 4);
+    GuardedBuf dO(on * es);
+    if (!dXi.p || !dW.p || !dO.p) return UMGEN_E_NOMEM;
+    if (up(dXi.p, x, xsz) || up(dW.p, w, (size_t)E * 4)) return UMGEN_E_HIP;
+    if (prec ? hipMemsetD16((hipDeviceptr_t)dO.p, nan16(prec), on) != hipSuccess : fill_nan32(dO.p, on) != 0) return UMGEN_E_HIP;
+    by_prec(prec, [&](auto tag) { launch_layernorm<decltype(tag)>(nullptr, (const float*)dXi.p, row_stride, n_rows, E, (const float*)dW.p, (decltype(tag)*)dO.p); });
+    if (int rc = finish()) return rc;
+    if (!dO.intact()) return UMGEN_E_STATE;
+    return down(out, dO.p, on * es);
+}
+
+// launch_cond_rows of one stack: X [B][T][stack_len][E], ln_w [E], warped_last [B][1024][E] or NULL (required for STACK_MAP) -> cond
+// [B][kSeq][E], in / out: the launch changes the stack's own rows only
+int umgen_dbg_cond_rows(int stack, int B, int T, int E, const float* X, const float* ln_w, const float* warped_last, float* cond) {
+    if (stack < STACK_MAP || stack > STACK_TAR || B < 1 || T < 1 || E < 1 || !X || !ln_w || !cond || (stack == STACK_MAP && !warped_last)) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * T * stack_len(stack) * E, wn = (size_t)B * kNMap * E, cn = (size_t)B * kSeq * E;
+    DevBuf dXi(xn * 4), dW((size_t)E * 4), dWL(wn * 4);
+    GuardedBuf dC(cn * 4);
+    if (!dXi.p || !dW.p || !dWL.p || !dC.p) return UMGEN_E_NOMEM;
+    if (up(dXi.p, X, xn * 4) || up(dW.p, ln_w, (size_t)E * 4) || up(dC.p, cond, cn * 4) || (warped_last && up(dWL.p, warped_last, wn * 4))) return UMGEN_E_HIP;
+    launch_cond_rows(nullptr, stack, B, T, E, (const float*)dXi.p, (const float*)dW.p, warped_last ? (const float*)dWL.p : nullptr, (float*)dC.p);
+    if (int rc = finish()) return rc;
+    if (!dC.intact()) return UMGEN_E_STATE;
+    return down(cond, dC.p, cn * 4);
+}
+
+// launch_first_input: x [B][E] = row [E] + cond[b][0] (cond [B][kSeq][E])
+int umgen_dbg_first_input(int B, int E, const float* row, const float* cond, float* x) {
+    if (B < 1 || E < 1 || !row || !cond || !x) return UMGEN_E_INVALID;
+    const size_t cn = (size_t)B * kSeq * E, xn = (size_t)B * E;
+    DevBuf dR((size_t)E * 4), dC(cn * 4);
+    GuardedBuf dXo(xn * 4);
+    if (!dR.p || !dC.p || !dXo.p) return UMGEN_E_NOMEM;
+    if (up(dR.p, row, (size_t)E * 4) || up(dC.p, cond, cn * 4) || fill_nan32(dXo.p, xn)) return UMGEN_E_HIP;
+    launch_first_input(nullptr, B, E, (const float*)dR.p, (const float*)dC.p, (float*)dXo.p);
+    if (int rc = finish()) return rc;
+    if (!dXo.intact()) return UMGEN_E_STATE;
+    return down(x, dXo.p, xn * 4);
+}
+
+// launch_ego_queries: x [B][3][E] = (egoe[j] + spe[j]) + tpe[T - 1]
+int umgen_dbg_ego_queries(const umgen_dbg_tables* t, int B, int T, float* x) {
+    if (!tables_sane(t) || B < 1 || T < 1 || T > t->n_tpe || !t->egoe || !t->spe || !t->tpe || !x) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * 3 * t->E;
+    TablesDev td(*t);
+    GuardedBuf dXo(xn * 4);
+    if (!td.ok || !dXo.p) return UMGEN_E_NOMEM;
+    if (fill_nan32(dXo.p, xn)) return UMGEN_E_HIP;
+    launch_ego_queries(nullptr, td.tb, B, T, (float*)dXo.p);
+    if (int rc = finish()) return rc;
+    if (!dXo.intact()) return UMGEN_E_STATE;
+    return down(x, dXo.p, xn * 4);
+}
+
+// launch_prefix_rows: the decode inputs of the given positions 0 .. P - 1 (tske_row [E], cond [B][kSeq][E], tokens [B][2199]) ->
+// X [B][P - 1][E] (rows 0 .. P - 2) and x_last [B][E] (row P - 1)
+int umgen_dbg_prefix_rows(const umgen_dbg_tables* t, const float* tske_row, const float* cond, const int32_t* tokens, int B, int P, float* X, float* x_last) {
+    if (!tables_sane(t) || B < 1 || P < 2 || P > kBoxEos + 2 || !tske_row || !cond || !tokens || !X || !x_last) return UMGEN_E_INVALID;
+    if (!t->axe || !t->be || !t->gmap || !t->fouier_pe) return UMGEN_E_INVALID;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* tk = tokens + (size_t)b * kTokPerFrame;
+        if (!in_range(tk, kNPose, t->n_pose) || !in_range(tk + kOffMap, kNMap, t->n_map) || !in_range(tk + kOffBox, kNBox, t->n_box)) return UMGEN_E_INVALID;
+    }
+    const size_t E = (size_t)t->E, cn = (size_t)B * kSeq * E, xn = (size_t)B * (P - 1) * E, ln = (size_t)B * E, tn = (size_t)B * kTokPerFrame;
+    TablesDev td(*t);
+    DevBuf dR(E * 4), dC(cn * 4), dT(tn * 4);
+    GuardedBuf dXo(xn * 4), dL(ln * 4);
+    if (!td.ok || !dR.p || !dC.p || !dT.p || !dXo.p || !dL.p) return UMGEN_E_NOMEM;
+    if (up(dR.p, tske_row, E * 4) || up(dC.p, cond, cn * 4) || up(dT.p, tokens, tn * 4) || fill_nan32(dXo.p, xn) || fill_nan32(dL.p, ln)) return UMGEN_E_HIP;
+    launch_prefix_rows(nullptr, td.tb, (const float*)dR.p, (const float*)dC.p, (const int*)dT.p, B, P, (float*)dXo.p, (float*)dL.p);
+    if (int rc = finish()) return rc;
+    if (!dXo.intact() || !dL.intact()) return UMGEN_E_STATE;
+    if (down(X, dXo.p, xn * 4)) return UMGEN_E_HIP;
+    return down(x_last, dL.p, ln * 4);
+}
+
+// launch_prefix_kv_to_cache<T>: qk [B * S][2E] (q | k rows) and vt [B][H][48][S_pad] of T -> cache [B][2][H][Lmax][48] of T (NaN at the launch) with
+// the product's scene stride 2 * H * Lmax * 48
+int umgen_dbg_prefix_kv_to_cache(int prec, const void* qk, const void* vt, int B, int S, int S_pad, int H, int Lmax, void* cache) {
+    if (prec < 0 || prec > 2 || !qk || !vt || !cache || B < 1 || S < 1 || S > S_pad || S > Lmax || H < 1) return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, E = (size_t)H * kHeadDim, qn = (size_t)B * S * 2 * E, vn = (size_t)B * E * S_pad, stride = (size_t)2 * H * Lmax * kHeadDim;
+    const size_t cn = (size_t)B * stride;
+    DevBuf dQ(qn * es), dV(vn * es);
+    GuardedBuf dC(cn * es, scene_band(stride * es, B));
+    if (!dQ.p || !dV.p || !dC.p) return UMGEN_E_NOMEM;
+    if (up(dQ.p, qk, qn * es) || up(dV.p, vt, vn * es)) return UMGEN_E_HIP;
+    if (prec ? hipMemsetD16((hipDeviceptr_t)dC.p, nan16(prec), cn) != hipSuccess : fill_nan32(dC.p, cn) != 0) return UMGEN_E_HIP;
+    by_prec(prec, [&](auto tag) {
+        typedef decltype(tag) TT;
+        launch_prefix_kv_to_cache<TT>(nullptr, (const TT*)dQ.p, (const TT*)dV.p, B, S, S_pad, H, Lmax, (TT*)dC.p, (long)stride);
+    });
+    if (int rc = finish()) return rc;
+    if (!dC.intact()) return UMGEN_E_STATE;
+    return down(cache, dC.p, cn * es);
+}
+
+// The sampler kernels of decode steps j0 .. j1 - 1 of one frame for B scenes, on an OarState and a SampleArgs of the hook's own: what enqueue_step
+// (engine.hip) launches behind the head at position j -- launch_fixed_token for bos / eos / the pose prefix and every position < given_end, else
+// launch_sample_token with the position's mod and vocabulary (tables: n_map | n_box | n_img) -- with that step's logits [B][ld_logits]
+// (logits [j1 - j0][B][ld_logits]).  logits_tar [B][660][n_box], prev_box [B][660], control_slot [B][60], forced [B][2199] (or NULL), seeds [B].
+// In / out: tokens [B][2199], counters [8], n_boxes [B], boxes [B][64][10].  Out: x_next [j1 - j0][B][E] (NaN before every step) and
+// state_log [j1 - j0][3] = OarState step, epoch, done behind every step.
+int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
+    if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
+    // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
+    if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
+    if (!a->cond || !a->logits || !a->logits_tar || !a->prev_box || !a->control_slot || !a->seeds || !a->tokens || !a->x_next || !a->counters ||
+        !a->n_boxes || !a->boxes || !a->state_log || (a->use_forced && !a->forced))
+        return UMGEN_E_INVALID;
+    if (!t->axe || !t->be || !t->gmap || !t->gimg || !t->fouier_pe || t->E > 6 * 256) return UMGEN_E_INVALID;   // CondRow: E <= 1536
+    const int vmax = std::max(t->n_map, std::max(t->n_box, t->n_img));
+    if (vmax > 8192 || a->ld_logits < vmax || t->n_map < 1 || t->n_img < 1 || t->n_box <= kBoxPad) return UMGEN_E_INVALID;
+    if (a->sp.method < 0 || a->sp.method > 1 || a->sp.top_k < 1 || a->sp.top_k_map < 1 || a->sp.topk_image < 1 || !(a->sp.temperature > 0.f)) return UMGEN_E_INVALID;
+    const int B = a->B, n = a->j1 - a->j0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* tk = a->tokens + (size_t)b * kTokPerFrame;
+        if (!in_range(tk, kNPose, t->n_pose) || !in_range(tk + kOffMap, kNMap, t->n_map) || !in_range(tk + kOffBox, kNBox, t->n_box) ||
+            !in_range(tk + kOffImg, kNImg, t->n_img))
+            return UMGEN_E_INVALID;
+        if (a->use_forced) {
+            const int32_t* ft = a->forced + (size_t)b * kTokPerFrame;
+            if (!in_range(ft, kNPose, t->n_pose)) return UMGEN_E_INVALID;
+            if (!in_range(ft + kOffMap, kNMap, t->n_map) || !in_range(ft + kOffBox, kNBox, t->n_box) || !in_range(ft + kOffImg, kNImg, t->n_img)) return UMGEN_E_INVALID;
+        }
+        if (a->n_boxes[b] < 0 || a->n_boxes[b] > 30) return UMGEN_E_INVALID;     // the kernel's box list and corner table hold 64
+    }
+    const size_t E = (size_t)t->E, cn = (size_t)B * kSeq * E, ln = (size_t)B * a->ld_logits, tarn = (size_t)B * kNBox * t->n_box, tn = (size_t)B * kTokPerFrame;
+    const size_t bn = (size_t)B * 64 * 10;
+    TablesDev td(*t);
+    DevBuf dSt(sizeof(OarState)), dC(cn * 4), dLg(ln * 4), dTar(tarn * 4), dPrev((size_t)B * kNBox * 4), dCtl((size_t)B * kSlots), dF(tn * 4), dSeed((size_t)B * 8);
+    GuardedBuf dXn((size_t)B * E * 4), dTok(tn * 4), dCnt(8 * 4), dNb((size_t)B * 4), dBx(bn * 8);
+    if (!td.ok || !dSt.p || !dC.p || !dLg.p || !dTar.p || !dPrev.p || !dCtl.p || !dF.p || !dSeed.p || !dXn.p || !dTok.p || !dCnt.p || !dNb.p || !dBx.p)
+        return UMGEN_E_NOMEM;
+    OarState s0{};
+    s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
+    s0.epoch = a->epoch0; s0.sp = a->sp;
+    if (up(dSt.p, &s0, sizeof(s0)) || up(dC.p, a->cond, cn * 4) || up(dTar.p, a->logits_tar, tarn * 4) || up(dPrev.p, a->prev_box, (size_t)B * kNBox * 4) ||
+        up(dCtl.p, a->control_slot, (size_t)B * kSlots) || up(dSeed.p, a->seeds, (size_t)B * 8) || up(dTok.p, a->tokens, tn * 4) ||
+        up(dCnt.p, a->counters, 8 * 4) || up(dNb.p, a->n_boxes, (size_t)B * 4) || up(dBx.p, a->boxes, bn * 8) || (a->use_forced && up(dF.p, a->forced, tn * 4)))
+        return UMGEN_E_HIP;
+    SampleArgs sa{};
+    sa.st = (OarState*)dSt.p; sa.tb = td.tb; sa.logits = (const float*)dLg.p; sa.logits_tar = (const float*)dTar.p; sa.ld_logits = a->ld_logits;
+    sa.ld_tar = t->n_box; sa.cond = (const float*)dC.p; sa.x_next = (float*)dXn.p; sa.tokens = (int*)dTok.p; sa.prev_box = (const int*)dPrev.p;
+    sa.control_slot = (const unsigned char*)dCtl.p; sa.boxes = (double*)dBx.p; sa.n_boxes = (int*)dNb.p; sa.seeds = (const unsigned long long*)dSeed.p;
+    sa.forced = (const int*)dF.p; sa.counters = (int*)dCnt.p;
+    for (int i = 0; i < n; ++i) {
+        const int j = a->j0 + i, mod = kind_of_pos(j, a->given_end);
+        if (fill_nan32(dXn.p, (size_t)B * E)) return UMGEN_E_HIP;
+        if (mod == 0) {
+            launch_fixed_token(nullptr, sa, B);
+        } else {
+            if (up(dLg.p, a->logits + (size_t)i * ln, ln * 4)) return UMGEN_E_HIP;
+            sa.mod = mod;
+            sa.vocab = mod == 1 ? t->n_map : (mod == 2 ? t->n_box : t->n_img);
+            launch_sample_token(nullptr, sa, B);
+        }
+        if (int rc = finish()) return rc;
+        OarState s1{};
+        if (down(&s1, dSt.p, sizeof(s1)) || down(a->x_next + (size_t)i * B * E, dXn.p, (size_t)B * E * 4)) return UMGEN_E_HIP;
+        a->state_log[3 * i] = (uint32_t)s1.step; a->state_log[3 * i + 1] = s1.epoch; a->state_log[3 * i + 2] = (uint32_t)s1.done;
+    }
+    if (!dXn.intact() || !dTok.intact() || !dCnt.intact() || !dNb.intact() || !dBx.intact()) return UMGEN_E_STATE;
+    if (down(a->tokens, dTok.p, tn * 4) || down(a->counters, dCnt.p, 8 * 4) || down(a->n_boxes, dNb.p, (size_t)B * 4)) return UMGEN_E_HIP;
+    return down(a->boxes, dBx.p, bn * 8);
+}
+
+// launch_sample_ego: logits [3 B][V] -> out_tokens [B][3]; the draw of row (b, jq) is rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN); forced
+// [B][2199] (or NULL) overrides with its pose tokens
+int umgen_dbg_sample_ego(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                         int32_t* out_tokens) {
+    if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
+        return UMGEN_E_INVALID;
+    const size_t ln = (size_t)B * 3 * V, tn = (size_t)B * kTokPerFrame;
+    DevBuf dL(ln * 4), dS((size_t)B * 8), dF(tn * 4), dOv(4);
+    GuardedBuf dT((size_t)B * 3 * 4);
+    if (!dL.p || !dS.p || !dF.p || !dOv.p || !dT.p) return UMGEN_E_NOMEM;
+    if (up(dL.p, logits, ln * 4) || up(dS.p, seeds, (size_t)B * 8) || (forced && up(dF.p, forced, tn * 4)) || hipMemset(dOv.p, 0, 4) != hipSuccess ||
+        hipMemset(dT.p, 0xff, (size_t)B * 3 * 4) != hipSuccess)
+        return UMGEN_E_HIP;
+    launch_sample_ego(nullptr, (const float*)dL.p, V, *sp, (const unsigned long long*)dS.p, frame_idx, forced ? (const int*)dF.p : nullptr, (int*)dT.p, B, (int*)dOv.p);
+    if (int rc = finish()) return rc;
+    int ovf = 0;
+    if (down(&ovf, dOv.p, 4)) return UMGEN_E_HIP;
+    if (!dT.intact() || ovf != 0) return UMGEN_E_STATE;      // (the overflow word is unused since the exhaustive tie walk: it must stay 0)
+    return down(out_tokens, dT.p, (size_t)B * 3 * 4);
 }
 
 }  // extern "C"
