@@ -207,6 +207,24 @@ int umgen_vq_decode(umgen_vq *d, int32_t n, const int64_t *codes, float *out);
 const char *umgen_vq_last_error(const umgen_vq *d);
 int umgen_vq_destroy(umgen_vq *d);
 
+/* ---- VQ encoders: map / image rasters -> tokens, fp32 ---------------------------------------------
+ * NormVQModel.encode (projects/tokenizer/vq_model.py:80-85, the call behind NormVQModelTokenizer.encode, vq_tokenizer.py:25-47) =
+ * Encoder.forward (projects/tokenizer/vq_modules.py:179-290) -> quant_conv -> the l2norm + nearest-code search of
+ * NormEMAVectorQuantizer.forward (projects/tokenizer/quantize.py:414-429).  A handle of its own: a decoder handle does not read encoder.* keys. */
+typedef struct umgen_vqenc umgen_vqenc; /* opaque */
+/* cfg: the same ddconfig mirror the decoder takes (out_ch, post_quant_* are ignored); in_channels = ddconfig["in_channels"] */
+int umgen_vqenc_create(const umgen_vq_config *cfg, int32_t in_channels, umgen_vqenc **out);
+/* reference key names: "encoder.conv_in.weight", "encoder.down.1.downsample.conv.bias", "encoder.mid.attn_1.q.weight",
+ * "quant_conv.weight", "quantize.embedding.weight", ...; entries the encode path does not read (decoder.*, post_quant_conv.*,
+ * cluster_size / embed_avg / initted buffers) return 1; known keys are shape-checked */
+int umgen_vqenc_load_tensor(umgen_vqenc *q, const char *key, const float *data, const int64_t *shape, int32_t ndim);
+int umgen_vqenc_finalize(umgen_vqenc *q);
+/* x [n][in_channels][H][W] fp32 (H = token_h * 2^(n_levels-1), W likewise; finite values, nominally in [-1, 1]) -> codes
+ * [n][token_h][token_w];  z: NULL, or [n][token_h][token_w][embed_dim], the l2-normalised rows the nearest-code search ran on */
+int umgen_vqenc_encode(umgen_vqenc *q, int32_t n, const float *x, int64_t *codes, float *z);
+const char *umgen_vqenc_last_error(const umgen_vqenc *q);
+int umgen_vqenc_destroy(umgen_vqenc *q);
+
 const char *umgen_last_error(const umgen_engine *e); /* never NULL */
 const char *umgen_version(void);
 int umgen_destroy(umgen_engine *e);

@@ -14,18 +14,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # UMGEN_LIB_PATH selects an alternative build of the SAME library (kernel experiments with extra -D flags); never a fallback
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
-SOURCES = ["engine.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "debug_api.hip"]
+SOURCES = ["engine.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip", "debug_api.hip"]
 EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
+           "umgen_vqenc_create", "umgen_vqenc_load_tensor", "umgen_vqenc_finalize", "umgen_vqenc_encode", "umgen_vqenc_last_error", "umgen_vqenc_destroy",
            "umgen_dbg_linear", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_oar_step", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
            "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
            "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer",
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego"]
 
-HEADERS = ("common.h", "kernels.h", "frame.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h")
+HEADERS = ("common.h", "kernels.h", "frame.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h")
 
 PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DT_F32, DT_BF16, DT_F16, DT_F64 = 0, 1, 2, 3
@@ -292,8 +293,15 @@ def load_library() -> C.CDLL:
     lib.umgen_vq_last_error.argtypes = [vp]
     lib.umgen_vq_last_error.restype = C.c_char_p
     lib.umgen_vq_destroy.argtypes = [vp]
+    lib.umgen_vqenc_create.argtypes = [C.POINTER(VQConfig), i32, C.POINTER(vp)]
+    lib.umgen_vqenc_load_tensor.argtypes = [vp, C.c_char_p, fp, i64p, i32]
+    lib.umgen_vqenc_finalize.argtypes = [vp]
+    lib.umgen_vqenc_encode.argtypes = [vp, i32, fp, i64p, fp]
+    lib.umgen_vqenc_last_error.argtypes = [vp]
+    lib.umgen_vqenc_last_error.restype = C.c_char_p
+    lib.umgen_vqenc_destroy.argtypes = [vp]
     for name in EXPORTS:
-        if name not in ("umgen_last_error", "umgen_version", "umgen_vq_last_error"):
+        if name not in ("umgen_last_error", "umgen_version", "umgen_vq_last_error", "umgen_vqenc_last_error"):
             getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
