@@ -6,7 +6,9 @@
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../umgen_amd/csrc"
-ALL="engine.hip gemm.hip gemm256.hip attn.hip gemv.hip oar_engine.hip oar_engine_wide.hip decode_batched.hip rowops.hip frame.hip tokenizers.hip vqdec.hip debug_api.hip"
+# the library's one source list (importing umgen_amd._lib loads nothing)
+ALL=$(cd ../.. && python3 -c "from umgen_amd._lib import SOURCES; print(' '.join(SOURCES))")
+[ -n "$ALL" ] || { echo "could not read SOURCES from umgen_amd/_lib.py"; exit 1; }
 SRC=${VARIANT_SOURCES:-$ALL}
 objs=""
 for f in $ALL; do

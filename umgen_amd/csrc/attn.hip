@@ -350,7 +350,7 @@ __global__ __launch_bounds__((OPT & 8192) ? 512 : 256) void attn_spatial_mfma2_k
 
 template <typename TT>
 void launch_attn_spatial_mfma(hipStream_t s, const TT* qk, const TT* vt, TT* y, int F, int S, int S_pad, int H) {
-    constexpr int QT = UMGEN_ATTN_QT;
+    constexpr int QT = kAttnQT;
     const int nq = (S + 4 * QT * 16 - 1) / (4 * QT * 16);
     // F*H pairs; groups of 8 pairs need F*H % 8 == 0 -- pad the pair count up and let the surplus blocks exit
     const int pairs = ((F * H + 7) / 8) * 8;
@@ -387,7 +387,7 @@ template void launch_attn_spatial_mfma<bf16_t>(hipStream_t, const bf16_t*, const
 template void launch_attn_spatial_mfma<f16_t>(hipStream_t, const f16_t*, const f16_t*, f16_t*, int, int, int, int);
 template <typename TT>
 void launch_attn_causal_mfma(hipStream_t s, const TT* qk, const TT* vt, TT* y, int F, int S, int S_pad, int H) {
-    constexpr int QT = UMGEN_ATTN_QT;
+    constexpr int QT = kAttnQT;
     const int nq = (S + 4 * QT * 16 - 1) / (4 * QT * 16);
     const int pairs = ((F * H + 7) / 8) * 8;
     hipLaunchKernelGGL((attn_spatial_mfma_kernel<QT, TT, true>), dim3(pairs * nq), dim3(256), 0, s, qk, vt, y, S, S_pad, H, nq, F * H);

@@ -5,12 +5,9 @@
 
 #include "kernels.h"
 
-#ifndef UMGEN_ATTN_QT
-#define UMGEN_ATTN_QT 2   // measured: 2 query tiles per wave (2 waves/SIMD) beats 4 (1 wave/SIMD)
-#endif
-
 namespace umgen {
 
+constexpr int kAttnQT = 2;   // measured: 2 query tiles per wave (2 waves/SIMD) beats 4 (1 wave/SIMD)
 constexpr float kScale = 0.14433756729740643f;          // float32(1/sqrt(48)), module.py:196-198
 constexpr float kLog2e = 1.4426950408889634f;
 

@@ -83,7 +83,7 @@ __device__ __noinline__ void bg_attn_s(const BgOp* op, int S, int S_pad, int H, 
     for (int u = done; u < done + n; ++u) {
         const int vb = 2 * (widx + u * nwk) + half;
         const bool valid = vb < o.i5;
-        attn_spatial_mfma_body<UMGEN_ATTN_QT, TT, false, true>(reinterpret_cast<const TT*>(o.p0), reinterpret_cast<const TT*>(o.p1), reinterpret_cast<TT*>(o.p2), S, S_pad, H, nq,
+        attn_spatial_mfma_body<kAttnQT, TT, false, true>(reinterpret_cast<const TT*>(o.p0), reinterpret_cast<const TT*>(o.p1), reinterpret_cast<TT*>(o.p2), S, S_pad, H, nq,
                                                                 o.i4, valid ? vb : 0, tid & 255, half * 2 * kTileBytes, valid);
     }
 }

@@ -70,8 +70,6 @@ struct umgen_engine {
     void *A = nullptr, *QKV = nullptr, *VT = nullptr, *Hb = nullptr;
     float *xdec = nullptr, *qdec = nullptr, *part = nullptr, *hdec = nullptr, *logits = nullptr, *logits_tar = nullptr, *qkv3 = nullptr;
     void* kvcache = nullptr;
-    void* vtcache = nullptr;            // UMGEN_ENG_MFMA & 16: the decode engine's dim-major copy of V [layer][scene][H][48][Lmax]
-    long vt_layer_stride = 0, vt_scene_stride = 0;
     long kv_layer_stride = 0, kv_scene_stride = 0;
     int Lmax = kAttnSplit * kAttnChunk, S_pad = 2240;   // cache rows per head: every split's fixed key range is addressable
     int *d_pose = nullptr, *d_pose_shift = nullptr, *d_map = nullptr, *d_box = nullptr, *d_img = nullptr;
@@ -145,7 +143,7 @@ struct umgen_engine {
     unsigned long long *eng_gx = nullptr, *eng_gloc = nullptr;
     unsigned int *eng_ticket = nullptr, *eng_err = nullptr;
     std::vector<void*> eng_wp2;             // per BlockOAR: mlp c_proj repacked for the engine's hidden-unit split (repack_mlp_proj)
-    std::vector<void*> eng_wf2;             // per BlockOAR: c_fc as matrix-core fragments (UMGEN_ENG_MFMA & 4)
+    std::vector<void*> eng_wf2;             // per BlockOAR: c_fc as matrix-core fragments (repack_mlp_proj)
     unsigned long long* eng_stamps = nullptr;   // UMGEN_DEBUG_TIMING: per-phase ticks of the engine (printed at destroy)
     size_t eng_gloc_bytes = 0;
     // Chip-wide decode engine for wide layers (oar_engine_wide.hip; n_embd 1536; one launch per scene and step).  Default: engines created for ONE scene per
@@ -598,7 +596,6 @@ int oar_layers(umgen_engine* e, int B, int ns) {
         OarEngineArgs a{};
         a.layers = e->d_layers; a.n_layers = (int)e->oar.size();
         a.kvcache = reinterpret_cast<bf16_t*>(e->kvcache); a.kv_layer_stride = e->kv_layer_stride; a.kv_scene_stride = e->kv_scene_stride; a.Lmax = e->Lmax;
-        a.vtcache = reinterpret_cast<bf16_t*>(e->vtcache); a.vt_layer_stride = e->vt_layer_stride; a.vt_scene_stride = e->vt_scene_stride;
         a.xdec = e->xdec; a.st = e->d_state; a.gx = e->eng_gx; a.gloc = e->eng_gloc; a.ticket = e->eng_ticket; a.err = e->eng_err;
         a.B = B; a.NG = es->NG;
         a.R = es->NG;
@@ -1475,9 +1472,9 @@ int build_tables(umgen_engine* e) {
 }
 
 // Decode engine (oar_engine.hip): the mlp c_proj of every BlockOAR, repacked for the hidden-unit split.  CU c of a group owns
-// hidden units 96 c .. 96 c + 95; thread t of its workgroup holds, as 16-byte units of 8 bf16 in the order it requests them,
-//   unit j < 12 : W[4 (t / 4) + j / 3][96 c + 24 (t % 4) + 8 (j % 3) .. + 7]      (four lanes share rows 4 (t / 4) .. + 3)
-//   units 12..17: 48 weights, weight i = W[512 + 4 (t / 8) + i / 12][96 c + 12 (t % 8) + i % 12]   (eight lanes share four of the rows 512..767)
+// hidden units 96 c .. 96 c + 95; thread t of its workgroup holds, as 16-byte units of 8 bf16 in the order it requests them, the matrix-core
+// A fragments of its wave: unit f = 3 tile + kstep of lane (t % 64) of wave (t / 64) is
+//   W[96 wave + 16 tile + lane % 16][96 c + 32 kstep + 8 (lane / 16) .. + 7]
 // layout [32 CUs][18 units][512 threads][8]: a wave's request of one unit is 1 KB contiguous.
 int repack_mlp_proj(umgen_engine* e) {
     const int E = e->E, F4 = 4 * E;
@@ -1495,24 +1492,12 @@ int repack_mlp_proj(umgen_engine* e) {
             for (int j = 0; j < kEngWpUnits; ++j)
                 for (int t = 0; t < kEngThreads; ++t) {
                     bf16_t* d8 = &dst[(((size_t)c * kEngWpUnits + j) * kEngThreads + t) * 8];
-                    if (UMGEN_ENG_MFMA & 8) {
-                        // matrix-core form (oar_engine.hip, kMfmaP): unit f = 3 tile + kstep of lane (t % 64) of wave (t / 64) is the A fragment
-                        // W[96 wave + 16 tile + lane % 16][96 c + 32 kstep + 8 (lane / 16) .. + 7]
-                        const int wave = t / 64, lane = t % 64, tile = j / 3, ks = j % 3;
-                        memcpy(d8, &src[(size_t)(96 * wave + 16 * tile + lane % 16) * F4 + 96 * c + 32 * ks + 8 * (lane / 16)], 8 * sizeof(bf16_t));
-                    } else if (j < 12) {
-                        memcpy(d8, &src[(size_t)(4 * (t / 4) + j / 3) * F4 + 96 * c + 24 * (t % 4) + 8 * (j % 3)], 8 * sizeof(bf16_t));
-                    } else {
-                        for (int k = 0; k < 8; ++k) {
-                            const int i = 8 * (j - 12) + k;
-                            d8[k] = src[(size_t)(512 + 4 * (t / 8) + i / 12) * F4 + 96 * c + 12 * (t % 8) + i % 12];
-                        }
-                    }
+                    const int wave = t / 64, lane = t % 64, tile = j / 3, ks = j % 3;
+                    memcpy(d8, &src[(size_t)(96 * wave + 16 * tile + lane % 16) * F4 + 96 * c + 32 * ks + 8 * (lane / 16)], 8 * sizeof(bf16_t));
                 }
         HIPCHK(e, hipMemcpy(e->eng_wp2[li], dst.data(), dst.size() * sizeof(bf16_t), hipMemcpyHostToDevice));
         hl[li].Wp2 = reinterpret_cast<const bf16_t*>(e->eng_wp2[li]);
-        hl[li].Wf2 = nullptr;
-        if (UMGEN_ENG_MFMA & 4) {
+        {
             // c_fc [4E][E] as the engine's A fragments: CU c owns rows 96 c .. + 95 (6 tiles of 16), wave v the k range 96 v .. + 95
             // (3 k-steps of 32); fragment f = 3 tile + kstep of lane l = W[96 c + 16 tile + l % 16][96 v + 32 kstep + 8 (l / 16) .. + 7],
             // stored [c][v][f][l][8]: a wave's request of one fragment is 1 KB contiguous (row-strided 64-byte pieces streamed at
@@ -1910,14 +1895,6 @@ int umgen_create(const umgen_config* cfg, umgen_engine** out) {
     if (int rc = dev_alloc(e, &e->kvcache, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz)) return rc;
     // (the engines' key loops request whole 16-key passes and mask the keys past the step: p = 0 times whatever bits lie there must be 0, not NaN)
     HIPCHK(e, hipMemset(e->kvcache, 0, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz));
-    if ((UMGEN_ENG_MFMA & 16) && e->tsz == 2) {
-        // the matrix-core attention multiplies whole 32-key tiles, masked keys included: no NaN bit patterns may sit behind the mask
-        HIPCHK(e, hipMemset(e->kvcache, 0, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz));
-        e->vt_scene_stride = (long)e->H * kHeadDim * e->Lmax;
-        e->vt_layer_stride = (long)Bm * e->vt_scene_stride;
-        if (int rc = dev_alloc(e, &e->vtcache, (size_t)cfg->n_oar_layer * e->vt_layer_stride * e->tsz)) return rc;
-        HIPCHK(e, hipMemset(e->vtcache, 0, (size_t)cfg->n_oar_layer * e->vt_layer_stride * e->tsz));
-    }
     // slot caches of the overlapped TAR pass: k | v rows of every temporal sub-block, all history slots (the foreground's growing-window
     // reuse allocates the same caches on first use, run_frame)
     if (e->overlap && !ensure_tcache(e)) e->overlap = false;     // keep the plain path rather than crowding the KV caches out

@@ -62,16 +62,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_mfma_kernel(GemmArgs a, int nI,
     const int wi = wave >> 1, wj = wave & 1;
     // XCD-aware tile map (block b runs on XCD b % 8): the nI feature tiles that share one activation (Q) tile are issued
     // back-to-back on the same XCD, so every activation tile is fetched into exactly one L2.
-#ifndef UMGEN_GEMM_XCD
-#define UMGEN_GEMM_XCD 1
-#endif
     const int b = blockIdx.x;
-#if UMGEN_GEMM_XCD
     const int grp = b / (8 * nI), rem = b % (8 * nI);
     const int tj = grp * 8 + (rem & 7), ti = rem >> 3;
-#else
-    const int tj = b / nI, ti = b % nI;
-#endif
     if (tj >= nJ) return;
     const int i_base = ti * BM, j_base = tj * BN;
     const TT* P = reinterpret_cast<const TT*>(a.P) + (long)z * a.strideP;
@@ -490,7 +483,6 @@ void launch_gemm_mfma(hipStream_t s, const GemmArgs& a) {
     }
     const int nI = (a.Mi + BM - 1) / BM, nJ = (a.Nj + BN - 1) / BN;
     dim3 grid(((nJ + 7) / 8) * 8 * nI, 1, a.batch), block(256);
-#ifndef UMGEN_NO_PERSISTENT_GEMM
     if (a.K % BK == 0 && a.batch == 1 && a.mode != GEMM_VT && (long)nI * nJ >= 1024) {
         static int n_cu = 0;
         if (!n_cu) {
@@ -506,7 +498,6 @@ void launch_gemm_mfma(hipStream_t s, const GemmArgs& a) {
         }
         return;
     }
-#endif
     if (a.K % BK == 0) {
         grid = dim3(8 * ((nI + 1) / 2) * ((nJ + 3) / 4), 1, a.batch);
         const dim3 block8(512);

@@ -7,7 +7,11 @@
 //     128 x 128 form;
 //   * operands go HBM -> LDS with global_load_lds (no staging registers), into a RING of 8 half-tile slots (128 rows x 64 k = 16 KB
 //     each, XOR-swizzled on the source side so that ds_read_b128 fragment reads are conflict-free): 2 k-tiles x {P half 0/1, Q half 0/1};
-//   * (round 4: the four phases below run as TWO of 32 MFMAs -- UMGEN_G256_PH2 -- with the same refill / wait points pairwise merged)
+//   * (round 4: the four phases below run as TWO of 32 MFMAs with the same refill / wait points pairwise merged -- 4 barriers per k-tile instead
+//     of 8: fragment reads 16 / 8 per phase, both P refills in the first, both Q refills and the counted wait in the second.  Same products in the
+//     same order (bit-identical outputs); 8 scenes' rows: q|k 936 -> 994, fc 1015 -> 1048, fc + GELU 833 -> 865, K = 3072 projection 957 -> 1019,
+//     V^T 855 -> 908, 4096^3 1283 -> 1402 TFLOP/s (profiles/r04_gemm_bench_ph2.txt).  The four-phase form, the alternating fragment preload and the
+//     unstaggered wave groups that were measured against it were removed: commit 539b5b8 is the last tree that builds them.)
 //   * a k-tile is 4 phases of 16 MFMAs (one quadrant of the wave's sub-tile x the whole k-tile).  Every phase issues ONE half-tile
 //     refill into the slot whose last reader retired a phase earlier: the P halves of k-tile kt+1 in phases 0 / 1, the Q halves of
 //     k-tile kt+2 in phases 2 / 3 -- every load has >= 3 phases (~1.5k cycles) to land, and the loads of an output tile's first
@@ -37,10 +41,6 @@ __device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((ch
 
 struct Src { int ti, trow0, tmax; };   // an output tile's feature tile, first token row and last addressable token row (wave-uniform)
 
-#ifndef UMGEN_GEMM256_STAGGER
-#define UMGEN_GEMM256_STAGGER 1
-#endif
-constexpr bool STAGGER = UMGEN_GEMM256_STAGGER;
 // Measurement builds only (tools/build_variant.sh; the shipped library has neither): UMGEN_G256_EPI = 1 keeps the epilogue's LDS pass but
 // drops its global stores, 2 stores without the nontemporal hint, 3 drops the residual epilogue's reads; UMGEN_G256_STAMPS accumulates
 // wall-clock ticks (100 MHz) of one workgroup's k-loops / first k-tiles / epilogues, read back by umgen_dbg_gemm_stamps.
@@ -48,16 +48,6 @@ constexpr bool STAGGER = UMGEN_GEMM256_STAGGER;
 #define UMGEN_G256_EPI 0
 #endif
 constexpr int EPI = UMGEN_G256_EPI;
-#ifndef UMGEN_G256_FBALT
-#define UMGEN_G256_FBALT 0
-#endif
-constexpr bool FBALT = UMGEN_G256_FBALT;
-#ifndef UMGEN_G256_PH2
-#define UMGEN_G256_PH2 1     // two phases of 32 MFMAs per k-tile -- 4 barriers instead of the 8 of the four-phase form (0): fragment reads 16 / 8 per
-                             // phase, both P refills in the first, both Q refills and the counted wait in the second.  Same products in the same
-                             // order (bit-identical outputs); 8 scenes' rows: q|k 936 -> 994, fc 1015 -> 1048, fc + GELU 833 -> 865, K = 3072
-                             // projection 957 -> 1019, V^T 855 -> 908, 4096^3 1283 -> 1402 TFLOP/s (profiles/r04_gemm_bench_ph2.txt)
-#endif
 #ifdef UMGEN_G256_STAMPS
 __device__ unsigned long long g256_stamps[16];
 #endif
@@ -122,7 +112,7 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
     issue(4 + 3, false, cur, 1, HK);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    // STAGGER: the waves of the second feature half (one per SIMD, like those of the first) run one barrier interval behind: while one
+    // Stagger: the waves of the second feature half (one per SIMD, like those of the first) run one barrier interval behind: while one
     // group issues its fragment reads and its share of a refill, the other group's 16 MFMAs own the matrix pipe (MI355X playbook: the
     // wave role split is what lets LDS reads, LDS-DMA and MFMAs overlap inside one workgroup).  Both groups pass the same number
     // of barriers: this one here, its counterpart for the first group behind the last tile.
@@ -146,18 +136,13 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
         for (int m = 0; m < 8; ++m)
 #pragma unroll
             for (int n = 0; n < 4; ++n) acc[m][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (STAGGER && wi == 1) __builtin_amdgcn_s_barrier();
+        if (wi == 1) __builtin_amdgcn_s_barrier();
 #ifdef UMGEN_G256_STAMPS
         st_t0 = wall_clock64();
         st_c0 = clock64();
 #endif
-        // one k-tile = 4 phases; FX / FY: the registers of the token fragments of the first / second 32 tokens.  FBALT (build option, off:
-        // measured on the shapes of the stacks, profiles/r04_gemm_bench_fbalt.txt -- 4096^3 +3 %, the K = 768 shapes -3 .. +3 %, no net gain): the first-token
-        // fragments of k-tile kt + 1 are read in phase 3 of k-tile kt (into FY, free since phase 2) instead of its own phase 0, and the two
-        // register sets swap roles every k-tile: 8 / 4 / 8 / 4 fragment reads per phase instead of 12 / 4 / 8 / 0 (the wave group that
-        // reads shares the LDS with the LDS-DMA while the other group's 16 MFMAs run: 12 reads are 384 LDS clocks against 256 MFMA clocks).
-        // Their slot (Q of k-tile kt + 1) is retired one phase earlier for it, by a counted wait in phase 2.
-        auto ktile = [&](const int kt, vec8 (&FX)[2][2], vec8 (&FY)[2][2], auto preloaded_tag, auto preload_tag) {
+        // one k-tile; FX / FY: the registers of the token fragments of the first / second 32 tokens
+        auto ktile = [&](const int kt, vec8 (&FX)[2][2], vec8 (&FY)[2][2], auto /* copy */) {
 #ifdef UMGEN_G256_STAMPS
             if (kt == 1) st_k0 += wall_clock64() - st_t0;
 #endif
@@ -171,29 +156,21 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
             const Src& s2 = in2 ? cur : nxt;
             const int k1 = (in1 ? kt + 1 : kt + 1 - nkt) * HK, k2 = (in2 ? kt + 2 : kt + 2 - nkt) * HK;
             const int par1 = par ^ 1;
-            // (k-tile 0 of an output tile neither finds its fragments preloaded nor preloads: its phase-2 wait would sit right behind the
-            //  previous tile's stores, which vmcnt counts too)
-            constexpr bool preloaded = FBALT && decltype(preloaded_tag)::value;
-            const bool preload = FBALT && decltype(preload_tag)::value && in1;
             vec8 fa[4][2];
-            // ---------------- phase 0: quadrant (features 0..63, tokens 0..31) ----------------
-            if (!preloaded) {
+            // ---------------- phase 0: quadrants (features 0..63, tokens 0..31) and (features 0..63, tokens 32..63) ----------------
 #pragma unroll
-                for (int n = 0; n < 2; ++n)
+            for (int n = 0; n < 2; ++n)
 #pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) FX[n][kk] = *reinterpret_cast<const vec8*>(sQ + swz(n * 16 + frow, kk * 4 + g));
-            }
+                for (int kk = 0; kk < 2; ++kk) FX[n][kk] = *reinterpret_cast<const vec8*>(sQ + swz(n * 16 + frow, kk * 4 + g));
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) fa[m][kk] = *reinterpret_cast<const vec8*>(sP + swz(m * 16 + frow, kk * 4 + g));
-#if UMGEN_G256_PH2
 #pragma unroll
             for (int n = 0; n < 2; ++n)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) FY[n][kk] = *reinterpret_cast<const vec8*>(sQ + swz((2 + n) * 16 + frow, kk * 4 + g));
             if (do1) issue(par1 * 4 + 1, true, s1, 1, k1);
-#endif
             if (do1) issue(par1 * 4 + 0, true, s1, 0, k1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragment reads retired BEFORE the barrier: the other wave group's next refill may target this slot
             __builtin_amdgcn_s_barrier();
@@ -205,20 +182,6 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
                     for (int n = 0; n < 2; ++n) acc[m][n] = Mma16<TT>::mfma(fa[m][kk], FX[n][kk], acc[m][n]);
-#if !UMGEN_G256_PH2
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_s_barrier();
-            // ---------------- phase 1: quadrant (features 0..63, tokens 32..63) ----------------
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) FY[n][kk] = *reinterpret_cast<const vec8*>(sQ + swz((2 + n) * 16 + frow, kk * 4 + g));
-            if (do1) issue(par1 * 4 + 1, true, s1, 1, k1);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragment reads retired BEFORE the barrier: the other wave group's next refill may target this slot
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -227,23 +190,17 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
                     for (int n = 0; n < 2; ++n) acc[m][2 + n] = Mma16<TT>::mfma(fa[m][kk], FY[n][kk], acc[m][2 + n]);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_s_barrier();
-            // ---------------- phase 2: quadrant (features 64..127, tokens 32..63) ----------------
+            // ---------------- phase 1: quadrants (features 64..127, tokens 32..63) and (features 64..127, tokens 0..31); the k-tile's one counted wait ----------------
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) fa[m][kk] = *reinterpret_cast<const vec8*>(sP + swz((4 + m) * 16 + frow, kk * 4 + g));
             if (do2) issue(par * 4 + 2, false, s2, 0, k2);       // (the Q slots of this k-tile: their last reads were phase 1's)
-#if UMGEN_G256_PH2
             if (do2) {
                 issue(par * 4 + 3, false, s2, 1, k2);
-                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // all of k-tile kt + 1 has landed (only this k-tile's two Q refills may be in flight)
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-#endif
-            if (preload) {     // the Q halves of k-tile kt + 1 (requested a k-tile ago) have landed: everything but this k-tile's 4 + 2 requests
-                if (do2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragment reads retired BEFORE the barrier: the other wave group's next refill may target this slot
             __builtin_amdgcn_s_barrier();
@@ -255,28 +212,6 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
                     for (int n = 0; n < 2; ++n) acc[4 + m][2 + n] = Mma16<TT>::mfma(fa[m][kk], FY[n][kk], acc[4 + m][2 + n]);
-#if !UMGEN_G256_PH2
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_s_barrier();
-            // ---------------- phase 3: quadrant (features 64..127, tokens 0..31); the k-tile's one counted wait ----------------
-            if (preload) {     // first-token fragments of k-tile kt + 1 into the registers phase 2 was the last to use
-                const unsigned char* sQn = lds + (par1 * 4 + 2 + (wj >> 1)) * kSlot + (wj & 1) * 64 * 128;
-#pragma unroll
-                for (int n = 0; n < 2; ++n)
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) FY[n][kk] = *reinterpret_cast<const vec8*>(sQn + swz(n * 16 + frow, kk * 4 + g));
-            }
-            if (do2) {
-                issue(par * 4 + 3, false, s2, 1, k2);
-                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // all of k-tile kt + 1 has landed (only this k-tile's two Q refills may be in flight)
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            if (FBALT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -287,13 +222,15 @@ __device__ __forceinline__ void gemm16_256_body(ARGS a, int nI, int nJ, int spli
             __builtin_amdgcn_s_barrier();
         };
         vec8 fbA[2][2], fbB[2][2];
-        ktile(0, fbA, fbB, std::false_type{}, std::false_type{});      // (nkt is even and >= 2: the launcher)
-        ktile(1, fbB, fbA, std::false_type{}, std::true_type{});
+        // (the last argument only gives k-tiles 0, 1 and the steady-state pair a copy of the body each, as the measured kernel has them: as ONE
+        //  function with four call sites the compiler lays the k-loop out differently)
+        ktile(0, fbA, fbB, std::integral_constant<int, 0>{});      // (nkt is even and >= 2: the launcher)
+        ktile(1, fbB, fbA, std::integral_constant<int, 1>{});
         for (int kt = 2; kt < nkt; kt += 2) {
-            ktile(kt, fbA, fbB, std::true_type{}, std::true_type{});
-            ktile(kt + 1, fbB, fbA, std::true_type{}, std::true_type{});
+            ktile(kt, fbA, fbB, std::integral_constant<int, 2>{});
+            ktile(kt + 1, fbB, fbA, std::integral_constant<int, 2>{});
         }
-        if (STAGGER && wi == 0) __builtin_amdgcn_s_barrier();
+        if (wi == 0) __builtin_amdgcn_s_barrier();
 #ifdef UMGEN_G256_STAMPS
         st_t1 = wall_clock64();
         st_main += st_t1 - st_t0;

@@ -24,13 +24,11 @@ typedef float f32x4v_t __attribute__((ext_vector_type(4)));
 // (NT = false when several workgroups of one XCD read the same rows: one scene per workgroup, the others hit the L2)
 template <bool NT = true>
 __device__ inline void wload(WChunk<bf16_t>& w, const bf16_t* p) {
-#ifndef UMGEN_NO_NT
     if (NT) {
         const u32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
         w.v = make_uint4(t.x, t.y, t.z, t.w);
         return;
     }
-#endif
     w.v = *reinterpret_cast<const uint4*>(p);
 }
 template <bool NT = true>
@@ -41,7 +39,6 @@ __device__ inline void wload(WChunk<f16_t>& w, const f16_t* p) {
 }
 template <bool NT = true>
 __device__ inline void wload(WChunk<float>& w, const float* p) {
-#ifndef UMGEN_NO_NT
     if (NT) {
         const f32x4v_t a = __builtin_nontemporal_load(reinterpret_cast<const f32x4v_t*>(p));
         const f32x4v_t b = __builtin_nontemporal_load(reinterpret_cast<const f32x4v_t*>(p + 4));
@@ -49,7 +46,6 @@ __device__ inline void wload(WChunk<float>& w, const float* p) {
         w.b = make_float4(b.x, b.y, b.z, b.w);
         return;
     }
-#endif
     w.a = *reinterpret_cast<const float4*>(p);
     w.b = *reinterpret_cast<const float4*>(p + 4);
 }
@@ -203,9 +199,6 @@ __device__ __forceinline__ void gemv_ln_body(const GemvArgs& a, int bid) {
 
 template <typename T, int MB, int NCH, int RPW, bool PERROW = false>
 __global__ __launch_bounds__(256) void gemv_ln_kernel(GemvArgs a) {
-#ifdef UMGEN_DRY_DECODE
-    return;   // launch-floor experiment: same graph, no work
-#endif
     gemv_ln_body<T, MB, NCH, RPW, PERROW>(a, blockIdx.x);
 }
 
@@ -241,9 +234,6 @@ template void launch_gemv<f16_t>(hipStream_t, const GemvArgs&);
 
 template <typename T, int MB, int NCH, bool COMBINE, bool PERROW = false>
 __global__ __launch_bounds__(256) void gemv_resid_kernel(GemvResidArgs a_in) {
-#ifdef UMGEN_DRY_DECODE
-    return;
-#endif
     extern __shared__ __attribute__((aligned(16))) float as[];   // [M][K] when COMBINE
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     GemvResidArgs a = a_in;
@@ -546,9 +536,6 @@ __device__ __forceinline__ void attn_body(const AttnGeom& g, int h, int split, i
 
 template <typename T>
 __global__ __launch_bounds__(256) void attn_partial_kernel(AttnGeom g) {
-#ifdef UMGEN_DRY_DECODE
-    return;
-#endif
     attn_body<T>(g, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 

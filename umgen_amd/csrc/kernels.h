@@ -175,12 +175,8 @@ template <typename TT> void launch_attn_decode_batched(hipStream_t s, const floa
 // XCD-resident decode engine (oar_engine.hip): all BlockOAR layers of one decode step in one launch, bf16 weights, n_embd 768
 // ------------------------------------------------------------------------------------------------
 constexpr int kEngE = 768, kEngH = 16;         // the width the engine is built for (UMGen_Large); other widths use the launches above
-// UMGEN_ENG_MFMA: which of the decode engine's row dot products run on the matrix cores (oar_engine.hip; bits: 1 q|k|v rows, 2 c_proj rows,
-// 4 c_fc rows, 8 mlp partial sums, 16 attention -- correct, but its 32-key register buffers leave room for one only: slower, off).  Bit 4 adds a fragment-ordered copy of c_fc, bit 8 changes the repacked mlp c_proj layout (engine.hip).
-// Measured (profiles/r03_engine_experiments.txt, sessions N-R): 12 is the best set -- 441 vs 462 us per launch at one scene, 710 vs 743 at eight
-#ifndef UMGEN_ENG_MFMA
-#define UMGEN_ENG_MFMA 12
-#endif
+// Of the decode engine's row dot products the c_fc rows and the mlp partial sums run on the matrix cores (oar_engine.hip); q|k|v rows, c_proj rows and the
+// attention on the VALU.  Measured (profiles/r03_engine_experiments.txt, sessions N-R): the best set -- 441 vs 462 us per launch at one scene, 710 vs 743 at eight
 constexpr int kEngThreads = 512;               // one workgroup per CU
 constexpr int kEngGroup = 32;                  // workgroups per group == CUs per XCD
 constexpr int kEngWpUnits = 18;                // 16-byte units of the repacked mlp c_proj slice per thread (12 of its full row + 6 of a shared row)
@@ -189,14 +185,15 @@ struct OarLayerDev {                           // one BlockOAR's parameters (mod
     const bf16_t *Wqkv, *Wo, *Wfc, *Wproj;
     const bf16_t *Wp2;                         // mlp c_proj repacked for the hidden-unit split: [32 CUs][18 units][512 threads][8] (engine.hip repack_mlp_proj)
     const float *bqkv, *bo, *ln_a, *ln_b;
-    const bf16_t *Wf2;                         // UMGEN_ENG_MFMA & 4: c_fc as matrix-core fragments [32 CUs][8 waves][6 tiles x 3 k-steps][64 lanes][8] (1 KB per request)
+    const bf16_t *Wf2;                         // c_fc as matrix-core fragments [32 CUs][8 waves][6 tiles x 3 k-steps][64 lanes][8] (1 KB per request)
 };
 struct OarState;
 struct BgQueue;
 struct OarEngineArgs {
     const OarLayerDev* layers; int n_layers;
     bf16_t* kvcache; long kv_layer_stride, kv_scene_stride; int Lmax;   // [layer][scene][2][H][Lmax][48]
-    bf16_t* vtcache; long vt_layer_stride, vt_scene_stride;             // UMGEN_ENG_MFMA & 16: V once more, dim-major [layer][scene][H][48][Lmax]
+    long unused_[3];                           // always 0.  24 bytes a removed variant's arguments occupied (commit 539b5b8): the offsets of the fields below,
+                                               // and with them the engine kernel's scalar-load schedule, stay those of the measured kernel
     float* xdec;                               // [B][E]: in = input of layer 0, out = output of the last layer
     const OarState* st;                        // step (cached keys) and epoch of the hand-off tags
     unsigned long long* gx;                    // [max_batch][E] cross-group x granules
@@ -223,10 +220,7 @@ struct OarEngineArgs {
 // ------------------------------------------------------------------------------------------------
 constexpr int kWideE = 1536;                   // the width this engine is built for (configs[4]: 2x UMGen_Large)
 constexpr int kWideGroups = 256;               // workgroups = ranks (one per CU)
-#ifndef UMGEN_WIDE_SPLITS
-#define UMGEN_WIDE_SPLITS 4
-#endif
-constexpr int kWideSplits = UMGEN_WIDE_SPLITS; // key splits per head in the attention phase: 4 = ranks 0..15 of an XCD (8 = every rank: 30 us per step slower below 1500 keys, 30 faster at 2200)
+constexpr int kWideSplits = 4;                 // key splits per head in the attention phase: 4 = ranks 0..15 of an XCD (8 = every rank: 30 us per step slower below 1500 keys, 30 faster at 2200)
 struct OarWideArgs {
     const OarLayerDev* layers; int n_layers;   // Wp2: mlp c_proj repacked [256 ranks][1536 rows][24 hidden units of the rank] (engine.hip repack_wide)
     bf16_t* kvcache; long kv_layer_stride, kv_scene_stride; int Lmax;   // [layer][scene][2][H][Lmax][48]

@@ -48,17 +48,9 @@ __device__ inline void wg_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// Polling with TWO requests of every granule in flight, half a round trip apart.  With one (round 2) a poll that just misses the
-// producer's store costs a whole further round trip (L2: ~0.7 us, another XCD: ~1.5 us), on average half of one per hand-off and five
-// hand-offs per layer; a wave's loads return in order, so `check(older)` waits for the older request only (s_waitcnt vmcnt(PER)) and
-// the next one leaves as soon as it is back: the initial stagger sustains itself.  Loads are unconditional (granules already
-// received are simply requested again) so that the loop is straight-line code and the wait counts are exact.
-#ifndef UMGEN_ENG_POLL2
-#define UMGEN_ENG_POLL2 0
-#endif
-#ifndef UMGEN_ENG_POLL_STAGGER
-#define UMGEN_ENG_POLL_STAGGER 6      // s_sleep units of 64 clocks between the first two requests
-#endif
+// One request of every granule in flight per round.  (Two, half a round trip apart, were measured in round 3 and lost; removed, commit
+// 539b5b8 is the last tree that builds that form.)  Loads are unconditional (granules already received are simply requested again) so
+// that the loop is straight-line code.
 // slot k of thread tid (bit k of need) waits for granule idx(k) and writes its value to dst[tid + k * NT]
 template <int PER, typename IDX>
 __device__ inline void poll_granules(Ctx& c, int tid, const u64* g, u32 need, IDX idx, u32 tag, float* dst) {
@@ -67,7 +59,7 @@ __device__ inline void poll_granules(Ctx& c, int tid, const u64* g, u32 need, ID
     u32 ix[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) ix[k] = idx(k);
-    u64 va[PER], vb[PER];
+    u64 va[PER];
     auto issue = [&](u64 (&v)[PER]) {
 #pragma unroll
         for (int k = 0; k < PER; ++k) v[k] = get(g, ix[k]);
@@ -79,17 +71,9 @@ __device__ inline void poll_granules(Ctx& c, int tid, const u64* g, u32 need, ID
         return !__any(got != need);
     };
     issue(va);
-    if (UMGEN_ENG_POLL2) __builtin_amdgcn_s_sleep(UMGEN_ENG_POLL_STAGGER);
     for (u32 spins = 0;;) {
-        if (UMGEN_ENG_POLL2) {
-            issue(vb);
-            if (check(va)) break;
-            issue(va);
-            if (check(vb)) break;
-        } else {
-            if (check(va)) break;
-            issue(va);
-        }
+        if (check(va)) break;
+        issue(va);
         if (++spins > kSpinLimit) { if ((tid & 63) == 0) atomicExch(c.err, tag | 0x80000000u); c.failed = true; break; }
         if ((spins & 255u) == 0 && __hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { c.failed = true; break; }
     }
@@ -166,20 +150,11 @@ __device__ inline void load8p(const float* p, f32x2_t (&o)[4]) {
 }
 
 // Attention lane mapping: LPK lanes per key, KPW keys per wave pass; a lane holds 12 of a key's 48 values: 16 bytes + 8 bytes
-#ifndef UMGEN_ENG_KP
-#define UMGEN_ENG_KP 1
-#endif
-#ifndef UMGEN_ENG_NBM
-#define UMGEN_ENG_NBM 2        // matrix-core attention: register buffers of 32 keys (28 VGPRs each)
-#endif
-#ifndef UMGEN_ENG_NB
-// measured (profiles/r03_engine_experiments.txt): VALU row products 2: 476 us per launch, 3: 476, 4: 471, 5 (15 spilled VGPRs): 504; with the c_fc
-// rows as matrix-core fragments (aligned register tuples) 4 buffers spill 8 VGPRs (462 us), 3 do not (443)
-#define UMGEN_ENG_NB ((UMGEN_ENG_MFMA & 4) ? 3 : 4)
-#endif
-#ifndef UMGEN_ENG_NB_SYS
-#define UMGEN_ENG_NB_SYS 3    // the systolic kernel keeps more of a layer live: 4 buffers spill 2-4 VGPRs there
-#endif
+constexpr int kEngKP = 1;       // 16-key passes per register buffer
+// register buffers of keys in flight.  Measured (profiles/r03_engine_experiments.txt): VALU row products 2: 476 us per launch, 3: 476, 4: 471,
+// 5 (15 spilled VGPRs): 504; with the c_fc rows as matrix-core fragments (aligned register tuples) 4 buffers spill 8 VGPRs (462 us), 3 do not (443)
+constexpr int kEngNB = 3;
+constexpr int kEngNBSys = 3;    // the systolic kernel keeps more of a layer live: 4 buffers spill 2-4 VGPRs there
 constexpr int LPK = 4, KPW = 64 / LPK;
 typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
 struct KVPiece {
@@ -223,26 +198,14 @@ __device__ inline float wave_sum_all(float v) {
 }
 
 template <int NTILE> struct WFrags { u32x4_t f[NTILE][3]; };
-template <int NTILE, bool KEEP, int T0 = 0, int T1 = NTILE>
-__device__ inline void req_frags(WFrags<NTILE>& w, const bf16_t* W, int row0, int nvalid, int wave, int lane) {
-    const bf16_t* base = W + (long)row0 * E + 96 * wave;
-#pragma unroll
-    for (int t = T0; t < T1; ++t) {
-        const u32 ro = (u32)min(16 * t + (lane & 15), nvalid - 1) * (u32)E + (u32)(lane >> 4) * 8u;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) w.f[t][j] = KEEP ? ldwk(base, ro + 32u * j) : ldwu(base, ro + 32u * j);
-    }
-}
-// the same fragments out of a repacked copy [..][NTILE x 3 fragments][64 lanes][8]: 1 KB contiguous per request
-template <int NTILE, bool KEEP, int T0 = 0, int T1 = NTILE>
+// fragment (tile t, k-step j) of lane l: 8 weights of row 16 t + l % 16, k 96 wave + 32 j + 8 (l / 16) .., out of a repacked copy
+// [..][NTILE x 3 fragments][64 lanes][8]: 1 KB contiguous per request
+template <int NTILE>
 __device__ inline void req_frags_packed(WFrags<NTILE>& w, const bf16_t* P, int lane) {
 #pragma unroll
-    for (int t = T0; t < T1; ++t)
+    for (int t = 0; t < NTILE; ++t)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const u32 off = (u32)((3 * t + j) * 64 + lane) * 8u;
-            w.f[t][j] = KEEP ? ldwk(P, off) : ldwu(P, off);
-        }
+        for (int j = 0; j < 3; ++j) w.f[t][j] = ldwu(P, (u32)((3 * t + j) * 64 + lane) * 8u);
 }
 // value -> (hi, lo) in the operand type, as raw 16-bit patterns
 template <typename TT>
@@ -270,13 +233,10 @@ __device__ inline void poll_wait(u64 (&v)[PER]) {
 #pragma unroll
     for (int k = 0; k < PER; ++k) asm volatile("" : "+v"(v[k]));     // (the values are defined behind the wait, not behind the request)
 }
-// slot k of thread tid (bit k of need) waits for granule idx(k) with `tag` and hands its value to sink(k, value).  Round 1 requests every
-// slot; while something is missing a lane asks for ONE of its missing granules per round with a short sleep in between (the gathers
-// of this engine are up to 12 granules per thread and 32 CUs: polling all of them would put 1.5 MB per round on the L2 / the fabric
-// while a group waits for its predecessor), then requests all its missing slots again.
-// ALL: every round requests every slot again (one round trip behind the producers; for the hand-offs at which the whole group
-// is waiting anyway -- nobody's K/V stream shares the L2 with the polls).
-template <int PER, bool ALL = false, typename IDX, typename SINK>
+// slot k of thread tid (bit k of need) waits for granule idx(k) with `tag` and hands its value to sink(k, value).  Every round requests
+// every slot again: one round trip behind the producers (the whole chip is waiting at these hand-offs anyway -- nobody's K/V stream
+// shares the L2 with the polls).
+template <int PER, typename IDX, typename SINK>
 __device__ inline void poll_ms(Ctx& c, int tid, const u64* g, u32 need, IDX idx, u32 tag, SINK sink) {
     if (c.failed || !__any(need != 0u)) return;
     g = uniform_ptr(g);
@@ -290,66 +250,9 @@ __device__ inline void poll_ms(Ctx& c, int tid, const u64* g, u32 need, IDX idx,
         for (int k = 0; k < PER; ++k)
             if ((((need & ~got) >> k) & 1u) && (u32)(v[k] >> 32) == tag) { sink(k, __uint_as_float((u32)v[k])); got |= 1u << k; }
         if (!__any(got != need)) break;
-        if (ALL) {
-            if (++spins > kSpinLimit / 8) { if ((tid & 63) == 0) atomicExch(c.err, tag | 0x80000000u); c.failed = true; break; }
-            if ((spins & 63u) == 0 && __hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { c.failed = true; break; }
-            continue;
-        }
-        // one missing granule per lane until it is there (lanes that have everything re-read a slot of theirs)
-        const u32 miss = need & ~got;
-        const u32 i1 = idx(miss ? __ffs((int)miss) - 1 : 0);
-        for (;;) {
-            __builtin_amdgcn_s_sleep(2);
-            u64 v1[1];
-            poll_issue(v1[0], g, i1);
-            poll_wait<1>(v1);
-            if (!__any(miss != 0u && (u32)(v1[0] >> 32) != tag)) break;
-            if (++spins > kSpinLimit) { if ((tid & 63) == 0) atomicExch(c.err, tag | 0x80000000u); c.failed = true; break; }
-            if ((spins & 255u) == 0 && __hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { c.failed = true; break; }
-        }
-        if (c.failed) break;
-    }
-}
-
-// The same hand-off with TWO requests of every slot in flight, `stagger` x 64 clocks apart (half a fabric round trip): a request that just misses the
-// producer's store is followed by one half a round trip behind it instead of a whole one.  A wave's loads return in order: s_waitcnt vmcnt(PER) is "the
-// older set is back".  Every round requests every slot (exact counts); both sets are drained before the registers are given back.
-template <int PER, typename IDX, typename SINK>
-__device__ inline void poll_stag(Ctx& c, int tid, const u64* g, u32 need, IDX idx, u32 tag, int stagger, SINK sink) {
-    if (c.failed || !__any(need != 0u)) return;
-    g = uniform_ptr(g);
-    u32 got = 0;
-    u64 va[PER], vb[PER];
-    auto issue = [&](u64 (&v)[PER]) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k) poll_issue(v[k], g, idx(k));
-    };
-    auto older_back = [&](u64 (&v)[PER]) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-#pragma unroll
-        for (int k = 0; k < PER; ++k) asm volatile("" : "+v"(v[k]));
-    };
-    auto check = [&](const u64 (&v)[PER]) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k)
-            if ((((need & ~got) >> k) & 1u) && (u32)(v[k] >> 32) == tag) { sink(k, __uint_as_float((u32)v[k])); got |= 1u << k; }
-        return !__any(got != need);
-    };
-    issue(va);
-    for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(1);
-    for (u32 spins = 0;;) {
-        issue(vb);
-        older_back(va);
-        if (check(va)) break;
-        issue(va);
-        older_back(vb);
-        if (check(vb)) break;
         if (++spins > kSpinLimit / 8) { if ((tid & 63) == 0) atomicExch(c.err, tag | 0x80000000u); c.failed = true; break; }
         if ((spins & 63u) == 0 && __hip_atomic_load(c.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { c.failed = true; break; }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { asm volatile("" : "+v"(va[k])); asm volatile("" : "+v"(vb[k])); }
 }
 
 }  // namespace

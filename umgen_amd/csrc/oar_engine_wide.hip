@@ -20,7 +20,7 @@
 //   Hand-offs are 8-byte {tag, value} granules: inside the XCD's L2 0.8-1.0 us, across the fabric 2.1-2.3 us PROVIDED the producer writes whole 64-byte
 //   pieces with one store instruction (x and x' live in one 128-byte line per rank for that; 8-byte stores of six waves into shared sectors: 3.5-5.3 us).
 //   Requests: a poll's answer queues behind whatever the XCD's link still has to deliver -- the weight groups go out as LATE as their consumer allows
-//   (UMGEN_WIDE_AT_* slots below), not as early as their registers are free.
+//   (kAt* slots below), not as early as their registers are free.
 // Arithmetic (fixed, independent of the placement): fp32 activations, 16-bit weights and K/V cache, fp32 accumulation; row dot products as in gemv.hip
 // (lane l owns k = 512 c + 8 l .. + 7, packed fp32 FMAs, wave sum); weight-only LayerNorm (eps 1e-5) with gemv.hip's statistics; exact erf-GELU; the
 // attention's new key / value out of the q|k|v exchange rounded to 16 bits.  Against the five-launch form only fp32 summation orders differ.
@@ -61,21 +61,12 @@ constexpr int W_XO = W_HS + 32;              // the six c_proj results of the wo
 constexpr int W_MISC = W_XO + 16;
 constexpr int W_TOTAL = W_MISC + 16;
 
-// Hand-off polls of the poll waves: 0 = request everything once, then one missing granule per lane until it is there, then everything missing again
-// (two fabric round trips behind the producers); 1 = every round requests every slot again (one round trip behind); 2 = the far hand-offs (x, attention
-// output, x', mlp partial sums) with two requests of every slot in flight, UMGEN_WIDE_STAGGER x 64 clocks apart (oar_common.h poll_stag)
-#ifndef UMGEN_WIDE_POLL
-#define UMGEN_WIDE_POLL 1
-#endif
-constexpr bool kPollAll = UMGEN_WIDE_POLL != 0;
-constexpr bool kPollStag = UMGEN_WIDE_POLL == 2;
-#ifndef UMGEN_WIDE_STAGGER
-#define UMGEN_WIDE_STAGGER 24
-#endif
+// Hand-off polls of the poll waves: every round requests every slot again (one fabric round trip behind the producers).  The two forms measured
+// against it -- one missing granule per lane and round; two staggered requests of every slot in flight -- were removed: commit 539b5b8 is the last
+// tree that builds them (profiles/r05_wide2x_engine.txt).
 template <typename IDX, typename SINK>
 __device__ inline void poll_far(Ctx& c, int tid, const u64* g, IDX idx, u32 tag, SINK sink) {
-    if (kPollStag) poll_stag<12>(c, tid, g, 0xfffu, idx, tag, UMGEN_WIDE_STAGGER, sink);
-    else poll_ms<12, kPollAll>(c, tid, g, 0xfffu, idx, tag, sink);
+    poll_ms<12>(c, tid, g, 0xfffu, idx, tag, sink);
 }
 // Measurement builds (tools/build_variant.sh; results are garbage, only the step time means something):
 //   UMGEN_WIDE_EXP_NOPOLL: the poll waves do not wait (a layer without its six fabric hops)
@@ -89,30 +80,13 @@ __device__ inline void poll_far(Ctx& c, int tid, const u64* g, IDX idx, u32 tag,
 // Granules per rank in the x / x' buffers: 8 / 16 = every rank writes whole 64 / 128-byte pieces with ONE store instruction (x': its six rows' results
 // collected through LDS behind one more workgroup barrier).  Compact (6 per rank: 48 bytes that share 64-byte sectors with the neighbours', written by six
 // waves' lane 0 one after the other) the x' hand-off took 5.3 us instead of 2.5 (profiles/r05_wide2x_engine.txt).
-#ifndef UMGEN_WIDE_PAD
-#define UMGEN_WIDE_PAD 16
-#endif
+constexpr int XPAD = 16;
 // Where the requests of a layer go out -- a poll's answer queues behind whatever the XCD's memory link still has to deliver, and a compute wave's loads
 // return in the order they were made.  Slots: 0 before B1 (under the x hand-off), 1 behind B1, 2 behind P1 (under q|k|v), 3 behind the keys, 4 behind B3's
 // merge (under the quarters), 5 behind B4's merge (under the attention output), 6 behind B5, 7 behind B6 (x' is there), 8 behind B7, 9 behind B8.
 // Measured (profiles/r05_wide2x_engine.txt): K/V + the c_proj row at 0, the c_fc rows at 3, the mlp slice at 5, the next layer's q|k|v rows at 7 -- "as late
 // as the registers' consumer allows" beats "as early as the registers are free": what is in the link's queue delays the polls.
-#ifndef UMGEN_WIDE_AT_KV
-#define UMGEN_WIDE_AT_KV 0
-#endif
-#ifndef UMGEN_WIDE_AT_O
-#define UMGEN_WIDE_AT_O 0
-#endif
-#ifndef UMGEN_WIDE_AT_F
-#define UMGEN_WIDE_AT_F 3
-#endif
-#ifndef UMGEN_WIDE_AT_P
-#define UMGEN_WIDE_AT_P 5
-#endif
-#ifndef UMGEN_WIDE_AT_Q
-#define UMGEN_WIDE_AT_Q 7
-#endif
-constexpr int XPAD = UMGEN_WIDE_PAD;
+constexpr int kAtKV = 0, kAtO = 0, kAtF = 3, kAtP = 5, kAtQ = 7;
 constexpr int XGR = 256 * 16;      // granules reserved for each of the x / x' buffers
 static_assert(XPAD == 8 || XPAD == 16, "x / x' granules per rank");
 __device__ inline u32 xslot(u32 n) { return (n / 6u) * (u32)XPAD + n % 6u; }
@@ -275,7 +249,7 @@ __global__ __launch_bounds__(kEngThreads) void oar_engine_wide_kernel(OarWideArg
             // hand-off 2: q_h | k_h | v_h of the attention ranks (lanes 0 .. 127: values 0 .. 127, lanes 0 .. 15 also 128 .. 143)
             if (att_rank) {
                 auto src = [&](int k) { const int e = min(pt + k * PT, 3 * kHeadDim - 1); return (u32)((e / kHeadDim) * WE + hh * kHeadDim + e % kHeadDim); };
-                if (!UMGEN_WIDE_EXP_NOPOLL) poll_ms<2, kPollAll>(c, tid, gqkv, pt < 16 ? 3u : 1u, src, tg + 1, [&](int k, float v) { qs[pt + k * PT] = v; });
+                if (!UMGEN_WIDE_EXP_NOPOLL) poll_ms<2>(c, tid, gqkv, pt < 16 ? 3u : 1u, src, tg + 1, [&](int k, float v) { qs[pt + k * PT] = v; });
             }
             wg_barrier();      // B2
             wg_barrier();      // B3
@@ -286,7 +260,7 @@ __global__ __launch_bounds__(kEngThreads) void oar_engine_wide_kernel(OarWideArg
                 u32 need = 0;
 #pragma unroll
                 for (int k = 0; k < PERQ; ++k) need |= (pt + k * PT < NREC) ? 1u << k : 0u;
-                if (!UMGEN_WIDE_EXP_NOPOLL) poll_ms<PERQ, kPollAll>(c, tid, gpart + (long)(hh * NSP) * PREC, need, src, tg + 2,
+                if (!UMGEN_WIDE_EXP_NOPOLL) poll_ms<PERQ>(c, tid, gpart + (long)(hh * NSP) * PREC, need, src, tg + 2,
                                      [&](int k, float v) { const int f = pt + k * PT; lds[W_SB + (f / (kHeadDim + 2)) * PREC + f % (kHeadDim + 2)] = v; });
             }
             wg_barrier();      // B4
@@ -350,7 +324,7 @@ __global__ __launch_bounds__(kEngThreads) void oar_engine_wide_kernel(OarWideArg
         };
         // ---------------- (hand-off 1: x) ----------------
         // (K/V of the cached keys do not depend on this layer's q: the first KG passes, 80 keys per wave = 1920 positions, are requested ahead; the passes
-        //  behind them pay a round trip each.  Where the requests go out: the UMGEN_WIDE_AT_* slots above.)
+        //  behind them pay a round trip each.  Where the requests go out: the kAt* slots above.)
         float bq[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) bq[i] = ldg(lw.bqkv + qkv_row(i));
@@ -382,11 +356,11 @@ __global__ __launch_bounds__(kEngThreads) void oar_engine_wide_kernel(OarWideArg
             for (int i = 0; i < 3; ++i) req_row(wq[i], ln.Wqkv, (long)qkv_row(i), lane);
         };
         auto at = [&](int slot) {      // (compile-time slots: each group's requests appear once)
-            if (slot == UMGEN_WIDE_AT_KV) req_kv();
-            if (slot == UMGEN_WIDE_AT_O) req_o();
-            if (slot == UMGEN_WIDE_AT_F) req_f();
-            if (slot == UMGEN_WIDE_AT_P) req_p();
-            if (slot == UMGEN_WIDE_AT_Q) req_q_next();
+            if (slot == kAtKV) req_kv();
+            if (slot == kAtO) req_o();
+            if (slot == kAtF) req_f();
+            if (slot == kAtP) req_p();
+            if (slot == kAtQ) req_q_next();
         };
         at(0);
         wg_barrier();      // B1
