@@ -336,3 +336,62 @@ def test_background_workers_with_a_long_window_and_eager_launches():
         e.close()
     for m in MOD_ORDER:
         np.testing.assert_array_equal(outs["1"][m], outs["0"][m], err_msg=m)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# launch bookkeeping of the step loops (umgen_timings): what every decode path counts per step
+# ---------------------------------------------------------------------------------------------------------------------
+def _step_kinds():
+    """Kind of every decode step of a video frame, from the token layout: step j consumes scene position j (the last position is never
+    consumed); the pose prefix is given, bos / eos are fixed tokens, the content positions of map / bbox3d / image are sampled."""
+    from umgen_amd.config import CONTENT_LEN, MOD_START, SEQ_LEN, TOKEN_LEN
+    kinds = []
+    for j in range(SEQ_LEN - 1):
+        kind = "fixed"
+        for m in MOD_ORDER[1:]:
+            if j >= TOKEN_LEN["pose"] and MOD_START[m] + 1 <= j < MOD_START[m] + 1 + CONTENT_LEN[m]:
+                kind = m
+        kinds.append(kind)
+    return kinds
+
+
+LANES_B = 25      # the smallest batch the lane tests above decode
+
+
+@pytest.mark.parametrize("path", ["launches", "engine", "batched_1_lane", "batched_2_lanes"])
+def test_step_and_launch_counters_follow_the_token_layout(setup, path):
+    """Two frames of a video rollout on each decode path: umgen_timings counts one step per consumed scene position and, per step, the
+    launches of the path's layers (five per layer; one for the XCD-resident engine) plus those behind them -- the fixed token's one,
+    head + sampler for map / image, head + sampler + box decode for bbox3d.  Every lane counts its own launches."""
+    cfg, sd = setup
+    frames = 2
+    old = {k: os.environ.get(k) for k in ("UMGEN_BG_ENGINE", "UMGEN_DECODE_LANES")}
+    try:
+        if path == "launches":
+            B, lanes, e = 1, 0, make(cfg, sd, engine_on=False)
+        elif path == "engine":
+            os.environ["UMGEN_BG_ENGINE"] = "0"
+            B, lanes, e = 1, 0, make(cfg, sd, engine_on=True)
+        else:
+            B, lanes = LANES_B, 1 if path == "batched_1_lane" else 2
+            os.environ["UMGEN_DECODE_LANES"] = str(lanes)
+            e = make_batched(cfg, sd, 1, max_batch=B)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    scenes = [synthetic_scene(40 + i, n_frames=2) for i in range(B)]
+    e.rollout({m: np.concatenate([s[m] for s in scenes]) for m in MOD_ORDER}, frames, cond_frames=3, input_cond_frames=2, seeds=list(range(B)))
+    t = e.timings()
+    e.close()
+    kinds = _step_kinds()
+    per_layers = 1 if path == "engine" else 5 * cfg.n_oar_layer
+    behind = {"fixed": 1, "map": 2, "bbox3d": 3, "image": 2}
+    want_kernels = frames * max(lanes, 1) * sum(per_layers + behind[k] for k in kinds)
+    print(f"{path}: oar_steps {t['oar_steps']} (want {frames * len(kinds)}), oar_kernels {t['oar_kernels']} (want {want_kernels}), "
+          f"engine {t['decode_engine']} batched {t['decode_batched']} lanes {t['decode_lanes']}")
+    assert t["oar_steps"] == frames * len(kinds)
+    assert t["oar_kernels"] == want_kernels
+    assert (t["decode_engine"], t["decode_batched"], t["decode_lanes"]) == ((1, 0, 0) if path == "engine" else (0, 1 if lanes else 0, lanes))

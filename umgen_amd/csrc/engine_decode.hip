@@ -1,0 +1,243 @@
+// One decode step: the BlockOAR layers on whichever path takes the step (batched layer, chip-wide engine, XCD-resident engine, five
+// launches per layer), the head and sampler behind them, a decode lane's view of the engine, and the one-step test hook.
+#include "engine_state.h"
+
+// host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
+#pragma clang fp contract(off)
+
+namespace {
+
+// one OAR decode step through the 36 BlockOAR layers (module.py:402-416) for the B scenes
+template <typename T>
+int oar_layers(umgen_engine* e, int B, int ns) {
+    const int E = e->E, H = e->H;
+    const int* d_len = &e->d_state->step;
+    if constexpr (sizeof(T) == 2) {
+        if (e->use_batched(B)) {      // five launches per layer for the whole batch: LN + q|k|v, attention, c_proj (+x), LN + c_fc + GELU, mlp c_proj (+x)
+            // activations between the launches are fragment-major (decode_batched.hip); x also stays row-major in xdec (sampler, residual)
+            launch_rows_to_frag(e->stream, e->xdec, E, B, E, e->xfrag);
+            for (size_t li = 0; li < e->oar.size(); ++li) {
+                const SubW& w = e->oar[e->dbg_same_layer ? 0 : li];
+                T* cache = reinterpret_cast<T*>(e->kvcache) + (long)li * e->kv_layer_stride;
+                RowsArgs r{};
+                r.x = e->xfrag; r.M = B; r.ln_w = w.ln_a; r.W = w.attn.Wqkv; r.bias = w.attn.bqkv; r.N = 3 * E; r.K = E; r.mode = ROWS_QKV;
+                r.out = e->qdec; r.ldo = E; r.cache = cache; r.scene_stride = e->kv_scene_stride; r.d_len = d_len; r.Lmax = e->Lmax; r.E = E;
+                launch_rows_mfma<T>(e->stream, r);
+                launch_attn_decode_batched<T>(e->stream, e->qdec, cache, e->kv_scene_stride, B, H, e->Lmax, d_len, e->afrag);
+                RowsArgs p{};
+                p.x = e->afrag; p.M = B; p.W = w.attn.Wo; p.bias = w.attn.bo; p.N = E; p.K = E; p.mode = ROWS_RESID; p.out = e->xdec; p.ldo = E; p.out_frag = e->xfrag; p.E = E;
+                launch_rows_mfma<T>(e->stream, p);
+                RowsArgs f{};
+                f.x = e->xfrag; f.M = B; f.ln_w = w.ln_b; f.W = w.mlp.Wfc; f.N = 4 * E; f.K = E; f.mode = ROWS_GELU; f.out_frag = e->hfrag; f.E = E;
+                launch_rows_mfma<T>(e->stream, f);
+                RowsArgs q{};
+                q.x = e->hfrag; q.M = B; q.W = w.mlp.Wproj; q.N = E; q.K = 4 * E; q.mode = ROWS_RESID; q.out = e->xdec; q.ldo = E; q.out_frag = e->xfrag; q.E = E;
+                launch_rows_mfma<T>(e->stream, q);
+            }
+            return 0;
+        }
+    }
+    if (sizeof(T) == 2 && e->use_wide(B)) {
+        OarWideArgs a{};
+        a.layers = e->d_layers_wide; a.n_layers = (int)e->oar.size();
+        a.kvcache = reinterpret_cast<bf16_t*>(e->kvcache); a.kv_layer_stride = e->kv_layer_stride; a.kv_scene_stride = e->kv_scene_stride; a.Lmax = e->Lmax;
+        a.xdec = e->xdec; a.st = e->d_state; a.gran = e->wide_gran; a.ticket = e->wide_ticket; a.err = e->wide_err;
+        a.fp16 = std::is_same<T, f16_t>::value ? 1 : 0;
+        a.stamps = e->wide_stamps;
+        for (int b = 0; b < B; ++b) {
+            a.scene = b;
+            HIPCHK(e, launch_oar_engine_wide(e->stream, a));
+        }
+        return 0;
+    }
+    if (const umgen_engine::EngStream* es = sizeof(T) == 2 ? e->eng_for(e->stream) : nullptr) {
+        OarEngineArgs a{};
+        a.layers = e->d_layers; a.n_layers = (int)e->oar.size();
+        a.kvcache = reinterpret_cast<bf16_t*>(e->kvcache); a.kv_layer_stride = e->kv_layer_stride; a.kv_scene_stride = e->kv_scene_stride; a.Lmax = e->Lmax;
+        a.xdec = e->xdec; a.st = e->d_state; a.gx = e->eng_gx; a.gloc = e->eng_gloc; a.ticket = e->eng_ticket; a.err = e->eng_err;
+        a.B = B; a.NG = es->NG;
+        a.R = es->NG;
+        for (int r = 1; r <= es->NG; ++r)
+            if (es->NG % r == 0 && r >= std::min(B, es->NG)) { a.R = r; break; }
+        if (const char* dd = getenv("UMGEN_DEBUG_ENGINE_D")) {   // debugging: fewer groups per scene than the batch size asks for
+            const int want = atoi(dd);
+            if (want >= 1 && es->NG % want == 0 && es->NG / want >= std::min(B, es->NG)) a.R = es->NG / want;
+        }
+        a.D = es->NG / a.R;
+        if (e->bg_engine && B == 1 && es->NG == 8 && !e->eng_stamps) {      // one scene on 4 XCD groups, the other 4 XCDs' workgroups are background workers (bg_worker.h)
+            a.R = 2; a.D = 4;
+            a.bg = e->d_bgq;
+        }
+        memcpy(a.xcc_group, es->map, 16);
+        if (const char* bs = getenv("UMGEN_DEBUG_BURN")) {      // measurement builds (-DUMGEN_ENG_BURN): "us,mfma,sleep,kb"
+            int us = 0, mf = 0, sl = 0, kb = 0;
+            if (sscanf(bs, "%d,%d,%d,%d", &us, &mf, &sl, &kb) >= 1) {
+                a.burn_ticks = us * 100; a.burn_mfma = mf; a.burn_sleep = sl; a.burn_kb = e->burn_buf ? kb : 0; a.burn_buf = e->burn_buf;
+            }
+        }
+        a.stamps = e->eng_stamps;
+        a.fp16 = std::is_same<T, f16_t>::value ? 1 : 0;
+        // More than 4 scenes: the systolic schedule (oar_engine.hip) -- the scenes flow through the 8 groups, group g working on layers
+        // g, g + 8, ...; up to 4 scenes keep disjoint group sets per scene (8 / 4 / 2 groups each), whose per-scene latency is lower.
+        // Measured (profiles/r03_systolic.txt): 5 scenes 704 vs 1014 us per step, 8 scenes 1034 vs 1037 us (the register file cannot
+        // keep a layer resident, so every item still streams 11 of its 14 MB).  UMGEN_ENGINE_SYSTOLIC=0/1 forces either form.
+        static const char* sys_env = getenv("UMGEN_ENGINE_SYSTOLIC");
+        a.systolic = sys_env ? (sys_env[0] == '1' && B > 1) : (B > 4);
+        if (a.systolic && B > kEngMaxSystolic) a.systolic = 0;
+        // hand-off tags of one step: (round or scene, layer, edge) must fit kEpochPerStep (umgen_create bounds n_oar_layer and max_batch)
+        const int slots = a.systolic ? B : (B + a.R - 1) / a.R;
+        if ((unsigned)(slots * 64 * 8) > kEpochPerStep) return e->fail(UMGEN_E_UNSUPPORTED, "decode engine: %d scenes need more hand-off tags than one step has", B);
+        HIPCHK(e, launch_oar_engine(e->stream, a));
+        return 0;
+    }
+    for (size_t li = 0; li < e->oar.size(); ++li) {
+        const SubW& w = e->oar[e->dbg_same_layer ? 0 : li];
+        DecodeLayerArgs d{};
+        d.ln_a = w.ln_a; d.Wqkv = w.attn.Wqkv; d.bqkv = w.attn.bqkv; d.Wo = w.attn.Wo; d.bo = w.attn.bo; d.ln_b = w.ln_b; d.Wfc = w.mlp.Wfc;
+        d.Wproj = w.mlp.Wproj; d.x = e->xdec; d.q = e->qdec; d.h = e->hdec; d.part = e->part;
+        d.cache = reinterpret_cast<T*>(e->kvcache) + (long)li * e->kv_layer_stride; d.scene_stride = e->kv_scene_stride; d.Lmax = e->Lmax;
+        d.d_len = d_len; d.B = B; d.E = E; d.H = H; d.ns = ns; d.rows_per_block = rows_per_block_for(e, B);
+        launch_decode_layer<T>(e->stream, d);
+    }
+    return 0;
+}
+
+// kernels of one decode step of kind mod (0 fixed token, 1 map, 2 bbox3d, 3 image) for B scenes
+template <typename T>
+int enqueue_step(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j) {
+    const int E = e->E;
+    hipStream_t st = e->stream;
+    const bool time_layers = e->profiling && !e->in_capture && !e->in_lanes;
+    if (time_layers) {
+        if (e->layer_ev_used == e->layer_ev.size()) {
+            hipEvent_t a0, a1;
+            hipEventCreate(&a0);
+            hipEventCreate(&a1);
+            e->layer_ev.emplace_back(a0, a1);
+        }
+        hipEventRecord(e->layer_ev[e->layer_ev_used].first, st);
+    }
+    if (int rc = oar_layers<T>(e, B, ns)) return rc;
+    if (time_layers) hipEventRecord(e->layer_ev[e->layer_ev_used++].second, st);
+    static FILE* dump = getenv("UMGEN_DEBUG_DUMP_X") ? fopen(getenv("UMGEN_DEBUG_DUMP_X"), "wb") : nullptr;   // debugging only (eager launches)
+    if (dump && tr == nullptr && !e->cfg.use_graphs) {
+        std::vector<float> hx((size_t)E);
+        hipMemcpyAsync(hx.data(), e->xdec, (size_t)E * 4, hipMemcpyDeviceToHost, st);
+        hipStreamSynchronize(st);
+        fwrite(hx.data(), 4, E, dump);
+        fflush(dump);
+    }
+    SampleArgs sa{};
+    sa.st = e->d_state; sa.tb = e->tb; sa.logits = e->logits; sa.logits_tar = e->logits_tar; sa.ld_logits = 8192; sa.ld_tar = e->cfg.bbox3d_vocab;
+    sa.cond = e->cond; sa.x_next = e->xdec; sa.tokens = e->d_tokens; sa.prev_box = e->d_prev_box; sa.control_slot = e->d_control;
+    sa.boxes = e->d_boxes; sa.n_boxes = e->d_nboxes; sa.seeds = e->d_seeds; sa.forced = e->d_forced; sa.counters = e->d_counters;
+    if (mod == 0) {
+        launch_fixed_token(st, sa, B);
+    } else {
+        const void* head = mod == 1 ? e->head_ar_map : (mod == 2 ? e->head_ar_box : e->head_ar_img);
+        const int V = mod == 1 ? e->cfg.map_vocab : (mod == 2 ? e->cfg.bbox3d_vocab : e->cfg.img_vocab);
+        bool head_done = false;
+        if constexpr (sizeof(T) == 2) {
+            if (e->use_batched(B)) {
+                RowsArgs r{};
+                r.x = e->xfrag; r.M = B; r.ln_w = e->ln_oar; r.W = head; r.N = V; r.K = E; r.mode = ROWS_F32; r.out = e->logits; r.ldo = sa.ld_logits; r.E = E;   // (xfrag: the last layer's copy of x)
+                launch_rows_mfma<T>(e->stream, r);
+                head_done = true;
+            }
+        }
+        if (!head_done) gemv_any(e, e->xdec, E, e->ln_oar, head, nullptr, V, E, B, GEMV_OUT_F32, e->logits, sa.ld_logits);
+        // (head_tar_bbox3d on the conditioning rows, UMGen.py:1087,1103: the rows do not depend on the decoded tokens, so all 660
+        //  positions were multiplied once before the loop -- tar_head_logits -- instead of one GEMV launch per bbox3d step)
+        if (tr) {
+            float* dst = mod == 1 ? tr->logits_map : (mod == 2 ? tr->logits_bbox3d : tr->logits_image);
+            const int k = mod == 1 ? j - kMapC0 : (mod == 2 ? j - kBoxC0 : j - kImgC0);
+            if (dst) HIPCHK(e, hipMemcpyAsync(dst + (size_t)k * V, e->logits, (size_t)V * 4, hipMemcpyDeviceToHost, st));
+        }
+        sa.mod = mod;
+        sa.vocab = V;
+        launch_sample_token(st, sa, B);
+    }
+    return 0;
+}
+
+}  // namespace
+
+namespace umgen {
+
+DecView current_view(const umgen_engine* e) {
+    return DecView{e->stream, e->xdec, e->qdec, e->logits, e->logits_tar, e->cond, e->xfrag, e->afrag, e->hfrag, e->kvcache,
+                   e->d_tokens, e->d_prev_box, e->d_nboxes, e->d_control, e->d_boxes, e->d_seeds, e->d_state};
+}
+void apply_view(umgen_engine* e, const DecView& v) {
+    e->stream = v.stream; e->xdec = v.xdec; e->qdec = v.qdec; e->logits = v.logits; e->logits_tar = v.logits_tar; e->cond = v.cond;
+    e->xfrag = v.xfrag; e->afrag = v.afrag; e->hfrag = v.hfrag; e->kvcache = v.kvcache; e->d_tokens = v.d_tokens; e->d_prev_box = v.d_prev_box;
+    e->d_nboxes = v.d_nboxes; e->d_control = v.d_control; e->d_boxes = v.d_boxes; e->d_seeds = v.d_seeds; e->d_state = v.d_state;
+}
+DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine::DecLane& ln, int b0) {
+    const long E = e->E;
+    DecView v = all;
+    v.stream = ln.s; v.d_state = ln.st; v.xfrag = ln.xfrag; v.afrag = ln.afrag; v.hfrag = ln.hfrag;
+    v.xdec = all.xdec + b0 * E; v.qdec = all.qdec + b0 * E; v.logits = all.logits + (long)b0 * 8192;
+    v.logits_tar = all.logits_tar + (long)b0 * kNBox * e->cfg.bbox3d_vocab; v.cond = all.cond + (long)b0 * kSeq * E;
+    v.kvcache = static_cast<unsigned char*>(all.kvcache) + (size_t)b0 * e->kv_scene_stride * e->tsz;
+    v.d_tokens = all.d_tokens + (long)b0 * kTokPerFrame; v.d_prev_box = all.d_prev_box + (long)b0 * kNBox; v.d_nboxes = all.d_nboxes + b0;
+    v.d_control = all.d_control + (long)b0 * kSlots; v.d_boxes = all.d_boxes + (long)b0 * 64 * 10; v.d_seeds = all.d_seeds + b0;
+    return v;
+}
+
+int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j) {
+    return e->cfg.precision == UMGEN_PREC_BF16 ? enqueue_step<bf16_t>(e, B, mod, ns, tr, j)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? enqueue_step<f16_t>(e, B, mod, ns, tr, j) : enqueue_step<float>(e, B, mod, ns, tr, j);
+}
+
+}  // namespace umgen
+
+extern "C" {
+
+// Test hook: ONE decode step through the BlockOAR layers (no head, no sampler) on caller-provided inputs, either as the five-launch
+// layer form or through the decode engine.  The K/V rows of position L are appended to the cache, so a test drives L = 0, 1, 2, ...
+int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in, float* x_out, int32_t use_engine, int32_t unmasked) {
+    if (!e || !x_in || !x_out) return UMGEN_E_INVALID;
+    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
+    if (e->cfg.precision == UMGEN_PREC_FP32) return e->fail(UMGEN_E_UNSUPPORTED, "16-bit engines only");
+    if (B < 1 || B > e->cfg.max_batch || L < 0 || L >= e->Lmax) return e->fail(UMGEN_E_INVALID, "B=%d L=%d", B, L);
+    if (use_engine != 0 && use_engine != 1 && use_engine != 3) return e->fail(UMGEN_E_INVALID, "use_engine %d (0: five launches per layer, 1: XCD-resident engine, 3: chip-wide engine)", use_engine);
+    if (use_engine == 1 && !e->eng_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "decode engine not available on this engine");
+    if (e->eng_epoch > 0xE0000000u) {   // same wrap rule as run_frame, for both engines' granule buffers
+        HIPCHK(e, hipDeviceSynchronize());
+        if (e->eng_enabled) {
+            HIPCHK(e, hipMemset(e->eng_gx, 0, (size_t)e->cfg.max_batch * kEngE * 8));
+            HIPCHK(e, hipMemset(e->eng_gloc, 0, e->eng_gloc_bytes));
+        }
+        if (e->wide_enabled) HIPCHK(e, hipMemset(e->wide_gran, 0, oar_engine_wide_granules() * 8));
+        e->eng_epoch = 16u;
+    }
+    const unsigned epoch = e->eng_epoch;   // tags never repeat across calls
+    e->eng_epoch += kEpochPerStep;
+    hipStream_t const keep = e->stream;
+    hipStream_t const st = (unmasked && e->full_stream) ? e->full_stream : e->stream;
+    OarState s0{L, 0, 0, 0, 0, epoch, SamplerParams{}};
+    HIPCHK(e, hipMemcpyAsync(e->d_state, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->xdec, x_in, (size_t)B * e->E * 4, hipMemcpyHostToDevice, st));
+    const bool en = e->eng_enabled, wide_keep = e->wide_enabled;
+    if (use_engine == 3 && !e->wide_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "chip-wide decode engine not available on this engine");
+    e->wide_enabled = wide_keep && use_engine == 3;
+    e->eng_enabled = en && use_engine == 1;
+    e->stream = st;
+    const int lrc = e->cfg.precision == UMGEN_PREC_FP16 ? oar_layers<f16_t>(e, B, attn_nsplit(L + 1)) : oar_layers<bf16_t>(e, B, attn_nsplit(L + 1));
+    e->stream = keep;
+    e->eng_enabled = en;
+    e->wide_enabled = wide_keep;
+    if (lrc) return lrc;
+    HIPCHK(e, hipMemcpyAsync(x_out, e->xdec, (size_t)B * e->E * 4, hipMemcpyDeviceToHost, st));
+    unsigned eng_err = 0;
+    if (use_engine) HIPCHK(e, hipMemcpyAsync(&eng_err, use_engine == 3 ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (eng_err) {      // clear the word of the engine that ran (the other engine's may not exist: ADVICE r5)
+        (void)hipMemset(use_engine == 3 ? e->wide_err : e->eng_err, 0, sizeof(unsigned));
+        return e->fail(UMGEN_E_HIP, "decode engine gave up waiting for hand-off tag 0x%08x", eng_err);
+    }
+    return UMGEN_OK;
+}
+
+}  // extern "C"

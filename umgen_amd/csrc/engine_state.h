@@ -1,0 +1,281 @@
+// State of the host engine, shared by the engine_*.hip files: the weight table and struct umgen_engine (one block of members per mechanism),
+// the per-frame call arguments (FrameIO), a decode lane's view of the engine (DecView), and the declarations of the functions that cross files.
+// No code that launches or decides anything lives here.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdarg>
+#include <cstdio>
+#include <chrono>
+#include <cstring>
+#include <map>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/umgen.h"
+#include "bg_queue.h"
+#include "frame.h"
+#include "kernels.h"
+
+using namespace umgen;
+
+#define HIPCHK(e, call)                                                                              \
+    do {                                                                                             \
+        hipError_t _err = (call);                                                                    \
+        if (_err != hipSuccess) return (e)->fail(UMGEN_E_HIP, "%s -> %s", #call, hipGetErrorString(_err)); \
+    } while (0)
+
+namespace umgen {
+
+struct AttnW { void* Wqkv; float* bqkv; void* Wo; float* bo; };
+struct MlpW { void* Wfc; void* Wproj; };
+struct SubW { float* ln_a; AttnW attn; float* ln_b; MlpW mlp; };
+struct TarW { SubW sub[3]; };
+struct DecW { float* ln1; AttnW self; float *ln2, *ln3; void* Wq; float* bq; void* Wkv; float* bkv; void* Wco; float* bco; float* ln4; MlpW mlp; };
+
+struct Slot {            // destination of one state-dict entry
+    void* dst;
+    std::vector<int64_t> shape;
+    int kind;            // 0: fp32 param, 1: T (precision dtype) weight, 2: bf16 table
+    bool loaded;
+    bool optional;
+};
+
+}  // namespace umgen
+
+struct umgen_engine {
+    umgen_config cfg{};
+    int E = 0, H = 0;
+    size_t tsz = 4;                      // sizeof(T)
+    hipStream_t stream = nullptr;
+    std::string err = "";
+    std::map<std::string, Slot> slots;
+    std::vector<void*> allocs;
+    bool finalized = false;
+    // weights
+    std::vector<TarW> stk[4];            // STACK_EGO, STACK_MAP, STACK_BOX, STACK_TAR
+    std::vector<SubW> oar;
+    std::vector<DecW> dec;
+    float *ln_ego_tar = nullptr, *ln_ego = nullptr, *ln_tar = nullptr, *ln_oar = nullptr, *ln_map_tar = nullptr, *ln_box_tar = nullptr;
+    void *head_ego = nullptr, *head_ar_map = nullptr, *head_ar_box = nullptr, *head_tar_box = nullptr, *head_ar_img = nullptr;
+    void *map_fc = nullptr, *map_proj = nullptr, *img_fc = nullptr, *img_proj = nullptr;
+    float *map_cb = nullptr, *img_cb = nullptr;
+    EmbedTables tb{};
+    // workspace
+    float *X = nullptr, *mapfeat = nullptr, *warped_last = nullptr, *cond = nullptr, *pose_diff = nullptr, *pego = nullptr;
+    void *A = nullptr, *QKV = nullptr, *VT = nullptr, *Hb = nullptr;
+    float *xdec = nullptr, *qdec = nullptr, *part = nullptr, *hdec = nullptr, *logits = nullptr, *logits_tar = nullptr, *qkv3 = nullptr;
+    void* kvcache = nullptr;
+    long kv_layer_stride = 0, kv_scene_stride = 0;
+    int Lmax = kAttnSplit * kAttnChunk, S_pad = 2240;   // cache rows per head: every split's fixed key range is addressable
+    int *d_pose = nullptr, *d_pose_shift = nullptr, *d_map = nullptr, *d_box = nullptr, *d_img = nullptr;
+    int *d_tokens = nullptr, *d_prev_box = nullptr, *d_forced = nullptr, *d_counters = nullptr, *d_nboxes = nullptr, *d_ego_tok = nullptr;
+    unsigned char* d_control = nullptr;
+    double* d_boxes = nullptr;
+    unsigned long long* d_seeds = nullptr;
+    OarState* d_state = nullptr;
+    // Overlapped TAR pass.  Causal temporal attention + frame-local spatial attention make every history
+    // slot but the last one of the NEXT frame's window independent of the frame being decoded, so those slots are pushed through
+    // the ego / map / box / TAR stacks on `bg_stream` (a CU-masked stream) while the latency-bound decode loop runs on the
+    // other CUs; their temporal k | v rows are kept per layer in `tcache`.  The next frame then only computes its last slot.
+    bool overlap = false, overlap_suspended = false;
+    bool conc_stacks = false;            // plain path: the map / box stacks on side streams beside the TAR stack (UMGEN_CONCURRENT_STACKS, default on)
+    int last_B = 0;
+    float last_full_pre_ms = 0.f, last_oar_ms = 0.f;   // ego + TAR phase of the last whole-window frame / decode loop of the last frame
+    int overlap_mode = 1;                // UMGEN_OVERLAP: 0 off, 1 on for one scene per GPU (default), 2 always
+    hipStream_t bg_stream = nullptr;
+    // the last-slot passes of the map / box stacks run beside the TAR stack's on their own streams and 1-slot workspaces
+    struct Work { float* X; void *A, *QKV, *VT, *Hb; float* mapfeat; };
+    Work w_main{}, w_side[2] = {};
+    hipStream_t side_stream[2] = {nullptr, nullptr};
+    hipEvent_t ev_side_in = nullptr, ev_side_done[2] = {nullptr, nullptr};
+    void set_work(const Work& w) { X = w.X; A = w.A; QKV = w.QKV; VT = w.VT; Hb = w.Hb; mapfeat = w.mapfeat; }
+    hipStream_t full_stream = nullptr;   // unmasked: whole-window passes, profiling frames and rollouts that do not overlap use all CUs
+    hipEvent_t ev_pre_done = nullptr;
+    hipEvent_t ev_tar_done = nullptr, ev_bg_done = nullptr, ev_bg0 = nullptr;
+    bool bg_pending = false;
+    // The overlapped pass ON THE DECODE ENGINE'S IDLE XCDs (round 6; bg_worker.h): one scene per GPU runs the engine on 4 of the 8 XCD groups (same step
+    // time) and the engine workgroups of the other four execute the pass as an op list, recorded from the very launchers of the stand-alone kernels
+    // (BgRecorder).  No second stream, no CU masks: the pass advances inside the decode steps' launches and is drained behind the frame's last step.
+    bool bg_engine = false;
+    BgQueue* d_bgq = nullptr;
+    struct BgHead { unsigned w[4]; EmbedTables tb; } bg_head{};      // staging of the queue's header (must outlive the asynchronous upload)
+    BgRecorder bg_rec;                   // host copy of the op list in flight (kept: the asynchronous uploads read it, and the next pass is compared with it)
+    std::vector<unsigned> bg_state_host; // worker states read back behind the drain
+    hipEvent_t ev_drain0 = nullptr, ev_drain1 = nullptr;
+    std::vector<void*> tcache[4];        // per stack, per BlockTAR: [max_batch][max_cond_frames][S_stack][2E] of T
+    // Growing window in the FOREGROUND (control mode starts with 13 history frames and grows to the cap,
+    // infer_fun.py:64-71, UMGen.py:1600-1603): while the window grows, slot t of frame n + 1's window is slot t of frame n's window --
+    // same tokens (the control overwrite of the last bbox3d frame persists, UMGen.py:1465-1467), same tpe row, and every later block
+    // sees it through frame-local spatial sub-blocks and a CAUSAL temporal sub-block (module.py:332-359) -- so a frame that is followed
+    // by a longer window leaves the temporal k | v rows of all its slots in the slot caches (allocated on first use), and the next
+    // frame pushes only its new last slot through the stacks.  No second stream: this is the production path with the decode engine.
+    bool grow_cache = true;              // UMGEN_GROW_CACHE=0: recompute the whole window every frame, like the reference
+    int tcache_state = 0;                // 0 not tried, 1 allocated, -1 does not fit (plain path)
+    struct Prefix {
+        bool valid = false, has_ego = false;
+        int B = 0, P = 0, Tfull = 0;
+        std::vector<int> pose, map, box, img;   // slots 0..P-1 of the window the pass was computed for, [B][P][S_mod]
+        std::vector<int> pose_next;             // [B][3] pose tokens the new frame must carry (they sit in shifted slot P-1)
+    } px;
+    std::vector<int> px_up[4], px_pshift;   // host staging of the background pass's uploads (must outlive the async copies)
+    std::vector<float> px_pdiff;
+    // timing
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    umgen_timings tm{};
+    bool profiling = false;
+    int rows_per_block = -1;              // few-row launches: rows per workgroup; -1 = by row count (1 up to 6 rows, else 2), 0 = row loop
+    bool dbg_same_layer = false;          // UMGEN_DEBUG_SAME_LAYER=1: timing experiment, every decode layer reads layer 0's weights
+    // decode step graphs per (kind: fixed / map / bbox3d / image, number of attention key splits 1..8)
+    hipGraphExec_t step_graph[4][kAttnSplit + 1] = {};
+    int step_graph_B = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> gemm_ev, attn_ev, layer_ev;
+    size_t gemm_ev_used = 0, attn_ev_used = 0, layer_ev_used = 0;
+    // XCD-resident decode engine (oar_engine.hip): one launch per decode step instead of five per layer
+    struct EngStream { bool ok = false; int NG = 0; unsigned char map[16]; };
+    bool eng_enabled = false, eng_fallback = false;   // eng_fallback: wanted, but the census failed (umgen_timings::engine_fallback)
+    EngStream eng_fg, eng_full;          // census of the decode stream (CU-masked when the overlap exists) and of the unmasked stream
+    OarLayerDev* d_layers = nullptr;
+    unsigned long long *eng_gx = nullptr, *eng_gloc = nullptr;
+    unsigned int *eng_ticket = nullptr, *eng_err = nullptr;
+    std::vector<void*> eng_wp2;             // per BlockOAR: mlp c_proj repacked for the engine's hidden-unit split (repack_mlp_proj)
+    std::vector<void*> eng_wf2;             // per BlockOAR: c_fc as matrix-core fragments (repack_mlp_proj)
+    unsigned long long* eng_stamps = nullptr;   // UMGEN_DEBUG_TIMING: per-phase ticks of the engine (printed at destroy)
+    size_t eng_gloc_bytes = 0;
+    // Chip-wide decode engine for wide layers (oar_engine_wide.hip; n_embd 1536; one launch per scene and step).  Default: engines created for ONE scene per
+    // call (two scenes as two launches: step 1696 us against 1523 on five launches per layer, four: 3382 against 2217 -- profiles/r05_wide2x_engine.txt);
+    // UMGEN_DECODE_WIDE=n (1..4): engines of up to n scenes per call; =0: five launches per layer
+    bool wide_enabled = false;
+    OarLayerDev* d_layers_wide = nullptr;
+    std::vector<void*> wide_wp2;            // per BlockOAR: mlp c_proj repacked [256 ranks][E rows][24 hidden units of the rank]
+    unsigned long long* wide_gran = nullptr;
+    unsigned int *wide_ticket = nullptr, *wide_err = nullptr;
+    unsigned long long* wide_stamps = nullptr;
+    bool use_wide(int B) const { return wide_enabled && tsz == 2 && B <= 4; }
+    void* burn_buf = nullptr;             // UMGEN_DEBUG_BURN (measurement builds): the synthetic load's stream buffer
+    int fg_xcds = 8;
+    unsigned eng_epoch = 16u;             // first hand-off tag of the next frame (see run_frame)
+    int step_graph_NG = -1;
+    bool in_capture = false;
+    const EngStream* eng_for(hipStream_t s) const {
+        if (!eng_enabled) return nullptr;
+        const EngStream* es = (full_stream && s == full_stream) ? &eng_full : &eng_fg;
+        return es->ok ? es : nullptr;
+    }
+    double gemm_flops_pending = 0, attn_flops_pending = 0;
+    // Batched decode layer (decode_batched.hip) from `batched_min` scenes per launch on (UMGEN_DECODE_BATCHED=n; 0 = never): the weights
+    // once per step for the whole batch, the scenes as the matrix-core instruction's B-columns
+    int batched_min = 24;               // measured crossover with the engine (profiles/r04_lanes_sweep.txt): 20 scenes 1546 (engine) vs 1674 us per step, 24: 1843 vs 1708, 28: 2104 vs 1775
+    float *xfrag = nullptr, *afrag = nullptr, *hfrag = nullptr;   // fragment-major x / attention output [64 E], gelu(c_fc) [64 x 4E] of the batched layer
+    bool use_batched(int B) const {      // (in_lanes: a lane's sub-batch of a batch that qualified)
+        return tsz == 2 && (in_lanes || (batched_min > 0 && B >= batched_min)) && B <= kRowsMaxM && E % 32 == 0 && E <= 768;
+    }
+    // Decode LANES: the scenes of a batch are independent until the frame is complete (own K/V rows, own sampler state, own RNG
+    // stream), and a batched layer launch for <= 16 scenes is latency-bound (5 dependent launches per layer, 48 - 96 workgroups each,
+    // 34 us per layer whatever the batch is) while its attention launch is the only part at the HBM roof.  The batch is therefore cut
+    // into `lanes` sub-batches, each with its own stream, OarState, fragment buffers and step graphs, forked once behind the TAR stacks
+    // and joined once before the token download: one lane's weight GEMMs run in the shadow of another lane's K/V stream.  Tokens are
+    // those of the single-lane batched layer bit for bit (a scene's column never mixes with another's, decode_batched.hip).
+    static constexpr int kMaxLanes = 8;
+    struct DecLane {
+        hipStream_t s = nullptr;
+        hipEvent_t done = nullptr;
+        OarState* st = nullptr;
+        float *xfrag = nullptr, *afrag = nullptr, *hfrag = nullptr;
+        hipGraphExec_t graph[4][3] = {};
+    };
+    DecLane lane[kMaxLanes];
+    hipEvent_t ev_lane_fork = nullptr;
+    int lanes_env = -1;                  // UMGEN_DECODE_LANES=n: n lanes whenever the batched layer runs (1 = off); -1: by batch size
+    int lane_graph_B = 0, lane_graph_n = 0;
+    bool in_lanes = false;               // enqueueing a lane's steps (a profiled frame times them around the graph launches, not inside enqueue_step)
+    int lane_count(int B) const {
+        if (!use_batched(B) || !lane[0].s) return 1;
+        // measured (profiles/r04_lanes_sweep.txt): lanes of 16 scenes (one full column block of the matrix-core instruction) are best --
+        // 32 scenes 2132 / 1829 / 2040 us per step on 1 / 2 / 4 lanes, 64 scenes 3284 / 2689 / 2532 on 1 / 2 / 4; the device runs four
+        // streams' kernels at a time (8 lanes: two rounds, 3784 / 4063 us)
+        // ; from the threshold of 24 scenes on at least two lanes (24 scenes: 1978 us on one lane, 1708 on two)
+        // ; lanes of at most 16 scenes: 40 scenes 2285 / 2020 / 2136 us on 2 / 3 / 4 lanes, 48: 2182 / 2231 on 3 / 4, 56: 2570 / 2369 on 3 / 4
+        int n = lanes_env > 0 ? lanes_env : std::min(4, std::max(B >= 24 ? 2 : 1, (B + 15) / 16));
+        return std::max(1, std::min(std::min(n, kMaxLanes), B));
+    }
+    hipError_t launch_status = hipSuccess;   // first refused kernel launch of the frame (hipGetLastError behind the GEMM launches): fails the frame
+
+    int fail(int code, const char* fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof(buf), fmt, ap);
+        va_end(ap);
+        err = buf;
+        return code;
+    }
+};
+
+namespace umgen {
+
+// ---- engine_setup.hip: device allocations owned by the engine, the slot caches --------------------------------------
+int dev_alloc(umgen_engine* e, void** p, size_t bytes);
+template <typename P>
+int dalloc(umgen_engine* e, P** p, size_t n) { return dev_alloc(e, reinterpret_cast<void**>(p), n * sizeof(P)); }
+bool ensure_tcache(umgen_engine* e);
+
+// Few-row launches with several rows (scenes, ego queries): one row per workgroup keeps the single-row dependency chain (4 scenes:
+// 2.58 vs 3.12 s of decode per frame) but re-reads the weights from L2 once per row; from 7 rows on, 2 rows per workgroup win
+// (8 scenes: 3.53 vs 3.77 s).  UMGEN_ROWS_PER_BLOCK overrides (0 = every workgroup loops over all rows).
+inline int rows_per_block_for(const umgen_engine* e, int M) { return e->rows_per_block >= 0 ? e->rows_per_block : (M <= 6 ? 1 : 2); }
+
+struct FrameIO {
+    int B, T;
+    const int *pose, *map, *box, *img;          // host window tokens [B][T][S_mod] (box already control-overwritten)
+    const int* ctrl_pose;                        // host [B][3] or nullptr: pose given (init_tokens["pose"])
+    const unsigned char* control_slot;           // host [B][60] or nullptr
+    int frame_idx;
+    const umgen_sampling* smp;
+    const umgen_trace* trace;                    // B == 1 only
+    int* out_tokens;                             // host [B][2199]
+    int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
+    bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
+    bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed
+    const int* given_map = nullptr;              // host [B][1024] or nullptr: the new frame's map is given (predefined-token prefix)
+    const int* given_box = nullptr;              // host [B][660] or nullptr: ... and its boxes (only behind a given map)
+};
+
+// ---- engine_weights.hip ---------------------------------------------------------------------------------------------
+void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);
+
+// ---- engine_stacks.hip: by-precision entry points of the templated compute path ------------------------------------
+void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode);
+void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode);
+int run_prefix_prefill_any(umgen_engine* e, int B, int P);
+int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego);
+void gemv_any(umgen_engine* e, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out, long ldo);
+int build_tables_any(umgen_engine* e);
+
+// What a decode step reads and writes per scene, as the engine's members: a decode lane swaps in the view of its sub-batch (scenes
+// b0 .. b0 + nb - 1 of every per-scene array, its own stream / step state / fragment buffers) around enqueue_step.
+struct DecView {
+    hipStream_t stream;
+    float *xdec, *qdec, *logits, *logits_tar, *cond, *xfrag, *afrag, *hfrag;
+    void* kvcache;
+    int *d_tokens, *d_prev_box, *d_nboxes;
+    unsigned char* d_control;
+    double* d_boxes;
+    unsigned long long* d_seeds;
+    OarState* d_state;
+};
+// ---- engine_decode.hip ----------------------------------------------------------------------------------------------
+DecView current_view(const umgen_engine* e);
+void apply_view(umgen_engine* e, const DecView& v);
+DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine::DecLane& ln, int b0);
+int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j);
+
+// ---- engine_frame.hip -----------------------------------------------------------------------------------------------
+int run_frame_any(umgen_engine* e, const FrameIO& io);
+
+}  // namespace umgen
