@@ -33,6 +33,37 @@ def from_bits16(b: np.ndarray, code: int) -> np.ndarray:
     return from_bits(b) if code == 1 else b.view(np.float16).astype(np.float32)
 
 
+NAN32 = 0x7FC00000
+NAN16 = {1: 0x7FC0, 2: 0x7E00}
+SCALE_QK = float(np.float32(1.0 / np.sqrt(48.0)))
+
+
+def ulp16(v, prec):
+    """spacing of the 16-bit type at |v| (the subnormal spacing below its normal range)"""
+    mant, emin = (7, -126) if prec == 1 else (10, -14)
+    return 2.0 ** (np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** emin))) - mant)
+
+
+def ln_input(rng, M, K):
+    """rows fed to LayerNorm: per-row means in [-4, 4] and standard deviations in [0.05, 3] (both ends present)"""
+    mu = rng.uniform(-4, 4, (M, 1))
+    sd = rng.uniform(0.05, 3, (M, 1))
+    mu[0], sd[0] = 4.0, 0.05
+    mu[-1], sd[-1] = -4.0, 3.0
+    return (mu + sd * rng.standard_normal((M, K))).astype(np.float32)
+
+
+def ref_ln(x, w):
+    x = x.astype(np.float64)
+    mu = x.mean(1, keepdims=True)
+    var = ((x - mu) ** 2).mean(1, keepdims=True)
+    return (x - mu) / np.sqrt(var + 1e-5) * w.astype(np.float64)
+
+
+def gelu64(v):
+    return torch.nn.functional.gelu(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))).numpy()
+
+
 def vp(a):
     return a.ctypes.data_as(C.c_void_p)
 

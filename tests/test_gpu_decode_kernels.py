@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_util import bits16, check, fp, lib, round16, vp
+from tests.gpu_util import NAN16, NAN32, SCALE_QK, bits16, check, fp, gelu64, lib, ln_input, ref_ln, round16, ulp16, vp
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
 import make_reference_checks as rc  # noqa: E402
@@ -28,36 +28,20 @@ ROWS_F32, ROWS_GELU, ROWS_QKV, ROWS_RESID = 0, 1, 2, 3
 # fp32 accumulation and the LayerNorm, not from the hi + lo split); a hi-only product misses by more than 40x | 7.8x the bar
 ROWS_BAR = {1: 2.5e-5, 2: 2e-5}
 ATTN_BAR = 2e-5                        # absolute (V ~ N(0, 1)), as tests/test_gpu_kernels.py::test_attn_decode; measured 9.7e-6 | 1.1e-5
-NAN32 = 0x7FC00000
-NAN16 = {1: 0x7FC0, 2: 0x7E00}
-SCALE_QK = float(np.float32(1.0 / np.sqrt(48.0)))
 M_SET = [1, 15, 16, 17, 31, 32, 33, 48, 49, 64]      # 1 .. 4 column blocks of 16 scenes, full and ragged
 ROWS_LMAX = 160
+
+
+def test_guard_bands_and_fragment_pads_detect_a_write():
+    """What every "was not written" assertion below rests on (csrc/debug_util.h): the hooks' guard bands notice one changed byte at either
+    end of a band, and the fragment-major download one written word in a scene column >= M or a pad column >= C.  The hook launches no
+    kernel and returns the number of the first step that gave another answer than expected."""
+    assert lib().umgen_dbg_guard_selftest() == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # rows_mfma_kernel (with rows_to_frag_kernel in front)
 # ---------------------------------------------------------------------------------------------------------------------------
-def ln_input(rng, M, K):
-    """rows fed to LayerNorm: per-scene means in [-4, 4] and standard deviations in [0.05, 3] (both ends present)"""
-    mu = rng.uniform(-4, 4, (M, 1))
-    sd = rng.uniform(0.05, 3, (M, 1))
-    mu[0], sd[0] = 4.0, 0.05
-    mu[-1], sd[-1] = -4.0, 3.0
-    return (mu + sd * rng.standard_normal((M, K))).astype(np.float32)
-
-
-def ref_ln(x, w):
-    x = x.astype(np.float64)
-    mu = x.mean(1, keepdims=True)
-    var = ((x - mu) ** 2).mean(1, keepdims=True)
-    return (x - mu) / np.sqrt(var + 1e-5) * w.astype(np.float64)
-
-
-def gelu64(v):
-    return torch.nn.functional.gelu(torch.from_numpy(v)).numpy()
-
-
 @functools.lru_cache(maxsize=None)
 def weights(prec, N, K, seed):
     rng = np.random.default_rng(seed)
@@ -78,12 +62,6 @@ def rows_call(prec, mode, x, lw, Wb, bias, N, K, E, ldo, x0=None, Lmax=ROWS_LMAX
     check(lib().umgen_dbg_rows(prec, mode, fp(np.ascontiguousarray(x)), fp(lw), vp(Wb), fp(bias), M, N, K, E, fp(out), ldo, fp(out_rows),
                                vp(cache) if cache is not None else None, Lmax if cache is not None else 0, pos))
     return out, out_rows, cache
-
-
-def ulp16(v, prec):
-    """spacing of the 16-bit type at |v| (the subnormal spacing below its normal range)"""
-    mant, emin = (7, -126) if prec == 1 else (10, -14)
-    return 2.0 ** (np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** emin))) - mant)
 
 
 ROWS_CASES = [  # (name, mode, N: "3E" | "4E" | "E" | absolute, K as a multiple of E, ldo - N)

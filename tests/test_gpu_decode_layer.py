@@ -28,7 +28,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_util import bits16, check, fp, from_bits16, lib, round16, vp
+from tests.gpu_util import NAN16, NAN32, SCALE_QK, bits16, check, fp, from_bits16, gelu64, lib, ln_input, ref_ln, round16, ulp16, vp
 
 GEMV_F32, GEMV_GELU, GEMV_QKV = 0, 1, 2
 GEO_DECODE, GEO_EGO_SELF, GEO_EGO_CROSS = 0, 1, 2
@@ -40,9 +40,6 @@ EGO_B = [1, 2, 3, 6]                                  # ego queries M = 3B: 3, 6
 LMAX = 2304                                           # kAttnSplit * kAttnChunk: cache rows per (scene, K / V, head)
 KSEQ = 2207
 CHUNK = 128
-NAN32 = 0x7FC00000
-NAN16 = {1: 0x7FC0, 2: 0x7E00}
-SCALE_QK = float(np.float32(1.0 / np.sqrt(48.0)))
 GEMV_BAR = 1e-4
 RESID_BAR = 2e-6
 ATTN_BAR = 2.5e-6
@@ -73,12 +70,6 @@ def raw(a):
     return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
-def ulp16(v, prec):
-    """spacing of the 16-bit type at |v| (the subnormal spacing below its normal range)"""
-    mant, emin = (7, -126) if prec == 1 else (10, -14)
-    return 2.0 ** (np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** emin))) - mant)
-
-
 def rel_err(got, ref):
     return float((np.abs(got.astype(np.float64) - ref) / np.maximum(1.0, np.abs(ref))).max())
 
@@ -90,26 +81,6 @@ def check_kv_row(got, ref, prec, bar):
     slack = ulp16(ref, prec) if prec else 0.0
     excess = np.abs(v - ref) - slack - bar * np.maximum(1.0, np.abs(ref))
     assert excess.max() <= 0, f"K/V row: {excess.max():.3e} beyond 1 ulp + bar of the fp64 value"
-
-
-def ln_input(rng, M, K):
-    """rows fed to LayerNorm: per-row means in [-4, 4] and standard deviations in [0.05, 3] (both ends present)"""
-    mu = rng.uniform(-4, 4, (M, 1))
-    sd = rng.uniform(0.05, 3, (M, 1))
-    mu[0], sd[0] = 4.0, 0.05
-    mu[-1], sd[-1] = -4.0, 3.0
-    return (mu + sd * rng.standard_normal((M, K))).astype(np.float32)
-
-
-def ref_ln(x, w):
-    x = x.astype(np.float64)
-    mu = x.mean(1, keepdims=True)
-    var = ((x - mu) ** 2).mean(1, keepdims=True)
-    return (x - mu) / np.sqrt(var + 1e-5) * w.astype(np.float64)
-
-
-def gelu64(v):
-    return torch.nn.functional.gelu(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))).numpy()
 
 
 @functools.lru_cache(maxsize=None)

@@ -14,19 +14,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # UMGEN_LIB_PATH selects an alternative build of the SAME library (kernel experiments with extra -D flags); never a fallback
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
-SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip", "debug_api.hip"]
+SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
+           "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip"]
 EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
            "umgen_vqenc_create", "umgen_vqenc_load_tensor", "umgen_vqenc_finalize", "umgen_vqenc_encode", "umgen_vqenc_last_error", "umgen_vqenc_destroy",
-           "umgen_dbg_linear", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_oar_step", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
+           "umgen_dbg_linear", "umgen_dbg_linear_vt", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_gemm_vt_bench", "umgen_dbg_gemm_stamps", "umgen_dbg_oar_step", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
            "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
-           "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer",
+           "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer", "umgen_dbg_guard_selftest",
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego"]
 
-HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h")
+HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
 
 PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DT_F32, DT_BF16, DT_F16, DT_F64 = 0, 1, 2, 3
@@ -65,7 +66,7 @@ class Trace(C.Structure):
 
 
 class DbgTables(C.Structure):
-    """umgen_dbg_tables (csrc/debug_api.hip): the embedding tables of a kernel-level hook as host arrays, with their row counts"""
+    """umgen_dbg_tables (csrc/debug_frame.hip): the embedding tables of a kernel-level hook as host arrays, with their row counts"""
     _fields_ = [(n, C.POINTER(C.c_float)) for n in ("egoe", "axe", "be", "tpe", "spe", "gmap", "gimg")] + \
         [(n, C.POINTER(C.c_uint16)) for n in ("fouier_pe", "posi", "grid_posi")] + \
         [(n, C.c_int32) for n in ("E", "n_tpe", "n_pose", "n_map", "n_box", "n_img", "n_posi")]
@@ -79,7 +80,7 @@ class DbgSamplerParams(C.Structure):
 
 
 class DbgSteps(C.Structure):
-    """umgen_dbg_steps (csrc/debug_api.hip): inputs and outputs of umgen_dbg_token_steps"""
+    """umgen_dbg_steps (csrc/debug_frame.hip): inputs and outputs of umgen_dbg_token_steps"""
     _fields_ = [("cond", C.POINTER(C.c_float)), ("logits", C.POINTER(C.c_float)), ("logits_tar", C.POINTER(C.c_float)),
                 ("prev_box", C.POINTER(C.c_int32)), ("control_slot", C.POINTER(C.c_ubyte)), ("forced", C.POINTER(C.c_int32)),
                 ("seeds", C.POINTER(C.c_uint64)), ("tokens", C.POINTER(C.c_int32)), ("x_next", C.POINTER(C.c_float)),
@@ -260,11 +261,14 @@ def load_library() -> C.CDLL:
     lib.umgen_detokenize_boxes.argtypes = [i64p, C.c_int64, f64p]
     fp = C.POINTER(C.c_float)
     lib.umgen_dbg_linear.argtypes = [i32, vp, vp, fp, i32, i32, i32, i32, i32, vp]
+    lib.umgen_dbg_linear_vt.argtypes = [i32, vp, vp, fp, i32, i32, i32, i32, vp]
     lib.umgen_dbg_attn_spatial.argtypes = [i32, vp, vp, i32, i32, i32, vp]
     lib.umgen_dbg_attn_temporal.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp]
     lib.umgen_dbg_attn_decode.argtypes = [i32, fp, vp, i32, i32, i32, fp]
     lib.umgen_dbg_gemv.argtypes = [i32, fp, fp, vp, fp, i32, i32, i32, i32, fp]
     lib.umgen_dbg_gemm_bench.argtypes = [i32, i32, i32, i32, i32, fp]
+    lib.umgen_dbg_gemm_vt_bench.argtypes = [i32, i32, i32, i32, i32, i32, fp]
+    lib.umgen_dbg_gemm_stamps.argtypes = [C.POINTER(C.c_ulonglong)]
     lib.umgen_dbg_oar_step.argtypes = [vp, i32, i32, fp, fp, i32, i32]
     lib.umgen_dbg_sample_topk.argtypes = [fp, i32, i32, i32, C.c_float, fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.umgen_dbg_batched_layer_bench.argtypes = [i32, i32, i32, i32, fp]
@@ -276,6 +280,7 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_gemv_resid.argtypes = [i32, i32, fp, C.c_long, vp, fp, i32, i32, i32, fp]
     lib.umgen_dbg_attn_partial.argtypes = [i32, i32, i32, fp, vp, i32, i32, i32, i32, i32, vp, fp, fp]
     lib.umgen_dbg_decode_layer.argtypes = [i32, i32, i32, i32, i32, i32, fp, vp, fp, vp, fp, fp, vp, vp, fp, fp, vp]
+    lib.umgen_dbg_guard_selftest.argtypes = []
     tp = C.POINTER(DbgTables)
     lib.umgen_dbg_embed_warp.argtypes = [i32, tp, i32p, i32p, i32p, i32p, i32, i32, i32, i32, fp, i32, fp, fp, fp]
     lib.umgen_dbg_layernorm.argtypes = [i32, fp, C.c_long, C.c_long, i32, fp, vp, C.c_long]

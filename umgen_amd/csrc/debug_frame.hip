@@ -1,0 +1,279 @@
+// Kernel-level test hooks of frame assembly (frame.hip, rowops.hip; host pointers in, host pointers out): token embedding + map warp, LayerNorm,
+// conditioning rows, first input, ego queries, the given-token prefix rows and their K/V move, the per-token step (fixed / sampled token with
+// the bbox3d control flow) and the ego sampler.  Each goes through the product's launcher.  Outputs start as NaN (or as the caller's buffer
+// where they are in / out) and carry guard bands; every token a launch may use as a table index is checked against the table's size on the
+// host first.  Used only by tests/; never called by the product path.
+#include "debug_util.h"
+
+// host image of EmbedTables: fp32 tables and raw bf16 bits, with their row counts (spe has kSeq rows, egoe 3, axe 8, grid_posi 1024)
+struct umgen_dbg_tables {
+    const float *egoe, *axe, *be, *tpe, *spe, *gmap, *gimg;
+    const uint16_t *fouier_pe, *posi, *grid_posi;
+    int32_t E, n_tpe, n_pose, n_map, n_box, n_img, n_posi;
+};
+
+// everything umgen_dbg_token_steps reads and writes (see there)
+struct umgen_dbg_steps {
+    const float *cond, *logits, *logits_tar;
+    const int32_t* prev_box;
+    const unsigned char* control_slot;
+    const int32_t* forced;
+    const uint64_t* seeds;
+    int32_t* tokens;
+    float* x_next;
+    int32_t *counters, *n_boxes;
+    double* boxes;
+    uint32_t* state_log;
+    SamplerParams sp;
+    int32_t B, j0, j1, given_end, ld_logits, use_forced, use_control, frame_idx;
+    uint32_t epoch0;
+};
+
+namespace {
+inline bool tables_sane(const umgen_dbg_tables* t) {
+    return t && t->E >= 1 && t->n_tpe >= 0 && t->n_pose >= 0 && t->n_map >= 0 && t->n_box >= 0 && t->n_img >= 0 && t->n_posi >= 0;
+}
+// the tables a hook was given, on the device (an absent one stays nullptr)
+EmbedTables tables_in(Scratch& s, const umgen_dbg_tables& t) {
+    const size_t E = (size_t)t.E;
+    EmbedTables tb{};
+    tb.E = t.E;
+    tb.egoe = s.in(t.egoe, 3 * E * 4);
+    tb.axe = s.in(t.axe, 8 * E * 4);
+    tb.be = s.in(t.be, (size_t)t.n_box * E * 4);
+    tb.tpe = s.in(t.tpe, (size_t)t.n_tpe * E * 4);
+    tb.spe = s.in(t.spe, (size_t)kSeq * E * 4);
+    tb.gmap = s.in(t.gmap, (size_t)t.n_map * E * 4);
+    tb.gimg = s.in(t.gimg, (size_t)t.n_img * E * 4);
+    tb.fouier_pe = s.in(t.fouier_pe, (size_t)t.n_pose * E * 2);
+    tb.posi = s.in(t.posi, (size_t)t.n_posi * E * 2);
+    tb.grid_posi = s.in(t.grid_posi, (size_t)kNMap * E * 2);
+    return tb;
+}
+}  // namespace
+
+extern "C" {
+
+// run_stack's first two launches (engine_stacks.hip): launch_embed_stack, then for every stack but STACK_EGO launch_warp_map.  Token arrays
+// [B][Tf][3 | 1024 | 660 | 512] and pose_diff [B][Tf][3] with Tf = Tfull (0: T); the pass covers slots t0 .. t0 + T - 1.
+// -> X [B][T][stack_len][E], mapfeat [B][T][1024][E], warped_last [B][1024][E] (handed to the launcher only when want_last != 0).
+int umgen_dbg_embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B,
+                         int T, int Tfull, int t0, const float* pose_diff, int want_last, float* X, float* mapfeat, float* warped_last) {
+    if (stack < STACK_EGO || stack > STACK_TAR || !tables_sane(t) || B < 1 || T < 1 || Tfull < 0 || t0 < 0) return UMGEN_E_INVALID;
+    const int Tf = Tfull ? Tfull : T;
+    if (t0 + T > Tf || Tf > t->n_tpe || !pose || !map || !box || !img || !pose_diff || !X || !mapfeat || !warped_last) return UMGEN_E_INVALID;
+    if (!t->axe || !t->be || !t->tpe || !t->spe || !t->gmap || !t->gimg || !t->fouier_pe || !t->posi || !t->grid_posi) return UMGEN_E_INVALID;
+    const size_t F = (size_t)B * Tf, E = (size_t)t->E;
+    if (!in_range(pose, F * kNPose, t->n_pose) || !in_range(map, F * kNMap, t->n_map) || !in_range(box, F * kNBox, t->n_box) ||
+        !in_range(img, F * kNImg, t->n_img))
+        return UMGEN_E_INVALID;
+    for (size_t f = 0; f < F; ++f)
+        for (int sl = 0; sl < kSlots; ++sl)
+            if (box[f * kNBox + sl * kSlotLen] >= t->n_posi || box[f * kNBox + sl * kSlotLen + 1] >= t->n_posi) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * T * stack_len(stack) * E, mn = (size_t)B * T * kNMap * E, wn = (size_t)B * kNMap * E;
+    Scratch s;
+    const EmbedTables tb = tables_in(s, *t);
+    WindowTokens w{};
+    w.pose = s.in(pose, F * kNPose * 4); w.map = s.in(map, F * kNMap * 4); w.box = s.in(box, F * kNBox * 4); w.img = s.in(img, F * kNImg * 4);
+    w.B = B; w.T = T; w.Tfull = Tfull; w.t0 = t0;
+    const float* dPD = s.in(pose_diff, F * 3 * 4);
+    float *dX = s.out(xn * 4), *dMF = s.out(mn * 4), *dWL = s.out(wn * 4);
+    if (s.rc) return s.rc;
+    if (fill_nan(dX, xn, 0) || fill_nan(dMF, mn, 0) || fill_nan(dWL, wn, 0)) return UMGEN_E_HIP;
+    launch_embed_stack(nullptr, stack, tb, w, dX, dMF);
+    if (stack != STACK_EGO) launch_warp_map(nullptr, stack, tb, B, T, dMF, dPD, dX, want_last ? dWL : nullptr, Tfull, t0);
+    if (int rc = s.finish()) return rc;
+    if (down(X, dX, xn * 4) || down(mapfeat, dMF, mn * 4)) return UMGEN_E_HIP;
+    return down(warped_last, dWL, wn * 4);
+}
+
+// launch_layernorm<T> (T by prec) on n_rows rows of x (row r at x + r * row_stride, E <= 1536 columns) -> out [out_rows][E] of T, out_rows >= n_rows:
+// NaN at the launch, so rows >= n_rows come back as NaN
+int umgen_dbg_layernorm(int prec, const float* x, long row_stride, long n_rows, int E, const float* w, void* out, long out_rows) {
+    if (prec < 0 || prec > 2 || !x || !w || !out || E < 1 || E > 64 * 24 || row_stride < E || n_rows < 1 || out_rows < n_rows) return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, on = (size_t)out_rows * E;
+    Scratch s;
+    const float *dXi = s.in(x, (size_t)n_rows * row_stride * 4), *dW = s.in(w, (size_t)E * 4);
+    void* dO = s.out(on * es);
+    if (s.rc) return s.rc;
+    if (int rc = fill_nan(dO, on, prec)) return rc;
+    by_prec(prec, [&](auto tag) { launch_layernorm<decltype(tag)>(nullptr, dXi, row_stride, n_rows, E, dW, (decltype(tag)*)dO); });
+    if (int rc = s.finish()) return rc;
+    return down(out, dO, on * es);
+}
+
+// launch_cond_rows of one stack: X [B][T][stack_len][E], ln_w [E], warped_last [B][1024][E] or NULL (required for STACK_MAP) -> cond
+// [B][kSeq][E], in / out: the launch changes the stack's own rows only
+int umgen_dbg_cond_rows(int stack, int B, int T, int E, const float* X, const float* ln_w, const float* warped_last, float* cond) {
+    if (stack < STACK_MAP || stack > STACK_TAR || B < 1 || T < 1 || E < 1 || !X || !ln_w || !cond || (stack == STACK_MAP && !warped_last)) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * T * stack_len(stack) * E, wn = (size_t)B * kNMap * E, cn = (size_t)B * kSeq * E;
+    Scratch s;
+    const float *dXi = s.in(X, xn * 4), *dW = s.in(ln_w, (size_t)E * 4), *dWL = s.in(warped_last, wn * 4);
+    float* dC = s.inout(cond, cn * 4);
+    if (s.rc) return s.rc;
+    launch_cond_rows(nullptr, stack, B, T, E, dXi, dW, dWL, dC);
+    if (int rc = s.finish()) return rc;
+    return down(cond, dC, cn * 4);
+}
+
+// launch_first_input: x [B][E] = row [E] + cond[b][0] (cond [B][kSeq][E])
+int umgen_dbg_first_input(int B, int E, const float* row, const float* cond, float* x) {
+    if (B < 1 || E < 1 || !row || !cond || !x) return UMGEN_E_INVALID;
+    const size_t cn = (size_t)B * kSeq * E, xn = (size_t)B * E;
+    Scratch s;
+    const float *dR = s.in(row, (size_t)E * 4), *dC = s.in(cond, cn * 4);
+    float* dXo = s.out(xn * 4);
+    if (s.rc) return s.rc;
+    if (int rc = fill_nan(dXo, xn, 0)) return rc;
+    launch_first_input(nullptr, B, E, dR, dC, dXo);
+    if (int rc = s.finish()) return rc;
+    return down(x, dXo, xn * 4);
+}
+
+// launch_ego_queries: x [B][3][E] = (egoe[j] + spe[j]) + tpe[T - 1]
+int umgen_dbg_ego_queries(const umgen_dbg_tables* t, int B, int T, float* x) {
+    if (!tables_sane(t) || B < 1 || T < 1 || T > t->n_tpe || !t->egoe || !t->spe || !t->tpe || !x) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * 3 * t->E;
+    Scratch s;
+    const EmbedTables tb = tables_in(s, *t);
+    float* dXo = s.out(xn * 4);
+    if (s.rc) return s.rc;
+    if (int rc = fill_nan(dXo, xn, 0)) return rc;
+    launch_ego_queries(nullptr, tb, B, T, dXo);
+    if (int rc = s.finish()) return rc;
+    return down(x, dXo, xn * 4);
+}
+
+// launch_prefix_rows: the decode inputs of the given positions 0 .. P - 1 (tske_row [E], cond [B][kSeq][E], tokens [B][2199]) ->
+// X [B][P - 1][E] (rows 0 .. P - 2) and x_last [B][E] (row P - 1)
+int umgen_dbg_prefix_rows(const umgen_dbg_tables* t, const float* tske_row, const float* cond, const int32_t* tokens, int B, int P, float* X, float* x_last) {
+    if (!tables_sane(t) || B < 1 || P < 2 || P > kBoxEos + 2 || !tske_row || !cond || !tokens || !X || !x_last) return UMGEN_E_INVALID;
+    if (!t->axe || !t->be || !t->gmap || !t->fouier_pe) return UMGEN_E_INVALID;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* tk = tokens + (size_t)b * kTokPerFrame;
+        if (!in_range(tk, kNPose, t->n_pose) || !in_range(tk + kOffMap, kNMap, t->n_map) || !in_range(tk + kOffBox, kNBox, t->n_box)) return UMGEN_E_INVALID;
+    }
+    const size_t E = (size_t)t->E, cn = (size_t)B * kSeq * E, xn = (size_t)B * (P - 1) * E, ln = (size_t)B * E, tn = (size_t)B * kTokPerFrame;
+    Scratch s;
+    const EmbedTables tb = tables_in(s, *t);
+    const float *dR = s.in(tske_row, E * 4), *dC = s.in(cond, cn * 4);
+    const int* dT = s.in(tokens, tn * 4);
+    float *dXo = s.out(xn * 4), *dL = s.out(ln * 4);
+    if (s.rc) return s.rc;
+    if (fill_nan(dXo, xn, 0) || fill_nan(dL, ln, 0)) return UMGEN_E_HIP;
+    launch_prefix_rows(nullptr, tb, dR, dC, dT, B, P, dXo, dL);
+    if (int rc = s.finish()) return rc;
+    if (down(X, dXo, xn * 4)) return UMGEN_E_HIP;
+    return down(x_last, dL, ln * 4);
+}
+
+// launch_prefix_kv_to_cache<T>: qk [B * S][2E] (q | k rows) and vt [B][H][48][S_pad] of T -> cache [B][2][H][Lmax][48] of T (NaN at the launch) with
+// the product's scene stride 2 * H * Lmax * 48
+int umgen_dbg_prefix_kv_to_cache(int prec, const void* qk, const void* vt, int B, int S, int S_pad, int H, int Lmax, void* cache) {
+    if (prec < 0 || prec > 2 || !qk || !vt || !cache || B < 1 || S < 1 || S > S_pad || S > Lmax || H < 1) return UMGEN_E_INVALID;
+    const size_t es = prec ? 2 : 4, E = (size_t)H * kHeadDim, qn = (size_t)B * S * 2 * E, vn = (size_t)B * E * S_pad, stride = (size_t)2 * H * Lmax * kHeadDim;
+    const size_t cn = (size_t)B * stride;
+    Scratch s;
+    const void *dQ = s.in(qk, qn * es), *dV = s.in(vt, vn * es);
+    void* dC = s.out(cn * es, scene_band(stride * es, B));
+    if (s.rc) return s.rc;
+    if (int rc = fill_nan(dC, cn, prec)) return rc;
+    by_prec(prec, [&](auto tag) {
+        typedef decltype(tag) TT;
+        launch_prefix_kv_to_cache<TT>(nullptr, (const TT*)dQ, (const TT*)dV, B, S, S_pad, H, Lmax, (TT*)dC, (long)stride);
+    });
+    if (int rc = s.finish()) return rc;
+    return down(cache, dC, cn * es);
+}
+
+// The sampler kernels of decode steps j0 .. j1 - 1 of one frame for B scenes, on an OarState and a SampleArgs of the hook's own: what enqueue_step
+// (engine_decode.hip) launches behind the head at position j -- launch_fixed_token for bos / eos / the pose prefix and every position < given_end,
+// else launch_sample_token with the position's mod and vocabulary (tables: n_map | n_box | n_img) -- with that step's logits [B][ld_logits]
+// (logits [j1 - j0][B][ld_logits]).  logits_tar [B][660][n_box], prev_box [B][660], control_slot [B][60], forced [B][2199] (or NULL), seeds [B].
+// In / out: tokens [B][2199], counters [8], n_boxes [B], boxes [B][64][10].  Out: x_next [j1 - j0][B][E] (NaN before every step) and
+// state_log [j1 - j0][3] = OarState step, epoch, done behind every step.
+int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
+    if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
+    // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
+    if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
+    if (!a->cond || !a->logits || !a->logits_tar || !a->prev_box || !a->control_slot || !a->seeds || !a->tokens || !a->x_next || !a->counters ||
+        !a->n_boxes || !a->boxes || !a->state_log || (a->use_forced && !a->forced))
+        return UMGEN_E_INVALID;
+    if (!t->axe || !t->be || !t->gmap || !t->gimg || !t->fouier_pe || t->E > 6 * 256) return UMGEN_E_INVALID;   // CondRow: E <= 1536
+    const int vmax = std::max(t->n_map, std::max(t->n_box, t->n_img));
+    if (vmax > 8192 || a->ld_logits < vmax || t->n_map < 1 || t->n_img < 1 || t->n_box <= kBoxPad) return UMGEN_E_INVALID;
+    if (a->sp.method < 0 || a->sp.method > 1 || a->sp.top_k < 1 || a->sp.top_k_map < 1 || a->sp.topk_image < 1 || !(a->sp.temperature > 0.f)) return UMGEN_E_INVALID;
+    const int B = a->B, n = a->j1 - a->j0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* tk = a->tokens + (size_t)b * kTokPerFrame;
+        if (!in_range(tk, kNPose, t->n_pose) || !in_range(tk + kOffMap, kNMap, t->n_map) || !in_range(tk + kOffBox, kNBox, t->n_box) ||
+            !in_range(tk + kOffImg, kNImg, t->n_img))
+            return UMGEN_E_INVALID;
+        if (a->use_forced) {
+            const int32_t* ft = a->forced + (size_t)b * kTokPerFrame;
+            if (!in_range(ft, kNPose, t->n_pose)) return UMGEN_E_INVALID;
+            if (!in_range(ft + kOffMap, kNMap, t->n_map) || !in_range(ft + kOffBox, kNBox, t->n_box) || !in_range(ft + kOffImg, kNImg, t->n_img)) return UMGEN_E_INVALID;
+        }
+        if (a->n_boxes[b] < 0 || a->n_boxes[b] > 30) return UMGEN_E_INVALID;     // the kernel's box list and corner table hold 64
+    }
+    const size_t E = (size_t)t->E, cn = (size_t)B * kSeq * E, ln = (size_t)B * a->ld_logits, tarn = (size_t)B * kNBox * t->n_box, tn = (size_t)B * kTokPerFrame;
+    const size_t bn = (size_t)B * 64 * 10, xn = (size_t)B * E;
+    OarState s0{};
+    s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
+    s0.epoch = a->epoch0; s0.sp = a->sp;
+    Scratch s;
+    SampleArgs sa{};
+    sa.tb = tables_in(s, *t);
+    sa.st = s.in(&s0, sizeof(s0));
+    float* dLg = s.raw(ln * 4);                 // the current step's logits
+    sa.logits = dLg; sa.logits_tar = s.in(a->logits_tar, tarn * 4); sa.ld_logits = a->ld_logits; sa.ld_tar = t->n_box; sa.cond = s.in(a->cond, cn * 4);
+    sa.prev_box = s.in(a->prev_box, (size_t)B * kNBox * 4); sa.control_slot = s.in(a->control_slot, (size_t)B * kSlots);
+    sa.seeds = s.in(a->seeds, (size_t)B * 8);
+    if (a->use_forced) sa.forced = s.in(a->forced, tn * 4); else sa.forced = s.raw(tn * 4);   // never read without use_forced
+    sa.x_next = s.out(xn * 4); sa.tokens = s.inout(a->tokens, tn * 4); sa.counters = s.inout(a->counters, 8 * 4);
+    sa.n_boxes = s.inout(a->n_boxes, (size_t)B * 4); sa.boxes = s.inout(a->boxes, bn * 8);
+    if (s.rc) return s.rc;
+    for (int i = 0; i < n; ++i) {
+        const int j = a->j0 + i, mod = kind_of_pos(j, a->given_end);
+        if (int rc = fill_nan(sa.x_next, xn, 0)) return rc;
+        if (mod == 0) {
+            launch_fixed_token(nullptr, sa, B);
+        } else {
+            if (up(dLg, a->logits + (size_t)i * ln, ln * 4)) return UMGEN_E_HIP;
+            sa.mod = mod;
+            sa.vocab = mod == 1 ? t->n_map : (mod == 2 ? t->n_box : t->n_img);
+            launch_sample_token(nullptr, sa, B);
+        }
+        if (int rc = finish()) return rc;
+        OarState s1{};
+        if (down(&s1, sa.st, sizeof(s1)) || down(a->x_next + (size_t)i * xn, sa.x_next, xn * 4)) return UMGEN_E_HIP;
+        a->state_log[3 * i] = (uint32_t)s1.step; a->state_log[3 * i + 1] = s1.epoch; a->state_log[3 * i + 2] = (uint32_t)s1.done;
+    }
+    if (!s.intact()) return UMGEN_E_STATE;
+    if (down(a->tokens, sa.tokens, tn * 4) || down(a->counters, sa.counters, 8 * 4) || down(a->n_boxes, sa.n_boxes, (size_t)B * 4)) return UMGEN_E_HIP;
+    return down(a->boxes, sa.boxes, bn * 8);
+}
+
+// launch_sample_ego: logits [3 B][V] -> out_tokens [B][3]; the draw of row (b, jq) is rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN); forced
+// [B][2199] (or NULL) overrides with its pose tokens
+int umgen_dbg_sample_ego(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                         int32_t* out_tokens) {
+    if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
+        return UMGEN_E_INVALID;
+    const size_t ln = (size_t)B * 3 * V, tn = (size_t)B * kTokPerFrame, osz = (size_t)B * 3 * 4;
+    Scratch s;
+    const float* dL = s.in(logits, ln * 4);
+    const unsigned long long* dS = s.in(seeds, (size_t)B * 8);
+    const int* dF = s.in(forced, tn * 4);
+    int *dOv = s.raw(4), *dT = s.out(osz);
+    if (s.rc) return s.rc;
+    if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
+    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv);
+    if (int rc = finish()) return rc;
+    int ovf = 0;
+    if (down(&ovf, dOv, 4)) return UMGEN_E_HIP;
+    if (!s.intact() || ovf != 0) return UMGEN_E_STATE;      // (the overflow word is unused since the exhaustive tie walk: it must stay 0)
+    return down(out_tokens, dT, osz);
+}
+
+}  // extern "C"

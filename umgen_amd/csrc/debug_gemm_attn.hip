@@ -1,0 +1,278 @@
+// Kernel-level test hooks of libumgen_hip.so (host pointers in, host pointers out) for the GEMMs, the stack attentions, the few-row GEMV and the
+// top-k sampler, and the timing hooks of tools/.  Used only by tests/ and tools/ to pin each HIP kernel against the CPU oracle at production
+// width; never called by the product path.  The hooks of this file give their outputs neither guard bands nor NaN fills (umgen_dbg_attn_spatial
+// excepted); those of debug_decode.hip and debug_frame.hip do.
+#include "debug_util.h"
+
+namespace {
+// out[R][N] = act[R][K] . W[N][K]^T as the engine's linears launch it (weights as the P operand)
+GemmArgs linear_args(const void* dW, const void* dA, int R, int N, int K, void* dO) {
+    GemmArgs g{};
+    g.P = dW; g.Q = dA; g.Mi = N; g.Nj = R; g.K = K; g.ldp = K; g.ldq = K; g.batch = 1; g.out = dO; g.ldo = N;
+    return g;
+}
+// the V^T GEMM of the spatial attention: F frames of S rows -> out [F][N][S_pad]
+GemmArgs vt_args(const void* dA, const void* dW, int F, int S, int S_pad, int N, int K, void* dO) {
+    GemmArgs g{};
+    g.P = dA; g.Q = dW; g.Mi = S; g.Nj = N; g.K = K; g.ldp = K; g.ldq = K; g.strideP = (long)S * K; g.strideQ = 0; g.batch = F;
+    g.mode = GEMM_VT; g.out = dO; g.ldo = S_pad; g.H = N / kHeadDim;
+    return g;
+}
+inline int pad64(int S) { return ((S + 63) / 64) * 64; }
+// random bf16 operands of the GEMM timing hooks: act [na] in [-1, 1), then W [nw] in [-0.05, 0.05), one sequence
+void lcg_operands(Scratch& s, size_t na, size_t nw, DevPtr& dA, DevPtr& dW) {
+    std::vector<bf16_t> h;
+    unsigned x = 12345u;
+    fill_lcg(h, na, x, 1.0f);
+    dA = s.in(h.data(), na * 2);
+    fill_lcg(h, nw, x, 0.05f);
+    dW = s.in(h.data(), nw * 2);
+}
+}  // namespace
+
+extern "C" {
+
+// out[R][N] = act[R][K] . W[N][K]^T + bias (+gelu) (+ residual into out when resid != 0).  bf16 != 0: operands are raw
+// bf16 bits (bf16 == 2: IEEE half bits) and the MFMA kernel runs; else fp32 operands and the exact VALU kernel.  out is fp32 for resid, operand dtype otherwise.
+int umgen_dbg_linear(int flags, const void* act, const void* W, const float* bias, int R, int N, int K, int gelu, int resid, void* out) {
+    const int bf16 = flags & 3;                 // precision code; flag 16: force the 256 x 256 kernel, 32: never use it
+    const size_t es = bf16 ? 2 : 4, osz = (size_t)R * N * (resid ? 4 : es);
+    Scratch s;
+    const void *dA = s.in(act, (size_t)R * K * es), *dW = s.in(W, (size_t)N * K * es);
+    const float* dB = s.in(bias, (size_t)N * 4);
+    void* dO = resid ? s.in(out, osz) : s.raw((size_t)R * N * 4);
+    if (s.rc) return s.rc;
+    GemmArgs g = linear_args(dW, dA, R, N, K, dO);
+    g.mode = resid ? GEMM_RESID : GEMM_STORE; g.bias = dB; g.gelu = gelu;
+    g.tile256 = (flags & 16) ? 1 : ((flags & 32) ? -1 : 0);
+    if (bf16) by_prec16(bf16, [&](auto t) { launch_gemm_mfma<decltype(t)>(nullptr, g); });
+    else launch_gemm_valu<float, float>(nullptr, g);
+    if (int rc = finish()) return rc;
+    return down(out, dO, osz);
+}
+
+// V^T GEMM of the spatial attention (GEMM_VT): act [F*S][K] rows, W [N][K], bias [N] -> out [F][N][S_pad] of the operand type
+// (S_pad = S rounded up to 64; pad columns are zero).  flag 16: force the 256 x 256 kernel, 32: the 128-tile kernels only.
+int umgen_dbg_linear_vt(int flags, const void* act, const void* W, const float* bias, int F, int S, int N, int K, void* out) {
+    const int prec = flags & 3;
+    if (prec != 1 && prec != 2) return UMGEN_E_UNSUPPORTED;
+    const int S_pad = pad64(S);
+    const size_t R = (size_t)F * S, osz = (size_t)F * N * S_pad * 2;
+    Scratch s;
+    const void *dA = s.in(act, R * K * 2), *dW = s.in(W, (size_t)N * K * 2);
+    const float* dB = s.in(bias, (size_t)N * 4);
+    void* dO = s.raw(osz);
+    if (s.rc) return s.rc;
+    (void)hipMemset(dO, 0, osz);
+    GemmArgs g = vt_args(dA, dW, F, S, S_pad, N, K, dO);
+    g.bias = dB;
+    g.tile256 = (flags & 16) ? 1 : ((flags & 32) ? -1 : 0);
+    by_prec16(prec, [&](auto t) { launch_gemm_mfma<decltype(t)>(nullptr, g); });
+    if (int rc = finish()) return rc;
+    return down(out, dO, osz);
+}
+
+// spatial attention on q|k rows [F*S][2E] and v rows [F*S][E] (both row-major on the host; V is transposed on the device
+// through the same GEMM_VT-layout the engine uses).  y [F*S][E].  flag 64: causal (query i sees keys 0 .. i), else every key.
+int umgen_dbg_attn_spatial(int flags, const void* qk, const void* v, int F, int S, int H, void* y) {
+    const int bf16 = flags & 3;                 // precision code; flag 32 (fp32 only): the VALU kernel instead of the matrix-core one
+    if ((flags & 64) && (flags & 32)) return UMGEN_E_UNSUPPORTED;   // the causal launchers have no kernel choice
+    const int E = H * kHeadDim, S_pad = pad64(S);
+    const size_t es = bf16 ? 2 : 4, R = (size_t)F * S;
+    // host-side transpose of V into [F][H][48][S_pad]
+    std::vector<unsigned char> vt((size_t)F * E * S_pad * es, 0);
+    const unsigned char* vs = (const unsigned char*)v;
+    for (int f = 0; f < F; ++f)
+        for (int sr = 0; sr < S; ++sr)
+            for (int c = 0; c < E; ++c)
+                memcpy(&vt[(((size_t)f * E + c) * S_pad + sr) * es], &vs[(((size_t)f * S + sr) * E + c) * es], es);
+    Scratch s;
+    const void *dQK = s.in(qk, R * 2 * E * es), *dVT = s.in(vt.data(), vt.size());
+    void* dY = s.out(R * E * es);
+    if (s.rc) return s.rc;
+    if (int rc = fill_nan(dY, R * E, bf16)) return rc;   // a row the kernel leaves out comes back as NaN
+    by_prec(bf16, [&](auto t) {
+        typedef decltype(t) T;
+        const T *q = (const T*)dQK, *vtp = (const T*)dVT;
+        if constexpr (std::is_same<T, float>::value) {
+            if (flags & 64) launch_attn_causal_f32(nullptr, q, vtp, (T*)dY, F, S, S_pad, H);
+            else if (flags & 32) launch_attn_spatial_valu<float>(nullptr, q, vtp, (T*)dY, F, S, S_pad, H);   // flag 32: the VALU kernel
+            else launch_attn_spatial_f32_mfma(nullptr, q, vtp, (T*)dY, F, S, S_pad, H);
+        } else if (flags & 64) {                // flag 64: the causal S x S form of the OAR prefix pass (run_prefix_prefill)
+            launch_attn_causal_mfma<T>(nullptr, q, vtp, (T*)dY, F, S, S_pad, H);
+        } else {
+            launch_attn_spatial_mfma<T>(nullptr, q, vtp, (T*)dY, F, S, S_pad, H);
+        }
+    });
+    if (int rc = s.finish()) return rc;
+    return down(y, dY, R * E * es);
+}
+
+// temporal causal attention on qkv rows [B*T*S][3E] -> y [B*T*S][E].  split = P > 0: slots 0..P-1 first (k | v appended to a
+// slot cache), then slots P..T-1 against that cache -- must equal the single pass bit for bit.
+int umgen_dbg_attn_temporal(int bf16, const void* qkv, int B, int T, int S, int H, int split, void* y) {
+    const int E = H * kHeadDim;
+    const size_t es = bf16 ? 2 : 4, row = (size_t)3 * E * es, orow = (size_t)E * es;
+    // one launch on the slots [t0, t0 + Tn) of every scene, gathered into a compact [B][Tn][S] block and scattered back into y
+    auto pass = [&](int t0, int Tn, TemporalRange tr) -> int {
+        const size_t Rn = (size_t)B * Tn * S;
+        std::vector<unsigned char> hq(Rn * row), hy(Rn * orow);
+        for (int b = 0; b < B; ++b)
+            memcpy(&hq[(size_t)b * Tn * S * row], (const unsigned char*)qkv + ((size_t)b * T + t0) * S * row, (size_t)Tn * S * row);
+        Scratch s;
+        const void* dQ = s.in(hq.data(), hq.size());
+        void* dY = s.raw(hy.size());
+        if (s.rc) return s.rc;
+        by_prec(bf16, [&](auto t) { typedef decltype(t) TT; launch_attn_temporal<TT>(nullptr, (const TT*)dQ, (TT*)dY, B, Tn, S, H, tr); });
+        if (int rc = finish()) return rc;
+        if (down(hy.data(), dY, hy.size())) return UMGEN_E_HIP;
+        for (int b = 0; b < B; ++b)
+            memcpy((unsigned char*)y + ((size_t)b * T + t0) * S * orow, &hy[(size_t)b * Tn * S * orow], (size_t)Tn * S * orow);
+        return UMGEN_OK;
+    };
+    if (split <= 0 || split >= T) return pass(0, T, TemporalRange{0, nullptr, 0, 0});
+    const int Tcap = T + 1;
+    Scratch s;
+    void* dC = s.raw((size_t)B * Tcap * S * 2 * E * es);
+    if (s.rc) return s.rc;
+    if (int rc = pass(0, split, TemporalRange{0, dC, Tcap, 1})) return rc;
+    return pass(split, T - split, TemporalRange{split, dC, Tcap, 0});
+}
+
+// decode-style attention: q [NQ][E] fp32, kv [L][2E] (k | v) of dtype bf16/fp32 shared by all queries -> y [NQ][E] fp32
+// (partial pass + the combine that normally runs in the projection prologue, here through an identity projection)
+int umgen_dbg_attn_decode(int bf16, const float* q, const void* kv, int NQ, int L, int H, float* y) {
+    const int E = H * kHeadDim;
+    const size_t es = bf16 ? 2 : 4;
+    std::vector<float> eye((size_t)E * E, 0.f);
+    for (int i = 0; i < E; ++i) eye[(size_t)i * E + i] = 1.f;
+    Scratch s;
+    const float* dQ = s.in(q, (size_t)NQ * E * 4);
+    const void *dKV = s.in(kv, (size_t)L * 2 * E * es), *dW = s.in(eye.data(), eye.size() * 4);
+    float *dP = s.raw((size_t)NQ * H * kAttnRec * 4), *dX = s.raw((size_t)NQ * E * 4);
+    if (s.rc) return s.rc;
+    (void)hipMemset(dX, 0, (size_t)NQ * E * 4);
+    by_prec(bf16, [&](auto t) {
+        typedef decltype(t) T;
+        launch_attn_partial<T>(nullptr, dQ, (const T*)dKV, 0, kHeadDim, 2L * E, E, NQ, NQ, H, nullptr, L, attn_nsplit(L), dP);
+    });
+    GemvResidArgs a{};
+    a.part = dP; a.H = H; a.ns = attn_nsplit(L); a.W = dW; a.N = E; a.K = E; a.M = NQ; a.x = dX; a.ldx = E;
+    launch_gemv_resid<float>(nullptr, a);
+    if (int rc = finish()) return rc;
+    return down(y, dX, (size_t)NQ * E * 4);
+}
+
+// times `iters` launches of the bf16 MFMA GEMM (mode: GEMM_STORE / GEMM_RESID) on device-resident random operands;
+// returns the average milliseconds per launch through *ms.  tokens R, features N, reduction K.
+int umgen_dbg_gemm_bench(int R, int N, int K, int mode, int iters, float* ms) {
+    Scratch s;
+    DevPtr dA, dW;
+    lcg_operands(s, (size_t)R * K, (size_t)N * K, dA, dW);
+    void* dO = s.raw((size_t)R * N * 4);
+    if (s.rc) return s.rc;
+    (void)hipMemset(dO, 0, (size_t)R * N * 4);
+    GemmArgs g = linear_args(dW, dA, R, N, K, dO);
+    g.mode = mode & 15; g.gelu = (mode >> 4) & 1;                             // mode bit 4: erf-GELU epilogue
+    g.tile256 = (mode & 64) ? -1 : ((mode & 32) ? 1 : 0);                     // bit 5: force the 256 x 256 kernel, bit 6: 128 x 128 kernels only
+    return time_launches(nullptr, 1, iters, 1, ms, [&](int) { launch_gemm_mfma<bf16_t>(nullptr, g); });
+}
+
+// timing of the V^T GEMM (GEMM_VT) of F frames x S tokens; flag 32: force the 256-tile kernel, 64: the 128-tile kernels only
+int umgen_dbg_gemm_vt_bench(int F, int S, int N, int K, int flag, int iters, float* ms) {
+    const int S_pad = pad64(S);
+    const size_t osz = (size_t)F * N * S_pad * 2;
+    Scratch s;
+    DevPtr dA, dW;
+    lcg_operands(s, (size_t)F * S * K, (size_t)N * K, dA, dW);
+    void* dO = s.raw(osz);
+    if (s.rc) return s.rc;
+    (void)hipMemset(dO, 0, osz);
+    GemmArgs g = vt_args(dA, dW, F, S, S_pad, N, K, dO);
+    g.tile256 = (flag & 64) ? -1 : ((flag & 32) ? 1 : 0);
+    return time_launches(nullptr, 1, iters, 1, ms, [&](int) { launch_gemm_mfma<bf16_t>(nullptr, g); });
+}
+
+int umgen_dbg_gemm_stamps(unsigned long long* out16) { return gemm256_read_stamps(out16); }
+
+// few-row linear: out[M][N] = LN(x[M][K]; ln_w) . W[N][K]^T + bias, optional GELU.  W dtype bf16/fp32, activations fp32.
+int umgen_dbg_gemv(int bf16, const float* x, const float* ln_w, const void* W, const float* bias, int M, int N, int K, int gelu, float* out) {
+    const size_t es = bf16 ? 2 : 4, osz = (size_t)M * N * 4;
+    Scratch s;
+    GemvArgs a{};
+    a.x = s.in(x, (size_t)M * K * 4); a.ldx = K; a.ln_w = s.in(ln_w, (size_t)K * 4); a.W = s.in(W, (size_t)N * K * es); a.bias = s.in(bias, (size_t)N * 4);
+    a.N = N; a.K = K; a.M = M; a.out_mode = gelu ? GEMV_OUT_GELU : GEMV_OUT_F32; a.out = s.raw(osz); a.ldo = N; a.E = K;
+    if (s.rc) return s.rc;
+    // the row-loop form, then (M > 1) the one-row-per-workgroup form the engine launches for several scenes: it must give the same bits
+    for (int rpb = 0; rpb <= (M > 1 ? 1 : 0); ++rpb) {
+        std::vector<float> got((size_t)M * N);
+        if (rpb) (void)hipMemset(a.out, 0, osz);
+        a.rows_per_block = rpb;
+        by_prec(bf16, [&](auto t) { launch_gemv<decltype(t)>(nullptr, a); });
+        if (int rc = finish()) return rc;
+        if (int rc = down(rpb ? got.data() : out, a.out, osz)) return rc;
+        if (rpb && memcmp(got.data(), out, osz) != 0) return UMGEN_E_STATE;
+    }
+    return UMGEN_OK;
+}
+
+// the top-k sampler (frame.hip block_sample_topk: UMGen.py:899-913 + 967-974 on the build's uniforms) on n independent rows of V <= 8192
+// logits; *overflow counts the rows whose kept set (ties at the k-th value) exceeded the sampler's 64 slots
+int umgen_dbg_sample_topk(const float* logits, int n, int V, int k, float temp, const float* u, int32_t* tokens, int32_t* overflow) {
+    if (V > 8192 || V < 1 || n < 1) return UMGEN_E_INVALID;
+    Scratch s;
+    const float *dL = s.in(logits, (size_t)n * V * 4), *dU = s.in(u, (size_t)n * 4);
+    int *dT = s.raw((size_t)n * 4), *dO = s.raw(4);
+    if (s.rc) return s.rc;
+    (void)hipMemset(dO, 0, 4);
+    launch_sample_rows(nullptr, dL, V, k, temp, dU, dT, dO, n);
+    if (int rc = finish()) return rc;
+    if (int rc = down(tokens, dT, (size_t)n * 4)) return rc;
+    return down(overflow, dO, 4);
+}
+
+// Timing hook of the batched decode layer's kernels (decode_batched.hip) on random data: one BlockOAR layer's five launches at M scenes and
+// KV length L, `iters` times back to back; us[0..4] = average microseconds of q|k|v, attention, c_proj, c_fc, mlp c_proj (HIP events
+// around each launch), us[5] = the five as one sequence.
+int umgen_dbg_batched_layer_bench(int prec, int M, int L, int iters, float* us) {
+    const int E = 768, H = 16, Lmax = 2304;
+    if (prec != 1 && prec != 2) return UMGEN_E_INVALID;
+    if (M < 1 || M > kRowsMaxM || L < 1 || L >= Lmax) return UMGEN_E_INVALID;
+    const size_t wsz = (size_t)12 * E * E * 2, csz = (size_t)M * 2 * H * Lmax * kHeadDim * 2, xsz = (size_t)64 * E * 4;
+    std::vector<unsigned short> hw(wsz / 2);
+    for (size_t i = 0; i < hw.size(); ++i) hw[i] = (unsigned short)(0x3c00 + (i * 2654435761u >> 24)) & (prec == 1 ? 0x3cff : 0x2fff);   // small positive values
+    std::vector<float> hx((size_t)64 * E, 0.25f), hl(E, 1.f), hb(4 * E, 0.f);
+    for (size_t i = 0; i < hx.size(); ++i) hx[i] = 0.25f + 1e-3f * (float)(i % 97);
+    Scratch s;
+    const char* Wq = s.in(hw.data(), wsz);
+    void* dC = s.raw(csz);
+    float *dx = s.in(hx.data(), xsz), *dxr = s.in(hx.data(), xsz), *dq = s.raw(xsz), *da = s.raw(xsz), *dh = s.raw(4 * xsz);
+    const float *dln = s.in(hl.data(), (size_t)E * 4), *db = s.in(hb.data(), (size_t)4 * E * 4);
+    const int* dlen = s.in(&L, 4);
+    if (s.rc) return s.rc;
+    if (hipMemset(da, 0, xsz) != hipSuccess || hipMemset(dh, 0, 4 * xsz) != hipSuccess || hipMemset(dC, 0, csz) != hipSuccess) return UMGEN_E_HIP;
+    Stream stream;
+    if (!stream.s) return UMGEN_E_HIP;
+    hipStream_t st = stream.s;
+    const long cstride = (long)2 * H * Lmax * kHeadDim;
+    auto run = [&](int which) {
+        by_prec16(prec, [&](auto tag) {
+            typedef decltype(tag) TT;
+            RowsArgs r{};
+            r.M = M; r.E = E;
+            switch (which) {
+                case 0: r.x = dx; r.ln_w = dln; r.W = Wq; r.bias = db; r.N = 3 * E; r.K = E; r.mode = ROWS_QKV; r.out = dq; r.ldo = E;
+                        r.cache = dC; r.scene_stride = cstride; r.d_len = dlen; r.Lmax = Lmax; launch_rows_mfma<TT>(st, r); break;
+                case 1: launch_attn_decode_batched<TT>(st, dq, (const TT*)dC, cstride, M, H, Lmax, dlen, da); break;
+                case 2: r.x = da; r.W = Wq + (size_t)3 * E * E * 2; r.bias = db; r.N = E; r.K = E; r.mode = ROWS_RESID; r.out = dxr; r.ldo = E; r.out_frag = dx; launch_rows_mfma<TT>(st, r); break;
+                case 3: r.x = dx; r.ln_w = dln; r.W = Wq + (size_t)4 * E * E * 2; r.N = 4 * E; r.K = E; r.mode = ROWS_GELU; r.out_frag = dh; launch_rows_mfma<TT>(st, r); break;
+                default: r.x = dh; r.W = Wq + (size_t)8 * E * E * 2; r.N = E; r.K = 4 * E; r.mode = ROWS_RESID; r.out = dxr; r.ldo = E; r.out_frag = dx; launch_rows_mfma<TT>(st, r); break;
+            }
+        });
+    };
+    if (int rc = time_launches(st, 3, iters, 6, us, [&](int which) { if (which < 5) run(which); else for (int k = 0; k < 5; ++k) run(k); })) return rc;
+    for (int i = 0; i < 6; ++i) us[i] *= 1000.f;
+    return UMGEN_OK;
+}
+
+}  // extern "C"

@@ -638,7 +638,7 @@ void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerPar
     hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow);
 }
 
-// test hook (debug_api.hip): the top-k sampler on n independent logit rows with given uniforms
+// test hook (debug_gemm_attn.hip): the top-k sampler on n independent logit rows with given uniforms
 __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ logits, int V, int k, float temp, const float* __restrict__ u,
                                                           int* __restrict__ out, int* overflow) {
     __shared__ SamplerLds sh;
@@ -649,7 +649,7 @@ void launch_sample_rows(hipStream_t s, const float* logits, int V, int k, float 
     hipLaunchKernelGGL(sample_rows_kernel, dim3(n), dim3(256), 0, s, logits, V, k, temp, u, out, overflow);
 }
 
-// test hook (debug_api.hip): block_sample -- the decode step's dispatch on SamplerParams.method -- on n independent rows with given
+// test hook (debug_decode.hip): block_sample -- the decode step's dispatch on SamplerParams.method -- on n independent rows with given
 // uniforms and one masked index (sample_token_kernel's control resample masks vocab - 1)
 __global__ __launch_bounds__(256) void sample_dbg_kernel(const float* __restrict__ logits, int V, SamplerParams sp, int k, float p,
                                                          const float* __restrict__ u, int mask_idx, int* __restrict__ out, int* overflow) {
@@ -662,7 +662,7 @@ void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerP
     hipLaunchKernelGGL(sample_dbg_kernel, dim3(n), dim3(256), 0, s, logits, V, sp, k, p, u, mask_idx, out, overflow);
 }
 
-// test hook (debug_api.hip): check_collision_dev on box set b = boxes[b][0 .. counts[b]), one block per set; thread 0 evaluates it with
+// test hook (debug_decode.hip): check_collision_dev on box set b = boxes[b][0 .. counts[b]), one block per set; thread 0 evaluates it with
 // the same LDS corner table sample_token_kernel gives it
 __global__ __launch_bounds__(64) void collision_rows_kernel(const double* __restrict__ boxes, const int* __restrict__ counts, int max_n,
                                                             int* __restrict__ out) {

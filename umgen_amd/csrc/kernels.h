@@ -114,7 +114,7 @@ template <typename T> void launch_gemv_resid(hipStream_t s, const GemvResidArgs&
 
 // One BlockOAR layer of the decode step as five launches (gemv.hip): LN + q|k|v (K/V rows into the head-major cache at *d_len),
 // attention partials over keys 0 .. *d_len, c_proj with the split merge (+x), LN + c_fc + GELU, mlp c_proj (+x).  oar_layers
-// (engine.hip) and the test hook umgen_dbg_decode_layer both launch through it.
+// (engine_decode.hip) and the test hook umgen_dbg_decode_layer both launch through it.
 struct DecodeLayerArgs {
     const float *ln_a, *bqkv, *bo, *ln_b;
     const void *Wqkv, *Wo, *Wfc, *Wproj;
@@ -125,7 +125,7 @@ struct DecodeLayerArgs {
 };
 template <typename T> void launch_decode_layer(hipStream_t s, const DecodeLayerArgs& a);
 
-// The ego decoder's two attentions (engine.hip run_ego, shared with the test hook umgen_dbg_attn_partial): 3 queries q [3B][E] per scene
+// The ego decoder's two attentions (engine_stacks.hip run_ego, shared with the test hook umgen_dbg_attn_partial): 3 queries q [3B][E] per scene
 //   self:  over the scene's own 3 packed q|k|v rows qkv3 [3B][3E] (fp32 in every precision mode), one split
 //   cross: over the scene's kSeq k|v rows kv [B * kSeq][2E] of T, attn_nsplit(kSeq) splits
 inline int ego_cross_nsplit() { return attn_nsplit(kSeq); }
