@@ -165,6 +165,23 @@ int umgen_frame(umgen_engine *e, int32_t T, const int64_t *pose, const int64_t *
                 const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
                 int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image);
 
+/* Per-token log-likelihoods of a GIVEN next frame: the reference's teacher-forced loss terms (get_targets, d_loss, F.cross_entropy per modality,
+ * UMGen.py:539-582) as one forward pass.  For B scenes with history windows pose/map/bbox3d/image [B][T][S_mod] and their next frames next_* [B][S_mod]:
+ *     logp_m[b][k]   = log_softmax(logits_m[k])[next_m[b][k]]   (natural log)
+ *     argmax_m[b][k] = the most likely token at that position (lowest index among equal maxima)
+ * where logits_m are the rows umgen_frame traces for the same window with forced_* = next_* (pose: its ego_logits): the plain AR heads head_ar_map /
+ * head_ar_bbox3d / head_ar_img and head_ego at temperature 1 -- not the sampler's distribution (no top-k / top-p, no resampling through head_tar_bbox3d, no
+ * rule constraint).  bos / eos positions carry no score; no RNG is involved.  All 2206 positions go through the BlockOAR layers as ONE pass with the
+ * arithmetic of the given-token prefix pass (umgen_rollout's given_*), not as 2206 decode steps: fp32 engines agree with the traced logits up to summation
+ * order, 16-bit engines the way the one-pass prefix agrees with its step-by-step replay.  B <= max_batch, T <= max_cond_frames; tokens are range-checked
+ * like umgen_rollout's.  Any pointer of `out` may be NULL. */
+typedef struct umgen_score_out {
+    float *logp_pose, *logp_map, *logp_bbox3d, *logp_image;           /* [B][3], [B][1024], [B][660], [B][512] */
+    int32_t *argmax_pose, *argmax_map, *argmax_bbox3d, *argmax_image; /* the same shapes */
+} umgen_score_out;
+int umgen_score(umgen_engine *e, int32_t B, int32_t T, const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                const int64_t *next_pose, const int64_t *next_map, const int64_t *next_bbox3d, const int64_t *next_image, umgen_score_out *out);
+
 int umgen_set_profiling(umgen_engine *e, int32_t enable); /* per-launch HIP-event timing of the GEMM / attention kernels and of the
                                                             * decode step's layer kernel(s); profiled frames launch eagerly */
 int umgen_get_timings(umgen_engine *e, umgen_timings *out);

@@ -1,0 +1,58 @@
+#!/usr/bin/env python
+"""Timing of umgen_score (one forward pass over a given frame) against the only earlier route to the same numbers, a teacher-forced
+umgen_frame (2206 decode steps): UMGen_Large, synthetic weights, bf16, one engine of 8 scenes, a window of T history frames.
+After one warm-up call each: the median of 5 host-clock calls of Engine.score at B = 1 and B = 8 and of Engine.frame(forced=..., trace=False).
+    python tools/score_bench.py [out.json] [--T=20]  ->  one JSON line (also written to out.json, default profiles/score_bench.json)"""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+from umgen_amd.config import MOD_ORDER, large_config  # noqa: E402
+from umgen_amd.engine import Engine  # noqa: E402
+from umgen_amd.synth import synthetic_scene  # noqa: E402
+from umgen_amd.weights import synthetic_items  # noqa: E402
+
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+T = next((int(a[4:]) for a in sys.argv[1:] if a.startswith("--T=")), 20)
+REPS = 5
+
+
+def median_ms(fn):
+    fn()
+    ts = []
+    for _ in range(REPS):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), ts
+
+
+cfg = large_config()
+e = Engine(cfg, precision="bf16", max_batch=8, max_cond_frames=T)
+e.load_state_dict(synthetic_items(cfg, seed=0))
+e.finalize()
+sc = [synthetic_scene(i, n_frames=T + 1) for i in range(8)]
+window = {m: np.concatenate([s[m][:, :T] for s in sc]) for m in MOD_ORDER}
+frame = {m: np.concatenate([s[m][:, T] for s in sc]) for m in MOD_ORDER}
+one_w, one_f = {m: window[m][0] for m in MOD_ORDER}, {m: frame[m][0] for m in MOD_ORDER}
+
+res = {"config": "UMGen_Large synthetic", "precision": "bf16", "history_frames": T, "reps": REPS}
+res["score_b1_ms"], res["score_b1_all_ms"] = median_ms(lambda: e.score(one_w, one_f))
+res["score_b8_ms"], res["score_b8_all_ms"] = median_ms(lambda: e.score(window, frame))
+res["forced_frame_b1_ms"], res["forced_frame_b1_all_ms"] = median_ms(lambda: e.frame(one_w, forced=one_f, trace=False))
+res["score_b8_ms_per_scene"] = res["score_b8_ms"] / 8
+res["forced_frame_over_score_b1"] = res["forced_frame_b1_ms"] / res["score_b1_ms"]
+r = e.score(one_w, one_f)
+res["nll_b1"] = {m: float(-r["logp"][m].astype(np.float64).mean()) for m in MOD_ORDER}
+e.close()
+line = json.dumps(res)
+print(line)
+out = args[0] if args else os.path.join(ROOT, "profiles", "score_bench.json")
+with open(out, "w") as f:
+    f.write(line + "\n")

@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame and the rollout driver umgen_rollout (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
+// umgen_frame, umgen_score and the rollout driver umgen_rollout (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
 #include "engine_state.h"
 
@@ -111,6 +111,44 @@ int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* 
     for (int i = 0; i < kNMap; ++i) out_map[i] = out[kOffMap + i];
     for (int i = 0; i < kNBox; ++i) out_bbox3d[i] = out[kOffBox + i];
     for (int i = 0; i < kNImg; ++i) out_image[i] = out[kOffImg + i];
+    return UMGEN_OK;
+}
+
+// log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes: engine_frame.hip run_score
+int umgen_score(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, umgen_score_out* out) {
+    if (!e) return UMGEN_E_INVALID;
+    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
+    if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
+    if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
+    if (!out) return e->fail(UMGEN_E_INVALID, "null output struct");
+    if (!pose || !map || !bbox3d || !image || !next_pose || !next_map || !next_bbox3d || !next_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
+    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
+    if (int rc = check_scene_tokens(e, (size_t)B * T, pose, map, bbox3d, image)) return rc;
+    if (int rc = check_scene_tokens(e, (size_t)B, next_pose, next_map, next_bbox3d, next_image)) {
+        e->err = "next frame: " + e->err;
+        return rc;
+    }
+    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
+    const int64_t* in[4] = {pose, map, bbox3d, image};
+    const int64_t* nx[4] = {next_pose, next_map, next_bbox3d, next_image};
+    std::vector<int> win[4], next((size_t)B * kTokPerFrame);
+    for (int m = 0; m < 4; ++m) {
+        win[m].resize((size_t)B * T * S[m]);
+        for (size_t i = 0; i < win[m].size(); ++i) win[m][i] = (int)in[m][i];
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < S[m]; ++i) next[(size_t)b * kTokPerFrame + off[m] + i] = (int)nx[m][(size_t)b * S[m] + i];
+    }
+    std::vector<float> logp((size_t)B * kTokPerFrame);
+    std::vector<int> arg((size_t)B * kTokPerFrame);
+    const ScoreIO sc{B, T, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), logp.data(), arg.data()};
+    if (int rc = run_score_any(e, sc)) return rc;
+    float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
+    int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
+    for (int m = 0; m < 4; ++m) {      // the engine's blocks are pose | map | bbox3d | image, each [B][S_mod]
+        if (lo[m]) memcpy(lo[m], &logp[(size_t)B * off[m]], (size_t)B * S[m] * sizeof(float));
+        if (ao[m]) memcpy(ao[m], &arg[(size_t)B * off[m]], (size_t)B * S[m] * sizeof(int32_t));
+    }
     return UMGEN_OK;
 }
 

@@ -1,6 +1,7 @@
 // One frame, UMGen._inference: run_frame<T> as a sequence of stages -- background pass, uploads, ego net and pose shift, decode state, the
-// stacks, first input and prefix pass, the lane loop or the single-stream step loop, drain, download, checks, bookkeeping -- and
-// run_frame_any, which picks the precision and cleans up behind a failed frame.
+// stacks, first input and prefix pass, the lane loop or the single-stream step loop, drain, download, checks, bookkeeping -- run_score<T>,
+// the scoring pass of umgen_score built from the same stages, and run_frame_any / run_score_any, which pick the precision and clean up
+// behind a failed call.
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -622,33 +623,94 @@ int run_frame(umgen_engine* e, const FrameIO& io) {
     return 0;
 }
 
+// umgen_score: log p of a GIVEN next frame for B scenes (the reference's teacher-forced loss, UMGen.py:539-582), from run_frame's own stages.  The
+// window, pose shift, map warp and conditioning rows are those of a teacher-forced frame; then all 2206 decode inputs of the frame go through
+// the BlockOAR layers as ONE pass (run_prefix_prefill: the stacks' arithmetic contract) and the scoring head (score.hip) reads ln_oar . head
+// off the rows of X: no decode step, no sampler, no RNG, no logit buffer.  The pass works in the stacks' workspaces and the decode cache, so
+// nothing an earlier rollout left in the slot caches is trusted afterwards (px.valid).
+template <typename T>
+int run_score(umgen_engine* e, const ScoreIO& sc) {
+    hipStream_t const fg = e->stream;
+    e->launch_status = hipSuccess;
+    (void)hipGetLastError();
+    struct RestoreStream { umgen_engine* e; hipStream_t s; ~RestoreStream() { e->stream = s; e->set_work(e->w_main); } } restore{e, fg};
+    const int E = e->E, B = sc.B;
+    // the ego net's sampler runs and is overridden by the given pose (run_ego's forced form): any valid parameters do
+    static const umgen_sampling smp{UMGEN_SAMPLE_TOPK, 1, 1, 1, 1.f, 1.f, 1.f, 0, 0, 0, nullptr};
+    const FrameIO io{B, sc.T, sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &smp, nullptr, nullptr};
+    FrameCtx ctx{};
+    ctx.fg = fg;
+    ctx.st = fg;
+    ctx.sp = SamplerParams{smp.method, smp.top_k, smp.top_k_map, smp.topk_image, smp.p, smp.p_map, smp.temperature, 0, 0, 0};
+    e->px.valid = false;                 // (before the stage below asks whether an earlier pass covers this window: the score is always a whole-window pass)
+    if (int rc = settle_background_pass(e, io, ctx)) return rc;
+    hipStream_t const st = ctx.st;
+    if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
+    HIPCHK(e, hipMemcpyAsync(e->d_forced, sc.next, (size_t)B * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
+    ctx.forced = true;                   // the ego net with the next pose forced: its logits stay in e->logits [3 B][pose_vocab]
+    if (int rc = ego_and_pose_shift(e, io, ctx)) return rc;
+    float* lp = e->score_logp;
+    int* am = e->score_arg;
+    launch_logits_nll(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, lp, am, nullptr, nullptr);
+    HIPCHK(e, hipMemcpyAsync(e->d_tokens, sc.next, (size_t)B * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
+    if (int rc = run_stacks(e, io, ctx)) return rc;
+    if (int rc = run_prefix_prefill_any(e, B, kSeq)) return rc;      // rows 0 .. 2205 of every scene in X; row j predicts the token at position j
+    const int c0[3] = {kMapC0, kBoxC0, kImgC0}, n[3] = {kNMap, kNBox, kNImg}, off[3] = {kOffMap, kOffBox, kOffImg};
+    const int V[3] = {e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
+    const void* head[3] = {e->head_ar_map, e->head_ar_box, e->head_ar_img};
+    for (int m = 0; m < 3; ++m) {
+        HeadNllArgs a{};
+        a.x = e->X + (long)c0[m] * E; a.ldx = E; a.rows_per_group = n[m]; a.group_stride = (long)(kSeq - 1) * E;
+        a.ln_w = e->ln_oar; a.W = head[m]; a.V = V[m]; a.K = E; a.M = B * n[m];
+        a.target = e->d_tokens + off[m]; a.target_group_stride = kTokPerFrame;
+        a.part = e->score_part; a.logp = lp + (long)B * off[m]; a.argmax = am + (long)B * off[m];
+        HIPCHK(e, launch_head_nll<T>(st, a));
+    }
+    HIPCHK(e, hipMemcpyAsync(sc.logp, lp, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(sc.argmax, am, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    const hipError_t le = e->launch_status != hipSuccess ? e->launch_status : hipGetLastError();
+    e->launch_status = hipSuccess;
+    if (le != hipSuccess) return e->fail(UMGEN_E_HIP, "a kernel launch of this scoring pass was refused: %s", hipGetErrorString(le));
+    return 0;
+}
+
+// A failed frame may have left a stream capture open, async copies in flight that read this call's host buffers, and a
+// background pass the next call would wait for: drain everything and forget the pass (the error message is kept).
+void drain_failed_frame(umgen_engine* e) {
+    const std::string msg = e->err;
+    for (hipStream_t s : {e->stream, e->full_stream, e->bg_stream, e->side_stream[0], e->side_stream[1], e->lane[0].s, e->lane[1].s, e->lane[2].s,
+                          e->lane[3].s, e->lane[4].s, e->lane[5].s, e->lane[6].s, e->lane[7].s}) {
+        if (!s) continue;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            hipGraph_t g = nullptr;
+            (void)hipStreamEndCapture(s, &g);
+            if (g) (void)hipGraphDestroy(g);
+        }
+    }
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    e->bg_pending = false;
+    e->px.valid = false;
+    e->err = msg;
+}
+
 }  // namespace
 
 namespace umgen {
 
+int run_score_any(umgen_engine* e, const ScoreIO& sc) {
+    const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_score<bf16_t>(e, sc)
+                 : e->cfg.precision == UMGEN_PREC_FP16 ? run_score<f16_t>(e, sc) : run_score<float>(e, sc);
+    if (rc != UMGEN_OK) drain_failed_frame(e);
+    return rc;
+}
+
 int run_frame_any(umgen_engine* e, const FrameIO& io) {
     const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_frame<bf16_t>(e, io)
                  : e->cfg.precision == UMGEN_PREC_FP16 ? run_frame<f16_t>(e, io) : run_frame<float>(e, io);
-    if (rc != UMGEN_OK) {
-        // A failed frame may have left a stream capture open, async copies in flight that read this call's host buffers, and a
-        // background pass the next call would wait for: drain everything and forget the pass (the error message is kept).
-        const std::string msg = e->err;
-        for (hipStream_t s : {e->stream, e->full_stream, e->bg_stream, e->side_stream[0], e->side_stream[1], e->lane[0].s, e->lane[1].s, e->lane[2].s,
-                              e->lane[3].s, e->lane[4].s, e->lane[5].s, e->lane[6].s, e->lane[7].s}) {
-            if (!s) continue;
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-                hipGraph_t g = nullptr;
-                (void)hipStreamEndCapture(s, &g);
-                if (g) (void)hipGraphDestroy(g);
-            }
-        }
-        (void)hipDeviceSynchronize();
-        (void)hipGetLastError();
-        e->bg_pending = false;
-        e->px.valid = false;
-        e->err = msg;
-    }
+    if (rc != UMGEN_OK) drain_failed_frame(e);
     return rc;
 }
 

@@ -366,6 +366,9 @@ int alloc_workspace(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dev_alloc(e, &e->Hb, R * 4 * E * e->tsz)) return rc;
     if (int rc = dalloc(e, &e->mapfeat, Bm * Tm * kNMap * E)) return rc;
     e->w_main = umgen_engine::Work{e->X, e->A, e->QKV, e->VT, e->Hb, e->mapfeat};
+    if (int rc = dalloc(e, &e->score_part, Bm * kNMap * 8 * 4)) return rc;      // (head_nll_nsplit <= 8)
+    if (int rc = dalloc(e, &e->score_logp, Bm * kTokPerFrame)) return rc;
+    if (int rc = dalloc(e, &e->score_arg, Bm * kTokPerFrame)) return rc;
     // The three TAR stacks of a frame are independent (UMGen.py:1484-1494 feeds each the same window): in the plain path the map and box
     // stacks run on two side streams with whole-window workspaces of their own, so that the tail of every launch (a persistent GEMM's
     // last partial round of tiles, the ragged last attention blocks, the gaps between dependent launches) is filled by the other

@@ -79,6 +79,10 @@ struct umgen_engine {
     double* d_boxes = nullptr;
     unsigned long long* d_seeds = nullptr;
     OarState* d_state = nullptr;
+    // umgen_score (engine_frame.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
+    // each block [max_batch][S_mod]
+    float *score_part = nullptr, *score_logp = nullptr;
+    int* score_arg = nullptr;
     // Overlapped TAR pass.  Causal temporal attention + frame-local spatial attention make every history
     // slot but the last one of the NEXT frame's window independent of the frame being decoded, so those slots are pushed through
     // the ego / map / box / TAR stacks on `bg_stream` (a CU-masked stream) while the latency-bound decode loop runs on the
@@ -246,6 +250,15 @@ struct FrameIO {
     const int* given_box = nullptr;              // host [B][660] or nullptr: ... and its boxes (only behind a given map)
 };
 
+// umgen_score's arguments: B scenes' history windows and the frame to score, as host int32 arrays
+struct ScoreIO {
+    int B, T;
+    const int *pose, *map, *box, *img;          // [B][T][S_mod]
+    const int* next;                             // [B][2199]: the scored frame, pose | map | bbox3d | image
+    float* logp;                                 // host [2199 B]: pose [B][3] | map [B][1024] | bbox3d [B][660] | image [B][512]
+    int* argmax;                                 // the same layout
+};
+
 // ---- engine_weights.hip ---------------------------------------------------------------------------------------------
 void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);
 
@@ -277,5 +290,6 @@ int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace*
 
 // ---- engine_frame.hip -----------------------------------------------------------------------------------------------
 int run_frame_any(umgen_engine* e, const FrameIO& io);
+int run_score_any(umgen_engine* e, const ScoreIO& sc);
 
 }  // namespace umgen

@@ -510,7 +510,8 @@ __global__ __launch_bounds__(256) void prefix_rows_kernel(EmbedTables tb, const 
         if (aux >= 0) ef = tb.axe + (long)aux * E;
         else if (jp < kPoseEos) eb = tb.fouier_pe + (long)toks[jp - 1] * E;
         else if (jp < kMapEos) ef = tb.gmap + (long)toks[kOffMap + (jp - kMapC0)] * E;
-        else ef = tb.be + (long)toks[kOffBox + (jp - kBoxC0)] * E;
+        else if (jp < kBoxEos) ef = tb.be + (long)toks[kOffBox + (jp - kBoxC0)] * E;
+        else ef = tb.gimg + (long)toks[kOffImg + (jp - kImgC0)] * E;      // (the scoring pass: every position of the frame is given)
     }
     for (int c = threadIdx.x; c < E; c += blockDim.x) xo[c] = (ef ? ef[c] : bf16_to_f32(eb[c])) + cr[c];
 }

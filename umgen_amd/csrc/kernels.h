@@ -172,6 +172,29 @@ template <typename TT> void launch_attn_decode_batched(hipStream_t s, const floa
                                                         const int* d_len, float* y);
 
 // ------------------------------------------------------------------------------------------------
+// scoring a given frame (score.hip): per row  log softmax(LN(x) W^T)[target]  without a logit buffer
+// ------------------------------------------------------------------------------------------------
+// Rows come in groups (the scenes of a call): row r is x + (r / rows_per_group) * group_stride + (r % rows_per_group) * ldx, its target
+// target[(r / rows_per_group) * target_group_stride + r % rows_per_group]; the outputs are dense [M].
+struct HeadNllArgs {
+    const float* x; long ldx; int rows_per_group; long group_stride;
+    const float* ln_w;                 // LayerNorm weight [K] (weight only, eps 1e-5)
+    const void* W; int V, K, M;        // head [V][K] of the weight type; K one of 96, 768, 1536 (head_nll_supported)
+    const int* target; long target_group_stride;
+    float* part;                       // scratch: M x head_nll_nsplit(V) records of 16 bytes (max, sum-exp, target logit, arg-max)
+    float* logp; int* argmax;          // [M] each; nullable
+    float *lse, *tlogit;               // [M] each; nullable (test hook): log-sum-exp and the target's logit
+};
+inline bool head_nll_supported(int K) { return K == 96 || K == 768 || K == 1536; }
+// the vocabulary is split over workgroups in whole tiles of 16 columns; a function of V alone (8192: 8 splits of 64 tiles, 1028: 5 of 13)
+__host__ __device__ inline int head_nll_tiles_per_split(int V) { const int nt = (V + 15) / 16, t = (nt + 7) / 8; return t < 13 ? 13 : t; }
+inline int head_nll_nsplit(int V) { const int nt = (V + 15) / 16, t = head_nll_tiles_per_split(V); return (nt + t - 1) / t; }
+template <typename T> hipError_t launch_head_nll(hipStream_t s, const HeadNllArgs& a);   // hipErrorInvalidValue: unsupported K
+// the same outputs for rows whose logits exist: logits [M][ld], V columns each
+void launch_logits_nll(hipStream_t s, const float* logits, long ld, int V, int M, const int* target, int rows_per_group, long target_group_stride,
+                       float* logp, int* argmax, float* lse, float* tlogit);
+
+// ------------------------------------------------------------------------------------------------
 // XCD-resident decode engine (oar_engine.hip): all BlockOAR layers of one decode step in one launch, bf16 weights, n_embd 768
 // ------------------------------------------------------------------------------------------------
 constexpr int kEngE = 768, kEngH = 16;         // the width the engine is built for (UMGen_Large); other widths use the launches above

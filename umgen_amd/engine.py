@@ -209,6 +209,46 @@ class Engine:
                                          "sampled_ne_forced"), counters[:6].tolist()))
         return outs, tbuf
 
+    def _score_args(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray]):
+        """Shapes and token ranges of a score call, checked before anything reaches the device.  Returns (w [B, T, S], nx [B, S], batched)."""
+        w = {m: _i64(window[m]) for m in MOD_ORDER}
+        nx = {m: _i64(next_frame[m]) for m in MOD_ORDER}
+        batched = w["pose"].ndim == 3
+        for m in MOD_ORDER:
+            if w[m].ndim != (3 if batched else 2) or nx[m].ndim != (2 if batched else 1):
+                raise UMGenError(f"score: window[{m}] has shape {w[m].shape} and next_frame[{m}] {nx[m].shape}; expected [B, T, S] with [B, S], or [T, S] with [S]")
+            if not batched:
+                w[m], nx[m] = w[m][None], nx[m][None]
+        B, T = w["pose"].shape[:2]
+        vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
+        for m in MOD_ORDER:
+            if w[m].shape != (B, T, CONTENT_LEN[m]):
+                raise UMGenError(f"score: window[{m}] has shape {w[m].shape}, expected {(B, T, CONTENT_LEN[m])}")
+            if nx[m].shape != (B, CONTENT_LEN[m]):
+                raise UMGenError(f"score: next_frame[{m}] has shape {nx[m].shape}, expected {(B, CONTENT_LEN[m])}")
+            for what, a in (("window", w[m]), ("next_frame", nx[m])):
+                bad = np.flatnonzero((a.reshape(-1) < 0) | (a.reshape(-1) >= vocab[m]))
+                if bad.size:
+                    raise UMGenError(f"score: {what}[{m}] token {int(a.reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
+        if T < 1:
+            raise UMGenError("score: the window has no history frame")
+        return w, nx, batched
+
+    def score(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray]) -> Dict[str, Dict[str, np.ndarray]]:
+        """Per-token log-likelihood of a given next frame (umgen_score: one forward pass, no sampling).
+        window: mod -> [B, T, S_mod] (or [T, S_mod]); next_frame: mod -> [B, S_mod] (or [S_mod]).
+        Returns {"logp": {mod: float32 [B, S_mod]}, "argmax": {mod: int64 [B, S_mod]}} (without the B axis for un-batched inputs):
+        logp[mod][b, k] = log softmax(AR head logits at that position)[next_frame[mod][b, k]], the teacher-forced trace of `frame` in closed form."""
+        w, nx, batched = self._score_args(window, next_frame)
+        B, T = w["pose"].shape[:2]
+        logp = {m: np.full((B, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
+        arg = {m: np.full((B, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
+        out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
+                            **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+        self._check(self.lib.umgen_score(self._h, B, T, *[_p64(w[m]) for m in MOD_ORDER], *[_p64(nx[m]) for m in MOD_ORDER], C.byref(out)), "score")
+        pick = (lambda a: a) if batched else (lambda a: a[0])
+        return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}}
+
     def dbg_oar_step(self, x: np.ndarray, L: int, use_engine: bool, unmasked: bool = True) -> np.ndarray:
         """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L)."""
         x = np.ascontiguousarray(x, dtype=np.float32)

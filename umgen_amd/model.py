@@ -156,3 +156,45 @@ class UMGen(nn.Module):
         seeds = kwargs.get("seeds", [self.seed + i for i in range(B)])
         return self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames,
                                    init_tokens=init, control_test=bool(control_test), seeds=seeds)
+
+    @staticmethod
+    def _score_window(cond: Dict[str, np.ndarray], tgt: Dict[str, np.ndarray], input_cond_frames: int, t: Optional[int], cap: int):
+        """What `score` hands the engine: (window mod -> [B, n, S], frame mod -> [B, S]).  Pure numpy, raises UMGenError on bad shapes."""
+        for m in MOD_ORDER:
+            if cond[m].ndim != 3 or tgt[m].ndim not in (2, 3) or cond[m].shape[0] != tgt[m].shape[0] or tgt[m].ndim != tgt["pose"].ndim:
+                raise UMGenError(f"score: input_cond_tokens[{m}] {cond[m].shape} / target_tokens[{m}] {tgt[m].shape}: expected [B, T, S] and [B, S] or [B, T_all, S]")
+        have = cond["pose"].shape[1]
+        if tgt["pose"].ndim == 2:      # one frame: scored against the last frames of the conditioning clip
+            if t is not None:
+                raise UMGenError("score: t selects a frame of 3-D target_tokens")
+            end, frame = have, tgt
+        else:                          # a clip: frame t against the frames before it (t counts in both clips)
+            T_all = tgt["pose"].shape[1]
+            t = min(have, T_all - 1) if t is None else t
+            if not 0 < t < T_all or t > have:
+                raise UMGenError(f"score: t={t} needs 1 <= t < {T_all} target frames and at least t of the {have} conditioning frames")
+            end, frame = t, {m: tgt[m][:, t] for m in MOD_ORDER}
+        n = min(end, cap) if input_cond_frames == -1 else input_cond_frames
+        if n < 1 or n > end or n > cap:
+            raise UMGenError(f"score: input_cond_frames={input_cond_frames} with {end} frames before the scored one (window cap {cap})")
+        return {m: np.ascontiguousarray(cond[m][:, end - n:end]) for m in MOD_ORDER}, frame
+
+    @torch.no_grad()
+    def score(self, input_cond_tokens: Dict[str, torch.Tensor], target_tokens: Dict[str, torch.Tensor], input_cond_frames: int = -1,
+              t: Optional[int] = None) -> Dict[str, dict]:
+        """Per-token log-likelihood of a recorded frame under the model: the reference's loss terms (get_targets, d_loss, F.cross_entropy per
+        modality, UMGen.py:539-582) without the sampler.  Scores ``target_tokens[m][:, t]`` ([B, T_all, S_mod]; default: the frame behind the
+        conditioning clip) -- or ``target_tokens[m]`` itself when it is one frame [B, S_mod] -- against the ``input_cond_frames`` frames of
+        ``input_cond_tokens`` before it (-1: as many as there are, at most the engine's window of 20).
+        Returns Engine.score's dict plus "nll": mod -> float64 [B], the mean negative log-likelihood per scene."""
+        if not self._loaded:
+            raise UMGenError("load_state_dict() has not provided every tensor the model reads")
+        np_ = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
+        window, frame = self._score_window({m: np_(input_cond_tokens[m]) for m in MOD_ORDER}, {m: np_(target_tokens[m]) for m in MOD_ORDER},
+                                           input_cond_frames, t, min(20, self.rcfg.max_frame_len))
+        B = window["pose"].shape[0]
+        if B > self._engine_args["max_batch"]:
+            self._recreate(max_batch=B)
+        res = self.engine.score(window, frame)
+        res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=1) for m in MOD_ORDER}
+        return res
