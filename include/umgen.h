@@ -165,6 +165,38 @@ int umgen_frame(umgen_engine *e, int32_t T, const int64_t *pose, const int64_t *
                 const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
                 int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image);
 
+/* ---- log-likelihoods of GENERATED frames: the counterpart of umgen_score on the generating side --------------------------------------
+ * umgen_rollout / umgen_frame with one more argument; lp == NULL or all-NULL members behave exactly like those (which are calls of these
+ * with lp = NULL), and the tokens are the same bits either way.  For every content token of every NEW frame a float32 natural-log value in
+ * umgen_score's measure -- the plain AR heads head_ar_map / head_ar_bbox3d / head_ar_img (head_ego for the pose) at temperature 1 over the
+ * whole vocabulary, not the sampler's truncated / tempered distribution, and never head_tar_bbox3d:
+ *     logp[k] = (row[t] - max row) - log sum exp(row - max row)
+ * with `row` the fp32 logit row the sampler of that decode step read (fixed summation order: the bits depend on the row and the token only,
+ * not on B) and t
+ *   - the token the step settled on BEFORE the rule constraint: the main draw, or the control / pad-avoid resample where the step took one
+ *     (drawn from the TAR head, scored under the AR row like everything else);
+ *   - under teacher forcing (umgen_trace::forced_*) the forced token: a forced frame is a step-by-step umgen_score;
+ *   - for the pose, the ego sampler's token on its head_ego row.
+ * NaN where no head was evaluated: the pose when ctrl_pose is given, every given map / bbox3d position (one-pass prefix or replayed steps).
+ * bos / eos carry nothing; history frames are not part of the output.
+ * Rule constraint: a slot the constraint blanks returns pad tokens, but its 11 entries keep the log-probabilities of the tokens that were
+ * DRAWN -- those are what the KV cache holds, what every later step of the frame was conditioned on, and the density of the sampled path.
+ * Consequence: these values and umgen_score of the RETURNED frame agree only for frames without a blanked slot (scoring conditions on the
+ * pads).  Without a blanked slot they agree the way the decode steps agree with the one-pass arithmetic (see umgen_score below). */
+typedef struct umgen_logp_out {
+    float *logp_pose, *logp_map, *logp_bbox3d, *logp_image; /* rollout: [B][new_frames][S_mod]; frame: [S_mod]; any may be NULL */
+} umgen_logp_out;
+int umgen_rollout_logp(umgen_engine *e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames,
+                       const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                       int32_t T_ctl, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                       const int64_t *given_map, const int64_t *given_bbox3d,
+                       const umgen_sampling *sampling,
+                       int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp);
+int umgen_frame_logp(umgen_engine *e, int32_t T, const int64_t *pose, const int64_t *map, const int64_t *bbox3d,
+                     const int64_t *image, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                     const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
+                     int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp);
+
 /* Per-token log-likelihoods of a GIVEN next frame: the reference's teacher-forced loss terms (get_targets, d_loss, F.cross_entropy per modality,
  * UMGen.py:539-582) as one forward pass.  For B scenes with history windows pose/map/bbox3d/image [B][T][S_mod] and their next frames next_* [B][S_mod]:
  *     logp_m[b][k]   = log_softmax(logits_m[k])[next_m[b][k]]   (natural log)

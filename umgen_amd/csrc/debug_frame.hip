@@ -50,6 +50,7 @@ EmbedTables tables_in(Scratch& s, const umgen_dbg_tables& t) {
     tb.grid_posi = s.in(t.grid_posi, (size_t)kNMap * E * 2);
     return tb;
 }
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp);
 }  // namespace
 
 extern "C" {
@@ -192,7 +193,16 @@ int umgen_dbg_prefix_kv_to_cache(int prec, const void* qk, const void* vt, int B
 // (logits [j1 - j0][B][ld_logits]).  logits_tar [B][660][n_box], prev_box [B][660], control_slot [B][60], forced [B][2199] (or NULL), seeds [B].
 // In / out: tokens [B][2199], counters [8], n_boxes [B], boxes [B][64][10].  Out: x_next [j1 - j0][B][E] (NaN before every step) and
 // state_log [j1 - j0][3] = OarState step, epoch, done behind every step.
-int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
+int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) { return token_steps(t, a, nullptr); }
+// The same with OarState::want_logp = 1 and SampleArgs::logp = logp [B][2199] (in / out: the sampled steps write their position, nothing else changes)
+int umgen_dbg_token_steps_logp(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp) {
+    return logp ? token_steps(t, a, logp) : UMGEN_E_INVALID;
+}
+
+}  // extern "C"
+
+namespace {
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp) {
     if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
     // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
     if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
@@ -220,7 +230,7 @@ int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
     const size_t bn = (size_t)B * 64 * 10, xn = (size_t)B * E;
     OarState s0{};
     s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
-    s0.epoch = a->epoch0; s0.sp = a->sp;
+    s0.epoch = a->epoch0; s0.sp = a->sp; s0.want_logp = logp ? 1 : 0;
     Scratch s;
     SampleArgs sa{};
     sa.tb = tables_in(s, *t);
@@ -232,6 +242,7 @@ int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
     if (a->use_forced) sa.forced = s.in(a->forced, tn * 4); else sa.forced = s.raw(tn * 4);   // never read without use_forced
     sa.x_next = s.out(xn * 4); sa.tokens = s.inout(a->tokens, tn * 4); sa.counters = s.inout(a->counters, 8 * 4);
     sa.n_boxes = s.inout(a->n_boxes, (size_t)B * 4); sa.boxes = s.inout(a->boxes, bn * 8);
+    if (logp) sa.logp = s.inout(logp, tn * 4);
     if (s.rc) return s.rc;
     for (int i = 0; i < n; ++i) {
         const int j = a->j0 + i, mod = kind_of_pos(j, a->given_end);
@@ -251,29 +262,42 @@ int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
     }
     if (!s.intact()) return UMGEN_E_STATE;
     if (down(a->tokens, sa.tokens, tn * 4) || down(a->counters, sa.counters, 8 * 4) || down(a->n_boxes, sa.n_boxes, (size_t)B * 4)) return UMGEN_E_HIP;
+    if (logp && down(logp, sa.logp, tn * 4)) return UMGEN_E_HIP;
     return down(a->boxes, sa.boxes, bn * 8);
 }
+}  // namespace
+
+extern "C" {
 
 // launch_sample_ego: logits [3 B][V] -> out_tokens [B][3]; the draw of row (b, jq) is rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN); forced
-// [B][2199] (or NULL) overrides with its pose tokens
-int umgen_dbg_sample_ego(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
-                         int32_t* out_tokens) {
+// [B][2199] (or NULL) overrides with its pose tokens.  logp [B][2199] (in / out, or NULL): entry [b][jq] receives the log-likelihood of pose token jq
+// of scene b on its row
+int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                              int32_t* out_tokens, float* logp) {
     if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
         return UMGEN_E_INVALID;
+    for (int b = 0; logp && forced && b < B; ++b)      // the scored token indexes the row
+        if (!in_range(forced + (size_t)b * kTokPerFrame, kNPose, V)) return UMGEN_E_INVALID;
     const size_t ln = (size_t)B * 3 * V, tn = (size_t)B * kTokPerFrame, osz = (size_t)B * 3 * 4;
     Scratch s;
     const float* dL = s.in(logits, ln * 4);
     const unsigned long long* dS = s.in(seeds, (size_t)B * 8);
     const int* dF = s.in(forced, tn * 4);
     int *dOv = s.raw(4), *dT = s.out(osz);
+    float* dLp = logp ? (float*)s.inout(logp, tn * 4) : nullptr;
     if (s.rc) return s.rc;
     if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
-    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv);
+    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, dLp);
     if (int rc = finish()) return rc;
     int ovf = 0;
     if (down(&ovf, dOv, 4)) return UMGEN_E_HIP;
     if (!s.intact() || ovf != 0) return UMGEN_E_STATE;      // (the overflow word is unused since the exhaustive tie walk: it must stay 0)
+    if (logp && down(logp, dLp, tn * 4)) return UMGEN_E_HIP;
     return down(out_tokens, dT, osz);
+}
+int umgen_dbg_sample_ego(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                         int32_t* out_tokens) {
+    return umgen_dbg_sample_ego_logp(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, nullptr);
 }
 
 }  // extern "C"

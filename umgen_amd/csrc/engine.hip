@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame, umgen_score and the rollout driver umgen_rollout (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
+// umgen_frame(_logp), umgen_score and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
 #include "engine_state.h"
 
@@ -61,9 +61,12 @@ static int check_scene_tokens(umgen_engine* e, size_t frames, const int64_t* pos
     return 0;
 }
 
-int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
-                const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
-                int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image) {
+static bool wants_logp(const umgen_logp_out* lp) { return lp && (lp->logp_pose || lp->logp_map || lp->logp_bbox3d || lp->logp_image); }
+
+int umgen_frame_logp(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                     const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
+                     int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                     const umgen_logp_out* lp) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
@@ -106,12 +109,27 @@ int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* 
             io.given_box = gb.data();
         }
     }
+    std::vector<float> flp(wants_logp(lp) ? (size_t)kTokPerFrame : 0);
+    if (!flp.empty()) io.out_logp = flp.data();
     if (int rc = run_frame_any(e, io)) return rc;
     for (int i = 0; i < kNPose; ++i) out_pose[i] = out[i];
     for (int i = 0; i < kNMap; ++i) out_map[i] = out[kOffMap + i];
     for (int i = 0; i < kNBox; ++i) out_bbox3d[i] = out[kOffBox + i];
     for (int i = 0; i < kNImg; ++i) out_image[i] = out[kOffImg + i];
+    if (!flp.empty()) {
+        if (lp->logp_pose) memcpy(lp->logp_pose, &flp[0], kNPose * sizeof(float));
+        if (lp->logp_map) memcpy(lp->logp_map, &flp[kOffMap], kNMap * sizeof(float));
+        if (lp->logp_bbox3d) memcpy(lp->logp_bbox3d, &flp[kOffBox], kNBox * sizeof(float));
+        if (lp->logp_image) memcpy(lp->logp_image, &flp[kOffImg], kNImg * sizeof(float));
+    }
     return UMGEN_OK;
+}
+
+int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
+                int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image) {
+    return umgen_frame_logp(e, T, pose, map, bbox3d, image, ctrl_pose, ctrl_bbox3d, control_test, sampling, frame_idx, trace, out_pose, out_map,
+                            out_bbox3d, out_image, nullptr);
 }
 
 // log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes: engine_frame.hip run_score
@@ -153,10 +171,11 @@ int umgen_score(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, cons
 }
 
 // UMGen.inference (UMGen.py:1542-1671)
-int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
-                  const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
-                  const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
-                  const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image) {
+int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
+                       const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
+                       const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
+                       const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                       const umgen_logp_out* lp) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
@@ -203,6 +222,8 @@ int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, 
     bool have_given = (given_map != nullptr) && T_ctl > 0;   // like every init_tokens entry: None past its last frame (get_mod_tokens), and gone
                                                               // for good with the pose tokens (UMGen.py:1613-1619)
     std::vector<int> frame_out((size_t)B * kTokPerFrame);
+    std::vector<float> frame_logp(wants_logp(lp) ? (size_t)B * kTokPerFrame : 0);      // the frame's log-likelihoods, scattered to [B][new_frames][S_mod] below
+    float* const lp_out[4] = {lp ? lp->logp_pose : nullptr, lp ? lp->logp_map : nullptr, lp ? lp->logp_bbox3d : nullptr, lp ? lp->logp_image : nullptr};
     for (int idx = 0; idx < new_frames; ++idx) {
         if (T_cur > cond_frames) {   // sliding window (UMGen.py:1600-1603)
             for (int m = 0; m < 4; ++m) {
@@ -254,6 +275,7 @@ int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, 
         io.next_has_ctrl_pose = have_ctl && idx + 1 < T_ctl;
         io.given_map = gm.empty() ? nullptr : gm.data();
         io.given_box = gb.empty() ? nullptr : gb.data();
+        io.out_logp = frame_logp.empty() ? nullptr : frame_logp.data();
         if (int rc = run_frame_any(e, io)) return rc;
         // append (UMGen.py:1636-1666): control pose tokens are copied verbatim; everything else is what was generated
         const int off[4] = {0, kOffMap, kOffBox, kOffImg};
@@ -268,10 +290,21 @@ int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, 
                 }
             }
             hist[m].swap(nw);
+            if (lp_out[m] && !frame_logp.empty())
+                for (int b = 0; b < B; ++b)
+                    memcpy(lp_out[m] + ((size_t)b * new_frames + idx) * S[m], &frame_logp[(size_t)b * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(float));
         }
         T_cur += 1;
     }
     return UMGEN_OK;
+}
+
+int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
+                  const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
+                  const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
+                  const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image) {
+    return umgen_rollout_logp(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map,
+                              given_bbox3d, sampling, out_pose, out_map, out_bbox3d, out_image, nullptr);
 }
 
 }  // extern "C"

@@ -109,6 +109,8 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     }
     HIPCHK(e, hipMemsetAsync(e->d_counters, 0, 8 * sizeof(int), st));
     HIPCHK(e, hipMemsetAsync(e->d_nboxes, 0, (size_t)B * sizeof(int), st));
+    // log-likelihoods of the new frame: NaN (all bits set) wherever no head is evaluated -- a given pose, given map / bbox3d positions
+    if (io.out_logp) HIPCHK(e, hipMemsetAsync(e->d_logp, 0xFF, (size_t)B * kTokPerFrame * sizeof(float), st));
     return 0;
 }
 
@@ -129,7 +131,7 @@ int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if (io.ctrl_pose) {
         for (int i = 0; i < B * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode);
+        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, io.out_logp ? e->d_logp : nullptr);
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }
@@ -181,7 +183,7 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipMemset(e->eng_gloc, 0, e->eng_gloc_bytes));
         e->eng_epoch = 16u;
     }
-    ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp};
+    ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, io.out_logp ? 1 : 0};
     e->eng_epoch += (unsigned)(kImgEos + 1) * kEpochPerStep;
     HIPCHK(e, hipMemcpyAsync(e->d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     ctx.n_lanes = (sizeof(T) == 2 && !tr) ? e->lane_count(B) : 1;      // decode lanes: every lane steps its own copy of the state
@@ -470,6 +472,7 @@ int drain_and_download(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     }
     HIPCHK(e, hipEventRecord(e->ev[3], st));
     HIPCHK(e, hipMemcpyAsync(io.out_tokens, e->d_tokens, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+    if (io.out_logp) HIPCHK(e, hipMemcpyAsync(io.out_logp, e->d_logp, (size_t)B * kTokPerFrame * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(ctx.counters, e->d_counters, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (eng) HIPCHK(e, hipMemcpyAsync(&ctx.eng_err, wide ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));

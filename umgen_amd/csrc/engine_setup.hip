@@ -473,6 +473,7 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dalloc(e, &e->d_boxes, Bm * 64 * 10)) return rc;
     if (int rc = dalloc(e, &e->d_seeds, Bm)) return rc;
     if (int rc = dalloc(e, &e->d_state, (size_t)1)) return rc;
+    if (int rc = dalloc(e, &e->d_logp, Bm * kTokPerFrame)) return rc;
     return 0;
 }
 

@@ -191,7 +191,7 @@ void gemv_resid(umgen_engine* e, const float* a_in, long lda, const float* part,
 // (UMGen.py:1002), so the 12 decoder blocks run on the last frame only -- identical outputs, 1/T of the work.
 template <typename T>
 void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits,
-             int cache_mode = 0) {
+             int cache_mode = 0, float* logp = nullptr) {
     const int E = e->E, H = e->H, B = w.B, Tn = w.T;   // Tn: slots in this pass (the last one is the window's last frame)
     run_stack<T>(e, STACK_EGO, w, cache_mode);
     // p = ln_ego_tar(x) of the last frame, kept in fp32 (every decoder block re-normalises it with its own ln_3)
@@ -221,7 +221,7 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
     gemv<T>(e, x, E, e->ln_ego, e->head_ego, nullptr, e->cfg.pose_vocab, E, M, GEMV_OUT_F32, e->logits, e->cfg.pose_vocab);
     if (trace_logits) hipMemcpyAsync(trace_logits, e->logits, (size_t)3 * e->cfg.pose_vocab * 4, hipMemcpyDeviceToHost, e->stream);
     launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, forced ? e->d_forced : nullptr, e->d_ego_tok, B,
-                      e->d_counters + 7);
+                      e->d_counters + 7, logp);
 }
 
 // The GIVEN-token prefix of a frame as ONE forward pass (infer_oar_net's first iteration pushes the whole predefined prefix through the 36
@@ -384,9 +384,11 @@ void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_
     e->cfg.precision == UMGEN_PREC_BF16 ? run_stack<bf16_t>(e, stack, w, cache_mode)
     : e->cfg.precision == UMGEN_PREC_FP16 ? run_stack<f16_t>(e, stack, w, cache_mode) : run_stack<float>(e, stack, w, cache_mode);
 }
-void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? run_ego<bf16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego<f16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode) : run_ego<float>(e, w, sp, frame_idx, forced, trace_logits, cache_mode);
+void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
+                 float* logp) {
+    e->cfg.precision == UMGEN_PREC_BF16 ? run_ego<bf16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego<f16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
+                                          : run_ego<float>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp);
 }
 int run_prefix_prefill_any(umgen_engine* e, int B, int P) {
     return e->cfg.precision == UMGEN_PREC_BF16 ? run_prefix_prefill<bf16_t>(e, B, P)

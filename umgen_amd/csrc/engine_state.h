@@ -79,6 +79,7 @@ struct umgen_engine {
     double* d_boxes = nullptr;
     unsigned long long* d_seeds = nullptr;
     OarState* d_state = nullptr;
+    float* d_logp = nullptr;             // [max_batch][2199] log-likelihoods of the frame being generated (umgen_rollout_logp / umgen_frame_logp; SampleArgs::logp)
     // umgen_score (engine_frame.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
@@ -243,6 +244,7 @@ struct FrameIO {
     const umgen_sampling* smp;
     const umgen_trace* trace;                    // B == 1 only
     int* out_tokens;                             // host [B][2199]
+    float* out_logp = nullptr;                   // host [B][2199] or nullptr: log-likelihood of every content token of the new frame (NaN where no head ran)
     int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
     bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
     bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed
@@ -264,7 +266,8 @@ void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vect
 
 // ---- engine_stacks.hip: by-precision entry points of the templated compute path ------------------------------------
 void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode);
-void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode);
+void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
+                 float* logp = nullptr);
 int run_prefix_prefill_any(umgen_engine* e, int B, int P);
 int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego);
 void gemv_any(umgen_engine* e, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out, long ldo);
@@ -281,6 +284,7 @@ struct DecView {
     double* d_boxes;
     unsigned long long* d_seeds;
     OarState* d_state;
+    float* d_logp;
 };
 // ---- engine_decode.hip ----------------------------------------------------------------------------------------------
 DecView current_view(const umgen_engine* e);

@@ -53,6 +53,7 @@ struct OarState {
     int done;        // blocks of the step's last kernel that have finished (the last one advances `step`)
     unsigned epoch;  // base of the decode engine's hand-off tags for this step (advanced with `step`, oar_engine.hip)
     SamplerParams sp;
+    int want_logp;   // the call asked for per-token log-likelihoods: sample_token_kernel also writes SampleArgs::logp (last member: older initialisers leave it 0)
 };
 
 // everything the per-token sampler kernel touches
@@ -76,6 +77,7 @@ struct SampleArgs {
     const int* forced;         // [B][2199] teacher forcing (valid when st->use_forced)
     int* counters;             // [8] per-frame event counters (pad_avoid, control, rule_checked, rule_collision, rule_blanked, sampled != forced,
                                //     -, 7: unused since round 5 -- more than 64 ties at the k-th logit are sampled by an exhaustive walk, frame.hip)
+    float* logp;               // [B][2199] or nullptr: log softmax(AR row over [0, vocab))[token the step settled on], written when st->want_logp
 };
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);
@@ -100,8 +102,9 @@ void launch_sample_rows(hipStream_t s, const float* logits, int V, int k, float 
 void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerParams& sp, int k, float p, const float* u, int mask_idx, int* out,
                        int* overflow, int n);
 void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts, int max_n, int* out, int n_sets);
+// logp: nullptr, or [B][2199] -- entry [b][jq] receives log softmax(head_ego row)[pose token jq of scene b]
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow);
+                       const int* forced, int* out_tokens, int B, int* overflow, float* logp = nullptr);
 // ego query rows: egoe[j] + spe[j] + tpe[T-1]
 void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x);
 

@@ -543,13 +543,46 @@ template void launch_prefix_kv_to_cache<float>(hipStream_t, const float*, const 
 template void launch_prefix_kv_to_cache<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, int, int, int, int, int, bf16_t*, long);
 template void launch_prefix_kv_to_cache<f16_t>(hipStream_t, const f16_t*, const f16_t*, int, int, int, int, int, f16_t*, long);
 
+// log softmax(row[0 .. V))[tok] at temperature 1 -- the measure of umgen_score -- for the 256-thread block of the samplers (all threads call, all
+// get the value; one call per kernel: the reduction words are not fenced behind it).  Columns >= V are never read (the rows are ld_logits
+// apart and stale past the head's vocabulary).  Maximum first, then the sum of exp_det(x - max) in a FIXED order -- a thread's columns
+// tid, tid + 256, ... ascending, the lanes of a wave by wave_sum's DPP schedule, waves 0..3 -- with separately rounded operations, so the
+// bits of the result are a function of the row and the token alone: not of the batch size, the scene's block or its launch neighbours.
+// V <= 8192 like the samplers.
+__device__ float block_logp(const float* __restrict__ row, int V, int tok) {
+    __shared__ float red[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float v[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int idx = tid + 256 * i;
+        v[i] = idx < V ? row[idx] : -INFINITY;
+    }
+    float mx = v[0];
+#pragma unroll
+    for (int i = 1; i < 32; ++i) mx = fmaxf(mx, v[i]);
+    mx = wave_max(mx);
+    if (lane == 0) red[0][wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+        if (tid + 256 * i < V) s = add_rn(s, exp_det(sub_rn(v[i], mx)));
+    s = wave_sum(s);
+    if (lane == 0) red[1][wave] = s;
+    __syncthreads();
+    const float total = add_rn(add_rn(add_rn(red[1][0], red[1][1]), red[1][2]), red[1][3]);
+    return sub_rn(sub_rn(row[tok], mx), logf(total));
+}
+
 __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     __shared__ SamplerLds sh;
     __shared__ float cor[64][8];
     __shared__ int s_tok;
     const int b = blockIdx.x, j = a.st->step, frame = a.st->frame_idx, E = a.tb.E;
     const SamplerParams sp = a.st->sp;
-    const bool use_forced = a.st->use_forced != 0, use_control = a.st->use_control != 0;
+    const bool use_forced = a.st->use_forced != 0, use_control = a.st->use_control != 0, want_logp = a.st->want_logp != 0;
     const int pos1 = j + 1;   // the reference's 1-based curr_seq_len
     const unsigned long long seed = a.seeds[b];
     const CondRow crow = load_cond_row(a, b, j);
@@ -563,9 +596,10 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     else if (a.mod == 2) { off = kOffBox; k = j - kBoxC0; }
     else { off = kOffImg; k = j - kImgC0; }
     int* toks = a.tokens + (long)b * kTokPerFrame;
+    int prev = kBoxPad;
     if (a.mod == 2) {
         const float* lt = a.logits_tar + ((long)b * kNBox + k) * a.ld_tar;
-        const int prev = a.prev_box[(long)b * kNBox + k];
+        prev = a.prev_box[(long)b * kNBox + k];
         if (use_control) {   // UMGen.py:1083-1089
             const int object_id = (pos1 - 1032) / kSlotLen;
             if (object_id < kSlots && a.control_slot[b * kSlots + object_id]) {
@@ -577,6 +611,15 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
             tok = block_sample(sp, lt, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_PAD_AVOID), -1, sh, a.counters + 7);
             if (threadIdx.x == 0) atomicAdd(a.counters + 0, 1);
         }
+    }
+    // The token is settled (main draw, control or pad-avoid resample; the forced token under teacher forcing): its log-likelihood under the
+    // plain AR row -- also where the token came from the TAR head -- before the rule constraint may blank the slot: the drawn tokens are what
+    // the KV cache holds and what the sampled path's density is made of.  Block-uniform, off unless the call asked (OarState::want_logp).
+    if (want_logp) {
+        const float lp = block_logp(lg, a.vocab, use_forced ? a.forced[(long)b * kTokPerFrame + off + k] : tok);
+        if (threadIdx.x == 0) a.logp[(long)b * kTokPerFrame + off + k] = lp;
+    }
+    if (a.mod == 2) {
         if (sp.rule_constrain && !use_forced && tok != kBoxPad && (pos1 - 1032) % kSlotLen == 0) {   // UMGen.py:1116-1123
             if (threadIdx.x == 0) {
                 double* boxes = a.boxes + (long)b * 64 * 10;
@@ -626,17 +669,22 @@ void launch_sample_token(hipStream_t s, const SampleArgs& a, int B) { hipLaunchK
 
 __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict__ logits, int vocab, SamplerParams sp,
                                                          const unsigned long long* __restrict__ seeds, int frame_idx,
-                                                         const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow) {
+                                                         const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow,
+                                                         float* __restrict__ logp) {
     __shared__ SamplerLds sh;
     const int b = blockIdx.x / 3, jq = blockIdx.x % 3;
     int tok = block_sample(sp, logits + (long)blockIdx.x * vocab, vocab, sp.top_k, sp.p,
                            rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN), -1, sh, overflow);
     if (forced) tok = forced[(long)b * kTokPerFrame + jq];
     if (threadIdx.x == 0) out_tokens[b * 3 + jq] = tok;
+    if (logp) {
+        const float lp = block_logp(logits + (long)blockIdx.x * vocab, vocab, tok);
+        if (threadIdx.x == 0) logp[(long)b * kTokPerFrame + jq] = lp;
+    }
 }
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow) {
-    hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow);
+                       const int* forced, int* out_tokens, int B, int* overflow, float* logp) {
+    hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow, logp);
 }
 
 // test hook (debug_gemm_attn.hip): the top-k sampler on n independent logit rows with given uniforms

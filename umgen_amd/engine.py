@@ -108,11 +108,22 @@ class Engine:
             seeds=s.ctypes.data_as(C.POINTER(C.c_uint64)))
         return smp, s
 
+    @staticmethod
+    def _logp_out(lead: Tuple[int, ...]):
+        """(mod -> float32 [*lead, S_mod] filled with NaN, the umgen_logp_out that points at them)"""
+        logp = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
+        return logp, _lib.LogpOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
+
     def rollout(self, tokens: Dict[str, np.ndarray], new_frames: int, cond_frames: int = 20,
                 input_cond_frames: int = -1, init_tokens: Optional[Dict[str, np.ndarray]] = None,
                 control_test: bool = False, seeds: Optional[Sequence[int]] = None,
-                sampling: Optional[RolloutConfig] = None) -> Dict[str, np.ndarray]:
-        """tokens: mod -> int64 [B, T, S_mod].  Returns mod -> int64 [B, input_cond_frames + new_frames, S_mod]."""
+                sampling: Optional[RolloutConfig] = None, return_logp: bool = False):
+        """tokens: mod -> int64 [B, T, S_mod].  Returns mod -> int64 [B, input_cond_frames + new_frames, S_mod].
+        return_logp: returns (tokens, mod -> float32 [B, new_frames, S_mod]) -- the log-likelihood of every generated token under the plain AR
+        heads at temperature 1 (umgen_rollout_logp, include/umgen.h: Engine.score's measure, taken from the decode steps that sampled the
+        token); NaN where no head ran (a controlled pose, given map / bbox3d tokens).  The tokens are the same either way."""
+        if new_frames < 0:
+            raise UMGenError(f"new_frames={new_frames}")
         if input_cond_frames == -1:
             input_cond_frames = cond_frames
         arrs = {m: _i64(tokens[m])[:, :input_cond_frames] for m in MOD_ORDER}
@@ -154,18 +165,26 @@ class Engine:
             elif cb.shape != (B, T_ctl, CONTENT_LEN["bbox3d"]):
                 raise UMGenError(f"init_tokens['bbox3d'] has shape {cb.shape}, expected {(B, T_ctl, CONTENT_LEN['bbox3d'])}")
         smp, keep = self._sampling(sampling or self.cfg, seeds if seeds is not None else [0] * B)
-        self._check(self.lib.umgen_rollout(
-            self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
-            _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
-            _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"])), "rollout")
+        args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
+                _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
+                _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
+        if not return_logp:
+            self._check(self.lib.umgen_rollout(*args), "rollout")
+            del keep
+            return outs
+        logp, lp = self._logp_out((B, new_frames))
+        self._check(self.lib.umgen_rollout_logp(*args, C.byref(lp)), "rollout")
         del keep
-        return outs
+        return outs, logp
 
     def frame(self, window: Dict[str, np.ndarray], frame_idx: int = 0, ctrl: Optional[Dict[str, np.ndarray]] = None,
               control_test: bool = False, seed: int = 0, sampling: Optional[RolloutConfig] = None,
-              forced: Optional[Dict[str, np.ndarray]] = None, trace: bool = False, given: Optional[Dict[str, np.ndarray]] = None):
+              forced: Optional[Dict[str, np.ndarray]] = None, trace: bool = False, given: Optional[Dict[str, np.ndarray]] = None,
+              logp: bool = False):
         """One frame of one scene.  window: mod -> [T, S_mod].  Returns (tokens dict, trace dict or None).
-        given: {"map": [1024]} or {"map": ..., "bbox3d": [660]}: the frame's GIVEN tokens (init_tokens of `rollout` for one frame)."""
+        given: {"map": [1024]} or {"map": ..., "bbox3d": [660]}: the frame's GIVEN tokens (init_tokens of `rollout` for one frame).
+        logp: the trace dict (created if need be) gains "logp": mod -> float32 [S_mod], `rollout(return_logp=True)` for this frame; under
+        `forced` the values are those of the forced tokens: a step-by-step `score`."""
         cfg = self.cfg
         w = {m: _i64(window[m]) for m in MOD_ORDER}
         T = w["pose"].shape[0]
@@ -198,15 +217,23 @@ class Engine:
                 fz = {m: _i64(forced[m]).reshape(-1) for m in MOD_ORDER}
                 tr.forced_pose, tr.forced_map = _p64(fz["pose"]), _p64(fz["map"])
                 tr.forced_bbox3d, tr.forced_image = _p64(fz["bbox3d"]), _p64(fz["image"])
-        self._check(self.lib.umgen_frame(
-            self._h, T, _p64(w["pose"]), _p64(w["map"]), _p64(w["bbox3d"]), _p64(w["image"]), _p64(cp), _p64(cb),
-            int(control_test), C.byref(smp), frame_idx, C.byref(tr) if tr is not None else None,
-            _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"])), "frame")
+        args = (self._h, T, _p64(w["pose"]), _p64(w["map"]), _p64(w["bbox3d"]), _p64(w["image"]), _p64(cp), _p64(cb),
+                int(control_test), C.byref(smp), frame_idx, C.byref(tr) if tr is not None else None,
+                _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
+        lpv = None
+        if logp:
+            lpv, lp = self._logp_out(())
+            self._check(self.lib.umgen_frame_logp(*args, C.byref(lp)), "frame")
+        else:
+            self._check(self.lib.umgen_frame(*args), "frame")
         del keep, fz, gz
         if tr is not None:
             tbuf = tbuf if tbuf is not None else {}
             tbuf["counters"] = dict(zip(("pad_avoid", "control_resample", "rule_checked", "rule_collision", "rule_blanked",
                                          "sampled_ne_forced"), counters[:6].tolist()))
+        if lpv is not None:
+            tbuf = tbuf if tbuf is not None else {}
+            tbuf["logp"] = lpv
         return outs, tbuf
 
     def _score_args(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray]):

@@ -137,8 +137,10 @@ class UMGen(nn.Module):
     def inference(self, new_frames: int, cond_frames: int = 1, input_cond_frames: int = -1, pred_task: str = "image",
                   input_cond_tokens: Optional[Dict[str, torch.Tensor]] = None,
                   init_tokens: Optional[Dict[str, torch.Tensor]] = None, cond_on_tar: bool = False,
-                  test_map_affine: bool = False, max_objects=100, control_test=False, **kwargs) -> Dict[str, np.ndarray]:
-        """UMGen.inference (UMGen.py:1542-1671).  ``cond_on_par`` / ``infer_from_gt`` are swallowed like the reference."""
+                  test_map_affine: bool = False, max_objects=100, control_test=False, return_logp: bool = False, **kwargs):
+        """UMGen.inference (UMGen.py:1542-1671).  ``cond_on_par`` / ``infer_from_gt`` are swallowed like the reference.
+        return_logp (extension): returns (tokens, mod -> torch.float32 [B, new_frames, S_mod]), the log-likelihood of every generated token
+        (Engine.rollout's return_logp; NaN on controlled / given positions), beside the tokens it returns today."""
         if pred_task != "pose_map_bbox3d_image":
             raise UMGenError(f"pred_task={pred_task!r}: only 'pose_map_bbox3d_image' (the evaluation task) is implemented")
         if not self._loaded:
@@ -154,8 +156,11 @@ class UMGen(nn.Module):
         if B > self._engine_args["max_batch"]:      # extension over the reference (B = 1): several scenes per call
             self._recreate(max_batch=B)
         seeds = kwargs.get("seeds", [self.seed + i for i in range(B)])
-        return self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames,
-                                   init_tokens=init, control_test=bool(control_test), seeds=seeds)
+        out = self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames,
+                                  init_tokens=init, control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp))
+        if not return_logp:
+            return out
+        return out[0], {m: torch.from_numpy(v) for m, v in out[1].items()}
 
     @staticmethod
     def _score_window(cond: Dict[str, np.ndarray], tgt: Dict[str, np.ndarray], input_cond_frames: int, t: Optional[int], cap: int):
