@@ -1,7 +1,7 @@
 // Kernel-level test hooks of libumgen_hip.so (host pointers in, host pointers out) for the GEMMs, the stack attentions, the few-row GEMV and the
 // top-k sampler, and the timing hooks of tools/.  Used only by tests/ and tools/ to pin each HIP kernel against the CPU oracle at production
-// width; never called by the product path.  The hooks of this file give their outputs neither guard bands nor NaN fills (umgen_dbg_attn_spatial
-// excepted); those of debug_decode.hip and debug_frame.hip do.
+// width; never called by the product path.  Like those of debug_decode.hip and debug_frame.hip, the hooks of this file put a guard band behind every
+// output and start it as NaN (in / out buffers as the caller's values); the timing hooks, which return no output, do neither.
 #include "debug_util.h"
 
 namespace {
@@ -19,6 +19,7 @@ GemmArgs vt_args(const void* dA, const void* dW, int F, int S, int S_pad, int N,
     return g;
 }
 inline int pad64(int S) { return ((S + 63) / 64) * 64; }
+constexpr int kTemporalSlots = 32;   // attn.hip's kTmax: the temporal kernels take up to twice as many slots (their 64-slot variants)
 // random bf16 operands of the GEMM timing hooks: act [na] in [-1, 1), then W [nw] in [-0.05, 0.05), one sequence
 void lcg_operands(Scratch& s, size_t na, size_t nw, DevPtr& dA, DevPtr& dW) {
     std::vector<bf16_t> h;
@@ -40,14 +41,16 @@ int umgen_dbg_linear(int flags, const void* act, const void* W, const float* bia
     Scratch s;
     const void *dA = s.in(act, (size_t)R * K * es), *dW = s.in(W, (size_t)N * K * es);
     const float* dB = s.in(bias, (size_t)N * 4);
-    void* dO = resid ? s.in(out, osz) : s.raw((size_t)R * N * 4);
+    void* dO = resid ? s.inout(out, osz) : s.out(osz);
     if (s.rc) return s.rc;
+    if (!resid)
+        if (int rc = fill_nan(dO, (size_t)R * N, bf16)) return rc;   // a tile the kernel leaves out comes back as NaN
     GemmArgs g = linear_args(dW, dA, R, N, K, dO);
     g.mode = resid ? GEMM_RESID : GEMM_STORE; g.bias = dB; g.gelu = gelu;
     g.tile256 = (flags & 16) ? 1 : ((flags & 32) ? -1 : 0);
     if (bf16) by_prec16(bf16, [&](auto t) { launch_gemm_mfma<decltype(t)>(nullptr, g); });
     else launch_gemm_valu<float, float>(nullptr, g);
-    if (int rc = finish()) return rc;
+    if (int rc = s.finish()) return rc;
     return down(out, dO, osz);
 }
 
@@ -61,15 +64,57 @@ int umgen_dbg_linear_vt(int flags, const void* act, const void* W, const float* 
     Scratch s;
     const void *dA = s.in(act, R * K * 2), *dW = s.in(W, (size_t)N * K * 2);
     const float* dB = s.in(bias, (size_t)N * 4);
-    void* dO = s.raw(osz);
+    std::vector<unsigned short> h0((size_t)F * N * S_pad, nan16(prec));   // columns < S start as NaN, the pad columns as the zeros they must stay
+    for (size_t r = 0; r < (size_t)F * N; ++r) std::fill(h0.begin() + r * S_pad + S, h0.begin() + (r + 1) * S_pad, (unsigned short)0);
+    void* dO = s.inout(h0.data(), osz);
     if (s.rc) return s.rc;
-    (void)hipMemset(dO, 0, osz);
     GemmArgs g = vt_args(dA, dW, F, S, S_pad, N, K, dO);
     g.bias = dB;
     g.tile256 = (flags & 16) ? 1 : ((flags & 32) ? -1 : 0);
     by_prec16(prec, [&](auto t) { launch_gemm_mfma<decltype(t)>(nullptr, g); });
-    if (int rc = finish()) return rc;
+    if (int rc = s.finish()) return rc;
     return down(out, dO, osz);
+}
+
+// One GEMM launch in the full GemmArgs geometry (kernels.h), for the forms the stacks launch and umgen_dbg_linear cannot express: a strided,
+// column-offset output, batches with operand and output strides, weights and activations of different types.  precP / precQ: precision codes
+// of P and Q (fp32 x fp32, 16-bit x fp32, or the same 16-bit type twice); mfma != 0 (two 16-bit operands): launch_gemm_mfma, else
+// launch_gemm_valu.  P [nP], Q [nQ] elements; bias [Mi] ([Nj] for GEMM_VT), nullable.  `out` is the caller's WHOLE buffer of out_n elements
+// (the operand type of the activations for GEMM_STORE / GEMM_VT, fp32 otherwise), uploaded as it is (NaN bits, residual values) and
+// downloaded whole; the GEMM's out pointer is element out_off of it.  Every address the geometry reaches is checked here first.
+int umgen_dbg_gemm(int precP, int precQ, int mfma, const void* P, long nP, const void* Q, long nQ, const float* bias, int Mi, int Nj, int K,
+                   long ldp, long ldq, long strideP, long strideQ, int batch, int mode, int gelu, long ldo, long strideO, int H, int tile256,
+                   void* out, long out_off, long out_n) {
+    const bool pair_ok = (precQ == 0 && precP >= 0 && precP <= 2) || (precP == precQ && (precP == 1 || precP == 2));
+    if (!pair_ok || !P || !Q || !out || Mi < 1 || Nj < 1 || K < 1 || batch < 1 || mode < GEMM_STORE || mode > GEMM_VT) return UMGEN_E_INVALID;
+    if (ldp < K || ldq < K || strideP < 0 || strideQ < 0 || strideO < 0 || out_off < 0) return UMGEN_E_INVALID;
+    const bool use_mfma = mfma && precP == precQ && precP != 0;
+    if (mfma && !use_mfma) return UMGEN_E_INVALID;
+    if (use_mfma && K % 8 != 0) return UMGEN_E_INVALID;                             // the matrix-core kernels load K in 16-byte pieces
+    if ((batch - 1) * strideP + (long)(Mi - 1) * ldp + K > nP || (batch - 1) * strideQ + (long)(Nj - 1) * ldq + K > nQ) return UMGEN_E_INVALID;
+    const int prec_o = mode == GEMM_STORE ? precQ : (mode == GEMM_VT ? precP : 0);   // output type: the activations' (Q; P for GEMM_VT), fp32 otherwise
+    const long al = prec_o ? 8 : 4;                                                 // 16-byte stores
+    if (ldo % al != 0 || strideO % al != 0 || out_off % al != 0 || ldo < Mi) return UMGEN_E_INVALID;
+    if (mode == GEMM_VT) {
+        if (H < 1 || Nj > H * kHeadDim || out_off + (long)batch * H * kHeadDim * ldo > out_n) return UMGEN_E_INVALID;
+    } else if (Mi % 4 != 0 || (batch > 1 && strideO < (long)(Nj - 1) * ldo + Mi) || out_off + (batch - 1) * strideO + (long)(Nj - 1) * ldo + Mi > out_n) {
+        return UMGEN_E_INVALID;
+    }
+    const size_t esP = precP ? 2 : 4, esQ = precQ ? 2 : 4, esO = prec_o ? 2 : 4;
+    Scratch s;
+    const void *dP = s.in(P, (size_t)nP * esP), *dQ = s.in(Q, (size_t)nQ * esQ);
+    const float* dB = s.in(bias, (size_t)(mode == GEMM_VT ? Nj : Mi) * 4);
+    unsigned char* dO = s.inout(out, (size_t)out_n * esO);
+    if (s.rc) return s.rc;
+    GemmArgs g{};
+    g.P = dP; g.Q = dQ; g.Mi = Mi; g.Nj = Nj; g.K = K; g.ldp = ldp; g.ldq = ldq; g.strideP = strideP; g.strideQ = strideQ; g.batch = batch;
+    g.mode = mode; g.bias = dB; g.gelu = gelu; g.out = dO + (size_t)out_off * esO; g.ldo = ldo; g.strideO = strideO; g.H = H; g.tile256 = tile256;
+    if (use_mfma) by_prec16(precP, [&](auto t) { launch_gemm_mfma<decltype(t)>(nullptr, g); });
+    else if (precP == 0) launch_gemm_valu<float, float>(nullptr, g);
+    else if (precQ == 0) by_prec16(precP, [&](auto t) { launch_gemm_valu<decltype(t), float>(nullptr, g); });
+    else by_prec16(precP, [&](auto t) { launch_gemm_valu<decltype(t), decltype(t)>(nullptr, g); });
+    if (int rc = s.finish()) return rc;
+    return down(out, dO, (size_t)out_n * esO);
 }
 
 // spatial attention on q|k rows [F*S][2E] and v rows [F*S][E] (both row-major on the host; V is transposed on the device
@@ -121,10 +166,11 @@ int umgen_dbg_attn_temporal(int bf16, const void* qkv, int B, int T, int S, int 
             memcpy(&hq[(size_t)b * Tn * S * row], (const unsigned char*)qkv + ((size_t)b * T + t0) * S * row, (size_t)Tn * S * row);
         Scratch s;
         const void* dQ = s.in(hq.data(), hq.size());
-        void* dY = s.raw(hy.size());
+        void* dY = s.out(hy.size());
         if (s.rc) return s.rc;
+        if (int rc = fill_nan(dY, Rn * E, bf16)) return rc;
         by_prec(bf16, [&](auto t) { typedef decltype(t) TT; launch_attn_temporal<TT>(nullptr, (const TT*)dQ, (TT*)dY, B, Tn, S, H, tr); });
-        if (int rc = finish()) return rc;
+        if (int rc = s.finish()) return rc;
         if (down(hy.data(), dY, hy.size())) return UMGEN_E_HIP;
         for (int b = 0; b < B; ++b)
             memcpy((unsigned char*)y + ((size_t)b * T + t0) * S * orow, &hy[(size_t)b * Tn * S * orow], (size_t)Tn * S * orow);
@@ -133,10 +179,37 @@ int umgen_dbg_attn_temporal(int bf16, const void* qkv, int B, int T, int S, int 
     if (split <= 0 || split >= T) return pass(0, T, TemporalRange{0, nullptr, 0, 0});
     const int Tcap = T + 1;
     Scratch s;
-    void* dC = s.raw((size_t)B * Tcap * S * 2 * E * es);
+    const size_t cn = (size_t)B * Tcap * S * 2 * E;
+    void* dC = s.out(cn * es);
     if (s.rc) return s.rc;
+    if (int rc = fill_nan(dC, cn, bf16)) return rc;               // a slot the second pass reads and the first did not write is NaN
     if (int rc = pass(0, split, TemporalRange{0, dC, Tcap, 1})) return rc;
-    return pass(split, T - split, TemporalRange{split, dC, Tcap, 0});
+    if (int rc = pass(split, T - split, TemporalRange{split, dC, Tcap, 0})) return rc;
+    return s.finish();
+}
+
+// ONE launch_attn_temporal call on an arbitrary slot range (TemporalRange, kernels.h): qkv [B][Tn][S][3E] holds the slots [t0, t0 + Tn), the
+// k | v rows of slots [0, t0) are read from cache [B][Tcap][S][2E], write != 0 appends the new slots' k | v rows to it, only query slots >= q0
+// are evaluated.  cache (nullable when t0 == 0 and write == 0) and y [B][Tn][S][E] are in / out: whatever the launch leaves alone keeps the
+// caller's fill.
+int umgen_dbg_attn_temporal_range(int prec, const void* qkv, int B, int Tn, int S, int H, int t0, int q0, int write, int Tcap, void* cache, void* y) {
+    if (prec < 0 || prec > 2 || !qkv || !y || B < 1 || Tn < 1 || S < 1 || H < 1 || t0 < 0 || q0 < 0 || q0 >= t0 + Tn || t0 + Tn > 2 * kTemporalSlots)
+        return UMGEN_E_INVALID;
+    if (cache ? Tcap < t0 + Tn : (t0 > 0 || write)) return UMGEN_E_INVALID;
+    const int E = H * kHeadDim;
+    const size_t es = prec ? 2 : 4, Rn = (size_t)B * Tn * S;
+    const size_t csz = cache ? (size_t)B * Tcap * S * 2 * E * es : 0;
+    Scratch s;
+    const void* dQ = s.in(qkv, Rn * 3 * E * es);
+    void* dY = s.inout(y, Rn * E * es);
+    void* dC = cache ? (void*)s.inout(cache, csz) : nullptr;
+    if (s.rc) return s.rc;
+    TemporalRange tr{t0, dC, Tcap, write};
+    tr.q0 = q0;
+    by_prec(prec, [&](auto t) { typedef decltype(t) TT; launch_attn_temporal<TT>(nullptr, (const TT*)dQ, (TT*)dY, B, Tn, S, H, tr); });
+    if (int rc = s.finish()) return rc;
+    if (cache && down(cache, dC, csz)) return UMGEN_E_HIP;
+    return down(y, dY, Rn * E * es);
 }
 
 // decode-style attention: q [NQ][E] fp32, kv [L][2E] (k | v) of dtype bf16/fp32 shared by all queries -> y [NQ][E] fp32
@@ -149,9 +222,11 @@ int umgen_dbg_attn_decode(int bf16, const float* q, const void* kv, int NQ, int 
     Scratch s;
     const float* dQ = s.in(q, (size_t)NQ * E * 4);
     const void *dKV = s.in(kv, (size_t)L * 2 * E * es), *dW = s.in(eye.data(), eye.size() * 4);
-    float *dP = s.raw((size_t)NQ * H * kAttnRec * 4), *dX = s.raw((size_t)NQ * E * 4);
+    const size_t psz = (size_t)NQ * H * kAttnRec;
+    const std::vector<float> x0((size_t)NQ * E, 0.f);            // the residual stream the projection adds into
+    float *dP = s.out(psz * 4), *dX = s.inout(x0.data(), x0.size() * 4);
     if (s.rc) return s.rc;
-    (void)hipMemset(dX, 0, (size_t)NQ * E * 4);
+    if (int rc = fill_stale(dP, psz)) return rc;
     by_prec(bf16, [&](auto t) {
         typedef decltype(t) T;
         launch_attn_partial<T>(nullptr, dQ, (const T*)dKV, 0, kHeadDim, 2L * E, E, NQ, NQ, H, nullptr, L, attn_nsplit(L), dP);
@@ -159,7 +234,7 @@ int umgen_dbg_attn_decode(int bf16, const float* q, const void* kv, int NQ, int 
     GemvResidArgs a{};
     a.part = dP; a.H = H; a.ns = attn_nsplit(L); a.W = dW; a.N = E; a.K = E; a.M = NQ; a.x = dX; a.ldx = E;
     launch_gemv_resid<float>(nullptr, a);
-    if (int rc = finish()) return rc;
+    if (int rc = s.finish()) return rc;
     return down(y, dX, (size_t)NQ * E * 4);
 }
 
@@ -201,15 +276,15 @@ int umgen_dbg_gemv(int bf16, const float* x, const float* ln_w, const void* W, c
     Scratch s;
     GemvArgs a{};
     a.x = s.in(x, (size_t)M * K * 4); a.ldx = K; a.ln_w = s.in(ln_w, (size_t)K * 4); a.W = s.in(W, (size_t)N * K * es); a.bias = s.in(bias, (size_t)N * 4);
-    a.N = N; a.K = K; a.M = M; a.out_mode = gelu ? GEMV_OUT_GELU : GEMV_OUT_F32; a.out = s.raw(osz); a.ldo = N; a.E = K;
+    a.N = N; a.K = K; a.M = M; a.out_mode = gelu ? GEMV_OUT_GELU : GEMV_OUT_F32; a.out = s.out(osz); a.ldo = N; a.E = K;
     if (s.rc) return s.rc;
     // the row-loop form, then (M > 1) the one-row-per-workgroup form the engine launches for several scenes: it must give the same bits
     for (int rpb = 0; rpb <= (M > 1 ? 1 : 0); ++rpb) {
         std::vector<float> got((size_t)M * N);
-        if (rpb) (void)hipMemset(a.out, 0, osz);
+        if (int rc = fill_nan(a.out, (size_t)M * N, 0)) return rc;
         a.rows_per_block = rpb;
         by_prec(bf16, [&](auto t) { launch_gemv<decltype(t)>(nullptr, a); });
-        if (int rc = finish()) return rc;
+        if (int rc = s.finish()) return rc;
         if (int rc = down(rpb ? got.data() : out, a.out, osz)) return rc;
         if (rpb && memcmp(got.data(), out, osz) != 0) return UMGEN_E_STATE;
     }
