@@ -1,5 +1,6 @@
 // One decode step: the BlockOAR layers on whichever path takes the step (batched layer, chip-wide engine, XCD-resident engine, five
-// launches per layer), the head and sampler behind them, a decode lane's view of the engine, and the one-step test hook.
+// launches per layer), the head and sampler behind them, a decode lane's view of the engine, and the test hooks on a live handle (one step, K/V cache
+// rows in and out, the tag epoch).
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -197,7 +198,8 @@ int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace*
 extern "C" {
 
 // Test hook: ONE decode step through the BlockOAR layers (no head, no sampler) on caller-provided inputs, either as the five-launch
-// layer form or through the decode engine.  The K/V rows of position L are appended to the cache, so a test drives L = 0, 1, 2, ...
+// layer form (use_engine 0), the XCD-resident engine (1) or the chip-wide engine (3).  The K/V rows of position L are appended to the cache: a
+// test drives L = 0, 1, 2, ... or sets the history with umgen_dbg_oar_cache.  A path that oar_layers would not take for this B is refused.
 int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in, float* x_out, int32_t use_engine, int32_t unmasked) {
     if (!e || !x_in || !x_out) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
@@ -205,6 +207,14 @@ int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in,
     if (B < 1 || B > e->cfg.max_batch || L < 0 || L >= e->Lmax) return e->fail(UMGEN_E_INVALID, "B=%d L=%d", B, L);
     if (use_engine != 0 && use_engine != 1 && use_engine != 3) return e->fail(UMGEN_E_INVALID, "use_engine %d (0: five launches per layer, 1: XCD-resident engine, 3: chip-wide engine)", use_engine);
     if (use_engine == 1 && !e->eng_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "decode engine not available on this engine");
+    if (use_engine == 3 && !e->wide_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "chip-wide decode engine not available on this engine");
+    // the step runs on the path that was asked for or not at all: oar_layers decides by B, and a test must not measure another path's arithmetic
+    hipStream_t const st = (unmasked && e->full_stream) ? e->full_stream : e->stream;
+    if (e->use_batched(B))
+        return e->fail(UMGEN_E_UNSUPPORTED, "%d scenes take the batched decode layer on this engine (UMGEN_DECODE_BATCHED), not %s", B,
+                       use_engine == 0 ? "five launches per layer" : "a decode engine");
+    if (use_engine == 3 && !e->use_wide(B)) return e->fail(UMGEN_E_UNSUPPORTED, "the chip-wide decode engine takes at most 4 scenes per call, not %d", B);
+    if (use_engine == 1 && !e->eng_for(st)) return e->fail(UMGEN_E_UNSUPPORTED, "the XCD-resident decode engine has no census for this stream");
     if (e->eng_epoch > 0xE0000000u) {   // same wrap rule as run_frame, for both engines' granule buffers
         HIPCHK(e, hipDeviceSynchronize());
         if (e->eng_enabled) {
@@ -217,12 +227,10 @@ int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in,
     const unsigned epoch = e->eng_epoch;   // tags never repeat across calls
     e->eng_epoch += kEpochPerStep;
     hipStream_t const keep = e->stream;
-    hipStream_t const st = (unmasked && e->full_stream) ? e->full_stream : e->stream;
     OarState s0{L, 0, 0, 0, 0, epoch, SamplerParams{}};
     HIPCHK(e, hipMemcpyAsync(e->d_state, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(e->xdec, x_in, (size_t)B * e->E * 4, hipMemcpyHostToDevice, st));
     const bool en = e->eng_enabled, wide_keep = e->wide_enabled;
-    if (use_engine == 3 && !e->wide_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "chip-wide decode engine not available on this engine");
     e->wide_enabled = wide_keep && use_engine == 3;
     e->eng_enabled = en && use_engine == 1;
     e->stream = st;
@@ -239,6 +247,31 @@ int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in,
         (void)hipMemset(use_engine == 3 ? e->wide_err : e->eng_err, 0, sizeof(unsigned));
         return e->fail(UMGEN_E_HIP, "decode engine gave up waiting for hand-off tag 0x%08x", eng_err);
     }
+    return UMGEN_OK;
+}
+
+// Test hook: rows [row0, row0 + n_rows) of every (K / V, head) of one (layer, scene) block of the decode K/V cache, device [layer][scene][2][H][Lmax][48],
+// to (upload 0) or from (upload 1) host [2][H][n_rows][48] in the cache type's bits.  16-bit engines only.
+int umgen_dbg_oar_cache(umgen_engine* e, int32_t layer, int32_t scene, int32_t row0, int32_t n_rows, void* host, int32_t upload) {
+    if (!e || !host) return UMGEN_E_INVALID;
+    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
+    if (e->cfg.precision == UMGEN_PREC_FP32) return e->fail(UMGEN_E_UNSUPPORTED, "16-bit engines only");
+    if (layer < 0 || layer >= (int)e->oar.size() || scene < 0 || scene >= e->cfg.max_batch || row0 < 0 || n_rows < 1 || (long)row0 + n_rows > e->Lmax)
+        return e->fail(UMGEN_E_INVALID, "layer=%d scene=%d rows [%d, %d + %d) of %d", layer, scene, row0, row0, n_rows, e->Lmax);
+    unsigned char* dev = static_cast<unsigned char*>(e->kvcache) + ((size_t)layer * e->kv_layer_stride + (size_t)scene * e->kv_scene_stride + (size_t)row0 * kHeadDim) * e->tsz;
+    const size_t dpitch = (size_t)e->Lmax * kHeadDim * e->tsz, width = (size_t)n_rows * kHeadDim * e->tsz, height = (size_t)2 * e->H;
+    if (upload) HIPCHK(e, hipMemcpy2DAsync(dev, dpitch, host, width, width, height, hipMemcpyHostToDevice, e->stream));
+    else HIPCHK(e, hipMemcpy2DAsync(host, width, dev, dpitch, width, height, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return UMGEN_OK;
+}
+
+// Test hook: moves the hand-off tag epoch of the decode engines FORWARD (towards the wrap that run_frame and umgen_dbg_oar_step handle).  Backwards is
+// refused: tags below the current epoch may still lie in the granule buffers, which only the wrap clears.
+int umgen_dbg_oar_epoch(umgen_engine* e, uint32_t epoch) {
+    if (!e) return UMGEN_E_INVALID;
+    if (epoch < e->eng_epoch) return e->fail(UMGEN_E_INVALID, "epoch 0x%08x is below the current 0x%08x", epoch, e->eng_epoch);
+    e->eng_epoch = epoch;
     return UMGEN_OK;
 }
 

@@ -276,13 +276,32 @@ class Engine:
         pick = (lambda a: a) if batched else (lambda a: a[0])
         return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}}
 
-    def dbg_oar_step(self, x: np.ndarray, L: int, use_engine: bool, unmasked: bool = True) -> np.ndarray:
-        """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L)."""
+    def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True) -> np.ndarray:
+        """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L).
+        use_engine goes through int() as it is: 0 / False five launches per layer, 1 / True the XCD-resident engine, 3 the chip-wide engine.
+        A path that a decode step of B scenes would not take on this engine is refused (UMGenError), never replaced by another."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         out = np.empty_like(x)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
         self._check(self.lib.umgen_dbg_oar_step(self._h, x.shape[0], L, fp(x), fp(out), int(use_engine), int(unmasked)), "dbg_oar_step")
         return out
+
+    def dbg_oar_cache_get(self, layer: int, scene: int, row0: int, n_rows: int) -> np.ndarray:
+        """Test hook: rows [row0, row0 + n_rows) of one (layer, scene) block of the decode K/V cache as uint16 bits [2, n_head, n_rows, 48]."""
+        out = np.empty((2, self.cfg.n_head, n_rows, 48), np.uint16)
+        self._check(self.lib.umgen_dbg_oar_cache(self._h, layer, scene, row0, n_rows, out.ctypes.data_as(C.c_void_p), 0), "dbg_oar_cache")
+        return out
+
+    def dbg_oar_cache_put(self, layer: int, scene: int, row0: int, rows: np.ndarray):
+        """Test hook: writes uint16 bits [2, n_head, n_rows, 48] over rows [row0, row0 + n_rows) of one (layer, scene) block of the decode K/V cache."""
+        rows = np.ascontiguousarray(rows)
+        if rows.dtype != np.uint16 or rows.ndim != 4 or rows.shape[:2] != (2, self.cfg.n_head) or rows.shape[3] != 48:
+            raise UMGenError(f"dbg_oar_cache_put: rows {rows.dtype} {rows.shape}, expected uint16 (2, {self.cfg.n_head}, n_rows, 48)")
+        self._check(self.lib.umgen_dbg_oar_cache(self._h, layer, scene, row0, rows.shape[2], rows.ctypes.data_as(C.c_void_p), 1), "dbg_oar_cache")
+
+    def dbg_oar_epoch(self, epoch: int):
+        """Test hook: moves the decode engines' hand-off tag epoch forward (towards its wrap at 0xE0000000); a smaller value is refused."""
+        self._check(self.lib.umgen_dbg_oar_epoch(self._h, int(epoch)), "dbg_oar_epoch")
 
     # -- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on: bool):
