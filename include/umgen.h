@@ -214,6 +214,29 @@ typedef struct umgen_score_out {
 int umgen_score(umgen_engine *e, int32_t B, int32_t T, const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
                 const int64_t *next_pose, const int64_t *next_map, const int64_t *next_bbox3d, const int64_t *next_image, umgen_score_out *out);
 
+/* Score diagnostics: what else the distribution behind every logp said.  umgen_score's arguments and rows; per content position, with v the fp32
+ * logit row, t = v[target] and lse as umgen_score forms them:
+ *     rank        number of n with v[n] > t, strictly (ties are not counted, like the sampler's "ties kept" threshold): rank < top_k means inside
+ *                 the top-k support, rank == 0 that the target's logit is the row maximum
+ *     mass_above  sum over v[n] > t of softmax(v / temperature)[n]; mass_above <= p is the reference's nucleus rule for "kept"
+ *                 ((cumsum - p_sorted) > p removes, UMGen.py:944-953).  The only output that depends on `temperature` (> 0, finite)
+ *     entropy     -sum p log p of softmax(v) in nats, at temperature 1
+ *     topk_tok    the `topk` (0 .. UMGEN_SCORE_TOPK_MAX) most likely tokens in descending order of logit, equal logits by ascending index;
+ *     topk_logp   v[topk_tok[i]] - lse, the bits of logp where the target is listed; -1 / -inf past a vocabulary smaller than topk.  topk_tok[0] is argmax
+ * `out` may be NULL; when given it is filled exactly as umgen_score fills it.  Any pointer of `detail` may be NULL (top-K pointers with topk == 0
+ * are refused).  The call costs one more sweep of the heads behind umgen_score's; its device buffers are allocated by the first call (UMGEN_E_NOMEM). */
+#define UMGEN_SCORE_TOPK_MAX 16
+typedef struct umgen_score_detail_out {
+    int32_t *rank_pose, *rank_map, *rank_bbox3d, *rank_image;                                 /* [B][S_mod] */
+    float *mass_above_pose, *mass_above_map, *mass_above_bbox3d, *mass_above_image;
+    float *entropy_pose, *entropy_map, *entropy_bbox3d, *entropy_image;
+    int32_t *topk_tok_pose, *topk_tok_map, *topk_tok_bbox3d, *topk_tok_image;                 /* [B][S_mod][topk] */
+    float *topk_logp_pose, *topk_logp_map, *topk_logp_bbox3d, *topk_logp_image;
+} umgen_score_detail_out;
+int umgen_score_detail(umgen_engine *e, int32_t B, int32_t T, const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                       const int64_t *next_pose, const int64_t *next_map, const int64_t *next_bbox3d, const int64_t *next_image, int32_t topk,
+                       float temperature, umgen_score_out *out, umgen_score_detail_out *detail);
+
 int umgen_set_profiling(umgen_engine *e, int32_t enable); /* per-launch HIP-event timing of the GEMM / attention kernels and of the
                                                             * decode step's layer kernel(s); profiled frames launch eagerly */
 int umgen_get_timings(umgen_engine *e, umgen_timings *out);

@@ -2,7 +2,9 @@
 """Timing of umgen_score (one forward pass over a given frame) against the only earlier route to the same numbers, a teacher-forced
 umgen_frame (2206 decode steps): UMGen_Large, synthetic weights, bf16, one engine of 8 scenes, a window of T history frames.
 After one warm-up call each: the median of 5 host-clock calls of Engine.score at B = 1 and B = 8 and of Engine.frame(forced=..., trace=False).
-    python tools/score_bench.py [out.json] [--T=20]  ->  one JSON line (also written to out.json, default profiles/score_bench.json)"""
+    python tools/score_bench.py [out.json] [--T=20] [--detail]  ->  one JSON line (also written to out.json, default profiles/score_bench.json)
+--detail adds the cost of asking for the score diagnostics (umgen_score_detail at topk 16, one more sweep of the heads): after one warm-up call each, 5
+alternating pairs of Engine.score and Engine.score(detail=True, topk=16) at B = 1 and B = 8, the median of each side."""
 import json
 import os
 import statistics
@@ -20,6 +22,7 @@ from umgen_amd.weights import synthetic_items  # noqa: E402
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 T = next((int(a[4:]) for a in sys.argv[1:] if a.startswith("--T=")), 20)
+DETAIL = "--detail" in sys.argv[1:]
 REPS = 5
 
 
@@ -31,6 +34,19 @@ def median_ms(fn):
         fn()
         ts.append((time.perf_counter() - t0) * 1e3)
     return statistics.median(ts), ts
+
+
+def alternating_ms(fa, fb):
+    """medians of REPS calls of each, taken in turns behind one warm-up call each"""
+    fa()
+    fb()
+    ta, tb = [], []
+    for _ in range(REPS):
+        for fn, ts in ((fa, ta), (fb, tb)):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ta), statistics.median(tb)
 
 
 cfg = large_config()
@@ -48,6 +64,10 @@ res["score_b8_ms"], res["score_b8_all_ms"] = median_ms(lambda: e.score(window, f
 res["forced_frame_b1_ms"], res["forced_frame_b1_all_ms"] = median_ms(lambda: e.frame(one_w, forced=one_f, trace=False))
 res["score_b8_ms_per_scene"] = res["score_b8_ms"] / 8
 res["forced_frame_over_score_b1"] = res["forced_frame_b1_ms"] / res["score_b1_ms"]
+if DETAIL:
+    for tag, w, f in (("b1", one_w, one_f), ("b8", window, frame)):
+        plain, det = alternating_ms(lambda: e.score(w, f), lambda: e.score(w, f, detail=True, topk=16, temperature=0.7))
+        res[f"detail_{tag}"] = {"score_ms": plain, "score_detail_topk16_ms": det, "extra_ms": det - plain, "ratio": det / plain}
 r = e.score(one_w, one_f)
 res["nll_b1"] = {m: float(-r["logp"][m].astype(np.float64).mean()) for m in MOD_ORDER}
 e.close()

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
 SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
            "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip"]
-EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_rollout_logp", "umgen_frame_logp",
+EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_rollout_logp", "umgen_frame_logp",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
@@ -26,7 +26,7 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer", "umgen_dbg_guard_selftest",
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego", "umgen_dbg_token_steps_logp", "umgen_dbg_sample_ego_logp",
-           "umgen_dbg_head_nll", "umgen_dbg_head_nll_split"]
+           "umgen_dbg_head_nll", "umgen_dbg_head_nll_split", "umgen_dbg_head_detail", "umgen_dbg_logits_detail"]
 
 HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
 
@@ -70,6 +70,15 @@ class ScoreOut(C.Structure):
     """umgen_score_out (include/umgen.h): per-modality log-probabilities [B][S_mod] and arg-max tokens; any pointer may be NULL"""
     _fields_ = [(f"logp_{m}", C.POINTER(C.c_float)) for m in ("pose", "map", "bbox3d", "image")] + \
         [(f"argmax_{m}", C.POINTER(C.c_int32)) for m in ("pose", "map", "bbox3d", "image")]
+
+
+SCORE_TOPK_MAX = 16
+
+
+class ScoreDetailOut(C.Structure):
+    """umgen_score_detail_out (include/umgen.h): rank, mass_above, entropy [B][S_mod] and topk_tok, topk_logp [B][S_mod][topk] per modality; any pointer may be NULL"""
+    _fields_ = [(f"{k}_{m}", C.POINTER(t)) for k, t in (("rank", C.c_int32), ("mass_above", C.c_float), ("entropy", C.c_float),
+                                                        ("topk_tok", C.c_int32), ("topk_logp", C.c_float)) for m in ("pose", "map", "bbox3d", "image")]
 
 
 class LogpOut(C.Structure):
@@ -263,6 +272,7 @@ def load_library() -> C.CDLL:
     lib.umgen_rollout_logp.argtypes = lib.umgen_rollout.argtypes + [C.POINTER(LogpOut)]
     lib.umgen_frame_logp.argtypes = lib.umgen_frame.argtypes + [C.POINTER(LogpOut)]
     lib.umgen_score.argtypes = [vp, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut)]
+    lib.umgen_score_detail.argtypes = lib.umgen_score.argtypes[:-1] + [i32, C.c_float, C.POINTER(ScoreOut), C.POINTER(ScoreDetailOut)]
     lib.umgen_set_profiling.argtypes = [vp, i32]
     lib.umgen_get_timings.argtypes = [vp, C.POINTER(Timings)]
     lib.umgen_last_error.argtypes = [vp]
@@ -315,6 +325,8 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_sample_ego_logp.argtypes = lib.umgen_dbg_sample_ego.argtypes + [fp]
     lib.umgen_dbg_head_nll.argtypes = [i32, i32, i32, i32, fp, C.c_long, fp, vp, i32p, fp, i32p, fp, fp]
     lib.umgen_dbg_head_nll_split.argtypes = [i32]
+    lib.umgen_dbg_head_detail.argtypes = [i32, i32, i32, i32, fp, C.c_long, fp, vp, i32p, i32, C.c_float, i32p, fp, fp, i32p, fp]
+    lib.umgen_dbg_logits_detail.argtypes = [i32, i32, fp, C.c_long, i32p, i32, C.c_float, i32p, fp, fp, i32p, fp]
     lib.umgen_vq_create.argtypes = [C.POINTER(VQConfig), C.POINTER(vp)]
     lib.umgen_vq_load_tensor.argtypes = [vp, C.c_char_p, fp, i64p, i32]
     lib.umgen_vq_finalize.argtypes = [vp]

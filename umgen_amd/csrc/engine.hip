@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
+// umgen_frame(_logp), umgen_score(_detail) and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
 #include "engine_state.h"
 
@@ -132,14 +132,23 @@ int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* 
                             out_bbox3d, out_image, nullptr);
 }
 
-// log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes: engine_frame.hip run_score
-int umgen_score(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
-                const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, umgen_score_out* out) {
+// umgen_score and umgen_score_detail: log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes, and
+// with `detail` the diagnostics of the same rows: engine_frame.hip run_score
+static int score_call(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                      const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, umgen_score_out* out,
+                      const umgen_score_detail_out* detail, int32_t topk, float temperature) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
     if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
-    if (!out) return e->fail(UMGEN_E_INVALID, "null output struct");
+    if (!out && !detail) return e->fail(UMGEN_E_INVALID, "null output struct");
+    if (detail) {
+        if (topk < 0 || topk > UMGEN_SCORE_TOPK_MAX) return e->fail(UMGEN_E_INVALID, "topk=%d out of range [0,%d]", topk, UMGEN_SCORE_TOPK_MAX);
+        if (!(temperature > 0.f) || !(temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0 and finite");
+        const bool lists = detail->topk_tok_pose || detail->topk_tok_map || detail->topk_tok_bbox3d || detail->topk_tok_image || detail->topk_logp_pose ||
+                           detail->topk_logp_map || detail->topk_logp_bbox3d || detail->topk_logp_image;
+        if (lists && topk == 0) return e->fail(UMGEN_E_INVALID, "top-K outputs requested with topk = 0");
+    }
     if (!pose || !map || !bbox3d || !image || !next_pose || !next_map || !next_bbox3d || !next_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
     if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
     if (int rc = check_scene_tokens(e, (size_t)B * T, pose, map, bbox3d, image)) return rc;
@@ -159,15 +168,48 @@ int umgen_score(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, cons
     }
     std::vector<float> logp((size_t)B * kTokPerFrame);
     std::vector<int> arg((size_t)B * kTokPerFrame);
-    const ScoreIO sc{B, T, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), logp.data(), arg.data()};
+    ScoreIO sc{B, T, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), logp.data(), arg.data()};
+    const size_t rows = (size_t)B * kTokPerFrame;
+    std::vector<int> rank(detail ? rows : 0), tok(detail ? rows * topk : 0);
+    std::vector<float> mass(detail ? rows : 0), ent(detail ? rows : 0), tlp(detail ? rows * topk : 0);
+    const ScoreDetailIO dio{topk, temperature, rank.data(), mass.data(), ent.data(), tok.data(), tlp.data()};
+    if (detail) sc.detail = &dio;
     if (int rc = run_score_any(e, sc)) return rc;
-    float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
-    int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
     for (int m = 0; m < 4; ++m) {      // the engine's blocks are pose | map | bbox3d | image, each [B][S_mod]
-        if (lo[m]) memcpy(lo[m], &logp[(size_t)B * off[m]], (size_t)B * S[m] * sizeof(float));
-        if (ao[m]) memcpy(ao[m], &arg[(size_t)B * off[m]], (size_t)B * S[m] * sizeof(int32_t));
+        const size_t b0 = (size_t)B * off[m], n = (size_t)B * S[m];
+        if (out) {
+            float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
+            int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
+            if (lo[m]) memcpy(lo[m], &logp[b0], n * sizeof(float));
+            if (ao[m]) memcpy(ao[m], &arg[b0], n * sizeof(int32_t));
+        }
+        if (detail) {
+            int32_t* ro[4] = {detail->rank_pose, detail->rank_map, detail->rank_bbox3d, detail->rank_image};
+            float* mo[4] = {detail->mass_above_pose, detail->mass_above_map, detail->mass_above_bbox3d, detail->mass_above_image};
+            float* eo[4] = {detail->entropy_pose, detail->entropy_map, detail->entropy_bbox3d, detail->entropy_image};
+            int32_t* to[4] = {detail->topk_tok_pose, detail->topk_tok_map, detail->topk_tok_bbox3d, detail->topk_tok_image};
+            float* po[4] = {detail->topk_logp_pose, detail->topk_logp_map, detail->topk_logp_bbox3d, detail->topk_logp_image};
+            if (ro[m]) memcpy(ro[m], &rank[b0], n * sizeof(int32_t));
+            if (mo[m]) memcpy(mo[m], &mass[b0], n * sizeof(float));
+            if (eo[m]) memcpy(eo[m], &ent[b0], n * sizeof(float));
+            if (to[m]) memcpy(to[m], &tok[b0 * topk], n * topk * sizeof(int32_t));
+            if (po[m]) memcpy(po[m], &tlp[b0 * topk], n * topk * sizeof(float));
+        }
     }
     return UMGEN_OK;
+}
+
+int umgen_score(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, umgen_score_out* out) {
+    if (e && !out) return e->fail(UMGEN_E_INVALID, "null output struct");
+    return score_call(e, B, T, pose, map, bbox3d, image, next_pose, next_map, next_bbox3d, next_image, out, nullptr, 0, 1.f);
+}
+
+int umgen_score_detail(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                       const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, int32_t topk,
+                       float temperature, umgen_score_out* out, umgen_score_detail_out* detail) {
+    if (e && !detail) return e->fail(UMGEN_E_INVALID, "null detail struct");
+    return score_call(e, B, T, pose, map, bbox3d, image, next_pose, next_map, next_bbox3d, next_image, out, detail, topk, temperature);
 }
 
 // UMGen.inference (UMGen.py:1542-1671)

@@ -631,6 +631,26 @@ int run_frame(umgen_engine* e, const FrameIO& io) {
 // the BlockOAR layers as ONE pass (run_prefix_prefill: the stacks' arithmetic contract) and the scoring head (score.hip) reads ln_oar . head
 // off the rows of X: no decode step, no sampler, no RNG, no logit buffer.  The pass works in the stacks' workspaces and the decode cache, so
 // nothing an earlier rollout left in the slot caches is trusted afterwards (px.valid).
+// device buffers of umgen_score_detail, on its first call: engines that never ask keep their footprint
+int ensure_score_detail(umgen_engine* e) {
+    if (e->det_part) return 0;
+    const size_t Bm = e->cfg.max_batch;
+    void* got[7] = {};
+    const size_t bytes[7] = {Bm * kNMap * 8 * kDetailRecFloats * 4, 4 * Bm * kNMap * 4, Bm * kTokPerFrame * 4, Bm * kTokPerFrame * 4,
+                             Bm * kTokPerFrame * kScoreTopK * 4, Bm * kTokPerFrame * 4, Bm * kTokPerFrame * kScoreTopK * 4};      // (head_nll_nsplit <= 8)
+    for (int i = 0; i < 7; ++i)
+        if (hipMalloc(&got[i], bytes[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int k = 0; k < i; ++k) (void)hipFree(got[k]);
+            return e->fail(UMGEN_E_NOMEM, "no device memory for the score-detail buffers (%zu bytes)", bytes[i]);
+        }
+    for (void* p : got) e->allocs.push_back(p);
+    e->det_row = (float*)got[1]; e->det_mass = (float*)got[2]; e->det_ent = (float*)got[3]; e->det_tlp = (float*)got[4];
+    e->det_rank = (int*)got[5]; e->det_tok = (int*)got[6];
+    e->det_part = (float*)got[0];
+    return 0;
+}
+
 template <typename T>
 int run_score(umgen_engine* e, const ScoreIO& sc) {
     hipStream_t const fg = e->stream;
@@ -638,6 +658,13 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
     (void)hipGetLastError();
     struct RestoreStream { umgen_engine* e; hipStream_t s; ~RestoreStream() { e->stream = s; e->set_work(e->w_main); } } restore{e, fg};
     const int E = e->E, B = sc.B;
+    const ScoreDetailIO* dt = sc.detail;
+    if (dt) { if (int rc = ensure_score_detail(e)) return rc; }
+    // block b0 of the detail results: topk per row in the lists
+    auto detail_out = [&](long b0) {
+        return ScoreDetailOut{e->det_rank + b0, e->det_mass + b0, e->det_ent + b0, e->det_tok + b0 * dt->topk, e->det_tlp + b0 * dt->topk, dt->topk,
+                              1.0f / dt->temperature};
+    };
     // the ego net's sampler runs and is overridden by the given pose (run_ego's forced form): any valid parameters do
     static const umgen_sampling smp{UMGEN_SAMPLE_TOPK, 1, 1, 1, 1.f, 1.f, 1.f, 0, 0, 0, nullptr};
     const FrameIO io{B, sc.T, sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &smp, nullptr, nullptr};
@@ -655,6 +682,7 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
     float* lp = e->score_logp;
     int* am = e->score_arg;
     launch_logits_nll(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, lp, am, nullptr, nullptr);
+    if (dt) HIPCHK(e, launch_logits_detail(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, detail_out(0)));
     HIPCHK(e, hipMemcpyAsync(e->d_tokens, sc.next, (size_t)B * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
     if (int rc = run_stacks(e, io, ctx)) return rc;
     if (int rc = run_prefix_prefill_any(e, B, kSeq)) return rc;      // rows 0 .. 2205 of every scene in X; row j predicts the token at position j
@@ -667,10 +695,25 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
         a.ln_w = e->ln_oar; a.W = head[m]; a.V = V[m]; a.K = E; a.M = B * n[m];
         a.target = e->d_tokens + off[m]; a.target_group_stride = kTokPerFrame;
         a.part = e->score_part; a.logp = lp + (long)B * off[m]; a.argmax = am + (long)B * off[m];
+        if (dt) {
+            const long nr = (long)e->cfg.max_batch * kNMap;
+            a.lse = e->det_row; a.tlogit = e->det_row + nr; a.rmax = e->det_row + 2 * nr; a.sumexp = e->det_row + 3 * nr;
+        }
         HIPCHK(e, launch_head_nll<T>(st, a));
+        if (dt) HIPCHK(e, launch_head_detail<T>(st, HeadDetailArgs{a, e->det_part, detail_out((long)B * off[m])}));
     }
     HIPCHK(e, hipMemcpyAsync(sc.logp, lp, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(sc.argmax, am, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+    if (dt) {
+        const size_t n = (size_t)B * kTokPerFrame * 4;
+        HIPCHK(e, hipMemcpyAsync(dt->rank, e->det_rank, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(dt->mass_above, e->det_mass, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(dt->entropy, e->det_ent, n, hipMemcpyDeviceToHost, st));
+        if (dt->topk) {
+            HIPCHK(e, hipMemcpyAsync(dt->topk_tok, e->det_tok, n * dt->topk, hipMemcpyDeviceToHost, st));
+            HIPCHK(e, hipMemcpyAsync(dt->topk_logp, e->det_tlp, n * dt->topk, hipMemcpyDeviceToHost, st));
+        }
+    }
     HIPCHK(e, hipStreamSynchronize(st));
     const hipError_t le = e->launch_status != hipSuccess ? e->launch_status : hipGetLastError();
     e->launch_status = hipSuccess;

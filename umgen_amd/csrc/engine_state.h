@@ -84,6 +84,10 @@ struct umgen_engine {
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
     int* score_arg = nullptr;
+    // umgen_score_detail: allocated by its first call (engine_frame.hip ensure_score_detail).  det_part: the detail sweep's (row, split) records; det_row:
+    // lse | target logit | row maximum | sum-exp of one modality's rows, [4][max_batch * 1024]; the results in score_logp's block layout, the lists with room for 16 per row (a call packs its topk)
+    float *det_part = nullptr, *det_row = nullptr, *det_mass = nullptr, *det_ent = nullptr, *det_tlp = nullptr;
+    int *det_rank = nullptr, *det_tok = nullptr;
     // Overlapped TAR pass.  Causal temporal attention + frame-local spatial attention make every history
     // slot but the last one of the NEXT frame's window independent of the frame being decoded, so those slots are pushed through
     // the ego / map / box / TAR stacks on `bg_stream` (a CU-masked stream) while the latency-bound decode loop runs on the
@@ -252,6 +256,12 @@ struct FrameIO {
     const int* given_box = nullptr;              // host [B][660] or nullptr: ... and its boxes (only behind a given map)
 };
 
+// what umgen_score_detail computes beside the scores
+struct ScoreDetailIO {
+    int topk; float temperature;
+    int* rank; float *mass_above, *entropy;      // host [2199 B] each, logp's layout
+    int* topk_tok; float* topk_logp;             // host [2199 B][topk]: the same blocks, topk per position (unused when topk == 0)
+};
 // umgen_score's arguments: B scenes' history windows and the frame to score, as host int32 arrays
 struct ScoreIO {
     int B, T;
@@ -259,6 +269,7 @@ struct ScoreIO {
     const int* next;                             // [B][2199]: the scored frame, pose | map | bbox3d | image
     float* logp;                                 // host [2199 B]: pose [B][3] | map [B][1024] | bbox3d [B][660] | image [B][512]
     int* argmax;                                 // the same layout
+    const ScoreDetailIO* detail = nullptr;       // umgen_score_detail: what else to compute
 };
 
 // ---- engine_weights.hip ---------------------------------------------------------------------------------------------

@@ -183,7 +183,8 @@ struct HeadNllArgs {
     const int* target; long target_group_stride;
     float* part;                       // scratch: M x head_nll_nsplit(V) records of 16 bytes (max, sum-exp, target logit, arg-max)
     float* logp; int* argmax;          // [M] each; nullable
-    float *lse, *tlogit;               // [M] each; nullable (test hook): log-sum-exp and the target's logit
+    float *lse, *tlogit;               // [M] each; nullable (test hook, detail pass): log-sum-exp and the target's logit
+    float *rmax, *sumexp;              // [M] each; nullable (detail pass): the row maximum and sum exp(logit - maximum), lse = rmax + log sumexp
 };
 inline bool head_nll_supported(int K) { return K == 96 || K == 768 || K == 1536; }
 // the vocabulary is split over workgroups in whole tiles of 16 columns; a function of V alone (8192: 8 splits of 64 tiles, 1028: 5 of 13)
@@ -193,6 +194,28 @@ template <typename T> hipError_t launch_head_nll(hipStream_t s, const HeadNllArg
 // the same outputs for rows whose logits exist: logits [M][ld], V columns each
 void launch_logits_nll(hipStream_t s, const float* logits, long ld, int V, int M, const int* target, int rows_per_group, long target_group_stride,
                        float* logp, int* argmax, float* lse, float* tlogit);
+
+// Score diagnostics (score.hip, umgen_score_detail): a second sweep behind launch_head_nll with the row's maximum and target logit known.  Per row
+//   rank        the number of logits strictly above the target's          mass_above  their share of softmax(logits / temperature)
+//   entropy     of softmax(logits), nats                                   topk_*      the topk most likely tokens, descending (ties: lower index), with
+//                                                                                      log-probabilities logit - lse; -1 / -inf past V
+constexpr int kScoreTopK = 16;         // UMGEN_SCORE_TOPK_MAX: the one compiled list length
+constexpr int kDetailRecFloats = 4 + 2 * kScoreTopK;      // a (row, split) record: count, A, Z, U, 16 logits, 16 indices
+struct ScoreDetailOut {                // dense [M] / [M][topk]; every pointer nullable
+    int* rank; float *mass_above, *entropy;
+    int* topk_tok; float* topk_logp;
+    int topk;                          // 0 .. kScoreTopK
+    float inv_temperature;
+};
+struct HeadDetailArgs {
+    HeadNllArgs h;                     // as given to launch_head_nll just before, with lse, tlogit, rmax and sumexp set: this pass reads them
+    float* part;                       // scratch: M x head_nll_nsplit(V) records of kDetailRecFloats floats
+    ScoreDetailOut out;
+};
+template <typename T> hipError_t launch_head_detail(hipStream_t s, const HeadDetailArgs& a);   // hipErrorInvalidValue: unsupported K, topk, a missing input
+// the same outputs for rows whose logits exist (needs no earlier pass)
+hipError_t launch_logits_detail(hipStream_t s, const float* logits, long ld, int V, int M, const int* target, int rows_per_group, long target_group_stride,
+                                const ScoreDetailOut& out);
 
 // ------------------------------------------------------------------------------------------------
 // XCD-resident decode engine (oar_engine.hip): all BlockOAR layers of one decode step in one launch, bf16 weights, n_embd 768

@@ -261,20 +261,63 @@ class Engine:
             raise UMGenError("score: the window has no history frame")
         return w, nx, batched
 
-    def score(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray]) -> Dict[str, Dict[str, np.ndarray]]:
+    DETAIL_KEYS = ("rank", "mass_above", "entropy", "topk_tokens", "topk_logp")
+
+    @classmethod
+    def _detail_args(cls, detail, topk, temperature):
+        """What a score call asks for beyond the scores, checked before anything reaches the device.  Returns (keys or None, topk, temperature)."""
+        if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)) or not 0 <= topk <= _lib.SCORE_TOPK_MAX:
+            raise UMGenError(f"score: topk={topk!r} is outside [0, {_lib.SCORE_TOPK_MAX}]")
+        temperature = float(temperature)
+        if not (np.isfinite(temperature) and temperature > 0):
+            raise UMGenError(f"score: temperature={temperature} must be positive and finite")
+        if isinstance(detail, (bool, np.bool_)) or detail is None:
+            keys = cls.DETAIL_KEYS if detail or topk > 0 else None
+            if keys and topk == 0:
+                keys = keys[:3]
+        else:
+            keys = tuple(detail)
+            unknown = [k for k in keys if k not in cls.DETAIL_KEYS]
+            if unknown:
+                raise UMGenError(f"score: unknown detail outputs {unknown}; known: {cls.DETAIL_KEYS}")
+            if topk == 0 and any(k.startswith("topk_") for k in keys):
+                raise UMGenError("score: topk_tokens / topk_logp requested with topk=0")
+        return keys, int(topk), temperature
+
+    def score(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray], detail=False, topk: int = 0,
+              temperature: float = 1.0) -> Dict[str, Dict[str, np.ndarray]]:
         """Per-token log-likelihood of a given next frame (umgen_score: one forward pass, no sampling).
         window: mod -> [B, T, S_mod] (or [T, S_mod]); next_frame: mod -> [B, S_mod] (or [S_mod]).
         Returns {"logp": {mod: float32 [B, S_mod]}, "argmax": {mod: int64 [B, S_mod]}} (without the B axis for un-batched inputs):
-        logp[mod][b, k] = log softmax(AR head logits at that position)[next_frame[mod][b, k]], the teacher-forced trace of `frame` in closed form."""
+        logp[mod][b, k] = log softmax(AR head logits at that position)[next_frame[mod][b, k]], the teacher-forced trace of `frame` in closed form.
+        With ``detail`` (True, or the names wanted among DETAIL_KEYS) or ``topk > 0`` the dict gains, per position (umgen_score_detail):
+        "rank" int64 (logits strictly above the target's: rank < k means inside a top-k sampler's support), "mass_above" (their share of
+        softmax(logits / temperature): <= p means kept by a nucleus sampler), "entropy" (nats, temperature 1), "topk_tokens" int64 [.., S_mod, topk]
+        and "topk_logp" (the topk <= 16 most likely tokens, best first, with their log-probabilities)."""
+        keys, topk, temperature = self._detail_args(detail, topk, temperature)
         w, nx, batched = self._score_args(window, next_frame)
         B, T = w["pose"].shape[:2]
         logp = {m: np.full((B, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
         arg = {m: np.full((B, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
         out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
                             **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
-        self._check(self.lib.umgen_score(self._h, B, T, *[_p64(w[m]) for m in MOD_ORDER], *[_p64(nx[m]) for m in MOD_ORDER], C.byref(out)), "score")
+        tokens = [_p64(w[m]) for m in MOD_ORDER] + [_p64(nx[m]) for m in MOD_ORDER]
         pick = (lambda a: a) if batched else (lambda a: a[0])
-        return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}}
+        res = {}
+        if keys is None:
+            self._check(self.lib.umgen_score(self._h, B, T, *tokens, C.byref(out)), "score")
+        else:
+            field = {"rank": ("rank", np.int32, ()), "mass_above": ("mass_above", np.float32, ()), "entropy": ("entropy", np.float32, ()),
+                     "topk_tokens": ("topk_tok", np.int32, (topk,)), "topk_logp": ("topk_logp", np.float32, (topk,))}
+            bufs = {k: {m: np.zeros((B, CONTENT_LEN[m]) + field[k][2], field[k][1]) for m in MOD_ORDER} for k in keys}
+            det = _lib.ScoreDetailOut(**{f"{field[k][0]}_{m}": bufs[k][m].ctypes.data_as(C.POINTER(C.c_int32 if field[k][1] is np.int32 else C.c_float))
+                                         for k in keys for m in MOD_ORDER})
+            self._check(self.lib.umgen_score_detail(self._h, B, T, *tokens, topk, temperature, C.byref(out), C.byref(det)), "score_detail")
+            for k in keys:
+                res[k] = {m: pick(bufs[k][m].astype(np.int64) if field[k][1] is np.int32 else bufs[k][m]) for m in MOD_ORDER}
+        res["logp"] = {m: pick(logp[m]) for m in MOD_ORDER}
+        res["argmax"] = {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}
+        return res
 
     def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True) -> np.ndarray:
         """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L).

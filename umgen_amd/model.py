@@ -184,14 +184,23 @@ class UMGen(nn.Module):
             raise UMGenError(f"score: input_cond_frames={input_cond_frames} with {end} frames before the scored one (window cap {cap})")
         return {m: np.ascontiguousarray(cond[m][:, end - n:end]) for m in MOD_ORDER}, frame
 
+    @staticmethod
+    def _topk_acc(rank: Dict[str, np.ndarray]) -> Dict[str, Dict[int, float]]:
+        """mod -> {k: share of positions whose target is among the k most likely tokens (rank < k)} for k in (1, 5, 16)"""
+        return {m: {k: float((np.asarray(rank[m]) < k).mean()) for k in (1, 5, 16)} for m in MOD_ORDER}
+
     @torch.no_grad()
     def score(self, input_cond_tokens: Dict[str, torch.Tensor], target_tokens: Dict[str, torch.Tensor], input_cond_frames: int = -1,
-              t: Optional[int] = None) -> Dict[str, dict]:
+              t: Optional[int] = None, detail=False, topk: int = 0, temperature: Optional[float] = None) -> Dict[str, dict]:
         """Per-token log-likelihood of a recorded frame under the model: the reference's loss terms (get_targets, d_loss, F.cross_entropy per
         modality, UMGen.py:539-582) without the sampler.  Scores ``target_tokens[m][:, t]`` ([B, T_all, S_mod]; default: the frame behind the
         conditioning clip) -- or ``target_tokens[m]`` itself when it is one frame [B, S_mod] -- against the ``input_cond_frames`` frames of
         ``input_cond_tokens`` before it (-1: as many as there are, at most the engine's window of 20).
-        Returns Engine.score's dict plus "nll": mod -> float64 [B], the mean negative log-likelihood per scene."""
+        Returns Engine.score's dict plus "nll": mod -> float64 [B], the mean negative log-likelihood per scene.
+        ``detail`` / ``topk`` / ``temperature`` are Engine.score's (rank, mass_above, entropy, the topk most likely tokens per position); a
+        temperature of None means the model's sfmx_temp, the one its sampler divides by.  With them the dict also carries "topk_acc":
+        mod -> {k: share of positions with rank < k} for k in (1, 5, 16)."""
+        Engine._detail_args(detail, topk, 1.0 if temperature is None else temperature)
         if not self._loaded:
             raise UMGenError("load_state_dict() has not provided every tensor the model reads")
         np_ = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
@@ -200,6 +209,8 @@ class UMGen(nn.Module):
         B = window["pose"].shape[0]
         if B > self._engine_args["max_batch"]:
             self._recreate(max_batch=B)
-        res = self.engine.score(window, frame)
+        res = self.engine.score(window, frame, detail=detail, topk=topk, temperature=self.rcfg.sfmx_temp if temperature is None else temperature)
+        if "rank" in res:
+            res["topk_acc"] = self._topk_acc(res["rank"])
         res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=1) for m in MOD_ORDER}
         return res
