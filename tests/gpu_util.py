@@ -44,6 +44,16 @@ def ulp16(v, prec):
     return 2.0 ** (np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** emin))) - mant)
 
 
+def attn_bound(ref, A, prec, S, vmax):
+    """Componentwise bar of an S-key softmax attention output against its fp64 reference `ref` on the operands as handed over, with
+    A = sum_j p_j |v_j| / sum_j p_j from that reference: u (A + |ref|) + 2e-5 max(1, A), u = 2^-8 (bf16) | 2^-11 (fp16) | 0 (fp32).  u A is
+    the worst case of rounding every p to the operand type while l sums the unrounded p, u |ref| the output rounding, 2e-5 the project's bar
+    for what is computed in fp32.  fp16 adds S 2^-25 max|v| (`vmax`, broadcastable): a p below fp16's subnormal range is lost."""
+    u = {0: 0.0, 1: 2.0 ** -8, 2: 2.0 ** -11}[prec]
+    b = u * (A + np.abs(ref)) + 2e-5 * np.maximum(1.0, A)
+    return b + S * 2.0 ** -25 * vmax if prec == 2 else b
+
+
 def ln_input(rng, M, K):
     """rows fed to LayerNorm: per-row means in [-4, 4] and standard deviations in [0.05, 3] (both ends present)"""
     mu = rng.uniform(-4, 4, (M, 1))

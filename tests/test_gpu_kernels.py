@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_util import bits16, check, fp, from_bits16, lib, round16, vp
+from tests.gpu_util import attn_bound, bits16, check, fp, from_bits16, lib, round16, vp
 
 PREC = [0, 1, 2]          # fp32 | bf16 | fp16 operands (precision code of the debug hooks)
 EPS16 = {1: 1.0, 2: 0.125}   # 16-bit tolerances are quoted for bf16 (8 mantissa bits); fp16 has 11
@@ -151,7 +151,8 @@ def test_fp32_mfma_gemm_is_the_fma_chain(R, N, K, gelu, resid):
     np.testing.assert_array_equal(outs[0], outs[1])
 
 
-def ref_attention(q, k, v, H, causal):
+def ref_attention(q, k, v, H, causal, with_abs=False):
+    """fp64 attention; with_abs: also A = softmax . |v|, the scale of the componentwise bar (tests/gpu_util.py attn_bound)"""
     B, Tq, E = q.shape
     D = E // H
     qh = torch.from_numpy(q).double().view(B, Tq, H, D).permute(0, 2, 1, 3)
@@ -163,7 +164,19 @@ def ref_attention(q, k, v, H, causal):
         i = torch.arange(Tq).view(-1, 1)
         j = torch.arange(Tk).view(1, -1)
         att = att.masked_fill(j > i + (Tk - Tq), float("-inf"))
-    return (torch.softmax(att, -1) @ vh).permute(0, 2, 1, 3).reshape(B, Tq, E).numpy()
+    p = torch.softmax(att, -1)
+    y = (p @ vh).permute(0, 2, 1, 3).reshape(B, Tq, E).numpy()
+    return (y, (p @ vh.abs()).permute(0, 2, 1, 3).reshape(B, Tq, E).numpy()) if with_abs else y
+
+
+def assert_attn_bound(got, ref, A, v, prec, H):
+    """the componentwise bar of tests/test_gpu_attn_patterns.py (max |v| per frame and head)"""
+    F, S, E = v.shape
+    vmax = np.broadcast_to(np.abs(v).reshape(F, S, H, E // H).max(axis=(1, 3))[:, None, :, None], (F, S, H, E // H)).reshape(F, S, E)
+    bound = attn_bound(ref, A, prec, S, vmax)
+    ratio = np.abs(got - ref) / bound
+    print(f"attention |got - ref| / componentwise bound: max {float(ratio.max()):.3f}")
+    assert np.all(ratio <= 1.0), f"{int((ratio > 1.0).sum())} elements outside the componentwise bound, worst {float(ratio.max()):.3f} x"
 
 
 @pytest.mark.parametrize("F,S,H", [(2, 2207, 16), (3, 1031, 2), (1, 70, 2), (2, 1693, 4)])
@@ -180,8 +193,9 @@ def test_attn_spatial(bf16, F, S, H):
     y = np.zeros((F, S, E), dtype=np.uint16 if bf16 else np.float32)
     check(lib().umgen_dbg_attn_spatial(bf16, vp(bits16(qk, bf16) if bf16 else qk), vp(bits16(v, bf16) if bf16 else v), F, S, H, vp(y)))
     got = from_bits16(y, bf16) if bf16 else y
-    ref = ref_attention(q, k, v, H, False)
+    ref, A = ref_attention(q, k, v, H, False, with_abs=True)
     np.testing.assert_allclose(got, ref, atol=(2e-2 * EPS16[bf16] if bf16 else 2e-5), rtol=0)
+    assert_attn_bound(got, ref, A, v, bf16, H)
 
 
 @pytest.mark.parametrize("F,S,H", [(2, 2207, 16), (3, 1031, 2), (1, 70, 2), (2, 1693, 4), (1, 33, 2), (1, 129, 2)])
@@ -222,8 +236,9 @@ def test_attn_causal(bf16, F, S, H):
     y = np.zeros((F, S, E), dtype=np.uint16 if bf16 else np.float32)       # (the hook's device buffer starts as NaN: an unwritten row stays NaN)
     check(lib().umgen_dbg_attn_spatial(bf16 | 64, vp(bits16(qk, bf16) if bf16 else qk), vp(bits16(v, bf16) if bf16 else v), F, S, H, vp(y)))
     got = from_bits16(y, bf16) if bf16 else y
-    ref = np.concatenate([ref_attention(q[f:f + 1], k[f:f + 1], v[f:f + 1], H, True) for f in range(F)])   # per frame: H * S * S doubles at a time
+    ref, A = (np.concatenate(a) for a in zip(*[ref_attention(q[f:f + 1], k[f:f + 1], v[f:f + 1], H, True, with_abs=True) for f in range(F)]))   # per frame: H * S * S doubles at a time
     np.testing.assert_allclose(got, ref, atol=(2e-2 * EPS16[bf16] if bf16 else 2e-5), rtol=0)
+    assert_attn_bound(got, ref, A, v, bf16, H)
     ulp = np.abs(v[:, 0]) * 2.0 ** -(23 if not bf16 else (7 if bf16 == 1 else 10))     # one unit in the last place of the output type (at most)
     assert np.all(np.abs(got[:, 0] - v[:, 0]) <= ulp), "query 0 (one key) is not v[0] up to the output rounding"
 

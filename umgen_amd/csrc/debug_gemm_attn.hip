@@ -119,6 +119,9 @@ int umgen_dbg_gemm(int precP, int precQ, int mfma, const void* P, long nP, const
 
 // spatial attention on q|k rows [F*S][2E] and v rows [F*S][E] (both row-major on the host; V is transposed on the device
 // through the same GEMM_VT-layout the engine uses).  y [F*S][E].  flag 64: causal (query i sees keys 0 .. i), else every key.
+// flag 128: the pad columns [S, S_pad) of V^T hold 7.0 instead of the zeros the product keeps there -- a finite guard value: the kernels load
+// the pad with the ragged last key tile and must give it the weight 0 (the masked probabilities are exactly 0; 0 x NaN / inf would not be 0,
+// and "pad columns are zero" stays the product's contract), so the result must not change by a bit.
 int umgen_dbg_attn_spatial(int flags, const void* qk, const void* v, int F, int S, int H, void* y) {
     const int bf16 = flags & 3;                 // precision code; flag 32 (fp32 only): the VALU kernel instead of the matrix-core one
     if ((flags & 64) && (flags & 32)) return UMGEN_E_UNSUPPORTED;   // the causal launchers have no kernel choice
@@ -127,6 +130,11 @@ int umgen_dbg_attn_spatial(int flags, const void* qk, const void* v, int F, int 
     // host-side transpose of V into [F][H][48][S_pad]
     std::vector<unsigned char> vt((size_t)F * E * S_pad * es, 0);
     const unsigned char* vs = (const unsigned char*)v;
+    if (flags & 128) {                          // 7.0 in the operand type: fp32 | bf16 | IEEE half
+        const unsigned guard = bf16 == 0 ? 0x40E00000u : (bf16 == 1 ? 0x40E0u : 0x4700u);
+        for (size_t r = 0; r < (size_t)F * E; ++r)
+            for (int sr = S; sr < S_pad; ++sr) memcpy(&vt[(r * S_pad + sr) * es], &guard, es);
+    }
     for (int f = 0; f < F; ++f)
         for (int sr = 0; sr < S; ++sr)
             for (int c = 0; c < E; ++c)
