@@ -129,9 +129,9 @@ def params(fam, prec):
     return [layer_params(prec, f.E, 1000 * (l + 1) + f.E + prec)[1] for l in range(f.layers)]
 
 
-def config(fam):
+def config(fam, **over):
     f = FAMILY[fam]
-    return tiny_config(n_embd=f.E, n_head=f.H, n_oar_layer=f.layers, rule_constrain=False).greedy()
+    return tiny_config(n_embd=f.E, n_head=f.H, n_oar_layer=f.layers, rule_constrain=False, **over).greedy()
 
 
 def oar_entries(P, i):
@@ -142,12 +142,12 @@ def oar_entries(P, i):
             f"{key}.mlp.c_fc.weight": P["Wfc"], f"{key}.mlp.c_proj.weight": P["Wproj"]}
 
 
-def state_items(fam, prec):
+def state_items(fam, prec, **over):
     """synthetic_state_dict(cfg) with the BlockOAR entries replaced by the layers' values as stored (fp32 holds them exactly), one tensor at a time"""
     oar = {}
     for i, P in enumerate(params(fam, prec)):
         oar.update(oar_entries(P, i))
-    for key, shape in expected_keys(config(fam)).items():
+    for key, shape in expected_keys(config(fam, **over)).items():
         yield key, (oar[key].astype(np.float32) if key in oar else synth_tensor(key, shape, 3))
 
 
@@ -282,16 +282,16 @@ def env(**kv):
                 os.environ[k] = v
 
 
-def create(which, prec, max_batch=None):
+def create(which, prec, max_batch=None, max_cond_frames=4, **over):
     """many: the XCD-resident engine for every batch size up to 33 (8 groups; 12 layers: the production tail sharing, 4 tail layers on two groups
     each; UMGEN_BG_ENGINE=0 keeps a fresh one-scene handle of this kind on 8 groups); one: one scene per call, so the kernel instance with background
-    workers on 4 groups; wide: the chip-wide engine for up to two scenes"""
+    workers on 4 groups; wide: the chip-wide engine for up to two scenes.  max_cond_frames / over (tiny_config fields): a longer window (tests/test_gpu_bg_pass.py)"""
     from umgen_amd.engine import Engine
     fam = "wide" if which == "wide" else "xcd"
     switches = {"many": dict(UMGEN_DECODE_BATCHED=0, UMGEN_BG_ENGINE=0), "one": {}, "wide": dict(UMGEN_DECODE_WIDE=2)}[which]
     with env(**switches):
-        e = Engine(config(fam), precision=PREC_NAME[prec], max_batch=max_batch or {"many": 33, "one": 1, "wide": 2}[which], max_cond_frames=4)
-    e.load_state_dict(state_items(fam, prec))
+        e = Engine(config(fam, **over), precision=PREC_NAME[prec], max_batch=max_batch or {"many": 33, "one": 1, "wide": 2}[which], max_cond_frames=max_cond_frames)
+    e.load_state_dict(state_items(fam, prec, **over))
     e.finalize()
     e.fam, e.prec = fam, prec
     return e

@@ -1,5 +1,5 @@
 // One decode step: the BlockOAR layers on whichever path takes the step (batched layer, chip-wide engine, XCD-resident engine, five
-// launches per layer), the head and sampler behind them, a decode lane's view of the engine, and the test hooks on a live handle (one step, K/V cache
+// launches per layer), the head and sampler behind them, a decode lane's view of the engine, the drain launch of the background workers, and the test hooks on a live handle (one step, K/V cache
 // rows in and out, the tag epoch).
 #include "engine_state.h"
 
@@ -186,6 +186,16 @@ DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine:
     v.d_control = all.d_control + (long)b0 * kSlots; v.d_boxes = all.d_boxes + (long)b0 * 64 * 10; v.d_seeds = all.d_seeds + b0;
     v.d_logp = all.d_logp + (long)b0 * kTokPerFrame;
     return v;
+}
+
+int launch_bg_drain(umgen_engine* e, hipStream_t st) {
+    OarEngineArgs a{};
+    a.NG = 8; a.R = 2; a.D = 4; a.B = 1; a.bg = e->d_bgq; a.bg_only = 1;
+    a.st = e->d_state; a.ticket = e->eng_ticket; a.err = e->eng_err;
+    memcpy(a.xcc_group, e->eng_fg.map, 16);
+    a.fp16 = e->cfg.precision == UMGEN_PREC_FP16 ? 1 : 0;
+    HIPCHK(e, launch_oar_engine(st, a));
+    return 0;
 }
 
 int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j) {

@@ -460,12 +460,7 @@ int drain_and_download(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     ctx.drained = e->bg_engine && e->bg_pending;
     if (ctx.drained) {      // what the decode steps' launches left of the background pass: one launch without an engine part runs it to the end
         HIPCHK(e, hipEventRecord(e->ev_drain0, st));
-        OarEngineArgs a{};
-        a.NG = 8; a.R = 2; a.D = 4; a.B = 1; a.bg = e->d_bgq; a.bg_only = 1;
-        a.st = e->d_state; a.ticket = e->eng_ticket; a.err = e->eng_err;
-        memcpy(a.xcc_group, e->eng_fg.map, 16);
-        a.fp16 = std::is_same<T, f16_t>::value ? 1 : 0;
-        HIPCHK(e, launch_oar_engine(st, a));
+        if (int rc = launch_bg_drain(e, st)) return rc;
         HIPCHK(e, hipEventRecord(e->ev_drain1, st));
         e->bg_state_host.assign((size_t)kBgMaxWorkers * 4, 0u);
         HIPCHK(e, hipMemcpyAsync(e->bg_state_host.data(), &e->d_bgq->state[0][0], sizeof(e->d_bgq->state), hipMemcpyDeviceToHost, st));

@@ -267,8 +267,10 @@ int run_prefix_prefill(umgen_engine* e, int B, int P) {
 // Background pass for the NEXT frame of the rollout: its window is this window moved on by one frame, and all its slots but the
 // last are known now (the new frame's pose tokens `ego` included).  They run through the four stacks on bg_stream while the
 // decode loop of the current frame owns the other CUs; the temporal k | v rows of every layer land in the slot caches.
+// dbg (the test hooks of debug_bg.hip; nullptr in the product): the very same pass either as stand-alone launches on the engine's stream, synchronised
+// (foreground), or recorded and uploaded with every op's chunk / the margin overridden; a pass the recorder refuses is then an error, not a frame on the plain path.
 template <typename T>
-int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego) {
+int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg) {
     const int B = io.B, Tn = io.T;
     const int Tnext = std::min(Tn + 1, io.cond_cap);
     const int off = (Tn + 1 > io.cond_cap) ? 1 : 0;     // the window slides (UMGen.py:1600-1603) or still grows
@@ -308,16 +310,27 @@ int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& eg
     HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, e->px_pshift.data(), e->px_pshift.size() * 4, hipMemcpyHostToDevice, bg));
     HIPCHK(e, hipMemcpyAsync(e->pose_diff, e->px_pdiff.data(), e->px_pdiff.size() * 4, hipMemcpyHostToDevice, bg));
     const WindowTokens ws{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0};
-    if (e->bg_engine) {
-        // the pass as an op list for the decode engine's background workers: the same run_stack calls, with the launchers recording instead of launching
-        BgRecorder rec;
-        g_bg_rec = &rec;
+    auto run_pass = [&]() {      // recorded, or launched on e->stream
         if (px.has_ego) run_stack<T>(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0}, 1);
         run_stack<T>(e, STACK_MAP, ws, 1);
         run_stack<T>(e, STACK_BOX, ws, 1);
         run_stack<T>(e, STACK_TAR, ws, 1);
+    };
+    if (dbg && dbg->foreground) {      // the reference of tests/test_gpu_bg_pass.py: the stand-alone kernels (bg == the engine's stream here); nothing stays pending
+        run_pass();
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return e->fail(UMGEN_E_HIP, "a kernel launch of the pass was refused: %s", hipGetErrorString(le));
+        return 0;
+    }
+    if (e->bg_engine) {
+        // the pass as an op list for the decode engine's background workers: the same run_stack calls, with the launchers recording instead of launching
+        BgRecorder rec;
+        g_bg_rec = &rec;
+        run_pass();
         g_bg_rec = nullptr;
         if (rec.failed || rec.ops.empty() || rec.ops.size() > (size_t)kBgMaxOps) {
+            if (dbg) return e->fail(UMGEN_E_UNSUPPORTED, "background pass not recordable (%s)", rec.failed ? rec.failed : "op count");
             if (getenv("UMGEN_DEBUG_TIMING")) fprintf(stderr, "[umgen] background pass not recordable (%s): this frame's successor computes its whole window\n", rec.failed ? rec.failed : "op count");
             return 0;      // (px.valid stays false: the next frame takes the plain path)
         }
@@ -325,23 +338,22 @@ int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& eg
         bool same = rec.ops.size() == e->bg_rec.ops.size();
         for (size_t i = 0; same && i < rec.ops.size(); ++i) same = memcmp(&rec.ops[i].h, &e->bg_rec.ops[i].h, sizeof(BgOpHead)) == 0;
         e->bg_rec = std::move(rec);
+        if (dbg && dbg->chunk > 0) for (BgOp& o : e->bg_rec.ops) o.h.chunk = dbg->chunk;
         // header: op count, engine_ticks = 0 (the first launch measures, the workers start with the second), margin 10 us, the embedding tables
         e->bg_head.w[0] = (unsigned)e->bg_rec.ops.size(); e->bg_head.w[1] = 0u; e->bg_head.w[2] = (unsigned)(getenv("UMGEN_BG_MARGIN_US") ? atoi(getenv("UMGEN_BG_MARGIN_US")) * 100 : 1000); e->bg_head.w[3] = 0u;
+        if (dbg && dbg->margin_ticks >= 0) e->bg_head.w[2] = (unsigned)dbg->margin_ticks;
         e->bg_head.tb = e->tb;
         static_assert(offsetof(BgQueue, tb) == 16 && offsetof(BgQueue, state) == 16 + sizeof(EmbedTables), "BgQueue header layout");
         HIPCHK(e, hipMemcpyAsync(&e->d_bgq->n_ops, &e->bg_head, sizeof(e->bg_head), hipMemcpyHostToDevice, fg));
         HIPCHK(e, hipMemsetAsync(&e->d_bgq->state[0][0], 0, sizeof(e->d_bgq->state) + sizeof(e->d_bgq->arrive), fg));
-        if (!same) HIPCHK(e, hipMemcpyAsync(&e->d_bgq->est[0], e->bg_rec.est.data(), e->bg_rec.est.size() * sizeof(unsigned), hipMemcpyHostToDevice, fg));
+        if (!same || dbg) HIPCHK(e, hipMemcpyAsync(&e->d_bgq->est[0], e->bg_rec.est.data(), e->bg_rec.est.size() * sizeof(unsigned), hipMemcpyHostToDevice, fg));
         HIPCHK(e, hipMemcpyAsync(&e->d_bgq->ops[0], e->bg_rec.ops.data(), e->bg_rec.ops.size() * sizeof(BgOp), hipMemcpyHostToDevice, fg));
         e->bg_pending = true;      // (px.valid: once the drain behind the frame's last step has seen every worker at the end of the list, run_frame)
         return 0;
     }
     HIPCHK(e, hipEventRecord(e->ev_bg0, bg));
     e->stream = bg;
-    if (px.has_ego) run_stack<T>(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0}, 1);
-    run_stack<T>(e, STACK_MAP, ws, 1);
-    run_stack<T>(e, STACK_BOX, ws, 1);
-    run_stack<T>(e, STACK_TAR, ws, 1);
+    run_pass();
     e->stream = fg;
     HIPCHK(e, hipEventRecord(e->ev_bg_done, bg));
     e->bg_pending = true;
@@ -394,9 +406,9 @@ int run_prefix_prefill_any(umgen_engine* e, int B, int P) {
     return e->cfg.precision == UMGEN_PREC_BF16 ? run_prefix_prefill<bf16_t>(e, B, P)
     : e->cfg.precision == UMGEN_PREC_FP16 ? run_prefix_prefill<f16_t>(e, B, P) : run_prefix_prefill<float>(e, B, P);
 }
-int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego) {
-    return e->cfg.precision == UMGEN_PREC_BF16 ? launch_prefix<bf16_t>(e, io, ego)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? launch_prefix<f16_t>(e, io, ego) : launch_prefix<float>(e, io, ego);
+int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg) {
+    return e->cfg.precision == UMGEN_PREC_BF16 ? launch_prefix<bf16_t>(e, io, ego, dbg)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? launch_prefix<f16_t>(e, io, ego, dbg) : launch_prefix<float>(e, io, ego, dbg);
 }
 void gemv_any(umgen_engine* e, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out, long ldo) {
     e->cfg.precision == UMGEN_PREC_BF16 ? gemv<bf16_t>(e, x, ldx, ln_w, W, bias, N, K, M, mode, out, ldo)

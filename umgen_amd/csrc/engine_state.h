@@ -280,7 +280,13 @@ void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
                  float* logp = nullptr);
 int run_prefix_prefill_any(umgen_engine* e, int B, int P);
-int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego);
+// what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
+struct BgPassDebug {
+    int foreground;                              // 1: the pass as stand-alone launches on the engine's stream, synchronised; 0: recorded and uploaded, nothing runs
+    int chunk;                                   // > 0: BgOpHead::chunk of every uploaded op
+    int margin_ticks;                            // >= 0: BgQueue::margin_ticks
+};
+int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg = nullptr);
 void gemv_any(umgen_engine* e, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out, long ldo);
 int build_tables_any(umgen_engine* e);
 
@@ -302,6 +308,7 @@ DecView current_view(const umgen_engine* e);
 void apply_view(umgen_engine* e, const DecView& v);
 DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine::DecLane& ln, int b0);
 int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j);
+int launch_bg_drain(umgen_engine* e, hipStream_t st);   // the launch without an engine part that runs what is left of the background workers' op list
 
 // ---- engine_frame.hip -----------------------------------------------------------------------------------------------
 int run_frame_any(umgen_engine* e, const FrameIO& io);

@@ -33,6 +33,7 @@ class Engine:
         max_cond_frames = min(max_cond_frames, cfg.max_frame_len)
         self.precision = precision
         self.max_batch = max_batch
+        self.max_cond_frames = max_cond_frames
         c = _lib.Config(
             abi_version=4, n_embd=cfg.n_embd, n_head=cfg.n_head, n_ego_tar_layer=cfg.n_ego_tar_layer,
             n_ego_ca_layer=cfg.n_ego_ca_layer, n_map_tar_layer=cfg.n_map_tar_layer, n_box_tar_layer=cfg.n_box_tar_layer,
@@ -345,6 +346,78 @@ class Engine:
     def dbg_oar_epoch(self, epoch: int):
         """Test hook: moves the decode engines' hand-off tag epoch forward (towards its wrap at 0xE0000000); a smaller value is refused."""
         self._check(self.lib.umgen_dbg_oar_epoch(self._h, int(epoch)), "dbg_oar_epoch")
+
+    # -- test hooks on the background pass of the decode engine's workers (csrc/debug_bg.hip) ---
+    STACK_LEN = (SEQ_LEN, 1031, 1693, SEQ_LEN)        # rows per slot of the ego, map, box and TAR stacks (csrc/frame.h stack_len)
+    BG_WORKERS = 128
+
+    def dbg_bg_begin(self, window: Dict[str, np.ndarray], ego, cond_cap: int, foreground: bool, chunk: int = 0, margin_ticks: int = -1) -> np.ndarray:
+        """Test hook: the next frame's pass over the known slots, as launch_prefix runs it behind a frame with this window (mod -> [T, S_mod]; ego: the
+        new frame's 3 pose tokens).  foreground: as stand-alone kernels, synchronised.  Otherwise recorded and uploaded for the workers, nothing runs yet;
+        chunk > 0 / margin_ticks >= 0 override every op's chunk / the margin.  Returns the recorded BgOpHead words int32 [n_ops, 8]
+        (kind, mode, n_units, chunk, i0..i3); empty for a foreground pass."""
+        w = {m: np.ascontiguousarray(np.asarray(window[m]), dtype=np.int32) for m in MOD_ORDER}
+        T = w["pose"].shape[0]
+        for m in MOD_ORDER:
+            if w[m].shape != (T, CONTENT_LEN[m]):
+                raise UMGenError(f"dbg_bg_begin: window[{m}] has shape {w[m].shape}, expected {(T, CONTENT_LEN[m])}")
+        ego = np.ascontiguousarray(np.asarray(ego).reshape(3), dtype=np.int32)
+        heads = np.zeros((4096, 8), np.int32)
+        n = C.c_int32(0)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        self._check(self.lib.umgen_dbg_bg_begin(self._h, T, cond_cap, ip(w["pose"]), ip(w["map"]), ip(w["bbox3d"]), ip(w["image"]), ip(ego), int(foreground),
+                                                int(chunk), int(margin_ticks), C.byref(n), ip(heads), heads.shape[0]), "dbg_bg_begin")
+        return heads[:n.value].copy()
+
+    def dbg_bg_est(self, value: int):
+        """Test hook: every unit-time estimate of the queue = value ticks; 0 restores the host's guesses."""
+        self._check(self.lib.umgen_dbg_bg_est(self._h, int(value)), "dbg_bg_est")
+
+    def dbg_bg_state(self, n_ops: int):
+        """Test hook: (state uint32 [128, 4] -- op, units done | arrived << 31, batch start, - --, ops_done, arrive uint32 [n_ops]) behind a stream sync."""
+        state = np.zeros((self.BG_WORKERS, 4), np.uint32)
+        arrive = np.zeros(max(n_ops, 1), np.uint32)
+        done = C.c_uint32(0)
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        self._check(self.lib.umgen_dbg_bg_state(self._h, up(state), C.byref(done), up(arrive), n_ops), "dbg_bg_state")
+        return state, int(done.value), arrive[:n_ops]
+
+    def dbg_bg_steps(self, n: int, est: int = 0, until_done: bool = True, states: bool = False):
+        """Test hook: up to n decode launches on the pending pass, est != 0 written over every estimate before each; until_done: stops once ops_done
+        is the op count and every worker stands at the end of the list.  Returns (ops_done behind every launch
+        uint32 [n_run], the workers' states behind every launch uint32 [n_run, 128, 4] or None)."""
+        done = np.zeros(max(n, 1), np.uint32)
+        st = np.zeros((max(n, 1), self.BG_WORKERS, 4), np.uint32) if states else None
+        n_run = C.c_int32(0)
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a is not None else None  # noqa: E731
+        self._check(self.lib.umgen_dbg_bg_steps(self._h, n, int(est), int(until_done), up(st), up(done), C.byref(n_run)), "dbg_bg_steps")
+        return done[:n_run.value], (st[:n_run.value] if states else None)
+
+    def dbg_bg_drain(self):
+        """Test hook: the launch without an engine part that runs the pending pass to its end, synchronised."""
+        self._check(self.lib.umgen_dbg_bg_drain(self._h), "dbg_bg_drain")
+
+    def dbg_bg_end(self):
+        """Test hook: empties the queue and forgets the pass: the handle serves ordinary rollouts again."""
+        self._check(self.lib.umgen_dbg_bg_end(self._h), "dbg_bg_end")
+
+    def _tcache_shape(self, stack: int):
+        if not 0 <= stack < 4:
+            raise UMGenError(f"dbg_tcache: stack={stack} (0 ego, 1 map, 2 box, 3 TAR)")
+        return (self.max_batch, self.max_cond_frames, self.STACK_LEN[stack], 2 * self.cfg.n_embd)
+
+    def dbg_tcache_get(self, stack: int, block: int) -> np.ndarray:
+        """Test hook: the slot cache of one (stack, block) as uint16 bits [max_batch, max_cond_frames, S_stack, 2 n_embd]."""
+        out = np.empty(self._tcache_shape(stack), np.uint16)
+        self._check(self.lib.umgen_dbg_tcache(self._h, stack, block, out.ctypes.data_as(C.c_void_p), 0), "dbg_tcache")
+        return out
+
+    def dbg_tcache_put(self, stack: int, block: int, bits: np.ndarray):
+        """Test hook: writes uint16 bits [max_batch, max_cond_frames, S_stack, 2 n_embd] over the slot cache of one (stack, block)."""
+        bits = np.ascontiguousarray(bits)
+        if bits.dtype != np.uint16 or bits.shape != self._tcache_shape(stack):
+            raise UMGenError(f"dbg_tcache_put: bits {bits.dtype} {bits.shape}, expected uint16 {self._tcache_shape(stack)}")
+        self._check(self.lib.umgen_dbg_tcache(self._h, stack, block, bits.ctypes.data_as(C.c_void_p), 1), "dbg_tcache")
 
     # -- measurement ---------------------------------------------------------------------------
     def set_profiling(self, on: bool):
