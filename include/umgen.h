@@ -237,6 +237,21 @@ int umgen_score_detail(umgen_engine *e, int32_t B, int32_t T, const int64_t *pos
                        const int64_t *next_pose, const int64_t *next_map, const int64_t *next_bbox3d, const int64_t *next_image, int32_t topk,
                        float temperature, umgen_score_out *out, umgen_score_detail_out *detail);
 
+/* Ranking futures: C given next frames per scene against ONE history.  Entry (b, c) of every output is bit for bit what
+ *     umgen_score(e, 1, T, window b, candidate (b, c))
+ * returns on the same engine, in every precision, whichever path ran and however the B * C items were chunked.  Only the last history slot of the map /
+ * bbox3d / TAR stacks sees a candidate (the pose shift hands slot T - 1 the candidate's pose), so for T >= 2 the ego net and slots 0 .. T - 2 are
+ * evaluated once per scene and the items, in chunks of at most max_batch, run their last slot against the scene's slot caches, then the BlockOAR pass and
+ * the heads: one history pass plus B * C small passes instead of B * C history passes.  T == 1, slot caches that do not fit in device memory, or
+ * UMGEN_SCORE_SHARE=0 in the environment (read per call) evaluate umgen_score's own pass on replicated windows -- the same bits.
+ * B <= max_batch, T <= max_cond_frames, C >= 1; B * C may exceed max_batch.  Tokens are range-checked like umgen_score's; `out` must not be NULL, any
+ * pointer in it may be.  Like umgen_score, the call leaves nothing an overlapped rollout could reuse in the slot caches. */
+int umgen_score_candidates(umgen_engine *e, int32_t B, int32_t T, int32_t C,
+                           const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,                     /* [B][T][S_mod] */
+                           const int64_t *next_pose, const int64_t *next_map, const int64_t *next_bbox3d, const int64_t *next_image, /* [B][C][S_mod] */
+                           umgen_score_out *out,   /* every array [B][C][S_mod]; any pointer may be NULL */
+                           int32_t *shared_slots); /* NULL, or receives T - 1 when the history slots were evaluated once per scene, 0 on the replicated path */
+
 int umgen_set_profiling(umgen_engine *e, int32_t enable); /* per-launch HIP-event timing of the GEMM / attention kernels and of the
                                                             * decode step's layer kernel(s); profiled frames launch eagerly */
 int umgen_get_timings(umgen_engine *e, umgen_timings *out);

@@ -4,7 +4,10 @@ umgen_frame (2206 decode steps): UMGen_Large, synthetic weights, bf16, one engin
 After one warm-up call each: the median of 5 host-clock calls of Engine.score at B = 1 and B = 8 and of Engine.frame(forced=..., trace=False).
     python tools/score_bench.py [out.json] [--T=20] [--detail]  ->  one JSON line (also written to out.json, default profiles/score_bench.json)
 --detail adds the cost of asking for the score diagnostics (umgen_score_detail at topk 16, one more sweep of the heads): after one warm-up call each, 5
-alternating pairs of Engine.score and Engine.score(detail=True, topk=16) at B = 1 and B = 8, the median of each side."""
+alternating pairs of Engine.score and Engine.score(detail=True, topk=16) at B = 1 and B = 8, the median of each side.
+--candidates C (or --candidates=C) measures only umgen_score_candidates: one scene, C candidate next frames, Engine.score_candidates against
+Engine.score with the window replicated C times (the same numbers, bit for bit), 5 alternating pairs behind one warm-up call each; the result
+is stored under "candidates" in out.json, whose other entries are kept."""
 import json
 import os
 import statistics
@@ -23,6 +26,11 @@ from umgen_amd.weights import synthetic_items  # noqa: E402
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 T = next((int(a[4:]) for a in sys.argv[1:] if a.startswith("--T=")), 20)
 DETAIL = "--detail" in sys.argv[1:]
+CAND = next((int(a[13:]) for a in sys.argv[1:] if a.startswith("--candidates=")), 0)
+if "--candidates" in sys.argv[1:]:
+    k = sys.argv.index("--candidates")
+    CAND = int(sys.argv[k + 1])
+    args.remove(sys.argv[k + 1])
 REPS = 5
 
 
@@ -49,6 +57,45 @@ def alternating_ms(fa, fb):
     return statistics.median(ta), statistics.median(tb)
 
 
+def candidates_bench(e, sc, out):
+    """one scene's window against CAND candidates (the frames behind the other synthetic scenes' windows)"""
+    w = {m: sc[0][m][0, :T] for m in MOD_ORDER}
+    cand = {m: np.stack([sc[i % 8][m][0, T] for i in range(CAND)]) for m in MOD_ORDER}
+    rep_w = {m: np.repeat(w[m][None], CAND, axis=0) for m in MOD_ORDER}
+    got = {}
+    fa = lambda: got.__setitem__("c", e.score_candidates(w, cand))  # noqa: E731
+    fb = lambda: got.__setitem__("r", e.score(rep_w, cand))  # noqa: E731
+    fa()
+    fb()
+    ta, tb = [], []
+    for _ in range(REPS):
+        for fn, ts in ((fa, ta), (fb, tb)):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+    same = all(got["c"]["logp"][m].tobytes() == got["r"]["logp"][m].tobytes() for m in MOD_ORDER)
+    r = {"candidates": CAND, "history_frames": T, "score_candidates_ms": statistics.median(ta), "score_candidates_all_ms": ta,
+         "replicated_score_ms": statistics.median(tb), "replicated_score_all_ms": tb, "replicated_spread_ms": max(tb) - min(tb),
+         "ratio": statistics.median(tb) / statistics.median(ta), "shared_slots": got["c"]["shared_slots"], "same_bytes": same,
+         "best": int(np.argmax(got["c"]["total"]))}
+    if "--profile" in sys.argv[1:]:      # one profiled call: where the time of a candidates call goes (per-launch events serialise the stacks)
+        e.set_profiling(True)
+        t0 = time.perf_counter()
+        e.score_candidates(w, cand)
+        r["profiled_call_ms"] = (time.perf_counter() - t0) * 1e3
+        r["profiled_timings"] = {k: v for k, v in e.timings().items() if k in ("total_ms", "ego_ms", "tar_ms", "oar_ms", "gemm_ms", "gemm_launches", "attn_ms", "attn_launches")}
+        e.set_profiling(False)
+    res = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            res = json.loads(f.read())
+    res["candidates"] = r
+    line = json.dumps(res)
+    print(json.dumps(r))
+    with open(out, "w") as f:
+        f.write(line + "\n")
+
+
 cfg = large_config()
 e = Engine(cfg, precision="bf16", max_batch=8, max_cond_frames=T)
 e.load_state_dict(synthetic_items(cfg, seed=0))
@@ -57,6 +104,10 @@ sc = [synthetic_scene(i, n_frames=T + 1) for i in range(8)]
 window = {m: np.concatenate([s[m][:, :T] for s in sc]) for m in MOD_ORDER}
 frame = {m: np.concatenate([s[m][:, T] for s in sc]) for m in MOD_ORDER}
 one_w, one_f = {m: window[m][0] for m in MOD_ORDER}, {m: frame[m][0] for m in MOD_ORDER}
+if CAND:
+    candidates_bench(e, sc, args[0] if args else os.path.join(ROOT, "profiles", "score_bench.json"))
+    e.close()
+    sys.exit(0)
 
 res = {"config": "UMGen_Large synthetic", "precision": "bf16", "history_frames": T, "reps": REPS}
 res["score_b1_ms"], res["score_b1_all_ms"] = median_ms(lambda: e.score(one_w, one_f))

@@ -650,4 +650,25 @@ template void launch_attn_temporal<float>(hipStream_t, const float*, float*, int
 template void launch_attn_temporal<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, int, int, int, TemporalRange);
 template void launch_attn_temporal<f16_t>(hipStream_t, const f16_t*, f16_t*, int, int, int, int, TemporalRange);
 
+// the last slot of N items over their scenes' cached slots [0, P) (attn_body.h attn_temporal_fan_kernel); heads per workgroup as above
+template <typename T>
+void launch_attn_temporal_fan(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P, const T* cache, int Tcap) {
+    if (BgRecorder* rec = g_bg_rec) { rec->failed = "temporal attention over shared caches"; return; }
+    if (N < 1 || B < 1) return;
+    const int HG = (P + 1 <= kTmax && H % 4 == 0) ? 4 : (H % 2 == 0 ? 2 : 1);
+    const size_t shm = (size_t)(2 * P + 3 * kFanItems(HG)) * HG * kHeadDim * sizeof(float);
+    const dim3 grid((unsigned)((long)B * S * (H / HG))), block(kFanItems(HG) * HG * 4);
+    auto launch = [&](auto kernel) {
+        if (shm > ((size_t)48 << 10) && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
+            return;      // (the refusal stays behind as the thread's last error: the engine fails the call, the test hook returns it)
+        hipLaunchKernelGGL(kernel, grid, block, shm, s, qkv, y, scene_of_item, N, S, H, P, cache, Tcap);
+    };
+    if (HG == 4) launch(attn_temporal_fan_kernel<T, 4>);
+    else if (HG == 2) launch(attn_temporal_fan_kernel<T, 2>);
+    else launch(attn_temporal_fan_kernel<T, 1>);
+}
+template void launch_attn_temporal_fan<float>(hipStream_t, const float*, float*, int, const int*, int, int, int, int, const float*, int);
+template void launch_attn_temporal_fan<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, const int*, int, int, int, int, const bf16_t*, int);
+template void launch_attn_temporal_fan<f16_t>(hipStream_t, const f16_t*, f16_t*, int, const int*, int, int, int, int, const f16_t*, int);
+
 }  // namespace umgen

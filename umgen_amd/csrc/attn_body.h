@@ -354,4 +354,101 @@ __global__ __launch_bounds__(HG * TMAX * 4) void attn_temporal_kernel(const T* _
     attn_temporal_body<T, HG, TMAX>(qkv, y, Tn, S, H, tr, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// Last-slot temporal attention of several ITEMS over one scene's slot cache (umgen_score_candidates: the candidate next frames of a scene share
+// its history).  qkv [N][S][3E] holds slot P of N items, scene_of_item[N] names the scene whose cache [B][Tcap][S][2E] holds every item's slots
+// [0, P) (the items of a scene are contiguous; a scene may have none).  A workgroup owns one (scene, position, group of HG heads): the P cached
+// k | v rows are staged into LDS once and serve all items of the scene, kFanItems(HG) at a time -- their own q | k | v rows sit behind the cached
+// rows, lane = (item, head, 12-wide head-dim part); more items are further rounds of the same workgroup over the same cached rows.  Per query
+// exactly attn_temporal_body's operations in its order (fmaf chain, two quad DPP adds, kScale, sequential online softmax over keys 0 .. P), so y
+// has the bits of the last-slot launch of that kernel on a per-item copy of the cache.  The cache is read only, and only its slots < P.
+// LDS: (2 P + 3 kFanItems) * HG * 48 floats -- at most 66048 B (HG 4, P 31) / 66816 B (HG 2, P 63), inside the 73728 B the temporal kernel requests.
+__host__ __device__ constexpr int kFanItems(int HG) { return HG == 4 ? 8 : 16; }
+template <typename T, int HG>
+__global__ __launch_bounds__(kFanItems(HG) * HG * 4) void attn_temporal_fan_kernel(const T* __restrict__ qkv, T* __restrict__ y,
+                                                                                   const int* __restrict__ scene_of_item, int N, int S, int H, int P,
+                                                                                   const T* __restrict__ cache, int Tcap) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char dyn_lds[];
+    constexpr int W = HG * kHeadDim, G = kFanItems(HG), NT = G * HG * 4, chunks_per_seg = W / 8;
+    float* const ck = reinterpret_cast<float*>(dyn_lds);   // [P][2][W]: k | v of the cached slots
+    float* const own = ck + P * 2 * W;                     // [G][3][W]: q | k | v of the round's items
+    const int tid = (int)threadIdx.x;
+    const long blk = (long)blockIdx.x;
+    const int hg = (int)(blk % (H / HG));
+    const long bs = blk / (H / HG);          // b*S + s
+    const int s = (int)(bs % S);
+    const int b = (int)(bs / S);
+    const int E = H * kHeadDim;
+    int first = 0, cnt = 0;                  // the scene's items [first, first + cnt)
+    for (int i = 0; i < N; ++i)
+        if (scene_of_item[i] == b) {
+            if (!cnt) first = i;
+            ++cnt;
+        }
+    if (!cnt) return;
+    for (int c = tid; c < P * 2 * chunks_per_seg; c += NT) {
+        const int cc = c % chunks_per_seg, seg = (c / chunks_per_seg) & 1, t = c / (2 * chunks_per_seg);
+        float v8[8];
+        load8(cache + (((long)b * Tcap + t) * S + s) * 2L * E + (long)seg * E + hg * W + cc * 8, v8);
+        float* d = ck + ((t * 2 + seg) * W + cc * 8);
+        *reinterpret_cast<float4*>(d) = make_float4(v8[0], v8[1], v8[2], v8[3]);
+        *reinterpret_cast<float4*>(d + 4) = make_float4(v8[4], v8[5], v8[6], v8[7]);
+    }
+    // 4 lanes per (item, head): lane part p owns head-dim slice [12p, 12p+12)
+    const int part = tid & 3, il = (tid >> 2) % G, hl = tid / (4 * G);
+    for (int i0 = 0; i0 < cnt; i0 += G) {
+        const int ni = min(G, cnt - i0);
+        if (i0) __syncthreads();             // the previous round's rows are read until here
+        for (int c = tid; c < ni * 3 * chunks_per_seg; c += NT) {
+            const int cc = c % chunks_per_seg, seg = (c / chunks_per_seg) % 3, it = c / (3 * chunks_per_seg);
+            float v8[8];
+            load8(qkv + ((long)(first + i0 + it) * S + s) * 3L * E + (long)seg * E + hg * W + cc * 8, v8);
+            float* d = own + ((it * 3 + seg) * W + cc * 8);
+            *reinterpret_cast<float4*>(d) = make_float4(v8[0], v8[1], v8[2], v8[3]);
+            *reinterpret_cast<float4*>(d + 4) = make_float4(v8[4], v8[5], v8[6], v8[7]);
+        }
+        __syncthreads();
+        if (il >= ni) continue;              // (whole quads: the DPP adds below stay inside a query's 4 lanes)
+        float q[12], o[12];
+        const float* qp = own + (il * 3 + 0) * W + hl * kHeadDim + part * 12;
+#pragma unroll
+        for (int d = 0; d < 12; d += 4) {
+            const float4 q4 = *reinterpret_cast<const float4*>(qp + d);
+            q[d] = q4.x; q[d + 1] = q4.y; q[d + 2] = q4.z; q[d + 3] = q4.w;
+            o[d] = 0.f; o[d + 1] = 0.f; o[d + 2] = 0.f; o[d + 3] = 0.f;
+        }
+        float m = -INFINITY, l = 0.f;
+        for (int tk = 0; tk <= P; ++tk) {
+            const float* kp = (tk < P ? ck + (tk * 2) * W : own + (il * 3 + 1) * W) + hl * kHeadDim + part * 12;
+            const float* vp = kp + W;
+            float a = 0.f;
+#pragma unroll
+            for (int d = 0; d < 12; d += 4) {
+                const float4 k4 = *reinterpret_cast<const float4*>(kp + d);
+                a = fmaf(q[d], k4.x, a); a = fmaf(q[d + 1], k4.y, a); a = fmaf(q[d + 2], k4.z, a); a = fmaf(q[d + 3], k4.w, a);
+            }
+            a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0xB1, 0xf, 0xf, true));
+            a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x4E, 0xf, 0xf, true));
+            a *= kScale;
+            const float mn = fmaxf(m, a);
+            const float alpha = sizeof(T) == 2 ? __expf(m - mn) : expf(m - mn);
+            const float p = sizeof(T) == 2 ? __expf(a - mn) : expf(a - mn);
+            m = mn;
+            l = l * alpha + p;
+#pragma unroll
+            for (int d = 0; d < 12; d += 4) {
+                const float4 v4 = *reinterpret_cast<const float4*>(vp + d);
+                o[d] = fmaf(p, v4.x, o[d] * alpha); o[d + 1] = fmaf(p, v4.y, o[d + 1] * alpha);
+                o[d + 2] = fmaf(p, v4.z, o[d + 2] * alpha); o[d + 3] = fmaf(p, v4.w, o[d + 3] * alpha);
+            }
+        }
+        const float inv = 1.0f / l;
+        T* yp = y + ((long)(first + i0 + il) * S + s) * (long)E + (hg * HG + hl) * kHeadDim + part * 12;
+#pragma unroll
+        for (int d = 0; d < 12; d += 4) {
+            float t4[4] = {o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv};
+            store4(yp + d, t4);
+        }
+    }
+}
+
 }  // namespace umgen

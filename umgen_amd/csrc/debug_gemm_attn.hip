@@ -220,6 +220,32 @@ int umgen_dbg_attn_temporal_range(int prec, const void* qkv, int B, int Tn, int 
     return down(y, dY, Rn * E * es);
 }
 
+// ONE launch_attn_temporal_fan call (kernels.h): qkv [N][S][3E] holds slot P of N items, item i reads the k | v rows of slots [0, P) from block
+// scene_of_item[i] of cache [B][Tcap][S][2E].  cache and y [N][S][E] are in / out: the cache must come back as it went in, and whatever the launch
+// leaves alone of y keeps the caller's fill.  The scene list is checked here (in range, every scene's items contiguous) before anything is launched.
+int umgen_dbg_attn_temporal_fan(int prec, const void* qkv, int N, const int32_t* scene_of_item, int B, int S, int H, int P, int Tcap, void* cache, void* y) {
+    if (prec < 0 || prec > 2 || !qkv || !y || !cache || !scene_of_item || N < 1 || B < 1 || S < 1 || H < 1 || P < 1 || P + 1 > 2 * kTemporalSlots || Tcap < P)
+        return UMGEN_E_INVALID;
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < N; ++i) {
+        const int sc = scene_of_item[i];
+        if (sc < 0 || sc >= B || (seen[sc] && scene_of_item[i - 1] != sc)) return UMGEN_E_INVALID;
+        seen[sc] = 1;
+    }
+    const int E = H * kHeadDim;
+    const size_t es = prec ? 2 : 4, Rn = (size_t)N * S, csz = (size_t)B * Tcap * S * 2 * E * es;
+    Scratch s;
+    const void* dQ = s.in(qkv, Rn * 3 * E * es);
+    const int* dS = s.in(scene_of_item, (size_t)N * 4);
+    void* dY = s.inout(y, Rn * E * es);
+    void* dC = s.inout(cache, csz);
+    if (s.rc) return s.rc;
+    by_prec(prec, [&](auto t) { typedef decltype(t) TT; launch_attn_temporal_fan<TT>(nullptr, (const TT*)dQ, (TT*)dY, N, dS, B, S, H, P, (const TT*)dC, Tcap); });
+    if (int rc = s.finish()) return rc;
+    if (down(cache, dC, csz)) return UMGEN_E_HIP;
+    return down(y, dY, Rn * E * es);
+}
+
 // decode-style attention: q [NQ][E] fp32, kv [L][2E] (k | v) of dtype bf16/fp32 shared by all queries -> y [NQ][E] fp32
 // (partial pass + the combine that normally runs in the projection prologue, here through an identity projection)
 int umgen_dbg_attn_decode(int bf16, const float* q, const void* kv, int NQ, int L, int H, float* y) {

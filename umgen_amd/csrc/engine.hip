@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score(_detail) and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
+// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
 #include "engine_state.h"
 
@@ -210,6 +210,49 @@ int umgen_score_detail(umgen_engine* e, int32_t B, int32_t T, const int64_t* pos
                        float temperature, umgen_score_out* out, umgen_score_detail_out* detail) {
     if (e && !detail) return e->fail(UMGEN_E_INVALID, "null detail struct");
     return score_call(e, B, T, pose, map, bbox3d, image, next_pose, next_map, next_bbox3d, next_image, out, detail, topk, temperature);
+}
+
+// umgen_score_candidates: C given next frames per scene against one history (engine_frame.hip run_score_candidates)
+int umgen_score_candidates(umgen_engine* e, int32_t B, int32_t T, int32_t C, const int64_t* pose, const int64_t* map, const int64_t* bbox3d,
+                           const int64_t* image, const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image,
+                           umgen_score_out* out, int32_t* shared_slots) {
+    if (!e) return UMGEN_E_INVALID;
+    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
+    if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
+    if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
+    if (C < 1) return e->fail(UMGEN_E_INVALID, "C=%d: at least one candidate per scene", C);
+    if (!out) return e->fail(UMGEN_E_INVALID, "null output struct");
+    if (!pose || !map || !bbox3d || !image || !next_pose || !next_map || !next_bbox3d || !next_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
+    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
+    if (int rc = check_scene_tokens(e, (size_t)B * T, pose, map, bbox3d, image)) return rc;
+    if (int rc = check_scene_tokens(e, (size_t)B * C, next_pose, next_map, next_bbox3d, next_image)) {
+        e->err = "candidate frames: " + e->err;
+        return rc;
+    }
+    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
+    const int64_t* in[4] = {pose, map, bbox3d, image};
+    const int64_t* nx[4] = {next_pose, next_map, next_bbox3d, next_image};
+    const size_t N = (size_t)B * C;
+    std::vector<int> win[4], next(N * kTokPerFrame);
+    for (int m = 0; m < 4; ++m) {
+        win[m].resize((size_t)B * T * S[m]);
+        for (size_t i = 0; i < win[m].size(); ++i) win[m][i] = (int)in[m][i];
+        for (size_t it = 0; it < N; ++it)
+            for (int i = 0; i < S[m]; ++i) next[it * kTokPerFrame + off[m] + i] = (int)nx[m][it * S[m] + i];
+    }
+    std::vector<float> logp(N * kTokPerFrame);
+    std::vector<int> arg(N * kTokPerFrame);
+    ScoreCandIO sc{B, T, C, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), logp.data(), arg.data(), 0};
+    if (int rc = run_score_candidates_any(e, sc)) return rc;
+    float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
+    int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
+    for (int m = 0; m < 4; ++m)
+        for (size_t it = 0; it < N; ++it) {
+            if (lo[m]) memcpy(lo[m] + it * S[m], &logp[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(float));
+            if (ao[m]) memcpy(ao[m] + it * S[m], &arg[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(int32_t));
+        }
+    if (shared_slots) *shared_slots = sc.shared_slots;
+    return UMGEN_OK;
 }
 
 // UMGen.inference (UMGen.py:1542-1671)

@@ -1,7 +1,7 @@
 // One frame, UMGen._inference: run_frame<T> as a sequence of stages -- background pass, uploads, ego net and pose shift, decode state, the
 // stacks, first input and prefix pass, the lane loop or the single-stream step loop, drain, download, checks, bookkeeping -- run_score<T>,
-// the scoring pass of umgen_score built from the same stages, and run_frame_any / run_score_any, which pick the precision and clean up
-// behind a failed call.
+// the scoring pass of umgen_score built from the same stages, run_score_candidates<T>, which scores several next frames per scene on one pass
+// over the history, and run_frame_any / run_score_any / run_score_candidates_any, which pick the precision and clean up behind a failed call.
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -529,6 +529,33 @@ int check_frame_results(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     return 0;
 }
 
+// a profiled call's per-launch events (gemm_timed, tar_sub, the decode loops) into the timings
+void fold_launch_events(umgen_engine* e) {
+    float ms;
+    for (size_t i = 0; i < e->gemm_ev_used; ++i) {
+        hipEventElapsedTime(&ms, e->gemm_ev[i].first, e->gemm_ev[i].second);
+        e->tm.gemm_ms += ms;
+    }
+    e->tm.gemm_launches += (int64_t)e->gemm_ev_used;
+    e->tm.gemm_flops += e->gemm_flops_pending;
+    e->gemm_ev_used = 0;
+    e->gemm_flops_pending = 0;
+    for (size_t i = 0; i < e->attn_ev_used; ++i) {
+        hipEventElapsedTime(&ms, e->attn_ev[i].first, e->attn_ev[i].second);
+        e->tm.attn_ms += ms;
+    }
+    for (size_t i = 0; i < e->layer_ev_used; ++i) {
+        hipEventElapsedTime(&ms, e->layer_ev[i].first, e->layer_ev[i].second);
+        e->tm.layers_ms += ms;
+    }
+    e->tm.layers_launches += (int64_t)e->layer_ev_used;
+    e->layer_ev_used = 0;
+    e->tm.attn_launches += (int64_t)e->attn_ev_used;
+    e->tm.attn_flops += e->attn_flops_pending;
+    e->attn_ev_used = 0;
+    e->attn_flops_pending = 0;
+}
+
 void frame_bookkeeping(umgen_engine* e, const FrameIO& io, const FrameCtx& ctx) {
     const int E = e->E, B = io.B, n_lanes = ctx.n_lanes;
     const bool use_px = ctx.use_px, batched = ctx.batched, wide = ctx.wide;
@@ -550,30 +577,7 @@ void frame_bookkeeping(umgen_engine* e, const FrameIO& io, const FrameCtx& ctx) 
     e->tm.decode_lanes = batched ? n_lanes : 0;
     e->tm.engine_fallback = e->eng_fallback ? 1 : 0;
     if (use_px) e->tm.overlapped_frames += 1;
-    if (e->profiling) {
-        for (size_t i = 0; i < e->gemm_ev_used; ++i) {
-            hipEventElapsedTime(&ms, e->gemm_ev[i].first, e->gemm_ev[i].second);
-            e->tm.gemm_ms += ms;
-        }
-        e->tm.gemm_launches += (int64_t)e->gemm_ev_used;
-        e->tm.gemm_flops += e->gemm_flops_pending;
-        e->gemm_ev_used = 0;
-        e->gemm_flops_pending = 0;
-        for (size_t i = 0; i < e->attn_ev_used; ++i) {
-            hipEventElapsedTime(&ms, e->attn_ev[i].first, e->attn_ev[i].second);
-            e->tm.attn_ms += ms;
-        }
-        for (size_t i = 0; i < e->layer_ev_used; ++i) {
-            hipEventElapsedTime(&ms, e->layer_ev[i].first, e->layer_ev[i].second);
-            e->tm.layers_ms += ms;
-        }
-        e->tm.layers_launches += (int64_t)e->layer_ev_used;
-        e->layer_ev_used = 0;
-        e->tm.attn_launches += (int64_t)e->attn_ev_used;
-        e->tm.attn_flops += e->attn_flops_pending;
-        e->attn_ev_used = 0;
-        e->attn_flops_pending = 0;
-    }
+    if (e->profiling) fold_launch_events(e);
     // algorithmic HBM bytes of this frame's decode steps: weights once per step + KV read + KV write
     {
         const double w_layer = (double)e->tsz * (12.0 * E * E) + 4.0 * (6.0 * E);   // 3E*E + E*E + 4E*E + 4E*E weights, biases/LN
@@ -646,20 +650,45 @@ int ensure_score_detail(umgen_engine* e) {
     return 0;
 }
 
+// block b0 of the detail results: topk per row in the lists
+ScoreDetailOut score_detail_out(const umgen_engine* e, const ScoreDetailIO* dt, long b0) {
+    return ScoreDetailOut{e->det_rank + b0, e->det_mass + b0, e->det_ent + b0, e->det_tok + b0 * dt->topk, e->det_tlp + b0 * dt->topk, dt->topk,
+                          1.0f / dt->temperature};
+}
+
+// the scoring head on the rows run_prefix_prefill left in X for B scenes (row j predicts the token at position j, targets in d_tokens): the map,
+// bbox3d and image blocks of score_logp / score_arg, each [B][S_mod]; with dt the detail sweep of the same rows
+template <typename T>
+int score_heads(umgen_engine* e, hipStream_t st, int B, const ScoreDetailIO* dt) {
+    const int E = e->E;
+    const int c0[3] = {kMapC0, kBoxC0, kImgC0}, n[3] = {kNMap, kNBox, kNImg}, off[3] = {kOffMap, kOffBox, kOffImg};
+    const int V[3] = {e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
+    const void* head[3] = {e->head_ar_map, e->head_ar_box, e->head_ar_img};
+    for (int m = 0; m < 3; ++m) {
+        HeadNllArgs a{};
+        a.x = e->X + (long)c0[m] * E; a.ldx = E; a.rows_per_group = n[m]; a.group_stride = (long)(kSeq - 1) * E;
+        a.ln_w = e->ln_oar; a.W = head[m]; a.V = V[m]; a.K = E; a.M = B * n[m];
+        a.target = e->d_tokens + off[m]; a.target_group_stride = kTokPerFrame;
+        a.part = e->score_part; a.logp = e->score_logp + (long)B * off[m]; a.argmax = e->score_arg + (long)B * off[m];
+        if (dt) {
+            const long nr = (long)e->cfg.max_batch * kNMap;
+            a.lse = e->det_row; a.tlogit = e->det_row + nr; a.rmax = e->det_row + 2 * nr; a.sumexp = e->det_row + 3 * nr;
+        }
+        HIPCHK(e, launch_head_nll<T>(st, a));
+        if (dt) HIPCHK(e, launch_head_detail<T>(st, HeadDetailArgs{a, e->det_part, score_detail_out(e, dt, (long)B * off[m])}));
+    }
+    return 0;
+}
+
 template <typename T>
 int run_score(umgen_engine* e, const ScoreIO& sc) {
     hipStream_t const fg = e->stream;
     e->launch_status = hipSuccess;
     (void)hipGetLastError();
     struct RestoreStream { umgen_engine* e; hipStream_t s; ~RestoreStream() { e->stream = s; e->set_work(e->w_main); } } restore{e, fg};
-    const int E = e->E, B = sc.B;
+    const int B = sc.B;
     const ScoreDetailIO* dt = sc.detail;
     if (dt) { if (int rc = ensure_score_detail(e)) return rc; }
-    // block b0 of the detail results: topk per row in the lists
-    auto detail_out = [&](long b0) {
-        return ScoreDetailOut{e->det_rank + b0, e->det_mass + b0, e->det_ent + b0, e->det_tok + b0 * dt->topk, e->det_tlp + b0 * dt->topk, dt->topk,
-                              1.0f / dt->temperature};
-    };
     // the ego net's sampler runs and is overridden by the given pose (run_ego's forced form): any valid parameters do
     static const umgen_sampling smp{UMGEN_SAMPLE_TOPK, 1, 1, 1, 1.f, 1.f, 1.f, 0, 0, 0, nullptr};
     const FrameIO io{B, sc.T, sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &smp, nullptr, nullptr};
@@ -677,26 +706,11 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
     float* lp = e->score_logp;
     int* am = e->score_arg;
     launch_logits_nll(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, lp, am, nullptr, nullptr);
-    if (dt) HIPCHK(e, launch_logits_detail(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, detail_out(0)));
+    if (dt) HIPCHK(e, launch_logits_detail(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, score_detail_out(e, dt, 0)));
     HIPCHK(e, hipMemcpyAsync(e->d_tokens, sc.next, (size_t)B * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
     if (int rc = run_stacks(e, io, ctx)) return rc;
     if (int rc = run_prefix_prefill_any(e, B, kSeq)) return rc;      // rows 0 .. 2205 of every scene in X; row j predicts the token at position j
-    const int c0[3] = {kMapC0, kBoxC0, kImgC0}, n[3] = {kNMap, kNBox, kNImg}, off[3] = {kOffMap, kOffBox, kOffImg};
-    const int V[3] = {e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
-    const void* head[3] = {e->head_ar_map, e->head_ar_box, e->head_ar_img};
-    for (int m = 0; m < 3; ++m) {
-        HeadNllArgs a{};
-        a.x = e->X + (long)c0[m] * E; a.ldx = E; a.rows_per_group = n[m]; a.group_stride = (long)(kSeq - 1) * E;
-        a.ln_w = e->ln_oar; a.W = head[m]; a.V = V[m]; a.K = E; a.M = B * n[m];
-        a.target = e->d_tokens + off[m]; a.target_group_stride = kTokPerFrame;
-        a.part = e->score_part; a.logp = lp + (long)B * off[m]; a.argmax = am + (long)B * off[m];
-        if (dt) {
-            const long nr = (long)e->cfg.max_batch * kNMap;
-            a.lse = e->det_row; a.tlogit = e->det_row + nr; a.rmax = e->det_row + 2 * nr; a.sumexp = e->det_row + 3 * nr;
-        }
-        HIPCHK(e, launch_head_nll<T>(st, a));
-        if (dt) HIPCHK(e, launch_head_detail<T>(st, HeadDetailArgs{a, e->det_part, detail_out((long)B * off[m])}));
-    }
+    if (int rc = score_heads<T>(e, st, B, dt)) return rc;
     HIPCHK(e, hipMemcpyAsync(sc.logp, lp, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(sc.argmax, am, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
     if (dt) {
@@ -710,6 +724,141 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
         }
     }
     HIPCHK(e, hipStreamSynchronize(st));
+    const hipError_t le = e->launch_status != hipSuccess ? e->launch_status : hipGetLastError();
+    e->launch_status = hipSuccess;
+    if (le != hipSuccess) return e->fail(UMGEN_E_HIP, "a kernel launch of this scoring pass was refused: %s", hipGetErrorString(le));
+    return 0;
+}
+
+// umgen_score_candidates: C given next frames per scene against one history.  Of run_score's work only the last history slot of the map / box / TAR
+// stacks (the pose shift hands slot t the pose of frame t + 1, so slot T - 1 carries the candidate's pose), the conditioning rows, the BlockOAR pass and
+// the heads depend on the candidate: the ego net (it reads the unshifted window) and slots [0, T - 1) of the three stacks run once per scene, the
+// latter in cache mode 1 -- the pass launch_prefix records for the background, as stand-alone launches -- and the items (b, c), in chunks of at most
+// max_batch, run their last slot against the scenes' slot caches (run_stack cache mode 5).  Every kernel's row arithmetic is that of run_score, so
+// entry (b, c) has the bits of umgen_score on window b and candidate (b, c).  T == 1, slot caches that do not fit and UMGEN_SCORE_SHARE=0 take
+// run_score itself on replicated windows, chunk by chunk.
+template <typename T>
+int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
+    const int E = e->E, B = sc.B, Tn = sc.T, C = sc.C, P = sc.T - 1, Bm = e->cfg.max_batch;
+    const long N = (long)B * C;
+    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
+    const int* win[4] = {sc.pose, sc.map, sc.box, sc.img};
+    const char* she = getenv("UMGEN_SCORE_SHARE");      // (read per call: the tests compare both forms in one process)
+    const bool share = Tn >= 2 && !(she && she[0] == '0') && ensure_tcache(e);
+    sc.shared_slots = share ? P : 0;
+    // host staging of a chunk (the asynchronous copies read it until the chunk's synchronisation)
+    std::vector<int> rep[4], cand_pose, item_scene, pshift, am;
+    std::vector<float> pdiff, lp;
+    auto replicate = [&](long i0, int n) {               // the windows of items [i0, i0 + n): [n][T][S_mod]
+        for (int m = 0; m < 4; ++m) {
+            rep[m].resize((size_t)n * Tn * S[m]);
+            for (int i = 0; i < n; ++i)
+                memcpy(&rep[m][(size_t)i * Tn * S[m]], win[m] + (size_t)((i0 + i) / C) * Tn * S[m], (size_t)Tn * S[m] * sizeof(int));
+        }
+    };
+    auto copy_out = [&](long i0, int n) {                // the chunk's blocks pose | map | bbox3d | image, each [n][S_mod] -> [b][c][2199]
+        for (int m = 0; m < 4; ++m)
+            for (int i = 0; i < n; ++i) {
+                memcpy(sc.logp + (size_t)(i0 + i) * kTokPerFrame + off[m], &lp[(size_t)n * off[m] + (size_t)i * S[m]], (size_t)S[m] * sizeof(float));
+                memcpy(sc.argmax + (size_t)(i0 + i) * kTokPerFrame + off[m], &am[(size_t)n * off[m] + (size_t)i * S[m]], (size_t)S[m] * sizeof(int));
+            }
+    };
+    if (!share) {
+        for (long i0 = 0; i0 < N; i0 += Bm) {
+            const int n = (int)std::min<long>(Bm, N - i0);
+            replicate(i0, n);
+            lp.resize((size_t)n * kTokPerFrame);
+            am.resize((size_t)n * kTokPerFrame);
+            const ScoreIO one{n, Tn, rep[0].data(), rep[1].data(), rep[2].data(), rep[3].data(), sc.next + (size_t)i0 * kTokPerFrame, lp.data(), am.data()};
+            if (int rc = run_score<T>(e, one)) return rc;
+            copy_out(i0, n);
+        }
+        return 0;
+    }
+    hipStream_t const fg = e->stream;
+    e->launch_status = hipSuccess;
+    (void)hipGetLastError();
+    struct RestoreStream { umgen_engine* e; hipStream_t s; ~RestoreStream() { e->stream = s; e->set_work(e->w_main); } } restore{e, fg};
+    // the ego net's sampler runs and its tokens are not used: any valid parameters do
+    static const umgen_sampling smp{UMGEN_SAMPLE_TOPK, 1, 1, 1, 1.f, 1.f, 1.f, 0, 0, 0, nullptr};
+    const FrameIO io{B, Tn, sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &smp, nullptr, nullptr};
+    FrameCtx ctx{};
+    ctx.fg = fg;
+    ctx.st = fg;
+    ctx.sp = SamplerParams{smp.method, smp.top_k, smp.top_k_map, smp.topk_image, smp.p, smp.p_map, smp.temperature, 0, 0, 0};
+    e->px.valid = false;                 // the passes below overwrite the slot caches and the stacks' workspaces
+    if (int rc = settle_background_pass(e, io, ctx)) return rc;
+    hipStream_t const st = ctx.st;
+    if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
+    // a profiled call (umgen_set_profiling) drains the stream at every stage boundary and books host time: ego_ms the ego net, tar_ms the history pass and
+    // the items' last-slot passes, oar_ms the BlockOAR pass and the heads
+    auto t_last = std::chrono::steady_clock::now();
+    auto stage = [&](double& acc) {
+        if (!e->profiling) return;
+        (void)hipStreamSynchronize(st);
+        const auto now = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(now - t_last).count();
+        acc += ms;
+        e->tm.total_ms += ms;
+        t_last = now;
+    };
+    double uploads_ms = 0;               // (in total_ms only)
+    stage(uploads_ms);
+    // once per scene: the ego net on the whole window (its three head_ego rows stay in e->logits [3 B][pose_vocab]) ...
+    run_ego_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, ctx.sp, 0, false, nullptr, 0);
+    stage(e->tm.ego_ms);
+    // ... and slots [0, T - 1) of the three stacks, their temporal k | v rows into the slot caches (slot T - 1 of the shifted pose is not read)
+    const std::vector<int> no_pose((size_t)B * 3, 0);
+    decode_pose_shift(sc.pose, no_pose.data(), B, Tn, ctx.pshift, ctx.pdiff);
+    HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, ctx.pshift.data(), ctx.pshift.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->pose_diff, ctx.pdiff.data(), ctx.pdiff.size() * 4, hipMemcpyHostToDevice, st));
+    const WindowTokens wh{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, Tn, 0};
+    run_stack_any(e, STACK_MAP, wh, 1);
+    run_stack_any(e, STACK_BOX, wh, 1);
+    run_stack_any(e, STACK_TAR, wh, 1);
+    stage(e->tm.tar_ms);
+    e->fan_scenes = B;
+    for (long i0 = 0; i0 < N; i0 += Bm) {
+        const int n = (int)std::min<long>(Bm, N - i0);
+        const int* next = sc.next + (size_t)i0 * kTokPerFrame;
+        replicate(i0, n);
+        cand_pose.resize((size_t)n * 3);
+        item_scene.resize(n);
+        for (int i = 0; i < n; ++i) {
+            item_scene[i] = (int)((i0 + i) / C);
+            for (int a = 0; a < 3; ++a) cand_pose[(size_t)i * 3 + a] = next[(size_t)i * kTokPerFrame + a];
+        }
+        decode_pose_shift(rep[0].data(), cand_pose.data(), n, Tn, pshift, pdiff);      // slot T - 1 of item (b, c): the candidate's pose
+        HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, pshift.data(), pshift.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->pose_diff, pdiff.data(), pdiff.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_map, rep[1].data(), rep[1].size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_box, rep[2].data(), rep[2].size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_img, rep[3].data(), rep[3].size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->d_tokens, next, (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
+        // a candidate's pose: a lookup in its scene's rows (the bits depend on the row and the target only)
+        for (int i = 0; i < n; ++i)
+            launch_logits_nll(st, e->logits + (long)item_scene[i] * 3 * e->cfg.pose_vocab, e->cfg.pose_vocab, e->cfg.pose_vocab, 3, e->d_tokens + (long)i * kTokPerFrame,
+                              kNPose, kTokPerFrame, e->score_logp + (long)i * 3, e->score_arg + (long)i * 3, nullptr, nullptr);
+        const WindowTokens wl{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, 1, Tn, P};
+        run_stack_any(e, STACK_MAP, wl, 5);
+        launch_cond_rows(st, STACK_MAP, n, 1, E, e->X, e->ln_map_tar, e->warped_last, e->cond);
+        run_stack_any(e, STACK_BOX, wl, 5);
+        launch_cond_rows(st, STACK_BOX, n, 1, E, e->X, e->ln_box_tar, nullptr, e->cond);
+        run_stack_any(e, STACK_TAR, wl, 5);
+        launch_cond_rows(st, STACK_TAR, n, 1, E, e->X, e->ln_tar, nullptr, e->cond);
+        stage(e->tm.tar_ms);
+        if (int rc = run_prefix_prefill_any(e, n, kSeq)) return rc;
+        if (int rc = score_heads<T>(e, st, n, nullptr)) return rc;
+        lp.resize((size_t)n * kTokPerFrame);
+        am.resize((size_t)n * kTokPerFrame);
+        HIPCHK(e, hipMemcpyAsync(lp.data(), e->score_logp, (size_t)n * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(am.data(), e->score_arg, (size_t)n * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        stage(e->tm.oar_ms);
+        copy_out(i0, n);
+    }
+    if (e->profiling) fold_launch_events(e);
     const hipError_t le = e->launch_status != hipSuccess ? e->launch_status : hipGetLastError();
     e->launch_status = hipSuccess;
     if (le != hipSuccess) return e->fail(UMGEN_E_HIP, "a kernel launch of this scoring pass was refused: %s", hipGetErrorString(le));
@@ -744,6 +893,13 @@ namespace umgen {
 int run_score_any(umgen_engine* e, const ScoreIO& sc) {
     const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_score<bf16_t>(e, sc)
                  : e->cfg.precision == UMGEN_PREC_FP16 ? run_score<f16_t>(e, sc) : run_score<float>(e, sc);
+    if (rc != UMGEN_OK) drain_failed_frame(e);
+    return rc;
+}
+
+int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc) {
+    const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_score_candidates<bf16_t>(e, sc)
+                 : e->cfg.precision == UMGEN_PREC_FP16 ? run_score_candidates<f16_t>(e, sc) : run_score_candidates<float>(e, sc);
     if (rc != UMGEN_OK) drain_failed_frame(e);
     return rc;
 }

@@ -469,6 +469,7 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dalloc(e, &e->d_counters, (size_t)8)) return rc;
     if (int rc = dalloc(e, &e->d_nboxes, Bm)) return rc;
     if (int rc = dalloc(e, &e->d_ego_tok, Bm * 3)) return rc;
+    if (int rc = dalloc(e, &e->d_item_scene, Bm)) return rc;
     if (int rc = dalloc(e, &e->d_control, Bm * kSlots)) return rc;
     if (int rc = dalloc(e, &e->d_boxes, Bm * 64 * 10)) return rc;
     if (int rc = dalloc(e, &e->d_seeds, Bm)) return rc;

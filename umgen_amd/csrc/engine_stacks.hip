@@ -80,7 +80,8 @@ void linear_resid(umgen_engine* e, const void* W, const float* bias, int N, int 
 //   tail 0: all rows;  tail 1 (temporal sub-block): LN + k|v of all rows, q / attention output / projection / MLP of the last frame;
 //   tail 2 (the spatial sub-block behind it): the whole sub-block on the last frame's rows.
 template <typename T>
-void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal, TemporalRange tr = TemporalRange{0, nullptr, 0, 0}, int tail = 0) {
+void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal, TemporalRange tr = TemporalRange{0, nullptr, 0, 0}, int tail = 0,
+             bool fan = false) {
     const int E = e->E, H = e->H;
     const long R = (long)B * Tn * S;
     T* A = reinterpret_cast<T*>(e->A);
@@ -127,7 +128,9 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
             for (const Range& r : rest) linear_store<T>(e, Wqkv, w.attn.bqkv, E, E, A + r.row0 * E, r.rows, QKV + r.row0 * 3 * E, 3L * E, 0);
             tr.q0 = tr.t0 + Tn - 1;
         }
-        launch_attn_temporal<T>(e->stream, QKV, A, B, Tn, S, H, tr);
+        // fan: the B rows-of-one-slot are items that share their scenes' cached slots [0, tr.t0) (cache mode 5 of run_stack)
+        if (fan) launch_attn_temporal_fan<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<const T*>(tr.cache), tr.Tcap);
+        else launch_attn_temporal<T>(e->stream, QKV, A, B, Tn, S, H, tr);
     } else if (tail == 0) {
         launch_layernorm<T>(e->stream, e->X, E, R, E, w.ln_a, A);
         spatial_attention(0, B * Tn);
@@ -148,7 +151,9 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
 
 // cache_mode: 0 = one pass over the whole window; 1 = prefix pass (slots [0, w.T), k | v appended to the slot caches);
 // 2 = last-slot pass (slots [w.t0, w.t0 + w.T) against the caches); 3 = whole window like 0, and its k | v rows are left in the slot
-// caches for a longer window that follows; 4 = last-slot pass like 2 that appends its own k | v rows (the window keeps growing)
+// caches for a longer window that follows; 4 = last-slot pass like 2 that appends its own k | v rows (the window keeps growing);
+// 5 = last-slot pass like 2 of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of e->fan_scenes scenes: item i reads the slots [0, P) of scene
+// e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window)
 template <typename T>
 void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode = 0) {
     const int S = stack_len(stack);
@@ -158,12 +163,12 @@ void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode
     static const bool no_tail = getenv("UMGEN_NO_TAIL") != nullptr;   // measurement: evaluate every block on every frame like the reference
     for (size_t i = 0; i < e->stk[stack].size(); ++i) {
         const TarW& blk = e->stk[stack][i];
-        TemporalRange tr{w.t0, cache_mode ? e->tcache[stack][i] : nullptr, e->cfg.max_cond_frames, (cache_mode == 1 || cache_mode >= 3) ? 1 : 0};
+        TemporalRange tr{w.t0, cache_mode ? e->tcache[stack][i] : nullptr, e->cfg.max_cond_frames, (cache_mode == 1 || cache_mode == 3 || cache_mode == 4) ? 1 : 0};
         // the final block's tail on the last frame only (f-3): whole-window passes with more than one slot (the temporal sub-block still
         // evaluates the k | v rows of every slot, so a pass that fills the slot caches keeps the shortcut)
         const bool last = i + 1 == e->stk[stack].size() && (cache_mode == 0 || cache_mode == 3) && w.T > 1 && !no_tail;
         tar_sub<T>(e, blk.sub[0], w.B, w.T, S, false);
-        tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0);
+        tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_mode == 5);
         tar_sub<T>(e, blk.sub[2], w.B, w.T, S, false, TemporalRange{0, nullptr, 0, 0}, last ? 2 : 0);
     }
 }

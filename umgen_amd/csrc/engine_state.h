@@ -84,6 +84,10 @@ struct umgen_engine {
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
     int* score_arg = nullptr;
+    // umgen_score_candidates (engine_frame.hip run_score_candidates): the scene of every item (b, c) of the chunk in flight, [max_batch], and the number of
+    // scenes whose slot caches the chunk's last-slot pass reads (run_stack cache mode 5)
+    int* d_item_scene = nullptr;
+    int fan_scenes = 0;
     // umgen_score_detail: allocated by its first call (engine_frame.hip ensure_score_detail).  det_part: the detail sweep's (row, split) records; det_row:
     // lse | target logit | row maximum | sum-exp of one modality's rows, [4][max_batch * 1024]; the results in score_logp's block layout, the lists with room for 16 per row (a call packs its topk)
     float *det_part = nullptr, *det_row = nullptr, *det_mass = nullptr, *det_ent = nullptr, *det_tlp = nullptr;
@@ -272,6 +276,16 @@ struct ScoreIO {
     const ScoreDetailIO* detail = nullptr;       // umgen_score_detail: what else to compute
 };
 
+// umgen_score_candidates' arguments: B scenes' history windows and C candidate next frames of every scene
+struct ScoreCandIO {
+    int B, T, C;
+    const int *pose, *map, *box, *img;          // [B][T][S_mod]
+    const int* next;                             // [B][C][2199]: the candidates, pose | map | bbox3d | image
+    float* logp;                                 // host [B][C][2199], each candidate pose | map | bbox3d | image
+    int* argmax;                                 // the same layout
+    int shared_slots;                            // out: T - 1 when the history slots ran once per scene, 0 on the replicated path
+};
+
 // ---- engine_weights.hip ---------------------------------------------------------------------------------------------
 void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);
 
@@ -313,5 +327,6 @@ int launch_bg_drain(umgen_engine* e, hipStream_t st);   // the launch without an
 // ---- engine_frame.hip -----------------------------------------------------------------------------------------------
 int run_frame_any(umgen_engine* e, const FrameIO& io);
 int run_score_any(umgen_engine* e, const ScoreIO& sc);
+int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc);
 
 }  // namespace umgen

@@ -63,6 +63,11 @@ void launch_attn_causal_f32(hipStream_t s, const float* qk, const float* vt, flo
 struct TemporalRange { int t0; void* cache; int Tcap; int write; int q0 = 0; };   // q0: only query slots >= q0 are evaluated / written
 template <typename T> void launch_attn_temporal(hipStream_t s, const T* qkv, T* y, int B, int Tn, int S, int H,
                                                 TemporalRange tr = TemporalRange{0, nullptr, 0, 0});
+// The last slot of N items whose earlier slots are shared per scene (umgen_score_candidates): qkv [N][S][3E] holds slot P of every item, item i reads the
+// k | v rows of slots [0, P) from block scene_of_item[i] (device, [N]; the items of a scene contiguous, a scene may have none) of cache [B][Tcap][S][2E];
+// y [N][S][E] has the bits of launch_attn_temporal with t0 = P, write = 0 on a per-item copy of the cache.  The cache is never written; P >= 1, P + 1 <= 64.
+template <typename T> void launch_attn_temporal_fan(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P,
+                                                    const T* cache, int Tcap);
 
 // few-query attention over a key/value stream (OAR decode, ego decoder): partial pass, NSPLIT splits of the keys.
 //   q   [NQ][E] fp32;  K row of (scene sc, head h, key k) = kv_base + sc*scene_stride + h*head_stride + k*key_stride (48 values),

@@ -320,6 +320,65 @@ class Engine:
         res["argmax"] = {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}
         return res
 
+    def _candidate_args(self, window: Dict[str, np.ndarray], candidates: Dict[str, np.ndarray]):
+        """Shapes and token ranges of a score_candidates call, checked before anything reaches the device.  Returns (w [B, T, S], cd [B, C, S], batched)."""
+        for what, d in (("window", window), ("candidates", candidates)):
+            for m in MOD_ORDER:
+                if np.asarray(d[m]).dtype.kind not in "iu":      # tokens are indices: a float array is a caller's mistake, not something to truncate
+                    raise UMGenError(f"score_candidates: {what}[{m}] has dtype {np.asarray(d[m]).dtype}, expected an integer type")
+        w = {m: _i64(window[m]) for m in MOD_ORDER}
+        cd = {m: _i64(candidates[m]) for m in MOD_ORDER}
+        batched = w["pose"].ndim == 3
+        for m in MOD_ORDER:
+            if w[m].ndim != (3 if batched else 2) or cd[m].ndim != (3 if batched else 2):
+                raise UMGenError(f"score_candidates: window[{m}] has shape {w[m].shape} and candidates[{m}] {cd[m].shape}; expected [B, T, S] with [B, C, S], or [T, S] with [C, S]")
+            if not batched:
+                w[m], cd[m] = w[m][None], cd[m][None]
+        B, T = w["pose"].shape[:2]
+        Cn = cd["pose"].shape[1]
+        vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
+        for m in MOD_ORDER:
+            if w[m].shape != (B, T, CONTENT_LEN[m]):
+                raise UMGenError(f"score_candidates: window[{m}] has shape {w[m].shape}, expected {(B, T, CONTENT_LEN[m])}")
+            if cd[m].shape != (B, Cn, CONTENT_LEN[m]):
+                raise UMGenError(f"score_candidates: candidates[{m}] has shape {cd[m].shape}, expected {(B, Cn, CONTENT_LEN[m])}")
+            for what, a in (("window", w[m]), ("candidates", cd[m])):
+                bad = np.flatnonzero((a.reshape(-1) < 0) | (a.reshape(-1) >= vocab[m]))
+                if bad.size:
+                    raise UMGenError(f"score_candidates: {what}[{m}] token {int(a.reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
+        if T < 1:
+            raise UMGenError("score_candidates: the window has no history frame")
+        if Cn < 1:
+            raise UMGenError("score_candidates: no candidate frame")
+        return w, cd, batched
+
+    @staticmethod
+    def _candidate_total(logp: Dict[str, np.ndarray]) -> np.ndarray:
+        """The ranking key: float64 sum of logp over all content positions of every candidate, [..]."""
+        return sum(np.asarray(logp[m]).astype(np.float64).sum(axis=-1) for m in MOD_ORDER)
+
+    def score_candidates(self, window: Dict[str, np.ndarray], candidates: Dict[str, np.ndarray]) -> dict:
+        """Per-token log-likelihoods of C candidate next frames per scene against one history (umgen_score_candidates: the history slots run once
+        per scene, every candidate only its last slot, the BlockOAR pass and the heads).
+        window: mod -> [B, T, S_mod] (or [T, S_mod]); candidates: mod -> [B, C, S_mod] (or [C, S_mod]).
+        Returns {"logp": {mod: float32 [B, C, S_mod]}, "argmax": {mod: int64 [B, C, S_mod]}, "total": float64 [B, C], "shared_slots": int} (without
+        the B axis for un-batched inputs).  Entry (b, c) has the bits of score(window[b], candidates[b, c]); "total" is the sum of logp over the 2199
+        content positions, the ranking key; "shared_slots" is T - 1 when the history was evaluated once per scene, 0 when every candidate ran the
+        whole window (T == 1, slot caches that do not fit, UMGEN_SCORE_SHARE=0)."""
+        w, cd, batched = self._candidate_args(window, candidates)
+        B, T = w["pose"].shape[:2]
+        Cn = cd["pose"].shape[1]
+        logp = {m: np.full((B, Cn, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
+        arg = {m: np.full((B, Cn, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
+        out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
+                            **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+        tokens = [_p64(w[m]) for m in MOD_ORDER] + [_p64(cd[m]) for m in MOD_ORDER]
+        shared = C.c_int32(-1)
+        self._check(self.lib.umgen_score_candidates(self._h, B, T, Cn, *tokens, C.byref(out), C.byref(shared)), "score_candidates")
+        pick = (lambda a: a) if batched else (lambda a: a[0])
+        return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER},
+                "total": pick(self._candidate_total(logp)), "shared_slots": int(shared.value)}
+
     def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True) -> np.ndarray:
         """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L).
         use_engine goes through int() as it is: 0 / False five launches per layer, 1 / True the XCD-resident engine, 3 the chip-wide engine.

@@ -185,6 +185,18 @@ class UMGen(nn.Module):
         return {m: np.ascontiguousarray(cond[m][:, end - n:end]) for m in MOD_ORDER}, frame
 
     @staticmethod
+    def _candidate_window(cond: Dict[str, np.ndarray], cand: Dict[str, np.ndarray], input_cond_frames: int, cap: int):
+        """What `score_candidates` hands the engine: the last frames of the conditioning clip, mod -> [B, n, S].  Pure numpy, raises UMGenError on bad shapes."""
+        for m in MOD_ORDER:
+            if cond[m].ndim != 3 or cand[m].ndim != 3 or cond[m].shape[0] != cand[m].shape[0]:
+                raise UMGenError(f"score_candidates: input_cond_tokens[{m}] {cond[m].shape} / candidate_tokens[{m}] {cand[m].shape}: expected [B, T, S] and [B, C, S]")
+        have = cond["pose"].shape[1]
+        n = min(have, cap) if input_cond_frames == -1 else input_cond_frames
+        if n < 1 or n > have or n > cap:
+            raise UMGenError(f"score_candidates: input_cond_frames={input_cond_frames} with {have} conditioning frames (window cap {cap})")
+        return {m: np.ascontiguousarray(cond[m][:, have - n:have]) for m in MOD_ORDER}
+
+    @staticmethod
     def _topk_acc(rank: Dict[str, np.ndarray]) -> Dict[str, Dict[int, float]]:
         """mod -> {k: share of positions whose target is among the k most likely tokens (rank < k)} for k in (1, 5, 16)"""
         return {m: {k: float((np.asarray(rank[m]) < k).mean()) for k in (1, 5, 16)} for m in MOD_ORDER}
@@ -213,4 +225,25 @@ class UMGen(nn.Module):
         if "rank" in res:
             res["topk_acc"] = self._topk_acc(res["rank"])
         res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=1) for m in MOD_ORDER}
+        return res
+
+    @torch.no_grad()
+    def score_candidates(self, input_cond_tokens: Dict[str, torch.Tensor], candidate_tokens: Dict[str, torch.Tensor],
+                         input_cond_frames: int = -1) -> Dict[str, dict]:
+        """Ranks C candidate next frames per scene: ``candidate_tokens[m]`` [B, C, S_mod] against the last ``input_cond_frames`` frames of
+        ``input_cond_tokens`` [B, T, S_mod] (-1: as many as there are, at most the engine's window of 20).  The history is evaluated once per
+        scene (Engine.score_candidates); every entry (b, c) has the bits of `score` on scene b with candidate (b, c) as its one target frame.
+        Returns Engine.score_candidates' dict -- "logp", "argmax", "total" (float64 [B, C], the sum of logp: the ranking key), "shared_slots" --
+        plus "nll": mod -> float64 [B, C], the mean negative log-likelihood, and "best": int64 [B], the candidate with the highest total."""
+        if not self._loaded:
+            raise UMGenError("load_state_dict() has not provided every tensor the model reads")
+        np_ = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
+        cand = {m: np_(candidate_tokens[m]) for m in MOD_ORDER}
+        window = self._candidate_window({m: np_(input_cond_tokens[m]) for m in MOD_ORDER}, cand, input_cond_frames, min(20, self.rcfg.max_frame_len))
+        B = window["pose"].shape[0]
+        if B > self._engine_args["max_batch"]:
+            self._recreate(max_batch=B)
+        res = self.engine.score_candidates(window, cand)
+        res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=-1) for m in MOD_ORDER}
+        res["best"] = np.argmax(res["total"], axis=-1).astype(np.int64)
         return res
