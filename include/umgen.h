@@ -252,6 +252,23 @@ int umgen_score_candidates(umgen_engine *e, int32_t B, int32_t T, int32_t C,
                            umgen_score_out *out,   /* every array [B][C][S_mod]; any pointer may be NULL */
                            int32_t *shared_slots); /* NULL, or receives T - 1 when the history slots were evaluated once per scene, 0 on the replicated path */
 
+/* Scoring a recorded clip: the teacher-forced counterpart of umgen_rollout.  For B clips of L frames, every frame f with T_in <= f < L is scored against
+ * the n_f = min(f, cond_frames) frames before it -- umgen_rollout's window rule (UMGen.py:1597-1603) with the recorded frames in place of generated ones.
+ * Entry (b, f - T_in) of every output is bit for bit what
+ *     umgen_score(e, 1, n_f, clip[b][f - n_f : f], clip[b][f])
+ * returns on the same engine, in every precision, whichever path ran.  While the window still starts at frame 0 (f <= cond_frames) slot t of every such
+ * window is the same computation -- the same tokens, tpe[t], the pose of frame t + 1 from the pose shift, frame-local spatial sub-blocks and a causal
+ * temporal attention -- so these G = min(L - 1, cond_frames) - T_in + 1 frames are read off ONE pass of the four stacks over frames [0, min(L - 1,
+ * cond_frames)) with every block evaluated on every slot, then one BlockOAR pass and one sweep of the heads over the B * G items.  The frames behind them,
+ * whose windows slide, are umgen_score's own pass in chunks of at most max_batch items.  G < 2, no device memory for the clip buffers (allocated by the
+ * first call), or UMGEN_SCORE_CLIP_SHARE=0 in the environment (read per call) evaluate umgen_score's pass for every frame -- the same bits.
+ * 1 <= T_in < L, 1 <= cond_frames <= max_cond_frames, B <= max_batch; L has no upper limit.  Tokens are range-checked like umgen_score's; `out` must not
+ * be NULL, any pointer in it may be.  Like umgen_score, the call settles a pending background pass and leaves nothing an overlapped rollout could reuse. */
+int umgen_score_clip(umgen_engine *e, int32_t B, int32_t L, int32_t T_in, int32_t cond_frames,
+                     const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image, /* [B][L][S_mod] */
+                     umgen_score_out *out,      /* every array [B][L - T_in][S_mod]; any pointer may be NULL, out itself not */
+                     int32_t *shared_frames);   /* NULL, or receives G when the growing windows shared one pass, 0 when nothing was shared */
+
 int umgen_set_profiling(umgen_engine *e, int32_t enable); /* per-launch HIP-event timing of the GEMM / attention kernels and of the
                                                             * decode step's layer kernel(s); profiled frames launch eagerly */
 int umgen_get_timings(umgen_engine *e, umgen_timings *out);

@@ -7,7 +7,10 @@ After one warm-up call each: the median of 5 host-clock calls of Engine.score at
 alternating pairs of Engine.score and Engine.score(detail=True, topk=16) at B = 1 and B = 8, the median of each side.
 --candidates C (or --candidates=C) measures only umgen_score_candidates: one scene, C candidate next frames, Engine.score_candidates against
 Engine.score with the window replicated C times (the same numbers, bit for bit), 5 alternating pairs behind one warm-up call each; the result
-is stored under "candidates" in out.json, whose other entries are kept."""
+is stored under "candidates" in out.json, whose other entries are kept.
+--clip measures only umgen_score_clip: one scene, a clip of L = 21 frames, input_frames 1, cond_frames 20, an engine of one scene; Engine.score_clip
+against the loop of 20 Engine.score calls on the growing windows (the same numbers, bit for bit) and against itself with UMGEN_SCORE_CLIP_SHARE=0, 5
+alternating rounds behind one warm-up call of each kind, and one profiled call's stage split; stored under "clip" in out.json."""
 import json
 import os
 import statistics
@@ -31,6 +34,7 @@ if "--candidates" in sys.argv[1:]:
     k = sys.argv.index("--candidates")
     CAND = int(sys.argv[k + 1])
     args.remove(sys.argv[k + 1])
+CLIP = "--clip" in sys.argv[1:]
 REPS = 5
 
 
@@ -95,6 +99,63 @@ def candidates_bench(e, sc, out):
     with open(out, "w") as f:
         f.write(line + "\n")
 
+
+def clip_bench(out, L=21, cond=20):
+    """one recorded clip of L frames: the clip call, the loop of Engine.score calls a user writes without it, and the clip call with nothing shared"""
+    cfg = large_config()
+    e = Engine(cfg, precision="bf16", max_batch=1, max_cond_frames=cond)
+    e.load_state_dict(synthetic_items(cfg, seed=0))
+    e.finalize()
+    clip = {m: v[0] for m, v in synthetic_scene(0, n_frames=L).items()}
+    windows = Engine.clip_windows(L, 1, cond)
+    got = {}
+
+    def loop():
+        got["l"] = [e.score({m: clip[m][s:s + n] for m in MOD_ORDER}, {m: clip[m][f] for m in MOD_ORDER}) for f, s, n in windows]
+
+    def unshared():
+        os.environ["UMGEN_SCORE_CLIP_SHARE"] = "0"
+        try:
+            got["u"] = e.score_clip(clip, 1, cond)
+        finally:
+            del os.environ["UMGEN_SCORE_CLIP_SHARE"]
+    kinds = ((lambda: got.__setitem__("c", e.score_clip(clip, 1, cond)), []), (loop, []), (unshared, []))
+    for fn, _ in kinds:
+        fn()
+    for _ in range(REPS):
+        for fn, ts in kinds:
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+    tc, tl, tu = (ts for _, ts in kinds)
+    same = all(got["c"][k][m][i].tobytes() == got["l"][i][k][m].tobytes() == got["u"][k][m][i].tobytes()
+               for k in ("logp", "argmax") for m in MOD_ORDER for i in range(len(windows)))
+    med = statistics.median
+    r = {"frames": L, "input_frames": 1, "cond_frames": cond, "reps": REPS, "score_clip_ms": med(tc), "score_clip_all_ms": tc, "score_clip_spread_ms": max(tc) - min(tc),
+         "score_loop_ms": med(tl), "score_loop_all_ms": tl, "score_loop_spread_ms": max(tl) - min(tl), "loop_over_clip": med(tl) / med(tc),
+         "unshared_clip_ms": med(tu), "unshared_clip_all_ms": tu, "unshared_clip_spread_ms": max(tu) - min(tu), "unshared_over_clip": med(tu) / med(tc),
+         "shared_frames": got["c"]["shared_frames"], "unshared_shared_frames": got["u"]["shared_frames"], "same_bytes": same,
+         "nll_per_frame": {m: (-got["c"]["logp"][m].astype(np.float64).mean(-1)).tolist() for m in MOD_ORDER}}
+    e.set_profiling(True)      # one profiled call: the stage split (the stream is drained at every stage boundary, per-launch events serialise the stacks)
+    t0 = time.perf_counter()
+    e.score_clip(clip, 1, cond)
+    r["profiled_call_ms"] = (time.perf_counter() - t0) * 1e3
+    r["profiled_timings"] = {k: v for k, v in e.timings().items() if k in ("total_ms", "ego_ms", "tar_ms", "oar_ms", "gemm_ms", "gemm_launches", "attn_ms", "attn_launches")}
+    e.set_profiling(False)
+    e.close()
+    res = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            res = json.loads(f.read())
+    res["clip"] = r
+    print(json.dumps(r))
+    with open(out, "w") as f:
+        f.write(json.dumps(res) + "\n")
+
+
+if CLIP:
+    clip_bench(args[0] if args else os.path.join(ROOT, "profiles", "score_bench.json"))
+    sys.exit(0)
 
 cfg = large_config()
 e = Engine(cfg, precision="bf16", max_batch=8, max_cond_frames=T)

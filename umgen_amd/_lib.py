@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
 SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
            "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip"]
-EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_rollout_logp", "umgen_frame_logp",
+EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
@@ -25,6 +25,7 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
            "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer", "umgen_dbg_guard_selftest",
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
+           "umgen_dbg_embed_warp_slots", "umgen_dbg_cond_rows_slots", "umgen_dbg_ego_queries_slots",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego", "umgen_dbg_token_steps_logp", "umgen_dbg_sample_ego_logp",
            "umgen_dbg_head_nll", "umgen_dbg_head_nll_split", "umgen_dbg_head_detail", "umgen_dbg_logits_detail",
            "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache"]
@@ -275,6 +276,7 @@ def load_library() -> C.CDLL:
     lib.umgen_score.argtypes = [vp, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut)]
     lib.umgen_score_detail.argtypes = lib.umgen_score.argtypes[:-1] + [i32, C.c_float, C.POINTER(ScoreOut), C.POINTER(ScoreDetailOut)]
     lib.umgen_score_candidates.argtypes = [vp, i32, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
+    lib.umgen_score_clip.argtypes = [vp, i32, i32, i32, i32, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
     lib.umgen_set_profiling.argtypes = [vp, i32]
     lib.umgen_get_timings.argtypes = [vp, C.POINTER(Timings)]
     lib.umgen_last_error.argtypes = [vp]
@@ -320,6 +322,9 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_cond_rows.argtypes = [i32, i32, i32, i32, fp, fp, fp, fp]
     lib.umgen_dbg_first_input.argtypes = [i32, i32, fp, fp, fp]
     lib.umgen_dbg_ego_queries.argtypes = [tp, i32, i32, fp]
+    lib.umgen_dbg_embed_warp_slots.argtypes = lib.umgen_dbg_embed_warp.argtypes + [fp]
+    lib.umgen_dbg_cond_rows_slots.argtypes = [i32, i32, i32, i32, fp, fp, fp, i32p, i32, fp]
+    lib.umgen_dbg_ego_queries_slots.argtypes = [tp, i32, i32p, fp]
     lib.umgen_dbg_prefix_rows.argtypes = [tp, fp, fp, i32p, i32, i32, fp, fp]
     lib.umgen_dbg_prefix_kv_to_cache.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.umgen_dbg_token_steps.argtypes = [tp, C.POINTER(DbgSteps)]

@@ -51,15 +51,10 @@ EmbedTables tables_in(Scratch& s, const umgen_dbg_tables& t) {
     return tb;
 }
 int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp);
-}  // namespace
 
-extern "C" {
-
-// run_stack's first two launches (engine_stacks.hip): launch_embed_stack, then for every stack but STACK_EGO launch_warp_map.  Token arrays
-// [B][Tf][3 | 1024 | 660 | 512] and pose_diff [B][Tf][3] with Tf = Tfull (0: T); the pass covers slots t0 .. t0 + T - 1.
-// -> X [B][T][stack_len][E], mapfeat [B][T][1024][E], warped_last [B][1024][E] (handed to the launcher only when want_last != 0).
-int umgen_dbg_embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B,
-                         int T, int Tfull, int t0, const float* pose_diff, int want_last, float* X, float* mapfeat, float* warped_last) {
+// the body of umgen_dbg_embed_warp and umgen_dbg_embed_warp_slots (warped_all: nullptr, or the host buffer of launch_warp_map's output of that name)
+int embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B, int T, int Tfull,
+               int t0, const float* pose_diff, int want_last, float* X, float* mapfeat, float* warped_last, float* warped_all) {
     if (stack < STACK_EGO || stack > STACK_TAR || !tables_sane(t) || B < 1 || T < 1 || Tfull < 0 || t0 < 0) return UMGEN_E_INVALID;
     const int Tf = Tfull ? Tfull : T;
     if (t0 + T > Tf || Tf > t->n_tpe || !pose || !map || !box || !img || !pose_diff || !X || !mapfeat || !warped_last) return UMGEN_E_INVALID;
@@ -78,14 +73,36 @@ int umgen_dbg_embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* po
     w.pose = s.in(pose, F * kNPose * 4); w.map = s.in(map, F * kNMap * 4); w.box = s.in(box, F * kNBox * 4); w.img = s.in(img, F * kNImg * 4);
     w.B = B; w.T = T; w.Tfull = Tfull; w.t0 = t0;
     const float* dPD = s.in(pose_diff, F * 3 * 4);
-    float *dX = s.out(xn * 4), *dMF = s.out(mn * 4), *dWL = s.out(wn * 4);
+    float *dX = s.out(xn * 4), *dMF = s.out(mn * 4), *dWL = s.out(wn * 4), *dWA = nullptr;
+    if (warped_all) dWA = s.out(mn * 4);
     if (s.rc) return s.rc;
-    if (fill_nan(dX, xn, 0) || fill_nan(dMF, mn, 0) || fill_nan(dWL, wn, 0)) return UMGEN_E_HIP;
+    if (fill_nan(dX, xn, 0) || fill_nan(dMF, mn, 0) || fill_nan(dWL, wn, 0) || (dWA && fill_nan(dWA, mn, 0))) return UMGEN_E_HIP;
     launch_embed_stack(nullptr, stack, tb, w, dX, dMF);
-    if (stack != STACK_EGO) launch_warp_map(nullptr, stack, tb, B, T, dMF, dPD, dX, want_last ? dWL : nullptr, Tfull, t0);
+    if (stack != STACK_EGO) launch_warp_map(nullptr, stack, tb, B, T, dMF, dPD, dX, want_last ? dWL : nullptr, Tfull, t0, dWA);
     if (int rc = s.finish()) return rc;
     if (down(X, dX, xn * 4) || down(mapfeat, dMF, mn * 4)) return UMGEN_E_HIP;
+    if (dWA && down(warped_all, dWA, mn * 4)) return UMGEN_E_HIP;
     return down(warped_last, dWL, wn * 4);
+}
+}  // namespace
+
+extern "C" {
+
+// run_stack's first two launches (engine_stacks.hip): launch_embed_stack, then for every stack but STACK_EGO launch_warp_map.  Token arrays
+// [B][Tf][3 | 1024 | 660 | 512] and pose_diff [B][Tf][3] with Tf = Tfull (0: T); the pass covers slots t0 .. t0 + T - 1.
+// -> X [B][T][stack_len][E], mapfeat [B][T][1024][E], warped_last [B][1024][E] (handed to the launcher only when want_last != 0).
+int umgen_dbg_embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B,
+                         int T, int Tfull, int t0, const float* pose_diff, int want_last, float* X, float* mapfeat, float* warped_last) {
+    return embed_warp(stack, t, pose, map, box, img, B, T, Tfull, t0, pose_diff, want_last, X, mapfeat, warped_last, nullptr);
+}
+
+// umgen_dbg_embed_warp with the warped map of EVERY slot of the pass beside warped_last (launch_warp_map's warped_all; every stack but STACK_EGO):
+// -> also warped_all [B][T][1024][E]
+int umgen_dbg_embed_warp_slots(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B,
+                               int T, int Tfull, int t0, const float* pose_diff, int want_last, float* X, float* mapfeat, float* warped_last,
+                               float* warped_all) {
+    if (stack == STACK_EGO || !warped_all) return UMGEN_E_INVALID;
+    return embed_warp(stack, t, pose, map, box, img, B, T, Tfull, t0, pose_diff, want_last, X, mapfeat, warped_last, warped_all);
 }
 
 // launch_layernorm<T> (T by prec) on n_rows rows of x (row r at x + r * row_stride, E <= 1536 columns) -> out [out_rows][E] of T, out_rows >= n_rows:
@@ -117,6 +134,25 @@ int umgen_dbg_cond_rows(int stack, int B, int T, int E, const float* X, const fl
     return down(cond, dC, cn * 4);
 }
 
+// launch_cond_rows_slots of one stack: X [B][T][stack_len][E], ln_w [E], warped_all [B][T][1024][E] or NULL (required for STACK_MAP), items [n_items][2] =
+// (scene, slot) -> cond_all [n_items][kSeq][E], in / out: the launch changes the stack's own rows only
+int umgen_dbg_cond_rows_slots(int stack, int B, int T, int E, const float* X, const float* ln_w, const float* warped_all, const int32_t* items, int n_items,
+                              float* cond_all) {
+    if (stack < STACK_MAP || stack > STACK_TAR || B < 1 || T < 1 || E < 1 || n_items < 1 || !X || !ln_w || !items || !cond_all || (stack == STACK_MAP && !warped_all))
+        return UMGEN_E_INVALID;
+    for (int i = 0; i < n_items; ++i)      // the items index X and warped_all
+        if (items[2 * i] < 0 || items[2 * i] >= B || items[2 * i + 1] < 0 || items[2 * i + 1] >= T) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)B * T * stack_len(stack) * E, wn = (size_t)B * T * kNMap * E, cn = (size_t)n_items * kSeq * E;
+    Scratch s;
+    const float *dXi = s.in(X, xn * 4), *dW = s.in(ln_w, (size_t)E * 4), *dWA = s.in(warped_all, wn * 4);
+    const int* dI = s.in(items, (size_t)n_items * 2 * 4);
+    float* dC = s.inout(cond_all, cn * 4);
+    if (s.rc) return s.rc;
+    launch_cond_rows_slots(nullptr, stack, T, E, dXi, dW, dWA, dI, n_items, dC);
+    if (int rc = s.finish()) return rc;
+    return down(cond_all, dC, cn * 4);
+}
+
 // launch_first_input: x [B][E] = row [E] + cond[b][0] (cond [B][kSeq][E])
 int umgen_dbg_first_input(int B, int E, const float* row, const float* cond, float* x) {
     if (B < 1 || E < 1 || !row || !cond || !x) return UMGEN_E_INVALID;
@@ -141,6 +177,23 @@ int umgen_dbg_ego_queries(const umgen_dbg_tables* t, int B, int T, float* x) {
     if (s.rc) return s.rc;
     if (int rc = fill_nan(dXo, xn, 0)) return rc;
     launch_ego_queries(nullptr, tb, B, T, dXo);
+    if (int rc = s.finish()) return rc;
+    return down(x, dXo, xn * 4);
+}
+
+// launch_ego_queries with a window length per item: x [n][3][E] = (egoe[j] + spe[j]) + tpe[item_T[i] - 1]
+int umgen_dbg_ego_queries_slots(const umgen_dbg_tables* t, int n, const int32_t* item_T, float* x) {
+    if (!tables_sane(t) || n < 1 || !item_T || !t->egoe || !t->spe || !t->tpe || !x) return UMGEN_E_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (item_T[i] < 1 || item_T[i] > t->n_tpe) return UMGEN_E_INVALID;
+    const size_t xn = (size_t)n * 3 * t->E;
+    Scratch s;
+    const EmbedTables tb = tables_in(s, *t);
+    const int* dT = s.in(item_T, (size_t)n * 4);
+    float* dXo = s.out(xn * 4);
+    if (s.rc) return s.rc;
+    if (int rc = fill_nan(dXo, xn, 0)) return rc;
+    launch_ego_queries(nullptr, tb, n, 0, dXo, dT);
     if (int rc = s.finish()) return rc;
     return down(x, dXo, xn * 4);
 }

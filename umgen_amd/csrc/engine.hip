@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
+// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_clip and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
 #include "engine_state.h"
 
@@ -252,6 +252,43 @@ int umgen_score_candidates(umgen_engine* e, int32_t B, int32_t T, int32_t C, con
             if (ao[m]) memcpy(ao[m] + it * S[m], &arg[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(int32_t));
         }
     if (shared_slots) *shared_slots = sc.shared_slots;
+    return UMGEN_OK;
+}
+
+// umgen_score_clip: every frame of B recorded clips against the frames before it, the growing windows off one pass (engine_frame.hip run_score_clip)
+int umgen_score_clip(umgen_engine* e, int32_t B, int32_t L, int32_t T_in, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                     const int64_t* bbox3d, const int64_t* image, umgen_score_out* out, int32_t* shared_frames) {
+    if (!e) return UMGEN_E_INVALID;
+    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
+    if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
+    if (L < 2) return e->fail(UMGEN_E_INVALID, "L=%d: a clip has at least two frames", L);
+    if (T_in < 1 || T_in >= L) return e->fail(UMGEN_E_INVALID, "T_in=%d out of range [1,%d) (L=%d)", T_in, L, L);
+    if (cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
+        return e->fail(UMGEN_E_INVALID, "cond_frames=%d out of range [1,%d]", cond_frames, e->cfg.max_cond_frames);
+    if (!out) return e->fail(UMGEN_E_INVALID, "null output struct");
+    if (!pose || !map || !bbox3d || !image) return e->fail(UMGEN_E_INVALID, "null token buffer");
+    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
+    if (int rc = check_scene_tokens(e, (size_t)B * L, pose, map, bbox3d, image)) return rc;
+    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
+    const int64_t* in[4] = {pose, map, bbox3d, image};
+    std::vector<int> clip[4];
+    for (int m = 0; m < 4; ++m) {
+        clip[m].resize((size_t)B * L * S[m]);
+        for (size_t i = 0; i < clip[m].size(); ++i) clip[m][i] = (int)in[m][i];
+    }
+    const size_t N = (size_t)B * (L - T_in);
+    std::vector<float> logp(N * kTokPerFrame);
+    std::vector<int> arg(N * kTokPerFrame);
+    ScoreClipIO sc{B, L, T_in, cond_frames, clip[0].data(), clip[1].data(), clip[2].data(), clip[3].data(), logp.data(), arg.data(), 0};
+    if (int rc = run_score_clip_any(e, sc)) return rc;
+    float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
+    int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
+    for (int m = 0; m < 4; ++m)
+        for (size_t it = 0; it < N; ++it) {
+            if (lo[m]) memcpy(lo[m] + it * S[m], &logp[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(float));
+            if (ao[m]) memcpy(ao[m] + it * S[m], &arg[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(int32_t));
+        }
+    if (shared_frames) *shared_frames = sc.shared_frames;
     return UMGEN_OK;
 }
 

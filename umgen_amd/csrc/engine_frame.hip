@@ -1,7 +1,8 @@
 // One frame, UMGen._inference: run_frame<T> as a sequence of stages -- background pass, uploads, ego net and pose shift, decode state, the
 // stacks, first input and prefix pass, the lane loop or the single-stream step loop, drain, download, checks, bookkeeping -- run_score<T>,
 // the scoring pass of umgen_score built from the same stages, run_score_candidates<T>, which scores several next frames per scene on one pass
-// over the history, and run_frame_any / run_score_any / run_score_candidates_any, which pick the precision and clean up behind a failed call.
+// over the history, run_score_clip<T>, which scores every frame of a recorded clip, the growing windows off one pass, and run_frame_any / run_score_any /
+// run_score_candidates_any / run_score_clip_any, which pick the precision and clean up behind a failed call.
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -656,10 +657,13 @@ ScoreDetailOut score_detail_out(const umgen_engine* e, const ScoreDetailIO* dt, 
                           1.0f / dt->temperature};
 }
 
+// where score_heads finds its targets and leaves its results when B may exceed max_batch (umgen_score_clip): d_tokens, score_part, score_logp, score_arg for B items
+struct ScoreBufs { const int* tokens; float *part, *logp; int* arg; };
+
 // the scoring head on the rows run_prefix_prefill left in X for B scenes (row j predicts the token at position j, targets in d_tokens): the map,
 // bbox3d and image blocks of score_logp / score_arg, each [B][S_mod]; with dt the detail sweep of the same rows
 template <typename T>
-int score_heads(umgen_engine* e, hipStream_t st, int B, const ScoreDetailIO* dt) {
+int score_heads(umgen_engine* e, hipStream_t st, int B, const ScoreDetailIO* dt, const ScoreBufs* sb = nullptr) {
     const int E = e->E;
     const int c0[3] = {kMapC0, kBoxC0, kImgC0}, n[3] = {kNMap, kNBox, kNImg}, off[3] = {kOffMap, kOffBox, kOffImg};
     const int V[3] = {e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
@@ -668,8 +672,9 @@ int score_heads(umgen_engine* e, hipStream_t st, int B, const ScoreDetailIO* dt)
         HeadNllArgs a{};
         a.x = e->X + (long)c0[m] * E; a.ldx = E; a.rows_per_group = n[m]; a.group_stride = (long)(kSeq - 1) * E;
         a.ln_w = e->ln_oar; a.W = head[m]; a.V = V[m]; a.K = E; a.M = B * n[m];
-        a.target = e->d_tokens + off[m]; a.target_group_stride = kTokPerFrame;
-        a.part = e->score_part; a.logp = e->score_logp + (long)B * off[m]; a.argmax = e->score_arg + (long)B * off[m];
+        a.target = (sb ? sb->tokens : e->d_tokens) + off[m]; a.target_group_stride = kTokPerFrame;
+        a.part = sb ? sb->part : e->score_part; a.logp = (sb ? sb->logp : e->score_logp) + (long)B * off[m];
+        a.argmax = (sb ? sb->arg : e->score_arg) + (long)B * off[m];
         if (dt) {
             const long nr = (long)e->cfg.max_batch * kNMap;
             a.lse = e->det_row; a.tlogit = e->det_row + nr; a.rmax = e->det_row + 2 * nr; a.sumexp = e->det_row + 3 * nr;
@@ -865,6 +870,187 @@ int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
     return 0;
 }
 
+// device buffers of umgen_score_clip's shared pass, on its first call (like ensure_score_detail); no room is not an error: the call takes the per-frame path
+bool ensure_score_clip(umgen_engine* e) {
+    if (e->clip_state) return e->clip_state > 0;
+    const size_t N = (size_t)e->cfg.max_batch * e->cfg.max_cond_frames, E = (size_t)e->E;
+    void* got[9] = {};
+    const size_t bytes[9] = {N * 2 * 4, N * 4, N * kTokPerFrame * 4, N * kTokPerFrame * 4, N * kNMap * E * 4, N * kSeq * E * 4, N * E * 4,
+                             N * kNMap * 8 * 16, N * kTokPerFrame * 4};      // (head_nll_nsplit <= 8, records of 16 bytes)
+    for (int i = 0; i < 9; ++i)
+        if (hipMalloc(&got[i], bytes[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int k = 0; k < i; ++k) (void)hipFree(got[k]);
+            e->clip_state = -1;
+            return false;
+        }
+    for (void* p : got) e->allocs.push_back(p);
+    e->clip_items = (int*)got[0]; e->clip_item_T = (int*)got[1]; e->clip_tokens = (int*)got[2]; e->clip_arg = (int*)got[3];
+    e->clip_warped = (float*)got[4]; e->clip_cond = (float*)got[5]; e->clip_xlast = (float*)got[6]; e->clip_part = (float*)got[7]; e->clip_logp = (float*)got[8];
+    e->clip_state = 1;
+    return true;
+}
+
+const int kModLen[4] = {kNPose, kNMap, kNBox, kNImg}, kModOff[4] = {0, kOffMap, kOffBox, kOffImg};
+
+// frame f of clip b as one [2199] row pose | map | bbox3d | image
+void clip_frame_row(const ScoreClipIO& sc, int b, int f, int* dst) {
+    const int* src[4] = {sc.pose, sc.map, sc.box, sc.img};
+    for (int m = 0; m < 4; ++m) memcpy(dst + kModOff[m], src[m] + ((size_t)b * sc.L + f) * kModLen[m], (size_t)kModLen[m] * sizeof(int));
+}
+// blocks pose | map | bbox3d | image, each [n][S_mod], of n items -> item i to frame fr[i] of clip sc[i] in [B][L - T_in][2199]
+void clip_scatter(const ScoreClipIO& sc, int n, const float* lp, const int* am, const int* item_b, const int* item_f) {
+    const int F = sc.L - sc.T_in;
+    for (int m = 0; m < 4; ++m)
+        for (int i = 0; i < n; ++i) {
+            const size_t dst = ((size_t)item_b[i] * F + (item_f[i] - sc.T_in)) * kTokPerFrame + kModOff[m], src = (size_t)n * kModOff[m] + (size_t)i * kModLen[m];
+            memcpy(sc.logp + dst, lp + src, (size_t)kModLen[m] * sizeof(float));
+            memcpy(sc.argmax + dst, am + src, (size_t)kModLen[m] * sizeof(int));
+        }
+}
+
+// frames [f0, f1) of every clip, each against its own window: run_score on items (f, b), in chunks of at most max_batch items of one window length
+template <typename T>
+int score_clip_frames(umgen_engine* e, const ScoreClipIO& sc, int f0, int f1) {
+    const int B = sc.B, Bm = e->cfg.max_batch;
+    const int* src[4] = {sc.pose, sc.map, sc.box, sc.img};
+    std::vector<int> win[4], next, am, ib, itf;
+    std::vector<float> lp;
+    const long N = (long)(f1 - f0) * B;
+    for (long i0 = 0; i0 < N;) {
+        const int Tn = std::min(f0 + (int)(i0 / B), sc.cond);
+        int n = 0;
+        while (n < Bm && i0 + n < N && std::min(f0 + (int)((i0 + n) / B), sc.cond) == Tn) ++n;
+        ib.resize(n); itf.resize(n);
+        next.resize((size_t)n * kTokPerFrame);
+        for (int m = 0; m < 4; ++m) win[m].resize((size_t)n * Tn * kModLen[m]);
+        for (int i = 0; i < n; ++i) {
+            const int f = f0 + (int)((i0 + i) / B), b = (int)((i0 + i) % B);
+            ib[i] = b; itf[i] = f;
+            for (int m = 0; m < 4; ++m)
+                memcpy(&win[m][(size_t)i * Tn * kModLen[m]], src[m] + ((size_t)b * sc.L + (f - Tn)) * kModLen[m], (size_t)Tn * kModLen[m] * sizeof(int));
+            clip_frame_row(sc, b, f, &next[(size_t)i * kTokPerFrame]);
+        }
+        lp.resize((size_t)n * kTokPerFrame);
+        am.resize((size_t)n * kTokPerFrame);
+        const ScoreIO one{n, Tn, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), lp.data(), am.data()};
+        if (int rc = run_score<T>(e, one)) return rc;
+        clip_scatter(sc, n, lp.data(), am.data(), ib.data(), itf.data());
+        i0 += n;
+    }
+    return 0;
+}
+
+// The growing group of umgen_score_clip: frames f in [T_in, P], P = min(L - 1, cond), whose windows [0, f) all start at frame 0.  Slot t of a window uses tpe[t]
+// whatever the window's length, the pose shift hands it the pose of frame t + 1, the spatial sub-blocks, LayerNorms and MLPs are frame-local and the temporal
+// attention is causal: slot f - 1 of ONE pass over [0, P) with every block on every slot is the last slot of umgen_score's pass over [0, f).  So the four stacks
+// run once, the ego decoder, the conditioning rows, the BlockOAR pass and the heads on the B * G items (b, slot), G = P - T_in + 1 -- the kernels and the row
+// arithmetic of run_score, launched over other row sets.
+template <typename T>
+int score_clip_shared(umgen_engine* e, const ScoreClipIO& sc, int P, int G) {
+    const int E = e->E, B = sc.B, L = sc.L, Bm = e->cfg.max_batch, n = B * G, pv = e->cfg.pose_vocab;
+    hipStream_t const fg = e->stream;
+    e->launch_status = hipSuccess;
+    (void)hipGetLastError();
+    struct RestoreStream { umgen_engine* e; hipStream_t s; ~RestoreStream() { e->stream = s; e->set_work(e->w_main); } } restore{e, fg};
+    // the window [0, P) of every clip, [B][P][S_mod], and frame P's pose, which the shift hands to slot P - 1
+    const int* src[4] = {sc.pose, sc.map, sc.box, sc.img};
+    std::vector<int> win[4], pose_P((size_t)B * 3), items((size_t)n * 2), item_T(n), item_b(n), item_f(n), next((size_t)n * kTokPerFrame);
+    for (int m = 0; m < 4; ++m) {
+        win[m].resize((size_t)B * P * kModLen[m]);
+        for (int b = 0; b < B; ++b) memcpy(&win[m][(size_t)b * P * kModLen[m]], src[m] + (size_t)b * L * kModLen[m], (size_t)P * kModLen[m] * sizeof(int));
+    }
+    for (int b = 0; b < B; ++b) {
+        memcpy(&pose_P[(size_t)b * 3], sc.pose + ((size_t)b * L + P) * 3, 3 * sizeof(int));
+        for (int g = 0; g < G; ++g) {      // item (b, g): slot t = T_in - 1 + g scores frame t + 1
+            const int i = b * G + g, t = sc.T_in - 1 + g;
+            items[2 * i] = b; items[2 * i + 1] = t; item_T[i] = t + 1; item_b[i] = b; item_f[i] = t + 1;
+            clip_frame_row(sc, b, t + 1, &next[(size_t)i * kTokPerFrame]);
+        }
+    }
+    static const umgen_sampling smp{UMGEN_SAMPLE_TOPK, 1, 1, 1, 1.f, 1.f, 1.f, 0, 0, 0, nullptr};      // (upload_frame_inputs reads the seeds pointer)
+    const FrameIO io{B, P, win[0].data(), win[1].data(), win[2].data(), win[3].data(), nullptr, nullptr, 0, &smp, nullptr, nullptr};
+    FrameCtx ctx{};
+    ctx.fg = fg;
+    ctx.st = fg;
+    e->px.valid = false;                 // the passes below overwrite the stacks' workspaces; nothing of them is for a later rollout
+    if (int rc = settle_background_pass(e, io, ctx)) return rc;
+    hipStream_t const st = ctx.st;
+    if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
+    HIPCHK(e, hipMemcpyAsync(e->clip_items, items.data(), items.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->clip_item_T, item_T.data(), item_T.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->clip_tokens, next.data(), next.size() * 4, hipMemcpyHostToDevice, st));
+    // a profiled call drains the stream at every stage boundary and books host time, like run_score_candidates: ego_ms the ego stack and decoder, tar_ms the
+    // three stacks and the conditioning rows, oar_ms the BlockOAR pass and the heads
+    auto t_last = std::chrono::steady_clock::now();
+    auto stage = [&](double& acc) {
+        if (!e->profiling) return;
+        (void)hipStreamSynchronize(st);
+        const auto now = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(now - t_last).count();
+        acc += ms;
+        e->tm.total_ms += ms;
+        t_last = now;
+    };
+    double uploads_ms = 0;               // (in total_ms only)
+    stage(uploads_ms);
+    // the ego stack over [0, P), every block on every slot; the decoder and head_ego on the items, in chunks that fit the 3 * max_batch-row buffers
+    run_stack_any(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, P, 0}, 0, TAIL_NONE);
+    std::vector<long> frame_of(Bm);
+    for (int i0 = 0; i0 < n; i0 += Bm) {
+        const int nc = std::min(Bm, n - i0);
+        for (int i = 0; i < nc; ++i) frame_of[i] = (long)items[2 * (i0 + i)] * P + items[2 * (i0 + i) + 1];
+        ego_decoder_any(e, nc, frame_of.data(), 0, e->clip_item_T + i0);
+        launch_logits_nll(st, e->logits, pv, pv, 3 * nc, e->clip_tokens + (long)i0 * kTokPerFrame, kNPose, kTokPerFrame, e->clip_logp + (long)i0 * 3,
+                          e->clip_arg + (long)i0 * 3, nullptr, nullptr);
+    }
+    stage(e->tm.ego_ms);
+    // one pose shift for the window: slot t carries the pose of frame t + 1, slot P - 1 that of frame P
+    decode_pose_shift(win[0].data(), pose_P.data(), B, P, ctx.pshift, ctx.pdiff);
+    HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, ctx.pshift.data(), ctx.pshift.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->pose_diff, ctx.pdiff.data(), ctx.pdiff.size() * 4, hipMemcpyHostToDevice, st));
+    const WindowTokens ws{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, P, 0};
+    run_stack_any(e, STACK_MAP, ws, 0, TAIL_NONE, e->clip_warped);
+    launch_cond_rows_slots(st, STACK_MAP, P, E, e->X, e->ln_map_tar, e->clip_warped, e->clip_items, n, e->clip_cond);
+    run_stack_any(e, STACK_BOX, ws, 0, TAIL_NONE);
+    launch_cond_rows_slots(st, STACK_BOX, P, E, e->X, e->ln_box_tar, nullptr, e->clip_items, n, e->clip_cond);
+    run_stack_any(e, STACK_TAR, ws, 0, TAIL_NONE);
+    launch_cond_rows_slots(st, STACK_TAR, P, E, e->X, e->ln_tar, nullptr, e->clip_items, n, e->clip_cond);
+    stage(e->tm.tar_ms);
+    // one BlockOAR pass and one head sweep for all items (n <= max_batch * max_cond_frames: the rows the stacks' workspaces hold)
+    const PrefillSrc ps{e->clip_cond, e->clip_tokens, e->clip_xlast, true};
+    if (int rc = run_prefix_prefill_any(e, n, kSeq, &ps)) return rc;
+    const ScoreBufs sb{e->clip_tokens, e->clip_part, e->clip_logp, e->clip_arg};
+    if (int rc = score_heads<T>(e, st, n, nullptr, &sb)) return rc;
+    std::vector<float> lp((size_t)n * kTokPerFrame);
+    std::vector<int> am((size_t)n * kTokPerFrame);
+    HIPCHK(e, hipMemcpyAsync(lp.data(), e->clip_logp, lp.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(am.data(), e->clip_arg, am.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    stage(e->tm.oar_ms);
+    if (e->profiling) fold_launch_events(e);
+    const hipError_t le = e->launch_status != hipSuccess ? e->launch_status : hipGetLastError();
+    e->launch_status = hipSuccess;
+    if (le != hipSuccess) return e->fail(UMGEN_E_HIP, "a kernel launch of this scoring pass was refused: %s", hipGetErrorString(le));
+    clip_scatter(sc, n, lp.data(), am.data(), item_b.data(), item_f.data());
+    return 0;
+}
+
+// umgen_score_clip: every frame f in [T_in, L) of B recorded clips against the min(f, cond) frames before it (umgen_rollout's window rule, teacher-forced).
+// The frames whose window still starts at frame 0 share one pass (score_clip_shared) when there are at least two of them; the frames behind them, whose
+// windows slide -- every slot's tpe row changes from frame to frame -- and everything when nothing is shared (UMGEN_SCORE_CLIP_SHARE=0, no room for the clip
+// buffers) are run_score itself.  Either way entry (b, f) has the bits of umgen_score on its own window.
+template <typename T>
+int run_score_clip(umgen_engine* e, ScoreClipIO& sc) {
+    const int P = std::min(sc.L - 1, sc.cond), G = std::max(0, P - sc.T_in + 1);
+    const char* she = getenv("UMGEN_SCORE_CLIP_SHARE");      // (read per call: the tests compare both forms in one process)
+    const bool share = G >= 2 && !(she && she[0] == '0') && ensure_score_clip(e);
+    sc.shared_frames = share ? G : 0;
+    if (!share) return score_clip_frames<T>(e, sc, sc.T_in, sc.L);
+    if (int rc = score_clip_shared<T>(e, sc, P, G)) return rc;
+    return score_clip_frames<T>(e, sc, P + 1, sc.L);
+}
+
 // A failed frame may have left a stream capture open, async copies in flight that read this call's host buffers, and a
 // background pass the next call would wait for: drain everything and forget the pass (the error message is kept).
 void drain_failed_frame(umgen_engine* e) {
@@ -900,6 +1086,13 @@ int run_score_any(umgen_engine* e, const ScoreIO& sc) {
 int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc) {
     const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_score_candidates<bf16_t>(e, sc)
                  : e->cfg.precision == UMGEN_PREC_FP16 ? run_score_candidates<f16_t>(e, sc) : run_score_candidates<float>(e, sc);
+    if (rc != UMGEN_OK) drain_failed_frame(e);
+    return rc;
+}
+
+int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc) {
+    const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_score_clip<bf16_t>(e, sc)
+                 : e->cfg.precision == UMGEN_PREC_FP16 ? run_score_clip<f16_t>(e, sc) : run_score_clip<float>(e, sc);
     if (rc != UMGEN_OK) drain_failed_frame(e);
     return rc;
 }

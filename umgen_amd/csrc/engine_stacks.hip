@@ -154,19 +154,21 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
 // caches for a longer window that follows; 4 = last-slot pass like 2 that appends its own k | v rows (the window keeps growing);
 // 5 = last-slot pass like 2 of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of e->fan_scenes scenes: item i reads the slots [0, P) of scene
 // e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window)
+// tail: TAIL_AUTO = the final block's last-frame shortcut wherever it applies (below); TAIL_NONE = every block on every slot (umgen_score_clip reads all of
+// them).  warped_all (STACK_MAP, or nullptr): [w.B][w.T][1024][E], the warped map of every slot beside warped_last.
 template <typename T>
-void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode = 0) {
+void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode = 0, int tail = TAIL_AUTO, float* warped_all = nullptr) {
     const int S = stack_len(stack);
     launch_embed_stack(e->stream, stack, e->tb, w, e->X, e->mapfeat);
     if (stack != STACK_EGO) launch_warp_map(e->stream, stack, e->tb, w.B, w.T, e->mapfeat, e->pose_diff, e->X,
-                                            stack == STACK_MAP ? e->warped_last : nullptr, w.Tfull, w.t0);
+                                            stack == STACK_MAP ? e->warped_last : nullptr, w.Tfull, w.t0, stack == STACK_MAP ? warped_all : nullptr);
     static const bool no_tail = getenv("UMGEN_NO_TAIL") != nullptr;   // measurement: evaluate every block on every frame like the reference
     for (size_t i = 0; i < e->stk[stack].size(); ++i) {
         const TarW& blk = e->stk[stack][i];
         TemporalRange tr{w.t0, cache_mode ? e->tcache[stack][i] : nullptr, e->cfg.max_cond_frames, (cache_mode == 1 || cache_mode == 3 || cache_mode == 4) ? 1 : 0};
         // the final block's tail on the last frame only (f-3): whole-window passes with more than one slot (the temporal sub-block still
         // evaluates the k | v rows of every slot, so a pass that fills the slot caches keeps the shortcut)
-        const bool last = i + 1 == e->stk[stack].size() && (cache_mode == 0 || cache_mode == 3) && w.T > 1 && !no_tail;
+        const bool last = i + 1 == e->stk[stack].size() && (cache_mode == 0 || cache_mode == 3) && w.T > 1 && !no_tail && tail == TAIL_AUTO;
         tar_sub<T>(e, blk.sub[0], w.B, w.T, S, false);
         tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_mode == 5);
         tar_sub<T>(e, blk.sub[2], w.B, w.T, S, false, TemporalRange{0, nullptr, 0, 0}, last ? 2 : 0);
@@ -192,19 +194,18 @@ void gemv_resid(umgen_engine* e, const float* a_in, long lda, const float* part,
     launch_gemv_resid<T>(e->stream, a);
 }
 
-// infer_ego_net / forward_ego_net (UMGen.py:994-1005, 634-687).  The Decoder is frame-local and only t = -1 is consumed
-// (UMGen.py:1002), so the 12 decoder blocks run on the last frame only -- identical outputs, 1/T of the work.
+// The ego decoder (Decoder.forward_func, module.py:662-683) and head_ego on n items (n <= max_batch): item i reads the frame whose 2207 rows start at row
+// frame_of[i] * 2207 of X (the ego stack's output) and takes the ego queries of window length Tq -- or of its own, d_item_T[i] (device, [n]), when given.
+// -> e->logits [3 n][pose_vocab]
 template <typename T>
-void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits,
-             int cache_mode = 0, float* logp = nullptr) {
-    const int E = e->E, H = e->H, B = w.B, Tn = w.T;   // Tn: slots in this pass (the last one is the window's last frame)
-    run_stack<T>(e, STACK_EGO, w, cache_mode);
-    // p = ln_ego_tar(x) of the last frame, kept in fp32 (every decoder block re-normalises it with its own ln_3)
+void ego_decoder(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T) {
+    const int E = e->E, H = e->H, B = n;
+    // p = ln_ego_tar(x) of the item's frame, kept in fp32 (every decoder block re-normalises it with its own ln_3)
     for (int b = 0; b < B; ++b)
-        launch_layernorm<float>(e->stream, e->X + (((long)b * Tn + (Tn - 1)) * kSeq) * E, E, kSeq, E, e->ln_ego_tar,
+        launch_layernorm<float>(e->stream, e->X + (frame_of[b] * kSeq) * E, E, kSeq, E, e->ln_ego_tar,
                                 e->pego + (long)b * kSeq * E);
     float* x = e->xdec;   // [3B][E] ego queries
-    launch_ego_queries(e->stream, e->tb, B, w.Tfull ? w.Tfull : Tn, x);
+    launch_ego_queries(e->stream, e->tb, B, Tq, x, d_item_T);
     const int M = 3 * B;
     T* PN = reinterpret_cast<T*>(e->A);         // ln_3(p)           [B*2207][E]
     T* KV = reinterpret_cast<T*>(e->QKV);       // k | v of ln_3(p)  [B*2207][2E]
@@ -224,6 +225,18 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
         gemv_resid<T>(e, e->hdec, 4L * E, nullptr, d.mlp.Wproj, nullptr, E, 4 * E, M, x, E);
     }
     gemv<T>(e, x, E, e->ln_ego, e->head_ego, nullptr, e->cfg.pose_vocab, E, M, GEMV_OUT_F32, e->logits, e->cfg.pose_vocab);
+}
+
+// infer_ego_net / forward_ego_net (UMGen.py:994-1005, 634-687).  The Decoder is frame-local and only t = -1 is consumed
+// (UMGen.py:1002), so the 12 decoder blocks run on the last frame only -- identical outputs, 1/T of the work.
+template <typename T>
+void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits,
+             int cache_mode = 0, float* logp = nullptr) {
+    const int B = w.B, Tn = w.T;   // Tn: slots in this pass (the last one is the window's last frame)
+    run_stack<T>(e, STACK_EGO, w, cache_mode);
+    std::vector<long> last(B);
+    for (int b = 0; b < B; ++b) last[b] = (long)b * Tn + (Tn - 1);
+    ego_decoder<T>(e, B, last.data(), w.Tfull ? w.Tfull : Tn, nullptr);
     if (trace_logits) hipMemcpyAsync(trace_logits, e->logits, (size_t)3 * e->cfg.pose_vocab * 4, hipMemcpyDeviceToHost, e->stream);
     launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, forced ? e->d_forced : nullptr, e->d_ego_tok, B,
                       e->d_counters + 7, logp);
@@ -236,8 +249,11 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
 // k | v rows in the decode cache.  Position P - 1 stays a decode step: its input goes to xdec and the step loop starts there.
 // Arithmetic: the stacks' contract (16-bit GEMM operands in the 16-bit modes, exact fp32 chains in fp32 mode) instead of the decode
 // step's fp32 activations -- the reference computes the prefix in one fp16-autocast pass as well.
+// src (umgen_score_clip; nullptr: the engine's own buffers): conditioning rows [B][2207][E], tokens [B][2199] and a [B][E] row buffer for position P - 1 that
+// may hold more than max_batch scenes (B <= max_batch * max_cond_frames: what the stacks' workspaces hold), and whether the decode cache, which holds
+// max_batch scenes, is left alone
 template <typename T>
-int run_prefix_prefill(umgen_engine* e, int B, int P) {
+int run_prefix_prefill(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr) {
     const int E = e->E, H = e->H, S = P - 1;
     if (S < 1 || S > e->S_pad) return e->fail(UMGEN_E_INVALID, "prefix pass over %d positions", S);
     hipStream_t st = e->stream;
@@ -246,7 +262,8 @@ int run_prefix_prefill(umgen_engine* e, int B, int P) {
     T* QKV = reinterpret_cast<T*>(e->QKV);
     T* Hb = reinterpret_cast<T*>(e->Hb);
     T* vt = reinterpret_cast<T*>(e->VT);
-    launch_prefix_rows(st, e->tb, e->tb.tske + (long)e->cfg.task_id * E, e->cond, e->d_tokens, B, P, e->X, e->xdec);
+    launch_prefix_rows(st, e->tb, e->tb.tske + (long)e->cfg.task_id * E, src ? src->cond : e->cond, src ? src->tokens : e->d_tokens, B, P, e->X,
+                       src ? src->x_last : e->xdec);
     const size_t wrow = (size_t)E * sizeof(T);
     for (size_t li = 0; li < e->oar.size(); ++li) {
         const SubW& w = e->oar[li];
@@ -258,8 +275,9 @@ int run_prefix_prefill(umgen_engine* e, int B, int P) {
         g.Mi = S; g.Nj = E; g.K = E; g.ldp = E; g.ldq = E; g.strideP = (long)S * E; g.strideQ = 0; g.batch = B;
         g.mode = GEMM_VT; g.bias = w.attn.bqkv + 2 * E; g.out = vt; g.ldo = e->S_pad; g.H = H;
         gemm_timed<T>(e, g);
-        launch_prefix_kv_to_cache<T>(st, QKV, vt, B, S, e->S_pad, H, e->Lmax, reinterpret_cast<T*>(e->kvcache) + (long)li * e->kv_layer_stride,
-                                     e->kv_scene_stride);
+        if (!src || !src->skip_cache)
+            launch_prefix_kv_to_cache<T>(st, QKV, vt, B, S, e->S_pad, H, e->Lmax, reinterpret_cast<T*>(e->kvcache) + (long)li * e->kv_layer_stride,
+                                         e->kv_scene_stride);
         Path<T>::attn_causal(st, QKV, vt, A, B, S, e->S_pad, H);
         linear_resid<T>(e, w.attn.Wo, w.attn.bo, E, E, A, R, e->X);
         launch_layernorm<T>(st, e->X, E, R, E, w.ln_b, A);
@@ -397,9 +415,13 @@ int build_tables(umgen_engine* e) {
 namespace umgen {
 
 // by-precision dispatchers, in run_frame_any's three-way form: templates on T do not cross files
-void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? run_stack<bf16_t>(e, stack, w, cache_mode)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_stack<f16_t>(e, stack, w, cache_mode) : run_stack<float>(e, stack, w, cache_mode);
+void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode, int tail, float* warped_all) {
+    e->cfg.precision == UMGEN_PREC_BF16 ? run_stack<bf16_t>(e, stack, w, cache_mode, tail, warped_all)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? run_stack<f16_t>(e, stack, w, cache_mode, tail, warped_all) : run_stack<float>(e, stack, w, cache_mode, tail, warped_all);
+}
+void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T) {
+    e->cfg.precision == UMGEN_PREC_BF16 ? ego_decoder<bf16_t>(e, n, frame_of, Tq, d_item_T)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? ego_decoder<f16_t>(e, n, frame_of, Tq, d_item_T) : ego_decoder<float>(e, n, frame_of, Tq, d_item_T);
 }
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
                  float* logp) {
@@ -407,9 +429,9 @@ void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp
     : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego<f16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
                                           : run_ego<float>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp);
 }
-int run_prefix_prefill_any(umgen_engine* e, int B, int P) {
-    return e->cfg.precision == UMGEN_PREC_BF16 ? run_prefix_prefill<bf16_t>(e, B, P)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_prefix_prefill<f16_t>(e, B, P) : run_prefix_prefill<float>(e, B, P);
+int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src) {
+    return e->cfg.precision == UMGEN_PREC_BF16 ? run_prefix_prefill<bf16_t>(e, B, P, src)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? run_prefix_prefill<f16_t>(e, B, P, src) : run_prefix_prefill<float>(e, B, P, src);
 }
 int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg) {
     return e->cfg.precision == UMGEN_PREC_BF16 ? launch_prefix<bf16_t>(e, io, ego, dbg)

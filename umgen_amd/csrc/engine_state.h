@@ -88,6 +88,13 @@ struct umgen_engine {
     // scenes whose slot caches the chunk's last-slot pass reads (run_stack cache mode 5)
     int* d_item_scene = nullptr;
     int fan_scenes = 0;
+    // umgen_score_clip (engine_frame.hip run_score_clip): allocated by its first call (ensure_score_clip), for max_batch * max_cond_frames items (b, slot) of one
+    // window pass.  clip_items [n][2] (scene, slot) and clip_item_T [n] (window length slot + 1); clip_warped [max_batch][max_cond_frames][1024][E], the map
+    // stack's warped map of every slot; clip_cond [n][2207][E]; clip_tokens [n][2199], each item's scored frame; clip_xlast [n][E] (the prefix rows' unused
+    // last position); clip_part / clip_logp / clip_arg: score_part / score_logp / score_arg for n items.  clip_state: 0 not tried, 1 allocated, -1 no room
+    int *clip_items = nullptr, *clip_item_T = nullptr, *clip_tokens = nullptr, *clip_arg = nullptr;
+    float *clip_warped = nullptr, *clip_cond = nullptr, *clip_xlast = nullptr, *clip_part = nullptr, *clip_logp = nullptr;
+    int clip_state = 0;
     // umgen_score_detail: allocated by its first call (engine_frame.hip ensure_score_detail).  det_part: the detail sweep's (row, split) records; det_row:
     // lse | target logit | row maximum | sum-exp of one modality's rows, [4][max_batch * 1024]; the results in score_logp's block layout, the lists with room for 16 per row (a call packs its topk)
     float *det_part = nullptr, *det_row = nullptr, *det_mass = nullptr, *det_ent = nullptr, *det_tlp = nullptr;
@@ -286,14 +293,34 @@ struct ScoreCandIO {
     int shared_slots;                            // out: T - 1 when the history slots ran once per scene, 0 on the replicated path
 };
 
+// umgen_score_clip's arguments: B recorded clips of L frames; every frame f in [T_in, L) is scored against the min(f, cond) frames before it
+struct ScoreClipIO {
+    int B, L, T_in, cond;
+    const int *pose, *map, *box, *img;          // [B][L][S_mod]
+    float* logp;                                 // host [B][L - T_in][2199], each frame pose | map | bbox3d | image
+    int* argmax;                                 // the same layout
+    int shared_frames;                           // out: frames per clip that were read off one window pass, 0 on the per-frame path
+};
+
+// what run_prefix_prefill reads and writes instead of the engine's per-scene buffers (umgen_score_clip: more items than max_batch)
+struct PrefillSrc {
+    const float* cond;                           // [B][2207][E]
+    const int* tokens;                           // [B][2199]
+    float* x_last;                               // [B][E]
+    bool skip_cache;                             // leave the decode cache alone (it holds max_batch scenes; a scoring pass never reads it)
+};
+// run_stack's `tail`
+enum { TAIL_AUTO = -1, TAIL_NONE = 0 };
+
 // ---- engine_weights.hip ---------------------------------------------------------------------------------------------
 void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);
 
 // ---- engine_stacks.hip: by-precision entry points of the templated compute path ------------------------------------
-void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode);
+void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
+void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
                  float* logp = nullptr);
-int run_prefix_prefill_any(umgen_engine* e, int B, int P);
+int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
     int foreground;                              // 1: the pass as stand-alone launches on the engine's stream, synchronised; 0: recorded and uploaded, nothing runs
@@ -328,5 +355,6 @@ int launch_bg_drain(umgen_engine* e, hipStream_t st);   // the launch without an
 int run_frame_any(umgen_engine* e, const FrameIO& io);
 int run_score_any(umgen_engine* e, const ScoreIO& sc);
 int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc);
+int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc);
 
 }  // namespace umgen

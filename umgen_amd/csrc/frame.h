@@ -83,10 +83,13 @@ struct SampleArgs {
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);
 // warp the map features by the ego motion and finish the map rows of X (UMGen.py:321-354, 729-736, 799-802, 836-840)
 void launch_warp_map(hipStream_t s, int stack, const EmbedTables& tb, int B, int T, const float* mapfeat, const float* pose_diff,
-                     float* X, float* warped_last, int Tfull = 0, int t0 = 0);
+                     float* X, float* warped_last, int Tfull = 0, int t0 = 0, float* warped_all = nullptr);   // warped_all: [B][T][1024][E], every slot's warped map
 // conditioning rows: LayerNorm of the last history frame of a stack (+ warped-map prior) -> cond[b][s] (UMGen.py:1496-1511)
 void launch_cond_rows(hipStream_t s, int stack, int B, int T, int E, const float* X, const float* ln_w, const float* warped_last,
                       float* cond);
+// the same rows of (scene, slot) items of a pass over T slots: items [n_items][2], warped_all [B][T][1024][E] (STACK_MAP) -> cond_all [n_items][2207][E]
+void launch_cond_rows_slots(hipStream_t s, int stack, int T, int E, const float* X, const float* ln_w, const float* warped_all, const int* items,
+                            int n_items, float* cond_all);
 // x[b] = row (+ cond[b][pos])
 void launch_first_input(hipStream_t s, int B, int E, const float* tske_row, const float* cond, float* x);
 void launch_fixed_token(hipStream_t s, const SampleArgs& a, int B);             // bos/eos/pose prefix steps
@@ -105,7 +108,7 @@ void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts
 // logp: nullptr, or [B][2199] -- entry [b][jq] receives log softmax(head_ego row)[pose token jq of scene b]
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
                        const int* forced, int* out_tokens, int B, int* overflow, float* logp = nullptr);
-// ego query rows: egoe[j] + spe[j] + tpe[T-1]
-void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x);
+// ego query rows: egoe[j] + spe[j] + tpe[T-1]; item_T [B] on the device (or nullptr): item i's own window length instead of T
+void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x, const int* item_T = nullptr);
 
 }  // namespace umgen

@@ -14,8 +14,8 @@ __global__ __launch_bounds__(128) void embed_stack_kernel(int stack, EmbedTables
 
 __global__ __launch_bounds__(128) void warp_map_kernel(int stack, EmbedTables tb, int T, const float* __restrict__ mapfeat,
                                                        const float* __restrict__ pose_diff, float* __restrict__ X,
-                                                       float* __restrict__ warped_last, int Tfull, int t0) {
-    warp_map_cell(stack, tb, T, mapfeat, pose_diff, X, warped_last, Tfull, t0, (long)blockIdx.x, (int)threadIdx.x);
+                                                       float* __restrict__ warped_last, int Tfull, int t0, float* __restrict__ warped_all) {
+    warp_map_cell(stack, tb, T, mapfeat, pose_diff, X, warped_last, Tfull, t0, (long)blockIdx.x, (int)threadIdx.x, warped_all);
 }
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat) {
@@ -32,8 +32,9 @@ void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const W
 
 
 void launch_warp_map(hipStream_t s, int stack, const EmbedTables& tb, int B, int T, const float* mapfeat, const float* pose_diff,
-                     float* X, float* warped_last, int Tfull, int t0) {
+                     float* X, float* warped_last, int Tfull, int t0, float* warped_all) {
     if (BgRecorder* rec = g_bg_rec) {
+        if (warped_all) { rec->failed = "warped map of every slot"; return; }      // (the recorded op has no such output: only stand-alone passes ask for it)
         const long cells = (long)B * T * kNMap;
         BgOp& o = rec->add(BG_WARP, 0, (cells + 3) / 4, 128, 80);
         o.h.i0 = stack; o.h.i1 = T; o.h.i2 = Tfull ? Tfull : T; o.h.i3 = t0; o.a.l1 = cells;
@@ -41,43 +42,77 @@ void launch_warp_map(hipStream_t s, int stack, const EmbedTables& tb, int B, int
         return;
     }
     hipLaunchKernelGGL(warp_map_kernel, dim3((unsigned)((long)B * T * kNMap)), dim3(128), 0, s, stack, tb, T, mapfeat, pose_diff, X,
-                       warped_last, Tfull ? Tfull : T, t0);
+                       warped_last, Tfull ? Tfull : T, t0, warped_all);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // conditioning rows of the OAR (UMGen.py:1496-1511, 1227-1231): last history frame of each stack after its final LN
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cond_rows_kernel(int stack, int T, int E, const float* __restrict__ X, const float* __restrict__ ln_w,
-                                                        const float* __restrict__ warped_last, float* __restrict__ cond, int n_rows) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int b = blockIdx.y;
-    if (r >= n_rows) return;
-    const int lane = threadIdx.x & 63;
-    int s;
-    if (stack == STACK_MAP) s = kMapBos + r;
-    else if (stack == STACK_BOX) s = kBoxBos + r;
-    else s = (r < 5) ? r : (kImgBos + (r - 5));
-    const int SS = stack_len(stack);
-    const float* xr = X + (((long)b * T + (T - 1)) * SS + s) * E;
+// one conditioning row by the 64 lanes of a wave: two-pass mean / variance of xr, (x - mean) * rstd * w, plus the warped-map prior wl (or nullptr)
+__device__ __forceinline__ void cond_row(const float* __restrict__ xr, const float* __restrict__ ln_w, const float* __restrict__ wl, float* __restrict__ o,
+                                         int E, int lane) {
     float sum = 0.f;
     for (int c = lane; c < E; c += 64) sum += xr[c];
     const float mean = wave_sum(sum) / (float)E;
     float q = 0.f;
     for (int c = lane; c < E; c += 64) { const float d = xr[c] - mean; q += d * d; }
     const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)E + 1e-5f);
-    float* o = cond + ((long)b * kSeq + s) * E;
-    const float* wl = (stack == STACK_MAP && s >= kMapC0 && s < kMapEos) ? warped_last + ((long)b * kNMap + (s - kMapC0)) * E : nullptr;
     for (int c = lane; c < E; c += 64) {
         float v = (xr[c] - mean) * rstd * ln_w[c];
         if (wl) v += wl[c];
         o[c] = v;
     }
 }
+// scene position of conditioning row r of a stack
+__device__ __forceinline__ int cond_row_pos(int stack, int r) {
+    if (stack == STACK_MAP) return kMapBos + r;
+    if (stack == STACK_BOX) return kBoxBos + r;
+    return (r < 5) ? r : (kImgBos + (r - 5));
+}
+
+__global__ __launch_bounds__(256) void cond_rows_kernel(int stack, int T, int E, const float* __restrict__ X, const float* __restrict__ ln_w,
+                                                        const float* __restrict__ warped_last, float* __restrict__ cond, int n_rows) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.y;
+    if (r >= n_rows) return;
+    const int lane = threadIdx.x & 63;
+    const int s = cond_row_pos(stack, r);
+    const int SS = stack_len(stack);
+    const float* xr = X + (((long)b * T + (T - 1)) * SS + s) * E;
+    float* o = cond + ((long)b * kSeq + s) * E;
+    const float* wl = (stack == STACK_MAP && s >= kMapC0 && s < kMapEos) ? warped_last + ((long)b * kNMap + (s - kMapC0)) * E : nullptr;
+    cond_row(xr, ln_w, wl, o, E, lane);
+}
+
+// the same rows for a list of (scene, slot) items of one pass over T slots: item i = (items[2 i], items[2 i + 1]) reads slot t of scene b -- rows
+// ((b T + t) S_stack + s) of X and warped_all[b][t] -- and writes cond_all[i] ([n_items][kSeq][E])
+__global__ __launch_bounds__(256) void cond_rows_slots_kernel(int stack, int T, int E, const float* __restrict__ X, const float* __restrict__ ln_w,
+                                                              const float* __restrict__ warped_all, const int* __restrict__ items,
+                                                              float* __restrict__ cond_all, int n_rows) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int i = blockIdx.y;
+    if (r >= n_rows) return;
+    const int lane = threadIdx.x & 63;
+    const int b = items[2 * i], t = items[2 * i + 1];
+    const int s = cond_row_pos(stack, r);
+    const int SS = stack_len(stack);
+    const float* xr = X + (((long)b * T + t) * SS + s) * E;
+    float* o = cond_all + ((long)i * kSeq + s) * E;
+    const float* wl = (stack == STACK_MAP && s >= kMapC0 && s < kMapEos) ? warped_all + (((long)b * T + t) * kNMap + (s - kMapC0)) * E : nullptr;
+    cond_row(xr, ln_w, wl, o, E, lane);
+}
+
+static int cond_row_count(int stack) { return stack == STACK_MAP ? 1026 : (stack == STACK_BOX ? 662 : 5 + 514); }
 
 void launch_cond_rows(hipStream_t s, int stack, int B, int T, int E, const float* X, const float* ln_w, const float* warped_last,
                       float* cond) {
-    const int n_rows = stack == STACK_MAP ? 1026 : (stack == STACK_BOX ? 662 : 5 + 514);
+    const int n_rows = cond_row_count(stack);
     hipLaunchKernelGGL(cond_rows_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, stack, T, E, X, ln_w, warped_last, cond, n_rows);
+}
+void launch_cond_rows_slots(hipStream_t s, int stack, int T, int E, const float* X, const float* ln_w, const float* warped_all, const int* items,
+                            int n_items, float* cond_all) {
+    const int n_rows = cond_row_count(stack);
+    hipLaunchKernelGGL(cond_rows_slots_kernel, dim3((n_rows + 3) / 4, n_items), dim3(256), 0, s, stack, T, E, X, ln_w, warped_all, items, cond_all, n_rows);
 }
 
 __global__ void first_input_kernel(int E, const float* __restrict__ row, const float* __restrict__ cond, float* __restrict__ x) {
@@ -88,14 +123,16 @@ void launch_first_input(hipStream_t s, int B, int E, const float* tske_row, cons
     hipLaunchKernelGGL(first_input_kernel, dim3(B), dim3(256), 0, s, E, tske_row, cond, x);
 }
 
-__global__ void ego_queries_kernel(EmbedTables tb, int T, float* __restrict__ x) {
+// item_T (or nullptr): the window length of every item, [B] -- item i takes tpe[item_T[i] - 1] instead of tpe[T - 1]
+__global__ void ego_queries_kernel(EmbedTables tb, int T, float* __restrict__ x, const int* __restrict__ item_T) {
     const int j = blockIdx.x % 3;
     const int E = tb.E;
+    const int Ti = item_T ? item_T[blockIdx.x / 3] : T;
     for (int c = threadIdx.x; c < E; c += blockDim.x)
-        x[(long)blockIdx.x * E + c] = (tb.egoe[(long)j * E + c] + tb.spe[(long)j * E + c]) + tb.tpe[(long)(T - 1) * E + c];
+        x[(long)blockIdx.x * E + c] = (tb.egoe[(long)j * E + c] + tb.spe[(long)j * E + c]) + tb.tpe[(long)(Ti - 1) * E + c];
 }
-void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x) {
-    hipLaunchKernelGGL(ego_queries_kernel, dim3(B * 3), dim3(256), 0, s, tb, T, x);
+void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x, const int* item_T) {
+    hipLaunchKernelGGL(ego_queries_kernel, dim3(B * 3), dim3(256), 0, s, tb, T, x, item_T);
 }
 
 // Last kernel of a decode step: every block has read st->step before it arrives here; the last block to arrive advances it.

@@ -77,9 +77,11 @@ __device__ inline float base_coord(int i) {   // at::linspace(-1, 1, 32) * 31 / 
     return (v * 31.0f) / 32.0f;
 }
 
-// grid cell `cell` = (b*T + t_local)*1024 + k by 128 threads
+// grid cell `cell` = (b*T + t_local)*1024 + k by 128 threads.  warped_all (or nullptr): [B][T][1024][E], the warped map of EVERY slot of the pass (the clip
+// scorer's conditioning rows read all of them); warped_last keeps slot Tfull - 1 only
 __device__ __forceinline__ void warp_map_cell(int stack, const EmbedTables tb, int T, const float* __restrict__ mapfeat, const float* __restrict__ pose_diff,
-                                              float* __restrict__ X, float* __restrict__ warped_last, int Tfull, int t0, long cell, int tid) {
+                                              float* __restrict__ X, float* __restrict__ warped_last, int Tfull, int t0, long cell, int tid,
+                                              float* __restrict__ warped_all = nullptr) {
     const int SS = stack_len(stack);
     const int k = (int)(cell % kNMap);
     const long fr = cell / kNMap;            // frame index inside this pass
@@ -113,6 +115,7 @@ __device__ __forceinline__ void warp_map_cell(int stack, const EmbedTables tb, i
     const float* spe = tb.spe + (long)s * E;
     const float* tpe = tb.tpe + (long)t * E;
     float* wl = (warped_last && t == Tfull - 1) ? warped_last + ((long)b * kNMap + k) * E : nullptr;
+    float* wa = warped_all ? warped_all + cell * E : nullptr;
     for (int c = tid; c < E; c += 128) {
         float o = 0.f;
         if (in_nw) o += pnw[c] * nw;
@@ -121,6 +124,7 @@ __device__ __forceinline__ void warp_map_cell(int stack, const EmbedTables tb, i
         if (in_se) o += pse[c] * se;
         xr[c] = ((o + f[c]) + spe[c]) + tpe[c];
         if (wl) wl[c] = o;
+        if (wa) wa[c] = o;
     }
 }
 

@@ -379,6 +379,66 @@ class Engine:
         return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER},
                 "total": pick(self._candidate_total(logp)), "shared_slots": int(shared.value)}
 
+    @staticmethod
+    def clip_windows(L: int, input_frames: int, cond_frames: int):
+        """The window rule of score_clip (and of a rollout, UMGen.py:1597-1603), stated once: [(f, start, n), ...] for every scored frame f in
+        [input_frames, L) -- frame f is scored against the n = min(f, cond_frames) frames clip[start : start + n], start = f - n."""
+        return [(f, f - min(f, cond_frames), min(f, cond_frames)) for f in range(input_frames, L)]
+
+    def _clip_args(self, clip: Dict[str, np.ndarray], input_frames, cond_frames):
+        """Shapes, token ranges and frame counts of a score_clip call, checked before anything reaches the device.  Returns (c [B, L, S], cond_frames, batched)."""
+        for m in MOD_ORDER:
+            if np.asarray(clip[m]).dtype.kind not in "iu":      # tokens are indices: a float array is a caller's mistake, not something to truncate
+                raise UMGenError(f"score_clip: clip[{m}] has dtype {np.asarray(clip[m]).dtype}, expected an integer type")
+        c = {m: _i64(clip[m]) for m in MOD_ORDER}
+        batched = c["pose"].ndim == 3
+        for m in MOD_ORDER:
+            if c[m].ndim != (3 if batched else 2):
+                raise UMGenError(f"score_clip: clip[{m}] has shape {c[m].shape}; expected [B, L, S] for every modality, or [L, S]")
+            if not batched:
+                c[m] = c[m][None]
+        B, L = c["pose"].shape[:2]
+        vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
+        for m in MOD_ORDER:
+            if c[m].shape != (B, L, CONTENT_LEN[m]):
+                raise UMGenError(f"score_clip: clip[{m}] has shape {c[m].shape}, expected {(B, L, CONTENT_LEN[m])}")
+            bad = np.flatnonzero((c[m].reshape(-1) < 0) | (c[m].reshape(-1) >= vocab[m]))
+            if bad.size:
+                raise UMGenError(f"score_clip: clip[{m}] token {int(c[m].reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
+        if isinstance(input_frames, bool) or not isinstance(input_frames, (int, np.integer)) or not 1 <= input_frames < L:
+            raise UMGenError(f"score_clip: input_frames={input_frames!r} must be an integer in [1, {L}) for a clip of {L} frames")
+        if cond_frames is None:
+            cond_frames = min(self.max_cond_frames, L - 1)
+        if isinstance(cond_frames, bool) or not isinstance(cond_frames, (int, np.integer)) or not 1 <= cond_frames <= self.max_cond_frames:
+            raise UMGenError(f"score_clip: cond_frames={cond_frames!r} must be an integer in [1, {self.max_cond_frames}] (max_cond_frames)")
+        if B < 1 or B > self.max_batch:
+            raise UMGenError(f"score_clip: {B} clips, the engine holds max_batch={self.max_batch}")
+        return c, int(cond_frames), batched
+
+    def score_clip(self, clip: Dict[str, np.ndarray], input_frames: int, cond_frames=None) -> dict:
+        """Per-token log-likelihoods of every frame of a recorded clip, each against the frames before it under the rollout's window rule
+        (umgen_score_clip: the teacher-forced counterpart of a rollout; the frames whose window starts at frame 0 are read off one pass).
+        clip: mod -> [B, L, S_mod] (or [L, S_mod]), an integer dtype; frames input_frames .. L - 1 are scored, frame f against the
+        min(f, cond_frames) frames before it (clip_windows); cond_frames defaults to min(max_cond_frames, L - 1).
+        Returns {"logp": {mod: float32 [B, F, S_mod]}, "argmax": {mod: int64 [B, F, S_mod]}, "total": float64 [B, F], "frames": int64 [F],
+        "shared_frames": int} with F = L - input_frames (without the B axis for un-batched inputs).  Entry (b, i) has the bits of
+        score(clip[b, start : f], clip[b, f]) for f = frames[i]; "total" is the sum of logp over the 2199 content positions of the frame;
+        "shared_frames" is the number of frames per clip that shared one pass, 0 when every frame ran its own (fewer than two growing windows,
+        no room for the clip buffers, UMGEN_SCORE_CLIP_SHARE=0)."""
+        c, cond_frames, batched = self._clip_args(clip, input_frames, cond_frames)
+        B, L = c["pose"].shape[:2]
+        F = L - int(input_frames)
+        logp = {m: np.full((B, F, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
+        arg = {m: np.full((B, F, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
+        out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
+                            **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+        shared = C.c_int32(-1)
+        self._check(self.lib.umgen_score_clip(self._h, B, L, int(input_frames), cond_frames, *[_p64(c[m]) for m in MOD_ORDER], C.byref(out), C.byref(shared)),
+                    "score_clip")
+        pick = (lambda a: a) if batched else (lambda a: a[0])
+        return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER},
+                "total": pick(self._candidate_total(logp)), "frames": np.arange(int(input_frames), L, dtype=np.int64), "shared_frames": int(shared.value)}
+
     def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True) -> np.ndarray:
         """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L).
         use_engine goes through int() as it is: 0 / False five launches per layer, 1 / True the XCD-resident engine, 3 the chip-wide engine.

@@ -247,3 +247,20 @@ class UMGen(nn.Module):
         res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=-1) for m in MOD_ORDER}
         res["best"] = np.argmax(res["total"], axis=-1).astype(np.int64)
         return res
+
+    @torch.no_grad()
+    def score_clip(self, tokens: Dict[str, torch.Tensor], input_cond_frames: int = 1, cond_frames: int = 20) -> Dict[str, dict]:
+        """The validation loss of the model over a recorded clip: ``tokens[m]`` [B, L, S_mod] (torch or numpy); every frame from
+        ``input_cond_frames`` on is scored against the frames before it, at most ``cond_frames`` of them -- `inference`'s window rule with the
+        recorded frames in place of generated ones (Engine.score_clip: the frames whose window starts at frame 0 share one pass).
+        Returns Engine.score_clip's dict -- "logp", "argmax", "total" (float64 [B, F]), "frames" (int64 [F]), "shared_frames" -- plus "nll":
+        mod -> float64 [B, F], the mean negative log-likelihood per frame."""
+        if not self._loaded:
+            raise UMGenError("load_state_dict() has not provided every tensor the model reads")
+        np_ = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
+        clip = {m: np_(tokens[m]) for m in MOD_ORDER}
+        if clip["pose"].ndim == 3 and clip["pose"].shape[0] > self._engine_args["max_batch"]:
+            self._recreate(max_batch=clip["pose"].shape[0])
+        res = self.engine.score_clip(clip, input_cond_frames, min(int(cond_frames), 20, self.rcfg.max_frame_len))      # (the engine's window cap)
+        res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=-1) for m in MOD_ORDER}
+        return res
