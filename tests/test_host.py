@@ -118,6 +118,25 @@ def test_library_exports_every_declared_symbol():
     assert lib.umgen_version().startswith(b"umgen_hip")
 
 
+VQ_HOOKS = {"umgen_dbg_vq_quantize": 8, "umgen_dbg_vq_quant_tile": 1, "umgen_dbg_vq_im2col": 8, "umgen_dbg_vq_im2col_s2": 6, "umgen_dbg_vq_upsample": 6,
+            "umgen_dbg_vq_from_nchw": 6, "umgen_dbg_vq_to_nchw": 6, "umgen_dbg_vq_group_norm": 8, "umgen_dbg_vq_softmax": 5}
+
+
+def test_library_exports_the_vq_kernel_hooks():
+    """The kernel-level hooks of csrc/debug_vq.hip: exported, listed, bound with their argument counts; the source is part of the build and of its hash."""
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build_library()
+    lib = _lib.load_library()
+    for name, n_args in VQ_HOOKS.items():
+        assert hasattr(lib, name), name
+        assert name in _lib.EXPORTS
+        assert len(getattr(lib, name).argtypes) == n_args and getattr(lib, name).restype is ctypes.c_int
+    assert {n for n in _lib.EXPORTS if n.startswith("umgen_dbg_vq_")} == set(VQ_HOOKS)
+    assert "debug_vq.hip" in _lib.SOURCES
+    src = open(os.path.join(_lib.CSRC, "debug_vq.hip")).read()
+    assert set(re.findall(r"^int (umgen_dbg_vq_[a-z_0-9]+)\(", src, re.M)) == set(VQ_HOOKS)
+
+
 def test_engine_fails_loudly_without_gpu():
     """No CPU fallback: on a box without a HIP device the product path raises instead of computing elsewhere."""
     if torch.cuda.is_available():

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 # UMGEN_LIB_PATH selects an alternative build of the SAME library (kernel experiments with extra -D flags); never a fallback
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
 SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
-           "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip"]
+           "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip", "debug_vq.hip"]
 EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
@@ -28,7 +28,9 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_embed_warp_slots", "umgen_dbg_cond_rows_slots", "umgen_dbg_ego_queries_slots",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego", "umgen_dbg_token_steps_logp", "umgen_dbg_sample_ego_logp",
            "umgen_dbg_head_nll", "umgen_dbg_head_nll_split", "umgen_dbg_head_detail", "umgen_dbg_logits_detail",
-           "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache"]
+           "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache",
+           "umgen_dbg_vq_quantize", "umgen_dbg_vq_quant_tile", "umgen_dbg_vq_im2col", "umgen_dbg_vq_im2col_s2", "umgen_dbg_vq_upsample", "umgen_dbg_vq_from_nchw", "umgen_dbg_vq_to_nchw",
+           "umgen_dbg_vq_group_norm", "umgen_dbg_vq_softmax"]
 
 HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
 
@@ -343,6 +345,15 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_bg_drain.argtypes = [vp]
     lib.umgen_dbg_bg_end.argtypes = [vp]
     lib.umgen_dbg_tcache.argtypes = [vp, i32, i32, vp, i32]
+    lib.umgen_dbg_vq_quantize.argtypes = [fp, i32, fp, i32, i32, C.c_long, i64p, fp]
+    lib.umgen_dbg_vq_quant_tile.argtypes = [i32]
+    lib.umgen_dbg_vq_im2col.argtypes = [fp, i32, i32, i32, i32, i32, fp, C.c_long]
+    lib.umgen_dbg_vq_im2col_s2.argtypes = [fp, i32, i32, i32, fp, C.c_long]
+    lib.umgen_dbg_vq_upsample.argtypes = [fp, i32, i32, i32, fp, C.c_long]
+    lib.umgen_dbg_vq_from_nchw.argtypes = [fp, C.c_long, i32, i32, fp, C.c_long]
+    lib.umgen_dbg_vq_to_nchw.argtypes = [fp, C.c_long, i32, i32, fp, C.c_long]
+    lib.umgen_dbg_vq_group_norm.argtypes = [fp, C.c_long, i32, fp, fp, i32, fp, C.c_long]
+    lib.umgen_dbg_vq_softmax.argtypes = [fp, i32, i32, i32, C.c_long]
     lib.umgen_vq_create.argtypes = [C.POINTER(VQConfig), C.POINTER(vp)]
     lib.umgen_vq_load_tensor.argtypes = [vp, C.c_char_p, fp, i64p, i32]
     lib.umgen_vq_finalize.argtypes = [vp]

@@ -82,6 +82,7 @@ int umgen_dbg_linear_vt(int flags, const void* act, const void* W, const float* 
 // launch_gemm_valu.  P [nP], Q [nQ] elements; bias [Mi] ([Nj] for GEMM_VT), nullable.  `out` is the caller's WHOLE buffer of out_n elements
 // (the operand type of the activations for GEMM_STORE / GEMM_VT, fp32 otherwise), uploaded as it is (NaN bits, residual values) and
 // downloaded whole; the GEMM's out pointer is element out_off of it.  Every address the geometry reaches is checked here first.
+// Mi need not be a multiple of 4 on the launch_gemm_valu path (its kernel stores the last 1 - 3 features one at a time); ldo must be.
 int umgen_dbg_gemm(int precP, int precQ, int mfma, const void* P, long nP, const void* Q, long nQ, const float* bias, int Mi, int Nj, int K,
                    long ldp, long ldq, long strideP, long strideQ, int batch, int mode, int gelu, long ldo, long strideO, int H, int tile256,
                    void* out, long out_off, long out_n) {
@@ -97,7 +98,7 @@ int umgen_dbg_gemm(int precP, int precQ, int mfma, const void* P, long nP, const
     if (ldo % al != 0 || strideO % al != 0 || out_off % al != 0 || ldo < Mi) return UMGEN_E_INVALID;
     if (mode == GEMM_VT) {
         if (H < 1 || Nj > H * kHeadDim || out_off + (long)batch * H * kHeadDim * ldo > out_n) return UMGEN_E_INVALID;
-    } else if (Mi % 4 != 0 || (batch > 1 && strideO < (long)(Nj - 1) * ldo + Mi) || out_off + (batch - 1) * strideO + (long)(Nj - 1) * ldo + Mi > out_n) {
+    } else if ((Mi % 4 != 0 && use_mfma) || (batch > 1 && strideO < (long)(Nj - 1) * ldo + Mi) || out_off + (batch - 1) * strideO + (long)(Nj - 1) * ldo + Mi > out_n) {
         return UMGEN_E_INVALID;
     }
     const size_t esP = precP ? 2 : 4, esQ = precQ ? 2 : 4, esO = prec_o ? 2 : 4;

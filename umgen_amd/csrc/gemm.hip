@@ -46,6 +46,21 @@ __device__ inline void epilogue4(const GemmArgs& a, int z, int i0, int j, const 
     }
 }
 
+// The last 1 - 3 features of an Mi that is no multiple of 4, one at a time: what epilogue4 computes for them, without its 16-byte
+// store (which would run into the next row, or past the buffer behind the last one).  GEMM_VT handles its own tail in epilogue4.
+template <int MODE, typename TO>
+__device__ inline void epilogue_tail(const GemmArgs& a, int z, int i0, int j, const float (&v)[4]) {
+    if (j >= a.Nj) return;
+    for (int r = 0; r < 4 && i0 + r < a.Mi; ++r) {
+        float t = v[r] + (a.bias ? a.bias[i0 + r] : 0.f);
+        if (MODE == GEMM_STORE && a.gelu) t = gelu_for<TO>(t);
+        const long at = (long)z * a.strideO + (long)j * a.ldo + i0 + r;
+        if (MODE == GEMM_RESID) reinterpret_cast<float*>(a.out)[at] += t;
+        else if (MODE == GEMM_STORE_F32) reinterpret_cast<float*>(a.out)[at] = t;
+        else reinterpret_cast<TO*>(a.out)[at] = Cvt<TO>::from_f(t);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // MFMA bf16
 // ---------------------------------------------------------------------------------------------------------
@@ -562,7 +577,9 @@ __global__ __launch_bounds__(256) void gemm_valu_kernel(GemmArgs a) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         float v[4] = {acc[0][c], acc[1][c], acc[2][c], acc[3][c]};
-        epilogue4<MODE, TO>(a, z, i_base + 4 * ti, j_base + 4 * tj + c, v);
+        const int i0 = i_base + 4 * ti;
+        if (MODE != GEMM_VT && i0 < a.Mi && i0 + 3 >= a.Mi) epilogue_tail<MODE, TO>(a, z, i0, j_base + 4 * tj + c, v);   // (only this kernel runs an Mi % 4 != 0)
+        else epilogue4<MODE, TO>(a, z, i0, j_base + 4 * tj + c, v);
     }
 }
 

@@ -121,11 +121,12 @@ __global__ void vq_gn_apply_kernel(const float* __restrict__ x, const float* __r
     y[i] = v;
 }
 
-// row softmax of the attention scores: w[i][:] = softmax(s[i][:] * scale)  (AttnBlock, vq_modules.py:158-160); one wave per row
-__global__ __launch_bounds__(256) void vq_softmax_kernel(float* __restrict__ s, int n, float scale) {
+// row softmax of the attention scores: w[i][:] = softmax(s[i][:] * scale)  (AttnBlock, vq_modules.py:158-160); one wave per row of
+// n scores, rows ld floats apart (columns n .. ld - 1 are left alone)
+__global__ __launch_bounds__(256) void vq_softmax_kernel(float* __restrict__ s, int n, int ld, float scale) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
-    float* r = s + (long)row * n;
+    float* r = s + (long)row * ld;
     float mx = -INFINITY;
     for (int j = lane; j < n; j += 64) mx = fmaxf(mx, r[j] * scale);
     mx = wave_max(mx);
@@ -136,7 +137,158 @@ __global__ __launch_bounds__(256) void vq_softmax_kernel(float* __restrict__ s, 
     for (int j = lane; j < n; j += 64) r[j] *= inv;
 }
 
+// nearest-neighbour x2 upsampling (F.interpolate(scale_factor=2, mode="nearest")), channels last
+__global__ void vq_upsample_kernel(const float* __restrict__ x, int H, int W, int C, float* __restrict__ y) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int C4 = C >> 2;
+    const long total = (long)4 * H * W * C4;
+    if (i >= total) return;
+    const int c4 = (int)(i % C4);
+    const long p = i / C4;
+    const int ox = (int)(p % (2 * W)), oy = (int)(p / (2 * W));
+    reinterpret_cast<float4*>(y + p * C)[c4] = reinterpret_cast<const float4*>(x + ((long)(oy >> 1) * W + (ox >> 1)) * C)[c4];
+}
+
+// out[c][p] (channels first, the reference's output layout) = x[p][c]
+__global__ void vq_to_nchw_kernel(const float* __restrict__ x, long n_px, int C, int ldx, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_px * C) return;
+    const long p = i % n_px;
+    const int c = (int)(i / n_px);
+    out[i] = x[p * ldx + c];
+}
+
+// y[p][c] = x[c][p] for c < C_in, 0 for the pad lanes C_in <= c < C (C a multiple of 4: the im2col kernels move float4s)
+__global__ void vq_from_nchw_kernel(const float* __restrict__ x, long n_px, int C_in, int C, float* __restrict__ y) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_px * C) return;
+    const long p = i / C;
+    const int c = (int)(i % C);
+    y[i] = c < C_in ? x[(long)c * n_px + p] : 0.f;
+}
+
+// Downsample: col[(oy, ox)][(ky * 3 + kx) * C + c] = x[2 oy + ky][2 ox + kx][c], zero where that is the pad column right of the
+// frame or the pad row below it (F.pad(x, (0, 1, 0, 1)), then a 3 x 3 stride-2 convolution without padding).  H, W even.
+__global__ void vq_im2col_s2_kernel(const float* __restrict__ x, int H, int W, int C, float* __restrict__ col) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // one float4 of 4 channels
+    const int C4 = C >> 2, Ho = H >> 1, Wo = W >> 1;
+    const long total = (long)Ho * Wo * 9 * C4;
+    if (i >= total) return;
+    const int c4 = (int)(i % C4);
+    const long r = i / C4;
+    const int kk = (int)(r % 9);
+    const long p = r / 9;
+    const int ox = (int)(p % Wo), oy = (int)(p / Wo);
+    const int sy = 2 * oy + kk / 3, sx = 2 * ox + kk % 3;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (sy < H && sx < W) v = reinterpret_cast<const float4*>(x + ((long)sy * W + sx) * C)[c4];
+    reinterpret_cast<float4*>(col + (p * 9 + kk) * C)[c4] = v;
+}
+
+// e2[n] = |e_n|^2 of every codebook row (once, at finalize)
+__global__ void vq_code_norms_kernel(const float* __restrict__ emb, int N, int D, float* __restrict__ e2) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float s = 0.f;
+    for (int c = 0; c < D; ++c) s = fmaf(emb[(long)n * D + c], emb[(long)n * D + c], s);
+    e2[n] = s;
+}
+
+// NormEMAVectorQuantizer.forward up to the arg-min (quantize.py:417-429): one wave per token position.
+//   z = row / max(|row|_2, 1e-12);   d_n = |z|^2 + |e_n|^2 - 2 z.e_n  (three terms, fp32);   code = first n with the smallest d_n
+// The codebook streams through LDS in tiles of `tile` rows (row stride D + 4 floats: a lane's float4 reads of its own row then
+// spread over the banks); lane l of a wave looks at rows l, l + 64, ... of every tile in ascending order and keeps the first
+// minimum, the wave reduction keeps the lower index on equal distance: torch.argmin's answer.  4 positions per workgroup.
+constexpr int kQuantMaxD = 64;
+__global__ __launch_bounds__(256) void vq_quantize_kernel(const float* __restrict__ h, int ldh, const float* __restrict__ emb,
+                                                          const float* __restrict__ e2, int N, int D, int tile, long n_pos,
+                                                          long long* __restrict__ codes, float* __restrict__ zn) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int LD = D + 4;
+    float* sE = smem;                        // [tile][LD]
+    float* sE2 = sE + (long)tile * LD;       // [tile]
+    float* sZ = sE2 + tile;                  // [4][kQuantMaxD]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long pos = (long)blockIdx.x * 4 + wave;
+    const bool live = pos < n_pos;           // (every wave stays for the barriers below)
+    float zz = 0.f;
+    if (live) {
+        const float* row = h + pos * ldh;
+        float ss = 0.f;
+        for (int c = 0; c < D; ++c) ss = fmaf(row[c], row[c], ss);
+        const float den = fmaxf(sqrtf(ss), 1e-12f);                       // F.normalize(p=2, dim=-1, eps=1e-12)
+        if (lane < D) {
+            const float v = row[lane] / den;
+            sZ[wave * kQuantMaxD + lane] = v;
+            zn[pos * D + lane] = v;
+        }
+    }
+    __syncthreads();
+    if (live)
+        for (int c = 0; c < D; ++c) zz = fmaf(sZ[wave * kQuantMaxD + c], sZ[wave * kQuantMaxD + c], zz);
+    float best = INFINITY;
+    int best_n = 0x7fffffff;
+    const int D4 = D >> 2;
+    for (int n0 = 0; n0 < N; n0 += tile) {
+        const int rows = min(tile, N - n0);
+        for (int i = threadIdx.x; i < rows * D4; i += 256) {
+            const int r = i / D4, c4 = i % D4;
+            *reinterpret_cast<float4*>(sE + r * LD + 4 * c4) = reinterpret_cast<const float4*>(emb + (long)(n0 + r) * D)[c4];
+        }
+        for (int i = threadIdx.x; i < rows; i += 256) sE2[i] = e2[n0 + i];
+        __syncthreads();
+        if (live)
+            for (int r = lane; r < rows; r += 64) {
+                float dot = 0.f;
+                for (int c4 = 0; c4 < D4; ++c4) {
+                    const float4 ev = *reinterpret_cast<const float4*>(sE + r * LD + 4 * c4);
+                    const float4 zv = *reinterpret_cast<const float4*>(sZ + wave * kQuantMaxD + 4 * c4);
+                    dot = fmaf(zv.x, ev.x, dot); dot = fmaf(zv.y, ev.y, dot); dot = fmaf(zv.z, ev.z, dot); dot = fmaf(zv.w, ev.w, dot);
+                }
+                const float d = (zz + sE2[r]) - 2.0f * dot;
+                if (d < best) { best = d; best_n = n0 + r; }             // ascending n per lane: the first minimum stays
+            }
+        __syncthreads();
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_xor(best, o);
+        const int on = __shfl_xor(best_n, o);
+        if (od < best || (od == best && on < best_n)) { best = od; best_n = on; }
+    }
+    if (live && lane == 0) codes[pos] = best_n == 0x7fffffff ? 0 : best_n;     // (no row compared below +inf: only a non-finite z)
+}
+
 inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
+
+// the one launch of each kernel above (the handles and the test hooks of debug_vq.hip go through these)
+inline void launch_im2col(hipStream_t s, const float* x, int H, int W, int C, int KS, int pad, float* col) {
+    hipLaunchKernelGGL(vq_im2col_kernel, grid1d((long)H * W * KS * KS * (C / 4)), dim3(256), 0, s, x, H, W, C, KS, pad, col);
+}
+inline void launch_im2col_s2(hipStream_t s, const float* x, int H, int W, int C, float* col) {
+    hipLaunchKernelGGL(vq_im2col_s2_kernel, grid1d((long)(H / 2) * (W / 2) * 9 * (C / 4)), dim3(256), 0, s, x, H, W, C, col);
+}
+inline void launch_upsample(hipStream_t s, const float* x, int H, int W, int C, float* y) {
+    hipLaunchKernelGGL(vq_upsample_kernel, grid1d((long)4 * H * W * (C / 4)), dim3(256), 0, s, x, H, W, C, y);
+}
+inline void launch_from_nchw(hipStream_t s, const float* x, long n_px, int C_in, int C, float* y) {
+    hipLaunchKernelGGL(vq_from_nchw_kernel, grid1d(n_px * C), dim3(256), 0, s, x, n_px, C_in, C, y);
+}
+inline void launch_to_nchw(hipStream_t s, const float* x, long n_px, int C, int ldx, float* out) {
+    hipLaunchKernelGGL(vq_to_nchw_kernel, grid1d(n_px * C), dim3(256), 0, s, x, n_px, C, ldx, out);
+}
+// softmax(scores * C^-0.5) over the n columns of n rows, ld floats apart: int(c) ** (-0.5)
+inline void launch_softmax(hipStream_t s, float* scores, int n, int ld, int C) {
+    hipLaunchKernelGGL(vq_softmax_kernel, dim3((n + 3) / 4), dim3(256), 0, s, scores, n, ld, 1.0f / sqrtf((float)C));
+}
+inline void launch_code_norms(hipStream_t s, const float* emb, int N, int D, float* e2) {
+    hipLaunchKernelGGL(vq_code_norms_kernel, grid1d(N), dim3(256), 0, s, emb, N, D, e2);
+}
+// codebook tile of the quantiser: at most 512 rows and 40 KB of LDS, a multiple of 64 rows
+inline int quant_tile(int D) { return std::max(64, std::min(512, (10240 / (D + 4)) & ~63)); }
+inline size_t quant_lds(int D) { return ((size_t)quant_tile(D) * (D + 4) + quant_tile(D) + 4 * kQuantMaxD) * sizeof(float); }
+inline void launch_quantize(hipStream_t s, const float* h, int ldh, const float* emb, const float* e2, int N, int D, long n_pos, long long* codes, float* zn) {
+    hipLaunchKernelGGL(vq_quantize_kernel, dim3((unsigned)((n_pos + 3) / 4)), dim3(256), quant_lds(D), s, h, ldh, emb, e2, N, D, quant_tile(D), n_pos, codes, zn);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host
@@ -231,8 +383,7 @@ void conv(Ctx* e, const Conv& c, const float* x, int H, int W, float* out, bool 
     const float* act = x;
     int K = c.cin;
     if (c.ks > 1) {
-        const long total = n_px * c.ks * c.ks * (c.cin / 4);
-        hipLaunchKernelGGL(vq_im2col_kernel, grid1d(total), dim3(256), 0, e->stream, x, H, W, c.cin, c.ks, c.pad, e->col);
+        launch_im2col(e->stream, x, H, W, c.cin, c.ks, c.pad, e->col);
         act = e->col;
         K = c.cin * c.ks * c.ks;
     }
@@ -255,27 +406,30 @@ void res_block(Ctx* e, const Res& r, int H, int W) {
     conv(e, r.c2, e->h, H, W, e->x, true);            // x + conv2(h)
 }
 // AttnBlock.forward (vq_modules.py:150-176): x += proj_out(softmax(q k^T / sqrt(C)) v)
+// The rows of the scores and of v^T are ld = n rounded up to 4 floats apart: the GEMM epilogues store 16 bytes at a time, and a row
+// of n floats would start off that alignment whenever n is no multiple of 4 (the columns n .. ld - 1 are never read)
+inline long attn_ld(long n) { return (n + 3) & ~3L; }
 void attn_block(Ctx* e, const Attn& a, int H, int W) {
-    const int n = H * W, C = a.n.c;
+    const int n = H * W, C = a.n.c, ld = (int)attn_ld(n);
     group_norm(e, a.n, e->x, n, false, e->h);
     conv(e, a.q, e->h, H, W, e->q, false);
     conv(e, a.k, e->h, H, W, e->k, false);
     {   // v^T[c][j] = sum_k Wv[c][k] h[j][k] + bv[c]: channels-first so that it is the K-contiguous operand of the second product
         GemmArgs g{};
         g.P = e->h; g.Q = a.v.w; g.Mi = n; g.Nj = C; g.K = C; g.ldp = C; g.ldq = C; g.batch = 1;
-        g.mode = GEMM_VT; g.bias = a.v.b; g.out = e->vt; g.ldo = n; g.H = C / kHeadDim;   // (row index (j / 48) * 48 + j % 48 = j)
+        g.mode = GEMM_VT; g.bias = a.v.b; g.out = e->vt; g.ldo = ld; g.H = C / kHeadDim;   // (row index (j / 48) * 48 + j % 48 = j)
         launch_gemm_valu<float, float>(e->stream, g);
     }
     {   // scores[i][j] = sum_c q[i][c] k[j][c]
         GemmArgs g{};
         g.P = e->k; g.Q = e->q; g.Mi = n; g.Nj = n; g.K = C; g.ldp = C; g.ldq = C; g.batch = 1;
-        g.mode = GEMM_STORE; g.out = e->scores; g.ldo = n;
+        g.mode = GEMM_STORE; g.out = e->scores; g.ldo = ld;
         launch_gemm_valu<float, float>(e->stream, g);
     }
-    hipLaunchKernelGGL(vq_softmax_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->scores, n, 1.0f / sqrtf((float)C));   // int(c) ** (-0.5)
+    launch_softmax(e->stream, e->scores, n, ld, C);
     {   // h[i][c] = sum_j w[i][j] v^T[c][j]
         GemmArgs g{};
-        g.P = e->vt; g.Q = e->scores; g.Mi = C; g.Nj = n; g.K = n; g.ldp = n; g.ldq = n; g.batch = 1;
+        g.P = e->vt; g.Q = e->scores; g.Mi = C; g.Nj = n; g.K = n; g.ldp = ld; g.ldq = ld; g.batch = 1;
         g.mode = GEMM_STORE; g.out = e->h; g.ldo = C;
         launch_gemm_valu<float, float>(e->stream, g);
     }

@@ -19,27 +19,6 @@ __global__ void vq_embed_kernel(const long long* __restrict__ codes, const float
     z[i] = emb[codes[p] * C + (i % C)];
 }
 
-// nearest-neighbour x2 upsampling (F.interpolate(scale_factor=2, mode="nearest")), channels last
-__global__ void vq_upsample_kernel(const float* __restrict__ x, int H, int W, int C, float* __restrict__ y) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int C4 = C >> 2;
-    const long total = (long)4 * H * W * C4;
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    const long p = i / C4;
-    const int ox = (int)(p % (2 * W)), oy = (int)(p / (2 * W));
-    reinterpret_cast<float4*>(y + p * C)[c4] = reinterpret_cast<const float4*>(x + ((long)(oy >> 1) * W + (ox >> 1)) * C)[c4];
-}
-
-// out[c][p] (channels first, the reference's output layout) = x[p][c]
-__global__ void vq_to_nchw_kernel(const float* __restrict__ x, long n_px, int C, int ldx, float* __restrict__ out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_px * C) return;
-    const long p = i % n_px;
-    const int c = (int)(i / n_px);
-    out[i] = x[p * ldx + c];
-}
-
 struct Level { std::vector<Res> block; std::vector<Attn> attn; Conv up; bool has_up = false; };
 
 }  // namespace
@@ -146,8 +125,8 @@ int umgen_vq_create(const umgen_vq_config* cfg, umgen_vq** out) {
             if (lv != 0) { res *= 2; n *= 4; }
         }
         if (n_att > 16384) return e->fail(UMGEN_E_UNSUPPORTED, "attention over %ld positions (scores would need %ld MB)", n_att, n_att * n_att * 4 >> 20);
-        if (int rc = vq_alloc(e, &e->scores, (size_t)n_att * n_att)) return rc;
-        for (float** p : {&e->q, &e->k, &e->vt}) { if (int rc = vq_alloc(e, p, (size_t)n_att * max_c)) return rc; }
+        if (int rc = vq_alloc(e, &e->scores, (size_t)n_att * attn_ld(n_att))) return rc;
+        for (float** p : {&e->q, &e->k, &e->vt}) { if (int rc = vq_alloc(e, p, (size_t)attn_ld(n_att) * max_c)) return rc; }
     }
     VQCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_codes), (size_t)cfg->token_h * cfg->token_w * sizeof(long long)));
     e->allocs.push_back(e->d_codes);
@@ -193,14 +172,14 @@ int umgen_vq_decode(umgen_vq* e, int32_t n, const int64_t* codes, float* out) {
                 if (!u.attn.empty()) attn_block(e, u.attn[b], H, W);
             }
             if (u.has_up) {
-                hipLaunchKernelGGL(vq_upsample_kernel, grid1d((long)4 * H * W * (u.up.cin / 4)), dim3(256), 0, e->stream, e->x, H, W, u.up.cin, e->h);
+                launch_upsample(e->stream, e->x, H, W, u.up.cin, e->h);
                 H *= 2; W *= 2;
                 conv(e, u.up, e->h, H, W, e->x, false);
             }
         }
         group_norm(e, e->norm_out, e->x, (long)H * W, true, e->h);
         conv(e, e->conv_out, e->h, H, W, e->t, false);
-        hipLaunchKernelGGL(vq_to_nchw_kernel, grid1d((long)H * W * cfg.out_ch), dim3(256), 0, e->stream, e->t, (long)H * W, cfg.out_ch, e->conv_out.cout_pad, e->d_out);
+        launch_to_nchw(e->stream, e->t, (long)H * W, cfg.out_ch, e->conv_out.cout_pad, e->d_out);
         VQCHK(e, hipMemcpyAsync(out + (size_t)f * cfg.out_ch * H * W, e->d_out, (size_t)cfg.out_ch * H * W * 4, hipMemcpyDeviceToHost, e->stream));
         VQCHK(e, hipStreamSynchronize(e->stream));
     }

@@ -8,110 +8,10 @@
 // not reproduced.
 //
 // Layout and arithmetic (channels-last fp32 activations, every convolution one fp32 GEMM of this library) and the blocks shared with
-// the decoder are in vq_common.h.  New here: the NCHW ingest, the stride-2 im2col of Downsample and the quantiser.
+// the decoder are in vq_common.h.  The NCHW ingest, the stride-2 im2col of Downsample and the quantiser used here are kept there too, beside their launchers.
 #include "vq_common.h"
 
 namespace {
-
-// y[p][c] = x[c][p] for c < C_in, 0 for the pad lanes C_in <= c < C (C a multiple of 4: the im2col kernels move float4s)
-__global__ void vq_from_nchw_kernel(const float* __restrict__ x, long n_px, int C_in, int C, float* __restrict__ y) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_px * C) return;
-    const long p = i / C;
-    const int c = (int)(i % C);
-    y[i] = c < C_in ? x[(long)c * n_px + p] : 0.f;
-}
-
-// Downsample: col[(oy, ox)][(ky * 3 + kx) * C + c] = x[2 oy + ky][2 ox + kx][c], zero where that is the pad column right of the
-// frame or the pad row below it (F.pad(x, (0, 1, 0, 1)), then a 3 x 3 stride-2 convolution without padding).  H, W even.
-__global__ void vq_im2col_s2_kernel(const float* __restrict__ x, int H, int W, int C, float* __restrict__ col) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // one float4 of 4 channels
-    const int C4 = C >> 2, Ho = H >> 1, Wo = W >> 1;
-    const long total = (long)Ho * Wo * 9 * C4;
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    const long r = i / C4;
-    const int kk = (int)(r % 9);
-    const long p = r / 9;
-    const int ox = (int)(p % Wo), oy = (int)(p / Wo);
-    const int sy = 2 * oy + kk / 3, sx = 2 * ox + kk % 3;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sy < H && sx < W) v = reinterpret_cast<const float4*>(x + ((long)sy * W + sx) * C)[c4];
-    reinterpret_cast<float4*>(col + (p * 9 + kk) * C)[c4] = v;
-}
-
-// e2[n] = |e_n|^2 of every codebook row (once, at finalize)
-__global__ void vq_code_norms_kernel(const float* __restrict__ emb, int N, int D, float* __restrict__ e2) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    float s = 0.f;
-    for (int c = 0; c < D; ++c) s = fmaf(emb[(long)n * D + c], emb[(long)n * D + c], s);
-    e2[n] = s;
-}
-
-// NormEMAVectorQuantizer.forward up to the arg-min (quantize.py:417-429): one wave per token position.
-//   z = row / max(|row|_2, 1e-12);   d_n = |z|^2 + |e_n|^2 - 2 z.e_n  (three terms, fp32);   code = first n with the smallest d_n
-// The codebook streams through LDS in tiles of `tile` rows (row stride D + 4 floats: a lane's float4 reads of its own row then
-// spread over the banks); lane l of a wave looks at rows l, l + 64, ... of every tile in ascending order and keeps the first
-// minimum, the wave reduction keeps the lower index on equal distance: torch.argmin's answer.  4 positions per workgroup.
-constexpr int kQuantMaxD = 64;
-__global__ __launch_bounds__(256) void vq_quantize_kernel(const float* __restrict__ h, int ldh, const float* __restrict__ emb,
-                                                          const float* __restrict__ e2, int N, int D, int tile, long n_pos,
-                                                          long long* __restrict__ codes, float* __restrict__ zn) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int LD = D + 4;
-    float* sE = smem;                        // [tile][LD]
-    float* sE2 = sE + (long)tile * LD;       // [tile]
-    float* sZ = sE2 + tile;                  // [4][kQuantMaxD]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long pos = (long)blockIdx.x * 4 + wave;
-    const bool live = pos < n_pos;           // (every wave stays for the barriers below)
-    float zz = 0.f;
-    if (live) {
-        const float* row = h + pos * ldh;
-        float ss = 0.f;
-        for (int c = 0; c < D; ++c) ss = fmaf(row[c], row[c], ss);
-        const float den = fmaxf(sqrtf(ss), 1e-12f);                       // F.normalize(p=2, dim=-1, eps=1e-12)
-        if (lane < D) {
-            const float v = row[lane] / den;
-            sZ[wave * kQuantMaxD + lane] = v;
-            zn[pos * D + lane] = v;
-        }
-    }
-    __syncthreads();
-    if (live)
-        for (int c = 0; c < D; ++c) zz = fmaf(sZ[wave * kQuantMaxD + c], sZ[wave * kQuantMaxD + c], zz);
-    float best = INFINITY;
-    int best_n = 0x7fffffff;
-    const int D4 = D >> 2;
-    for (int n0 = 0; n0 < N; n0 += tile) {
-        const int rows = min(tile, N - n0);
-        for (int i = threadIdx.x; i < rows * D4; i += 256) {
-            const int r = i / D4, c4 = i % D4;
-            *reinterpret_cast<float4*>(sE + r * LD + 4 * c4) = reinterpret_cast<const float4*>(emb + (long)(n0 + r) * D)[c4];
-        }
-        for (int i = threadIdx.x; i < rows; i += 256) sE2[i] = e2[n0 + i];
-        __syncthreads();
-        if (live)
-            for (int r = lane; r < rows; r += 64) {
-                float dot = 0.f;
-                for (int c4 = 0; c4 < D4; ++c4) {
-                    const float4 ev = *reinterpret_cast<const float4*>(sE + r * LD + 4 * c4);
-                    const float4 zv = *reinterpret_cast<const float4*>(sZ + wave * kQuantMaxD + 4 * c4);
-                    dot = fmaf(zv.x, ev.x, dot); dot = fmaf(zv.y, ev.y, dot); dot = fmaf(zv.z, ev.z, dot); dot = fmaf(zv.w, ev.w, dot);
-                }
-                const float d = (zz + sE2[r]) - 2.0f * dot;
-                if (d < best) { best = d; best_n = n0 + r; }             // ascending n per lane: the first minimum stays
-            }
-        __syncthreads();
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float od = __shfl_xor(best, o);
-        const int on = __shfl_xor(best_n, o);
-        if (od < best || (od == best && on < best_n)) { best = od; best_n = on; }
-    }
-    if (live && lane == 0) codes[pos] = best_n == 0x7fffffff ? 0 : best_n;     // (no row compared below +inf: only a non-finite z)
-}
 
 struct Level { std::vector<Res> block; std::vector<Attn> attn; Conv down; bool has_down = false; };
 
@@ -130,8 +30,7 @@ struct umgen_vqenc : Ctx {
     float* d_in = nullptr;         // one frame [in_ch][H][W]
     long long* d_codes = nullptr;
     float* d_z = nullptr;          // normalised rows of one frame
-    int in_h = 0, in_w = 0, q_tile = 0;
-    size_t q_lds = 0;
+    int in_h = 0, in_w = 0;
 };
 
 extern "C" {
@@ -212,16 +111,13 @@ int umgen_vqenc_create(const umgen_vq_config* cfg, int32_t in_channels, umgen_vq
     if (int rc = vq_alloc(e, &e->col, colsz)) return rc;
     if (int rc = vq_alloc(e, &e->stats, 64)) return rc;
     if (n_att > 16384) return e->fail(UMGEN_E_UNSUPPORTED, "attention over %ld positions (scores would need %ld MB)", n_att, n_att * n_att * 4 >> 20);
-    if (int rc = vq_alloc(e, &e->scores, (size_t)n_att * n_att)) return rc;
-    for (float** p : {&e->q, &e->k, &e->vt}) { if (int rc = vq_alloc(e, p, (size_t)n_att * max_c)) return rc; }
+    if (int rc = vq_alloc(e, &e->scores, (size_t)n_att * attn_ld(n_att))) return rc;
+    for (float** p : {&e->q, &e->k, &e->vt}) { if (int rc = vq_alloc(e, p, (size_t)attn_ld(n_att) * max_c)) return rc; }
     const size_t n_tok = (size_t)cfg->token_h * cfg->token_w;
     if (int rc = vq_alloc(e, &e->d_in, (size_t)in_channels * e->in_h * e->in_w)) return rc;
     if (int rc = vq_alloc(e, &e->d_z, n_tok * cfg->embed_dim)) return rc;
     VQCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_codes), n_tok * sizeof(long long)));
     e->allocs.push_back(e->d_codes);
-    // codebook tile of the quantiser: at most 512 rows and 40 KB of LDS, a multiple of 64 rows
-    e->q_tile = std::max(64, std::min(512, (10240 / (cfg->embed_dim + 4)) & ~63));
-    e->q_lds = ((size_t)e->q_tile * (cfg->embed_dim + 4) + e->q_tile + 4 * kQuantMaxD) * sizeof(float);
     return UMGEN_OK;
 }
 
@@ -234,7 +130,7 @@ int umgen_vqenc_finalize(umgen_vqenc* e) {
     if (!e) return UMGEN_E_INVALID;
     if (int rc = check_slots(e, "encoder")) return rc;
     VQCHK(e, hipSetDevice(e->cfg.device));
-    hipLaunchKernelGGL(vq_code_norms_kernel, grid1d(e->cfg.n_embed), dim3(256), 0, e->stream, e->emb, e->cfg.n_embed, e->cfg.embed_dim, e->e2);
+    launch_code_norms(e->stream, e->emb, e->cfg.n_embed, e->cfg.embed_dim, e->e2);
     VQCHK(e, hipStreamSynchronize(e->stream));
     VQCHK(e, hipGetLastError());
     e->finalized = true;
@@ -255,7 +151,7 @@ int umgen_vqenc_encode(umgen_vqenc* e, int32_t n, const float* x, int64_t* codes
     for (int f = 0; f < n; ++f) {
         int H = e->in_h, W = e->in_w;
         VQCHK(e, hipMemcpyAsync(e->d_in, x + (long)f * n_in, n_in * sizeof(float), hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(vq_from_nchw_kernel, grid1d((long)H * W * e->in_pad), dim3(256), 0, e->stream, e->d_in, (long)H * W, e->in_ch, e->in_pad, e->h);
+        launch_from_nchw(e->stream, e->d_in, (long)H * W, e->in_ch, e->in_pad, e->h);
         conv(e, e->conv_in, e->h, H, W, e->x, false);                      // Encoder.forward
         for (int lv = 0; lv < L; ++lv) {
             const Level& d = e->down[lv];
@@ -265,7 +161,7 @@ int umgen_vqenc_encode(umgen_vqenc* e, int32_t n, const float* x, int64_t* codes
             }
             if (d.has_down) {
                 const int C = d.down.cin;
-                hipLaunchKernelGGL(vq_im2col_s2_kernel, grid1d((long)(H / 2) * (W / 2) * 9 * (C / 4)), dim3(256), 0, e->stream, e->x, H, W, C, e->col);
+                launch_im2col_s2(e->stream, e->x, H, W, C, e->col);
                 H /= 2; W /= 2;
                 conv_gemm(e, d.down, e->col, 9 * C, (long)H * W, e->t, false);
                 std::swap(e->x, e->t);
@@ -277,8 +173,7 @@ int umgen_vqenc_encode(umgen_vqenc* e, int32_t n, const float* x, int64_t* codes
         group_norm(e, e->norm_out, e->x, (long)H * W, true, e->h);
         conv(e, e->conv_out, e->h, H, W, e->t, false);
         conv(e, e->quant_conv, e->t, H, W, e->h, false);                   // NormVQModel.encode: quant_conv
-        hipLaunchKernelGGL(vq_quantize_kernel, dim3((unsigned)((n_tok + 3) / 4)), dim3(256), e->q_lds, e->stream, e->h, e->quant_conv.cout_pad,
-                           e->emb, e->e2, cfg.n_embed, cfg.embed_dim, e->q_tile, n_tok, e->d_codes, e->d_z);
+        launch_quantize(e->stream, e->h, e->quant_conv.cout_pad, e->emb, e->e2, cfg.n_embed, cfg.embed_dim, n_tok, e->d_codes, e->d_z);
         VQCHK(e, hipMemcpyAsync(codes + (long)f * n_tok, e->d_codes, n_tok * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
         if (z) VQCHK(e, hipMemcpyAsync(z + (long)f * n_tok * cfg.embed_dim, e->d_z, n_tok * cfg.embed_dim * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         VQCHK(e, hipStreamSynchronize(e->stream));     // once per frame: the frame's buffers are reused by the next one
