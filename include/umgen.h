@@ -197,6 +197,27 @@ int umgen_frame_logp(umgen_engine *e, int32_t T, const int64_t *pose, const int6
                      const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
                      int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp);
 
+/* ---- fan-out rollout: N sampled futures of every scene off one pass over its history --------------------------------------------------
+ * Contract: branch (b, s) of every output is bit for bit what umgen_rollout_logp returns for scene b*N + s on the same engine when it is called with
+ * B*N scenes, history b replicated N times, the control / given arrays replicated likewise, and the same seeds[b*N + s] -- in every precision, tokens
+ * and log-likelihoods.  (The sampler's RNG is a function of seed, frame, position and draw kind; the scene index does not enter.)
+ *   - pose/map/bbox3d/image [B][T_in][S_mod]; ctrl_* / given_* NULL or [B][T_ctl][S_mod]: a scene's branches share them; sampling->seeds [B*N] (NULL: 0),
+ *     branch (b, s) at b*N + s; out_* [B][N][T_in + new_frames][S_mod]; lp NULL or arrays [B][N][new_frames][S_mod].
+ *   - B >= 1, N >= 1, B*N <= max_batch; everything else is checked like umgen_rollout's arguments.  N == 1 is umgen_rollout_logp itself.
+ *   - What is saved: in the FIRST frame, with n0 = min(T_in, cond_frames) window slots, the ego net and slots 0 .. n0-2 of the map / box / TAR stacks run
+ *     once per scene, and only slot n0-1 -- the one the pose shift hands the branch's own new pose -- runs per branch, against the scene's slot caches.
+ *     When the window then grows (n0 + 1 <= cond_frames) every branch's slot caches are completed from its scene's, so later frames push one slot per
+ *     branch as in umgen_rollout.  From the decode loop of the first frame on, the call is umgen_rollout_logp on B*N scenes.
+ *   - *shared_slots (NULL allowed): n0 - 1 when the first frame ran that way; 0 when the call took the replicated path with the same bits: N == 1, n0 == 1,
+ *     slot caches that do not fit, UMGEN_FAN_SHARE=0 in the environment (read per call), or new_frames == 0. */
+int umgen_rollout_fan(umgen_engine *e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames,
+                      const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                      int32_t T_ctl, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                      const int64_t *given_map, const int64_t *given_bbox3d,
+                      const umgen_sampling *sampling,
+                      int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image,
+                      const umgen_logp_out *lp, int32_t *shared_slots);
+
 /* Per-token log-likelihoods of a GIVEN next frame: the reference's teacher-forced loss terms (get_targets, d_loss, F.cross_entropy per modality,
  * UMGen.py:539-582) as one forward pass.  For B scenes with history windows pose/map/bbox3d/image [B][T][S_mod] and their next frames next_* [B][S_mod]:
  *     logp_m[b][k]   = log_softmax(logits_m[k])[next_m[b][k]]   (natural log)

@@ -650,9 +650,10 @@ template void launch_attn_temporal<float>(hipStream_t, const float*, float*, int
 template void launch_attn_temporal<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, int, int, int, TemporalRange);
 template void launch_attn_temporal<f16_t>(hipStream_t, const f16_t*, f16_t*, int, int, int, int, TemporalRange);
 
-// the last slot of N items over their scenes' cached slots [0, P) (attn_body.h attn_temporal_fan_kernel); heads per workgroup as above
-template <typename T>
-void launch_attn_temporal_fan(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P, const T* cache, int Tcap) {
+// the last slot of N items over their scenes' cached slots [0, P) (attn_body.h attn_temporal_fan_kernel); heads per workgroup as above.  WRITE: the form that
+// also leaves item i's k | v rows in block i, slot P -- the same geometry and LDS request; the cache then holds at least N blocks
+template <typename T, bool WRITE>
+static void launch_fan(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P, const T* cache, int Tcap) {
     if (BgRecorder* rec = g_bg_rec) { rec->failed = "temporal attention over shared caches"; return; }
     if (N < 1 || B < 1) return;
     const int HG = (P + 1 <= kTmax && H % 4 == 0) ? 4 : (H % 2 == 0 ? 2 : 1);
@@ -663,12 +664,49 @@ void launch_attn_temporal_fan(hipStream_t s, const T* qkv, T* y, int N, const in
             return;      // (the refusal stays behind as the thread's last error: the engine fails the call, the test hook returns it)
         hipLaunchKernelGGL(kernel, grid, block, shm, s, qkv, y, scene_of_item, N, S, H, P, cache, Tcap);
     };
-    if (HG == 4) launch(attn_temporal_fan_kernel<T, 4>);
-    else if (HG == 2) launch(attn_temporal_fan_kernel<T, 2>);
-    else launch(attn_temporal_fan_kernel<T, 1>);
+    if (HG == 4) launch(attn_temporal_fan_kernel<T, 4, WRITE>);
+    else if (HG == 2) launch(attn_temporal_fan_kernel<T, 2, WRITE>);
+    else launch(attn_temporal_fan_kernel<T, 1, WRITE>);
+}
+template <typename T>
+void launch_attn_temporal_fan(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P, const T* cache, int Tcap) {
+    launch_fan<T, false>(s, qkv, y, N, scene_of_item, B, S, H, P, cache, Tcap);
 }
 template void launch_attn_temporal_fan<float>(hipStream_t, const float*, float*, int, const int*, int, int, int, int, const float*, int);
 template void launch_attn_temporal_fan<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, const int*, int, int, int, int, const bf16_t*, int);
 template void launch_attn_temporal_fan<f16_t>(hipStream_t, const f16_t*, f16_t*, int, const int*, int, int, int, int, const f16_t*, int);
+template <typename T>
+void launch_attn_temporal_fan_write(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P, T* cache, int Tcap) {
+    launch_fan<T, true>(s, qkv, y, N, scene_of_item, B, S, H, P, cache, Tcap);
+}
+template void launch_attn_temporal_fan_write<float>(hipStream_t, const float*, float*, int, const int*, int, int, int, int, float*, int);
+template void launch_attn_temporal_fan_write<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, const int*, int, int, int, int, bf16_t*, int);
+template void launch_attn_temporal_fan_write<f16_t>(hipStream_t, const f16_t*, f16_t*, int, const int*, int, int, int, int, f16_t*, int);
+
+// One scene of the spread behind a fan frame (umgen_rollout_fan): slots [0, P) of block `b` of a slot cache [blocks][Tcap][S][2E] -- `n16` 16-byte
+// vectors from the block's start, a block being `blk16` vectors -- to the blocks b*N + s, s = 0 .. N-1; a block's slots >= P are not touched.
+// The source block b is itself the destination of item b of scene b / N, so a cache is spread scene by scene in DESCENDING b, one launch each in
+// stream order (launch_tcache_spread): every destination of scene b is >= b*N, above every lower scene whose source is still unread, and equals b
+// only for b == 0, s == 0 -- the self-copy this kernel skips.
+__global__ __launch_bounds__(256) void tcache_spread_kernel(uint4* __restrict__ cache, long blk16, long n16, int b, int N) {
+    const uint4* src = cache + (long)b * blk16;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) {
+        const uint4 v = src[i];
+        for (int s = 0; s < N; ++s) {
+            const long d = (long)b * N + s;
+            if (d != b) cache[d * blk16 + i] = v;
+        }
+    }
+}
+
+// slots [0, P) of the scene blocks b = 0 .. B-1 of one slot cache to the blocks b*N + s: one launch of tcache_spread_kernel per scene, in DESCENDING b on
+// the one stream (the aliasing rule stated at the kernel).  row_bytes: bytes of one slot, S * 2E * sizeof(T), a multiple of 16.
+void launch_tcache_spread(hipStream_t s, void* cache, int B, int N, int P, int Tcap, size_t row_bytes) {
+    if (BgRecorder* rec = g_bg_rec) { rec->failed = "slot cache spread"; return; }
+    if (B < 1 || N < 2 || P < 1) return;
+    const long blk16 = (long)((size_t)Tcap * row_bytes / 16), n16 = (long)((size_t)P * row_bytes / 16);
+    const unsigned grid = (unsigned)std::min<long>((n16 + 255) / 256, 2048);
+    for (int b = B - 1; b >= 0; --b) hipLaunchKernelGGL(tcache_spread_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<uint4*>(cache), blk16, n16, b, N);
+}
 
 }  // namespace umgen

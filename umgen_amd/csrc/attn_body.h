@@ -360,10 +360,14 @@ __global__ __launch_bounds__(HG * TMAX * 4) void attn_temporal_kernel(const T* _
 // k | v rows are staged into LDS once and serve all items of the scene, kFanItems(HG) at a time -- their own q | k | v rows sit behind the cached
 // rows, lane = (item, head, 12-wide head-dim part); more items are further rounds of the same workgroup over the same cached rows.  Per query
 // exactly attn_temporal_body's operations in its order (fmaf chain, two quad DPP adds, kScale, sequential online softmax over keys 0 .. P), so y
-// has the bits of the last-slot launch of that kernel on a per-item copy of the cache.  The cache is read only, and only its slots < P.
+// has the bits of the last-slot launch of that kernel on a per-item copy of the cache.  The cache is read only (WRITE = false), and only its slots < P.
 // LDS: (2 P + 3 kFanItems) * HG * 48 floats -- at most 66048 B (HG 4, P 31) / 66816 B (HG 2, P 63), inside the 73728 B the temporal kernel requests.
 __host__ __device__ constexpr int kFanItems(int HG) { return HG == 4 ? 8 : 16; }
-template <typename T, int HG>
+// WRITE (umgen_rollout_fan ahead of a longer window): beside y, item i leaves the k | v rows of its own slot P -- the bits of its qkv rows, through the float
+// round trip of attn_temporal_body's append -- in block i, slot P of the cache, which then holds at least N blocks and has Tcap > P.  Nothing reads slot P of
+// any block during the launch and the slots < P are only read, so the order of the workgroups does not matter; staging order, LDS layout and every query's
+// operations are those of the read-only form, which is this kernel with WRITE = false.
+template <typename T, int HG, bool WRITE = false>
 __global__ __launch_bounds__(kFanItems(HG) * HG * 4) void attn_temporal_fan_kernel(const T* __restrict__ qkv, T* __restrict__ y,
                                                                                    const int* __restrict__ scene_of_item, int N, int S, int H, int P,
                                                                                    const T* __restrict__ cache, int Tcap) {
@@ -405,6 +409,14 @@ __global__ __launch_bounds__(kFanItems(HG) * HG * 4) void attn_temporal_fan_kern
             float* d = own + ((it * 3 + seg) * W + cc * 8);
             *reinterpret_cast<float4*>(d) = make_float4(v8[0], v8[1], v8[2], v8[3]);
             *reinterpret_cast<float4*>(d + 4) = make_float4(v8[4], v8[5], v8[6], v8[7]);
+            if constexpr (WRITE) {
+                if (seg > 0) {
+                    T* cp = const_cast<T*>(cache) + (((long)(first + i0 + it) * Tcap + P) * S + s) * 2L * E + (long)(seg - 1) * E + hg * W + cc * 8;
+                    const float lo4[4] = {v8[0], v8[1], v8[2], v8[3]}, hi4[4] = {v8[4], v8[5], v8[6], v8[7]};
+                    store4(cp, lo4);
+                    store4(cp + 4, hi4);
+                }
+            }
         }
         __syncthreads();
         if (il >= ni) continue;              // (whole quads: the DPP adds below stay inside a query's 4 lanes)

@@ -247,6 +247,45 @@ int umgen_dbg_attn_temporal_fan(int prec, const void* qkv, int N, const int32_t*
     return down(y, dY, Rn * E * es);
 }
 
+// ONE launch_attn_temporal_fan_write call (kernels.h): umgen_dbg_attn_temporal_fan's arguments, but the cache has `blocks` >= max(B, N) blocks and Tcap > P:
+// item i also leaves its k | v rows of slot P in block i.  cache and y are in / out: whatever the launch leaves alone keeps the caller's fill.
+int umgen_dbg_attn_temporal_fan_write(int prec, const void* qkv, int N, const int32_t* scene_of_item, int B, int S, int H, int P, int Tcap, int blocks, void* cache,
+                                      void* y) {
+    if (prec < 0 || prec > 2 || !qkv || !y || !cache || !scene_of_item || N < 1 || B < 1 || S < 1 || H < 1 || P < 1 || P + 1 > 2 * kTemporalSlots || Tcap < P + 1 ||
+        blocks < std::max(B, N))
+        return UMGEN_E_INVALID;
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < N; ++i) {
+        const int sc = scene_of_item[i];
+        if (sc < 0 || sc >= B || (seen[sc] && scene_of_item[i - 1] != sc)) return UMGEN_E_INVALID;
+        seen[sc] = 1;
+    }
+    const int E = H * kHeadDim;
+    const size_t es = prec ? 2 : 4, Rn = (size_t)N * S, csz = (size_t)blocks * Tcap * S * 2 * E * es;
+    Scratch s;
+    const void* dQ = s.in(qkv, Rn * 3 * E * es);
+    const int* dS = s.in(scene_of_item, (size_t)N * 4);
+    void* dY = s.inout(y, Rn * E * es);
+    void* dC = s.inout(cache, csz);
+    if (s.rc) return s.rc;
+    by_prec(prec, [&](auto t) { typedef decltype(t) TT; launch_attn_temporal_fan_write<TT>(nullptr, (const TT*)dQ, (TT*)dY, N, dS, B, S, H, P, (TT*)dC, Tcap); });
+    if (int rc = s.finish()) return rc;
+    if (down(cache, dC, csz)) return UMGEN_E_HIP;
+    return down(y, dY, Rn * E * es);
+}
+
+// ONE launch_tcache_spread call (kernels.h) on cache [blocks][Tcap][row_bytes] (in / out), blocks >= B * N: slots [0, P) of block b < B to the blocks b*N + s
+int umgen_dbg_tcache_spread(void* cache, int blocks, int B, int N, int P, int Tcap, long row_bytes) {
+    if (!cache || B < 1 || N < 1 || P < 1 || P > Tcap || row_bytes < 16 || row_bytes % 16 || (long)B * N > blocks) return UMGEN_E_INVALID;
+    const size_t csz = (size_t)blocks * Tcap * (size_t)row_bytes;
+    Scratch s;
+    void* dC = s.inout(cache, csz);
+    if (s.rc) return s.rc;
+    launch_tcache_spread(nullptr, dC, B, N, P, Tcap, (size_t)row_bytes);
+    if (int rc = s.finish()) return rc;
+    return down(cache, dC, csz);
+}
+
 // decode-style attention: q [NQ][E] fp32, kv [L][2E] (k | v) of dtype bf16/fp32 shared by all queries -> y [NQ][E] fp32
 // (partial pass + the combine that normally runs in the projection prologue, here through an identity projection)
 int umgen_dbg_attn_decode(int bf16, const float* q, const void* kv, int NQ, int L, int H, float* y) {

@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_clip and the rollout driver umgen_rollout(_logp) (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
+// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
 #include "engine_state.h"
 
@@ -292,12 +292,14 @@ int umgen_score_clip(umgen_engine* e, int32_t B, int32_t L, int32_t T_in, int32_
     return UMGEN_OK;
 }
 
-// UMGen.inference (UMGen.py:1542-1671)
-int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
-                       const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
-                       const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
-                       const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
-                       const umgen_logp_out* lp) {
+// UMGen.inference (UMGen.py:1542-1671).  fan_N >= 2 (umgen_rollout_fan): the B scenes are B / fan_N recorded scenes of fan_N branches each, branch (b, s) at
+// b*fan_N + s with scene b's arrays replicated -- the first frame then runs its history once per scene (run_frame_fan) when its window has at least two slots,
+// the slot caches fit and UMGEN_FAN_SHARE is not 0, and *shared_slots reports the slots that were shared.
+static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
+                          const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
+                          const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
+                          const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                          const umgen_logp_out* lp, int32_t fan_N, int32_t* shared_slots) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
@@ -398,7 +400,10 @@ int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_fra
         io.given_map = gm.empty() ? nullptr : gm.data();
         io.given_box = gb.empty() ? nullptr : gb.data();
         io.out_logp = frame_logp.empty() ? nullptr : frame_logp.data();
-        if (int rc = run_frame_any(e, io)) return rc;
+        const char* fse = getenv("UMGEN_FAN_SHARE");      // (read per call: the tests compare both forms in one process)
+        const bool fan = idx == 0 && fan_N >= 2 && T_cur >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
+        if (fan && shared_slots) *shared_slots = T_cur - 1;
+        if (int rc = fan ? run_frame_fan_any(e, io, fan_N) : run_frame_any(e, io)) return rc;
         // append (UMGen.py:1636-1666): control pose tokens are copied verbatim; everything else is what was generated
         const int off[4] = {0, kOffMap, kOffBox, kOffImg};
         for (int m = 0; m < 4; ++m) {
@@ -419,6 +424,53 @@ int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_fra
         T_cur += 1;
     }
     return UMGEN_OK;
+}
+
+int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
+                       const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
+                       const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
+                       const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                       const umgen_logp_out* lp) {
+    return rollout_driver(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr);
+}
+
+// umgen_rollout_fan: N sampled futures per scene.  The branches are the scenes of an ordinary rollout of B * N scenes on replicated inputs -- the driver above,
+// whose first frame shares the history between a scene's branches (engine_frame.hip run_frame_fan); outputs [B][N][..] are that rollout's [B * N][..].
+int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                      const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                      const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                      int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots) {
+    if (!e) return UMGEN_E_INVALID;
+    if (shared_slots) *shared_slots = 0;
+    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
+    if (B < 1) return e->fail(UMGEN_E_INVALID, "B=%d: at least one scene", B);
+    if (N < 1) return e->fail(UMGEN_E_INVALID, "N=%d: at least one sample per scene", N);
+    if ((int64_t)B * N > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B*N=%lld (B=%d, N=%d) exceeds max_batch=%d", (long long)B * N, B, N, e->cfg.max_batch);
+    if (N == 1)
+        return rollout_driver(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
+                              sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr);
+    // what the replication below reads; the driver checks everything again, and everything else, on the replicated arrays
+    if (T_in < 1 || new_frames < 0 || cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
+        return e->fail(UMGEN_E_INVALID, "T_in=%d new_frames=%d cond_frames=%d (max %d)", T_in, new_frames, cond_frames, e->cfg.max_cond_frames);
+    if (!pose || !map || !bbox3d || !image || !out_pose || !out_map || !out_bbox3d || !out_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
+    if ((ctrl_pose || ctrl_bbox3d) && T_ctl < 1) return e->fail(UMGEN_E_INVALID, "control tokens given with T_ctl=%d", T_ctl);
+    if ((given_map || given_bbox3d) && T_ctl < 1) return e->fail(UMGEN_E_INVALID, "given tokens with T_ctl=%d", T_ctl);
+    auto replicate = [&](const int64_t* a, size_t per_scene) {      // [B][per_scene] -> [B][N][per_scene]
+        std::vector<int64_t> r;
+        if (!a) return r;
+        r.resize((size_t)B * N * per_scene);
+        for (int b = 0; b < B; ++b)
+            for (int s = 0; s < N; ++s) memcpy(&r[((size_t)b * N + s) * per_scene], a + (size_t)b * per_scene, per_scene * sizeof(int64_t));
+        return r;
+    };
+    const std::vector<int64_t> rp = replicate(pose, (size_t)T_in * kNPose), rm = replicate(map, (size_t)T_in * kNMap), rb = replicate(bbox3d, (size_t)T_in * kNBox),
+                               ri = replicate(image, (size_t)T_in * kNImg), cp = replicate(ctrl_pose, (size_t)T_ctl * kNPose),
+                               cb = replicate(ctrl_bbox3d, (size_t)T_ctl * kNBox), gm = replicate(given_map, (size_t)T_ctl * kNMap),
+                               gb = replicate(given_bbox3d, (size_t)T_ctl * kNBox);
+    return rollout_driver(e, B * N, T_in, new_frames, cond_frames, rp.data(), rm.data(), rb.data(), ri.data(), T_ctl, ctrl_pose ? cp.data() : nullptr,
+                          ctrl_bbox3d ? cb.data() : nullptr, control_test, given_map ? gm.data() : nullptr, given_bbox3d ? gb.data() : nullptr, sampling, out_pose,
+                          out_map, out_bbox3d, out_image, lp, N, shared_slots);
 }
 
 int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,

@@ -1,8 +1,9 @@
 // One frame, UMGen._inference: run_frame<T> as a sequence of stages -- background pass, uploads, ego net and pose shift, decode state, the
 // stacks, first input and prefix pass, the lane loop or the single-stream step loop, drain, download, checks, bookkeeping -- run_score<T>,
 // the scoring pass of umgen_score built from the same stages, run_score_candidates<T>, which scores several next frames per scene on one pass
-// over the history, run_score_clip<T>, which scores every frame of a recorded clip, the growing windows off one pass, and run_frame_any / run_score_any /
-// run_score_candidates_any / run_score_clip_any, which pick the precision and clean up behind a failed call.
+// over the history, run_score_clip<T>, which scores every frame of a recorded clip, the growing windows off one pass, run_frame_fan<T>, the first frame of
+// umgen_rollout_fan with the history once per scene, and run_frame_any / run_frame_fan_any / run_score_any / run_score_candidates_any / run_score_clip_any,
+// which pick the precision and clean up behind a failed call.
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -595,6 +596,22 @@ void frame_bookkeeping(umgen_engine* e, const FrameIO& io, const FrameCtx& ctx) 
     }
 }
 
+// a frame from the first decode input on, behind the stacks and the conditioning rows: run_frame's and run_frame_fan's common end
+template <typename T>
+int decode_and_finish(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
+    if (int rc = begin_decode<T>(e, io, ctx)) return rc;
+    if (int rc = prefix_pass(e, io, ctx)) return rc;
+    plan_decode_steps<T>(e, io, ctx);
+    if (ctx.n_lanes > 1) {
+        if (int rc = run_lane_loop(e, io, ctx)) return rc;
+    }
+    if (int rc = run_step_loop(e, io, ctx)) return rc;
+    if (int rc = drain_and_download<T>(e, io, ctx)) return rc;
+    if (int rc = check_frame_results(e, io, ctx)) return rc;
+    frame_bookkeeping(e, io, ctx);
+    return 0;
+}
+
 // UMGen._inference (UMGen.py:1406-1540) for B scenes
 template <typename T>
 int run_frame(umgen_engine* e, const FrameIO& io) {
@@ -613,17 +630,109 @@ int run_frame(umgen_engine* e, const FrameIO& io) {
     if (int rc = ego_and_pose_shift(e, io, ctx)) return rc;
     if (int rc = init_decode_state<T>(e, io, ctx)) return rc;
     if (int rc = run_stacks(e, io, ctx)) return rc;
-    if (int rc = begin_decode<T>(e, io, ctx)) return rc;
-    if (int rc = prefix_pass(e, io, ctx)) return rc;
-    plan_decode_steps<T>(e, io, ctx);
-    if (ctx.n_lanes > 1) {
-        if (int rc = run_lane_loop(e, io, ctx)) return rc;
+    return decode_and_finish<T>(e, io, ctx);
+}
+
+// every BlockTAR cache of one stack: slots [0, P) of the scene blocks b < B to the blocks b*N + s (launch_tcache_spread: scene by scene in descending b)
+void spread_tcaches(umgen_engine* e, hipStream_t st, int stack, int B, int N, int P) {
+    const size_t row_bytes = (size_t)stack_len(stack) * 2 * e->E * e->tsz;
+    for (void* c : e->tcache[stack]) launch_tcache_spread(st, c, B, N, P, e->cfg.max_cond_frames, row_bytes);
+}
+
+// The first frame of umgen_rollout_fan: io holds the B * N branches as scenes -- branch (b, s) at b*N + s, every scene's window, control slots and given tokens
+// replicated N times, the seeds per branch -- and everything that does not depend on the branch runs once per scene, as in run_score_candidates.  The ego net
+// reads the unshifted window, so it runs on the B scenes and every branch draws its pose from its scene's head_ego rows (run_ego_fan).  The pose shift hands
+// only slot T - 1 the new frame's pose, so slots [0, T - 1) of the map / box / TAR stacks run on the B scenes in cache mode 1 and the branches push their last
+// slot against their scene's caches (cache mode 5).  Every kernel's row arithmetic is that of run_frame, so the conditioning rows, and from begin_decode on the
+// whole frame -- an ordinary frame of B * N scenes -- have the bits of run_frame on io.
+// When the next frame's window is this one plus a slot (run_frame's fg_write rule) the slot caches must end up as run_frame's cache mode 3 leaves them for all
+// B * N scenes: the ego stack fills the scenes' blocks in mode 3, the last-slot passes append every branch's own slot T - 1 to its own block (cache mode 6),
+// and then every cache is spread -- block b*N + s receives slots [0, T - 1) ([0, T) of the ego stack) of scene block b, behind ALL reads of the scene blocks and
+// scene by scene in descending b (tcache_spread_kernel states why) -- and px is filled for B * N scenes like run_stacks fills it.
+template <typename T>
+int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
+    const int E = e->E, BN = io.B, B = io.B / N, Tn = io.T, P = io.T - 1;
+    hipStream_t const fg = e->stream;
+    e->launch_status = hipSuccess;
+    (void)hipGetLastError();
+    struct RestoreStream { umgen_engine* e; hipStream_t s; ~RestoreStream() { e->stream = s; e->set_work(e->w_main); } } restore{e, fg};
+    FrameCtx ctx{};
+    ctx.fg = fg;
+    ctx.st = fg;
+    ctx.sp = SamplerParams{io.smp->method, io.smp->top_k, io.smp->top_k_map, io.smp->topk_image, io.smp->p, io.smp->p_map, io.smp->temperature,
+                           io.smp->rule_constrain, io.smp->merge_ar_tar, io.smp->only_ar};
+    e->px.valid = false;                 // the passes below overwrite the slot caches: nothing an earlier call left there covers this window
+    if (int rc = settle_background_pass(e, io, ctx)) return rc;
+    if (int rc = upload_frame_inputs(e, io, ctx)) return rc;      // seeds, counters and logp of the B * N branches; the token arrays follow below
+    hipStream_t const st = ctx.st;
+    // the scenes' windows [B][T][S_mod] (branch (b, 0) holds scene b's) for the passes that run once per scene
+    const int S[4] = {kNPose, kNMap, kNBox, kNImg};
+    const int* src[4] = {io.pose, io.map, io.box, io.img};
+    int* dev[4] = {e->d_pose, e->d_map, e->d_box, e->d_img};
+    std::vector<int> win[4], item_scene(BN), hshift;
+    std::vector<float> hdiff;
+    for (int m = 0; m < 4; ++m) {
+        win[m].resize((size_t)B * Tn * S[m]);
+        for (int b = 0; b < B; ++b)
+            memcpy(&win[m][(size_t)b * Tn * S[m]], src[m] + (size_t)b * N * Tn * S[m], (size_t)Tn * S[m] * sizeof(int));
+        HIPCHK(e, hipMemcpyAsync(dev[m], win[m].data(), win[m].size() * 4, hipMemcpyHostToDevice, st));
     }
-    if (int rc = run_step_loop(e, io, ctx)) return rc;
-    if (int rc = drain_and_download<T>(e, io, ctx)) return rc;
-    if (int rc = check_frame_results(e, io, ctx)) return rc;
-    frame_bookkeeping(e, io, ctx);
-    return 0;
+    ctx.fg_write = !e->overlap && e->grow_cache && io.next_follows && io.cond_cap > 0 && Tn + 1 <= io.cond_cap && Tn + 1 <= e->cfg.max_cond_frames && ensure_tcache(e);
+    ctx.t0 = 0; ctx.Tc = Tn; ctx.cmode = ctx.fg_write ? 3 : 0;
+    // Step 1: the ego net once per scene, a pose per branch
+    ctx.ego.resize((size_t)BN * 3);
+    HIPCHK(e, hipEventRecord(e->ev[0], st));
+    if (io.ctrl_pose) {
+        for (int i = 0; i < BN * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
+    } else {
+        run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, io.out_logp ? e->d_logp : nullptr);
+        HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)BN * 3 * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+    }
+    HIPCHK(e, hipEventRecord(e->ev[1], st));
+    if (int rc = init_decode_state<T>(e, io, ctx)) return rc;
+    // Step 2a: slots [0, T - 1) of the three stacks once per scene, their temporal k | v rows into the scenes' blocks of the slot caches (slot T - 1 of the
+    // shifted pose is not read)
+    const std::vector<int> no_pose((size_t)B * 3, 0);
+    decode_pose_shift(win[0].data(), no_pose.data(), B, Tn, hshift, hdiff);
+    HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, hshift.data(), hshift.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->pose_diff, hdiff.data(), hdiff.size() * 4, hipMemcpyHostToDevice, st));
+    const WindowTokens wh{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, Tn, 0};
+    run_stack_any(e, STACK_MAP, wh, 1);
+    run_stack_any(e, STACK_BOX, wh, 1);
+    run_stack_any(e, STACK_TAR, wh, 1);
+    // Step 2b: slot T - 1 of every branch -- its own pose in the shift, its own window rows -- against its scene's caches, and the conditioning rows
+    decode_pose_shift(io.pose, ctx.ego.data(), BN, Tn, ctx.pshift, ctx.pdiff);
+    HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, ctx.pshift.data(), ctx.pshift.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->pose_diff, ctx.pdiff.data(), ctx.pdiff.size() * 4, hipMemcpyHostToDevice, st));
+    for (int m = 0; m < 4; ++m) HIPCHK(e, hipMemcpyAsync(dev[m], src[m], (size_t)BN * Tn * S[m] * 4, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < BN; ++i) item_scene[i] = i / N;
+    HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)BN * 4, hipMemcpyHostToDevice, st));
+    e->fan_scenes = B;
+    const int lmode = ctx.fg_write ? 6 : 5;
+    const WindowTokens wl{e->d_pose_shift, e->d_map, e->d_box, e->d_img, BN, 1, Tn, P};
+    run_stack_any(e, STACK_MAP, wl, lmode);
+    launch_cond_rows(st, STACK_MAP, BN, 1, E, e->X, e->ln_map_tar, e->warped_last, e->cond);
+    run_stack_any(e, STACK_BOX, wl, lmode);
+    launch_cond_rows(st, STACK_BOX, BN, 1, E, e->X, e->ln_box_tar, nullptr, e->cond);
+    run_stack_any(e, STACK_TAR, wl, lmode);
+    launch_cond_rows(st, STACK_TAR, BN, 1, E, e->X, e->ln_tar, nullptr, e->cond);
+    if (ctx.fg_write) {   // behind every read of the scene blocks: each branch's block gets its scene's slots; then the caches hold slots 0 .. T-1 of all B * N windows
+        spread_tcaches(e, st, STACK_MAP, B, N, P);
+        spread_tcaches(e, st, STACK_BOX, B, N, P);
+        spread_tcaches(e, st, STACK_TAR, B, N, P);
+        if (!io.ctrl_pose) spread_tcaches(e, st, STACK_EGO, B, N, Tn);
+        umgen_engine::Prefix& px = e->px;
+        px.B = BN; px.P = Tn; px.Tfull = Tn + 1; px.has_ego = !io.ctrl_pose;
+        px.pose.assign(io.pose, io.pose + (size_t)BN * Tn * kNPose);
+        px.map.assign(io.map, io.map + (size_t)BN * Tn * kNMap);
+        px.box.assign(io.box, io.box + (size_t)BN * Tn * kNBox);
+        px.img.assign(io.img, io.img + (size_t)BN * Tn * kNImg);
+        px.pose_next.assign(ctx.ego.begin(), ctx.ego.end());
+        px.valid = true;
+    }
+    HIPCHK(e, hipEventRecord(e->ev[2], st));
+    return decode_and_finish<T>(e, io, ctx);      // Step 3 on: an ordinary frame of B * N scenes
 }
 
 // umgen_score: log p of a GIVEN next frame for B scenes (the reference's teacher-forced loss, UMGen.py:539-582), from run_frame's own stages.  The
@@ -1100,6 +1209,13 @@ int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc) {
 int run_frame_any(umgen_engine* e, const FrameIO& io) {
     const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_frame<bf16_t>(e, io)
                  : e->cfg.precision == UMGEN_PREC_FP16 ? run_frame<f16_t>(e, io) : run_frame<float>(e, io);
+    if (rc != UMGEN_OK) drain_failed_frame(e);
+    return rc;
+}
+
+int run_frame_fan_any(umgen_engine* e, const FrameIO& io, int N) {
+    const int rc = e->cfg.precision == UMGEN_PREC_BF16 ? run_frame_fan<bf16_t>(e, io, N)
+                 : e->cfg.precision == UMGEN_PREC_FP16 ? run_frame_fan<f16_t>(e, io, N) : run_frame_fan<float>(e, io, N);
     if (rc != UMGEN_OK) drain_failed_frame(e);
     return rc;
 }

@@ -81,7 +81,7 @@ void linear_resid(umgen_engine* e, const void* W, const float* bias, int N, int 
 //   tail 2 (the spatial sub-block behind it): the whole sub-block on the last frame's rows.
 template <typename T>
 void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal, TemporalRange tr = TemporalRange{0, nullptr, 0, 0}, int tail = 0,
-             bool fan = false) {
+             int fan = 0) {
     const int E = e->E, H = e->H;
     const long R = (long)B * Tn * S;
     T* A = reinterpret_cast<T*>(e->A);
@@ -128,8 +128,10 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
             for (const Range& r : rest) linear_store<T>(e, Wqkv, w.attn.bqkv, E, E, A + r.row0 * E, r.rows, QKV + r.row0 * 3 * E, 3L * E, 0);
             tr.q0 = tr.t0 + Tn - 1;
         }
-        // fan: the B rows-of-one-slot are items that share their scenes' cached slots [0, tr.t0) (cache mode 5 of run_stack)
-        if (fan) launch_attn_temporal_fan<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<const T*>(tr.cache), tr.Tcap);
+        // fan: the B rows-of-one-slot are items that share their scenes' cached slots [0, tr.t0) (cache mode 5 of run_stack); 2: item i also leaves its own
+        // k | v rows in block i, slot tr.t0 (cache mode 6)
+        if (fan == 2) launch_attn_temporal_fan_write<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<T*>(tr.cache), tr.Tcap);
+        else if (fan) launch_attn_temporal_fan<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<const T*>(tr.cache), tr.Tcap);
         else launch_attn_temporal<T>(e->stream, QKV, A, B, Tn, S, H, tr);
     } else if (tail == 0) {
         launch_layernorm<T>(e->stream, e->X, E, R, E, w.ln_a, A);
@@ -153,7 +155,8 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
 // 2 = last-slot pass (slots [w.t0, w.t0 + w.T) against the caches); 3 = whole window like 0, and its k | v rows are left in the slot
 // caches for a longer window that follows; 4 = last-slot pass like 2 that appends its own k | v rows (the window keeps growing);
 // 5 = last-slot pass like 2 of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of e->fan_scenes scenes: item i reads the slots [0, P) of scene
-// e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window)
+// e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window); 6 = 5, and item i appends its own k | v rows to
+// block i of the caches (umgen_rollout_fan ahead of a longer window: spread_tcaches then hands every item its scene's slots [0, P))
 // tail: TAIL_AUTO = the final block's last-frame shortcut wherever it applies (below); TAIL_NONE = every block on every slot (umgen_score_clip reads all of
 // them).  warped_all (STACK_MAP, or nullptr): [w.B][w.T][1024][E], the warped map of every slot beside warped_last.
 template <typename T>
@@ -170,7 +173,7 @@ void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode
         // evaluates the k | v rows of every slot, so a pass that fills the slot caches keeps the shortcut)
         const bool last = i + 1 == e->stk[stack].size() && (cache_mode == 0 || cache_mode == 3) && w.T > 1 && !no_tail && tail == TAIL_AUTO;
         tar_sub<T>(e, blk.sub[0], w.B, w.T, S, false);
-        tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_mode == 5);
+        tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_mode == 5 ? 1 : (cache_mode == 6 ? 2 : 0));
         tar_sub<T>(e, blk.sub[2], w.B, w.T, S, false, TemporalRange{0, nullptr, 0, 0}, last ? 2 : 0);
     }
 }
@@ -240,6 +243,25 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
     if (trace_logits) hipMemcpyAsync(trace_logits, e->logits, (size_t)3 * e->cfg.pose_vocab * 4, hipMemcpyDeviceToHost, e->stream);
     launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, forced ? e->d_forced : nullptr, e->d_ego_tok, B,
                       e->d_counters + 7, logp);
+}
+
+// run_ego for the fan frame of umgen_rollout_fan: the ego stack and decoder once per scene (the w.B scenes' whole windows), then every branch (b, s) -- item
+// b*N + s of e->d_seeds / e->d_ego_tok / logp -- draws its own pose from its scene's three head_ego rows with its own seed.  The rows are copied to the items'
+// places in e->logits scene by scene in DESCENDING b: scene b's rows lie where item b's go, and every destination of scene b is >= b*N, above every lower scene
+// whose rows are still unread (b == 0, s == 0 is the self-copy that is skipped).  The sampler and its logp then read the rows the replicated call's would.
+template <typename T>
+void run_ego_fan(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, int cache_mode, float* logp) {
+    const int B = w.B, Tn = w.T;
+    run_stack<T>(e, STACK_EGO, w, cache_mode);
+    std::vector<long> last(B);
+    for (int b = 0; b < B; ++b) last[b] = (long)b * Tn + (Tn - 1);
+    ego_decoder<T>(e, B, last.data(), w.Tfull ? w.Tfull : Tn, nullptr);
+    const size_t row3 = (size_t)3 * e->cfg.pose_vocab;
+    for (int b = B - 1; b >= 0; --b)
+        for (int s = N - 1; s >= 0; --s)
+            if (b * N + s != b)
+                hipMemcpyAsync(e->logits + (size_t)(b * N + s) * row3, e->logits + (size_t)b * row3, row3 * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
+    launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, nullptr, e->d_ego_tok, B * N, e->d_counters + 7, logp);
 }
 
 // The GIVEN-token prefix of a frame as ONE forward pass (infer_oar_net's first iteration pushes the whole predefined prefix through the 36
@@ -428,6 +450,10 @@ void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp
     e->cfg.precision == UMGEN_PREC_BF16 ? run_ego<bf16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
     : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego<f16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
                                           : run_ego<float>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp);
+}
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, int cache_mode, float* logp) {
+    e->cfg.precision == UMGEN_PREC_BF16 ? run_ego_fan<bf16_t>(e, w, N, sp, frame_idx, cache_mode, logp)
+    : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego_fan<f16_t>(e, w, N, sp, frame_idx, cache_mode, logp) : run_ego_fan<float>(e, w, N, sp, frame_idx, cache_mode, logp);
 }
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src) {
     return e->cfg.precision == UMGEN_PREC_BF16 ? run_prefix_prefill<bf16_t>(e, B, P, src)

@@ -85,7 +85,8 @@ struct umgen_engine {
     float *score_part = nullptr, *score_logp = nullptr;
     int* score_arg = nullptr;
     // umgen_score_candidates (engine_frame.hip run_score_candidates): the scene of every item (b, c) of the chunk in flight, [max_batch], and the number of
-    // scenes whose slot caches the chunk's last-slot pass reads (run_stack cache mode 5)
+    // scenes whose slot caches the chunk's last-slot pass reads (run_stack cache mode 5); umgen_rollout_fan's first frame (run_frame_fan) uses both the same way
+    // for its B * N branches (cache modes 5 / 6)
     int* d_item_scene = nullptr;
     int fan_scenes = 0;
     // umgen_score_clip (engine_frame.hip run_score_clip): allocated by its first call (ensure_score_clip), for max_batch * max_cond_frames items (b, slot) of one
@@ -320,6 +321,7 @@ void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_
 void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
                  float* logp = nullptr);
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, int cache_mode, float* logp);
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
@@ -353,6 +355,8 @@ int launch_bg_drain(umgen_engine* e, hipStream_t st);   // the launch without an
 
 // ---- engine_frame.hip -----------------------------------------------------------------------------------------------
 int run_frame_any(umgen_engine* e, const FrameIO& io);
+// umgen_rollout_fan's first frame: io.B = B * N branches as scenes (branch (b, s) at b*N + s, scene b's window replicated), io.T >= 2, slot caches allocated
+int run_frame_fan_any(umgen_engine* e, const FrameIO& io, int N);
 int run_score_any(umgen_engine* e, const ScoreIO& sc);
 int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc);
 int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc);

@@ -68,6 +68,14 @@ template <typename T> void launch_attn_temporal(hipStream_t s, const T* qkv, T* 
 // y [N][S][E] has the bits of launch_attn_temporal with t0 = P, write = 0 on a per-item copy of the cache.  The cache is never written; P >= 1, P + 1 <= 64.
 template <typename T> void launch_attn_temporal_fan(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P,
                                                     const T* cache, int Tcap);
+// The same launch that also leaves every item's own k | v rows in the cache (umgen_rollout_fan, a window that grows next): item i's rows of slot P, with the
+// bits of its qkv rows, go to block i, slot P -- the cache holds at least max(B, N) blocks and Tcap > P.  y has the bits of the read-only form; slots < P of
+// every block are only read, no other byte of the cache is written.
+template <typename T> void launch_attn_temporal_fan_write(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P,
+                                                          T* cache, int Tcap);
+// Behind it: slots [0, P) of the scene blocks b < B of cache [>= B*N blocks][Tcap][row_bytes] to the blocks b*N + s, s < N, in 16-byte vectors; slots >= P of
+// every block stay.  Scene by scene in descending b on the stream (block b is both scene b's source and item b's destination).  row_bytes % 16 == 0.
+void launch_tcache_spread(hipStream_t s, void* cache, int B, int N, int P, int Tcap, size_t row_bytes);
 
 // few-query attention over a key/value stream (OAR decode, ego decoder): partial pass, NSPLIT splits of the keys.
 //   q   [NQ][E] fp32;  K row of (scene sc, head h, key k) = kv_base + sc*scene_stride + h*head_stride + k*key_stride (48 values),

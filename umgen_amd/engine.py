@@ -34,6 +34,7 @@ class Engine:
         self.precision = precision
         self.max_batch = max_batch
         self.max_cond_frames = max_cond_frames
+        self.last_shared_slots = 0          # of the last rollout(samples=N): window slots of its first frame that ran once per scene
         c = _lib.Config(
             abi_version=4, n_embd=cfg.n_embd, n_head=cfg.n_head, n_ego_tar_layer=cfg.n_ego_tar_layer,
             n_ego_ca_layer=cfg.n_ego_ca_layer, n_map_tar_layer=cfg.n_map_tar_layer, n_box_tar_layer=cfg.n_box_tar_layer,
@@ -118,8 +119,13 @@ class Engine:
     def rollout(self, tokens: Dict[str, np.ndarray], new_frames: int, cond_frames: int = 20,
                 input_cond_frames: int = -1, init_tokens: Optional[Dict[str, np.ndarray]] = None,
                 control_test: bool = False, seeds: Optional[Sequence[int]] = None,
-                sampling: Optional[RolloutConfig] = None, return_logp: bool = False):
+                sampling: Optional[RolloutConfig] = None, return_logp: bool = False, samples: Optional[int] = None):
         """tokens: mod -> int64 [B, T, S_mod].  Returns mod -> int64 [B, input_cond_frames + new_frames, S_mod].
+        samples=N (umgen_rollout_fan): N sampled futures of every scene off one pass over its history.  seeds: [B, N] or flat B*N (default 0), branch
+        (b, s) at b*N + s; init_tokens stay per scene, a scene's branches share them.  Returns mod -> int64 [B, N, input_cond_frames + new_frames, S_mod],
+        and with return_logp also mod -> float32 [B, N, new_frames, S_mod]: branch (b, s) has the bits of scene b*N + s of this call on the inputs
+        replicated N times.  last_shared_slots records the first frame's window slots that ran once per scene (0: the replicated path).
+        samples=None is the plain call.
         return_logp: returns (tokens, mod -> float32 [B, new_frames, S_mod]) -- the log-likelihood of every generated token under the plain AR
         heads at temperature 1 (umgen_rollout_logp, include/umgen.h: Engine.score's measure, taken from the decode steps that sampled the
         token); NaN where no head ran (a controlled pose, given map / bbox3d tokens).  The tokens are the same either way."""
@@ -133,7 +139,19 @@ class Engine:
         for m in MOD_ORDER:
             if arrs[m].shape != (B, T_in, CONTENT_LEN[m]):
                 raise UMGenError(f"tokens[{m}] has shape {arrs[m].shape}, expected {(B, T_in, CONTENT_LEN[m])}")
-        outs = {m: np.empty((B, T_in + new_frames, CONTENT_LEN[m]), dtype=np.int64) for m in MOD_ORDER}
+        lead = (B,)
+        if samples is not None:
+            if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:
+                raise UMGenError(f"rollout: samples={samples!r} must be an integer >= 1")
+            samples = int(samples)
+            lead = (B, samples)
+            sd = np.zeros(B * samples, np.uint64) if seeds is None else np.asarray(seeds)
+            if sd.shape not in ((B, samples), (B * samples,)):
+                raise UMGenError(f"rollout: seeds has shape {sd.shape}, expected {(B, samples)} or {(B * samples,)}")
+            if sd.dtype.kind not in "iu":
+                raise UMGenError(f"rollout: seeds has dtype {sd.dtype}, expected an integer type")
+            seeds = sd.reshape(-1)
+        outs = {m: np.empty(lead + (T_in + new_frames, CONTENT_LEN[m]), dtype=np.int64) for m in MOD_ORDER}
         cp = cb = gm = gb = None
         T_ctl = 0
         if init_tokens is not None:
@@ -169,6 +187,13 @@ class Engine:
         args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
+        if samples is not None:
+            logp, lp = self._logp_out(lead + (new_frames,)) if return_logp else (None, None)
+            shared = C.c_int32(-1)
+            self._check(self.lib.umgen_rollout_fan(self._h, B, samples, *args[2:], C.byref(lp) if lp is not None else None, C.byref(shared)), "rollout")
+            del keep
+            self.last_shared_slots = int(shared.value)
+            return (outs, logp) if return_logp else outs
         if not return_logp:
             self._check(self.lib.umgen_rollout(*args), "rollout")
             del keep

@@ -137,10 +137,14 @@ class UMGen(nn.Module):
     def inference(self, new_frames: int, cond_frames: int = 1, input_cond_frames: int = -1, pred_task: str = "image",
                   input_cond_tokens: Optional[Dict[str, torch.Tensor]] = None,
                   init_tokens: Optional[Dict[str, torch.Tensor]] = None, cond_on_tar: bool = False,
-                  test_map_affine: bool = False, max_objects=100, control_test=False, return_logp: bool = False, **kwargs):
+                  test_map_affine: bool = False, max_objects=100, control_test=False, return_logp: bool = False,
+                  num_samples: Optional[int] = None, **kwargs):
         """UMGen.inference (UMGen.py:1542-1671).  ``cond_on_par`` / ``infer_from_gt`` are swallowed like the reference.
         return_logp (extension): returns (tokens, mod -> torch.float32 [B, new_frames, S_mod]), the log-likelihood of every generated token
-        (Engine.rollout's return_logp; NaN on controlled / given positions), beside the tokens it returns today."""
+        (Engine.rollout's return_logp; NaN on controlled / given positions), beside the tokens it returns today.
+        num_samples=N (extension): N sampled futures of every scene off one pass over its history (Engine.rollout's samples).  Returns mod -> torch.int64
+        [B, N, T, S_mod]; with return_logp (tokens, logp) where logp holds mod -> torch.float32 [B, N, new_frames, S_mod] and "total", torch.float64
+        [B, N, new_frames]: the host sum over a frame's finite entries, the ranking key for best-of-N.  seeds: [B, N] or flat B*N (default seed + i)."""
         if pred_task != "pose_map_bbox3d_image":
             raise UMGenError(f"pred_task={pred_task!r}: only 'pose_map_bbox3d_image' (the evaluation task) is implemented")
         if not self._loaded:
@@ -153,6 +157,20 @@ class UMGen(nn.Module):
             init = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v))
                     for k, v in init_tokens.items() if v is not None}      # (pose / bbox3d control, given map / map + bbox3d; the engine rejects anything else)
         B = toks["pose"].shape[0]
+        if num_samples is not None:
+            if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or num_samples < 1:
+                raise UMGenError(f"num_samples={num_samples!r} must be an integer >= 1")
+            N = int(num_samples)
+            if B * N > self._engine_args["max_batch"]:
+                self._recreate(max_batch=B * N)
+            seeds = kwargs.get("seeds", [self.seed + i for i in range(B * N)])
+            out = self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames, init_tokens=init,
+                                      control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp), samples=N)
+            if not return_logp:
+                return {m: torch.from_numpy(v) for m, v in out.items()}
+            lp = {m: torch.from_numpy(v) for m, v in out[1].items()}
+            lp["total"] = torch.from_numpy(sum(np.where(np.isfinite(v), v, 0).astype(np.float64).sum(axis=-1) for v in out[1].values()))
+            return {m: torch.from_numpy(v) for m, v in out[0].items()}, lp
         if B > self._engine_args["max_batch"]:      # extension over the reference (B = 1): several scenes per call
             self._recreate(max_batch=B)
         seeds = kwargs.get("seeds", [self.seed + i for i in range(B)])
