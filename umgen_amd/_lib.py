@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # UMGEN_LIB_PATH selects an alternative build of the SAME library (kernel experiments with extra -D flags); never a fallback
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
-SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
+SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "engine_score.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
            "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip", "debug_vq.hip"]
 EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp", "umgen_rollout_fan",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
@@ -32,7 +32,7 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_vq_quantize", "umgen_dbg_vq_quant_tile", "umgen_dbg_vq_im2col", "umgen_dbg_vq_im2col_s2", "umgen_dbg_vq_upsample", "umgen_dbg_vq_from_nchw", "umgen_dbg_vq_to_nchw",
            "umgen_dbg_vq_group_norm", "umgen_dbg_vq_softmax"]
 
-HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
+HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "engine_frame.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
 
 PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DT_F32, DT_BF16, DT_F16, DT_F64 = 0, 1, 2, 3

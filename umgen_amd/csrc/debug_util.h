@@ -144,7 +144,7 @@ inline bool in_range(const int32_t* t, size_t n, int hi) {
         if (t[i] < 0 || t[i] >= hi) return false;
     return true;
 }
-inline int kind_of_pos(int j, int given_end) {    // the decode loops' kind_of (engine_frame.hip): 0 fixed token, 1 map, 2 bbox3d, 3 image
+inline int kind_of_pos(int j, int given_end) {    // the decode loops' step_kind (engine_frame.hip): 0 fixed token, 1 map, 2 bbox3d, 3 image
     if (j < given_end) return 0;
     return (j >= kMapC0 && j < kMapEos) ? 1 : (j >= kBoxC0 && j < kBoxEos) ? 2 : (j >= kImgC0 && j < kImgEos) ? 3 : 0;
 }

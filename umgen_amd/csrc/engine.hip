@@ -1,6 +1,6 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan (UMGen.inference).  Creation, weights, the compute path and the frame itself are in
-// engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip and engine_frame.hip.
+// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan (UMGen.inference).  Creation, weights, the compute path, the frame itself and the scoring passes are in
+// engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip, engine_frame.hip and engine_score.hip.
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -132,71 +132,80 @@ int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* 
                             out_bbox3d, out_image, nullptr);
 }
 
-// umgen_score and umgen_score_detail: log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes, and
-// with `detail` the diagnostics of the same rows: engine_frame.hip run_score
-static int score_call(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
-                      const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, umgen_score_out* out,
-                      const umgen_score_detail_out* detail, int32_t topk, float temperature) {
+// ---- umgen_score(_detail), umgen_score_candidates, umgen_score_clip: the passes of engine_score.hip behind the argument checks ----
+
+// What the three calls check alike, in their common order: the engine and B first; then, behind what only the call itself takes, the output struct,
+// the token buffers -- a history of `frames` frames and, with next, n_next frames to score that an error names next_what -- the head, and every token
+static int check_score_engine(umgen_engine* e, int32_t B) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
-    if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
-    if (!out && !detail) return e->fail(UMGEN_E_INVALID, "null output struct");
-    if (detail) {
+    return 0;
+}
+static int check_score_common(umgen_engine* e, bool have_out, const int64_t* const win[4], size_t frames, const int64_t* const* next, size_t n_next,
+                              const char* next_what) {
+    if (!have_out) return e->fail(UMGEN_E_INVALID, "null output struct");
+    for (int m = 0; m < 4; ++m)
+        if (!win[m] || (next && !next[m])) return e->fail(UMGEN_E_INVALID, "null token buffer");
+    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
+    if (int rc = check_scene_tokens(e, frames, win[0], win[1], win[2], win[3])) return rc;
+    if (!next) return 0;
+    const int rc = check_scene_tokens(e, n_next, next[0], next[1], next[2], next[3]);
+    if (rc) e->err = std::string(next_what) + ": " + e->err;
+    return rc;
+}
+static int check_window_length(umgen_engine* e, int32_t T) {
+    return T < 1 || T > e->cfg.max_cond_frames ? e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames) : 0;
+}
+
+// int64 tokens [frames][S_mod] of every modality as int32
+static void narrow_tokens(const int64_t* const in[4], size_t frames, std::vector<int> out[4]) {
+    for (int m = 0; m < 4; ++m) {
+        out[m].resize(frames * kModLen[m]);
+        for (size_t i = 0; i < out[m].size(); ++i) out[m][i] = (int)in[m][i];
+    }
+}
+// n frames, [n][S_mod] per modality, as int32 rows [n][2199] pose | map | bbox3d | image
+static std::vector<int> frame_rows(const int64_t* const in[4], size_t n) {
+    std::vector<int> rows(n * kTokPerFrame);
+    for (int m = 0; m < 4; ++m)
+        for (size_t it = 0; it < n; ++it)
+            for (int i = 0; i < kModLen[m]; ++i) rows[it * kTokPerFrame + kModOff[m] + i] = (int)in[m][it * kModLen[m] + i];
+    return rows;
+}
+static ScoreDst score_dst(const umgen_score_out* o) {
+    if (!o) return ScoreDst{};
+    return ScoreDst{{o->logp_pose, o->logp_map, o->logp_bbox3d, o->logp_image}, {o->argmax_pose, o->argmax_map, o->argmax_bbox3d, o->argmax_image}};
+}
+
+// umgen_score and umgen_score_detail: log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes, and
+// with `detail` the diagnostics of the same rows: engine_score.hip run_score
+static int score_call(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                      const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image, umgen_score_out* out,
+                      const umgen_score_detail_out* d, int32_t topk, float temperature) {
+    const int64_t *in[4] = {pose, map, bbox3d, image}, *nx[4] = {next_pose, next_map, next_bbox3d, next_image};
+    if (int rc = check_score_engine(e, B)) return rc;
+    if (int rc = check_window_length(e, T)) return rc;
+    if (d) {
         if (topk < 0 || topk > UMGEN_SCORE_TOPK_MAX) return e->fail(UMGEN_E_INVALID, "topk=%d out of range [0,%d]", topk, UMGEN_SCORE_TOPK_MAX);
         if (!(temperature > 0.f) || !(temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0 and finite");
-        const bool lists = detail->topk_tok_pose || detail->topk_tok_map || detail->topk_tok_bbox3d || detail->topk_tok_image || detail->topk_logp_pose ||
-                           detail->topk_logp_map || detail->topk_logp_bbox3d || detail->topk_logp_image;
+        const bool lists = d->topk_tok_pose || d->topk_tok_map || d->topk_tok_bbox3d || d->topk_tok_image || d->topk_logp_pose || d->topk_logp_map ||
+                           d->topk_logp_bbox3d || d->topk_logp_image;
         if (lists && topk == 0) return e->fail(UMGEN_E_INVALID, "top-K outputs requested with topk = 0");
     }
-    if (!pose || !map || !bbox3d || !image || !next_pose || !next_map || !next_bbox3d || !next_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
-    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
-    if (int rc = check_scene_tokens(e, (size_t)B * T, pose, map, bbox3d, image)) return rc;
-    if (int rc = check_scene_tokens(e, (size_t)B, next_pose, next_map, next_bbox3d, next_image)) {
-        e->err = "next frame: " + e->err;
-        return rc;
-    }
-    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
-    const int64_t* in[4] = {pose, map, bbox3d, image};
-    const int64_t* nx[4] = {next_pose, next_map, next_bbox3d, next_image};
-    std::vector<int> win[4], next((size_t)B * kTokPerFrame);
-    for (int m = 0; m < 4; ++m) {
-        win[m].resize((size_t)B * T * S[m]);
-        for (size_t i = 0; i < win[m].size(); ++i) win[m][i] = (int)in[m][i];
-        for (int b = 0; b < B; ++b)
-            for (int i = 0; i < S[m]; ++i) next[(size_t)b * kTokPerFrame + off[m] + i] = (int)nx[m][(size_t)b * S[m] + i];
-    }
-    std::vector<float> logp((size_t)B * kTokPerFrame);
-    std::vector<int> arg((size_t)B * kTokPerFrame);
-    ScoreIO sc{B, T, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), logp.data(), arg.data()};
-    const size_t rows = (size_t)B * kTokPerFrame;
-    std::vector<int> rank(detail ? rows : 0), tok(detail ? rows * topk : 0);
-    std::vector<float> mass(detail ? rows : 0), ent(detail ? rows : 0), tlp(detail ? rows * topk : 0);
-    const ScoreDetailIO dio{topk, temperature, rank.data(), mass.data(), ent.data(), tok.data(), tlp.data()};
-    if (detail) sc.detail = &dio;
-    if (int rc = run_score_any(e, sc)) return rc;
-    for (int m = 0; m < 4; ++m) {      // the engine's blocks are pose | map | bbox3d | image, each [B][S_mod]
-        const size_t b0 = (size_t)B * off[m], n = (size_t)B * S[m];
-        if (out) {
-            float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
-            int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
-            if (lo[m]) memcpy(lo[m], &logp[b0], n * sizeof(float));
-            if (ao[m]) memcpy(ao[m], &arg[b0], n * sizeof(int32_t));
-        }
-        if (detail) {
-            int32_t* ro[4] = {detail->rank_pose, detail->rank_map, detail->rank_bbox3d, detail->rank_image};
-            float* mo[4] = {detail->mass_above_pose, detail->mass_above_map, detail->mass_above_bbox3d, detail->mass_above_image};
-            float* eo[4] = {detail->entropy_pose, detail->entropy_map, detail->entropy_bbox3d, detail->entropy_image};
-            int32_t* to[4] = {detail->topk_tok_pose, detail->topk_tok_map, detail->topk_tok_bbox3d, detail->topk_tok_image};
-            float* po[4] = {detail->topk_logp_pose, detail->topk_logp_map, detail->topk_logp_bbox3d, detail->topk_logp_image};
-            if (ro[m]) memcpy(ro[m], &rank[b0], n * sizeof(int32_t));
-            if (mo[m]) memcpy(mo[m], &mass[b0], n * sizeof(float));
-            if (eo[m]) memcpy(eo[m], &ent[b0], n * sizeof(float));
-            if (to[m]) memcpy(to[m], &tok[b0 * topk], n * topk * sizeof(int32_t));
-            if (po[m]) memcpy(po[m], &tlp[b0 * topk], n * topk * sizeof(float));
-        }
-    }
-    return UMGEN_OK;
+    if (int rc = check_score_common(e, out || d, in, (size_t)B * T, nx, (size_t)B, "next frame")) return rc;
+    std::vector<int> win[4];
+    narrow_tokens(in, (size_t)B * T, win);
+    const std::vector<int> next = frame_rows(nx, (size_t)B);
+    ScoreIO sc{B, T, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), score_dst(out)};
+    const ScoreDetailIO dio = !d ? ScoreDetailIO{}
+                                 : ScoreDetailIO{topk, temperature, {d->rank_pose, d->rank_map, d->rank_bbox3d, d->rank_image},
+                                                 {d->mass_above_pose, d->mass_above_map, d->mass_above_bbox3d, d->mass_above_image},
+                                                 {d->entropy_pose, d->entropy_map, d->entropy_bbox3d, d->entropy_image},
+                                                 {d->topk_tok_pose, d->topk_tok_map, d->topk_tok_bbox3d, d->topk_tok_image},
+                                                 {d->topk_logp_pose, d->topk_logp_map, d->topk_logp_bbox3d, d->topk_logp_image}};
+    if (d) sc.detail = &dio;
+    return run_score_any(e, sc);
 }
 
 int umgen_score(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
@@ -212,82 +221,38 @@ int umgen_score_detail(umgen_engine* e, int32_t B, int32_t T, const int64_t* pos
     return score_call(e, B, T, pose, map, bbox3d, image, next_pose, next_map, next_bbox3d, next_image, out, detail, topk, temperature);
 }
 
-// umgen_score_candidates: C given next frames per scene against one history (engine_frame.hip run_score_candidates)
+// umgen_score_candidates: C given next frames per scene against one history (engine_score.hip run_score_candidates)
 int umgen_score_candidates(umgen_engine* e, int32_t B, int32_t T, int32_t C, const int64_t* pose, const int64_t* map, const int64_t* bbox3d,
                            const int64_t* image, const int64_t* next_pose, const int64_t* next_map, const int64_t* next_bbox3d, const int64_t* next_image,
                            umgen_score_out* out, int32_t* shared_slots) {
-    if (!e) return UMGEN_E_INVALID;
-    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
-    if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
-    if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
+    const int64_t *in[4] = {pose, map, bbox3d, image}, *nx[4] = {next_pose, next_map, next_bbox3d, next_image};
+    if (int rc = check_score_engine(e, B)) return rc;
+    if (int rc = check_window_length(e, T)) return rc;
     if (C < 1) return e->fail(UMGEN_E_INVALID, "C=%d: at least one candidate per scene", C);
-    if (!out) return e->fail(UMGEN_E_INVALID, "null output struct");
-    if (!pose || !map || !bbox3d || !image || !next_pose || !next_map || !next_bbox3d || !next_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
-    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
-    if (int rc = check_scene_tokens(e, (size_t)B * T, pose, map, bbox3d, image)) return rc;
-    if (int rc = check_scene_tokens(e, (size_t)B * C, next_pose, next_map, next_bbox3d, next_image)) {
-        e->err = "candidate frames: " + e->err;
-        return rc;
-    }
-    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
-    const int64_t* in[4] = {pose, map, bbox3d, image};
-    const int64_t* nx[4] = {next_pose, next_map, next_bbox3d, next_image};
-    const size_t N = (size_t)B * C;
-    std::vector<int> win[4], next(N * kTokPerFrame);
-    for (int m = 0; m < 4; ++m) {
-        win[m].resize((size_t)B * T * S[m]);
-        for (size_t i = 0; i < win[m].size(); ++i) win[m][i] = (int)in[m][i];
-        for (size_t it = 0; it < N; ++it)
-            for (int i = 0; i < S[m]; ++i) next[it * kTokPerFrame + off[m] + i] = (int)nx[m][it * S[m] + i];
-    }
-    std::vector<float> logp(N * kTokPerFrame);
-    std::vector<int> arg(N * kTokPerFrame);
-    ScoreCandIO sc{B, T, C, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), logp.data(), arg.data(), 0};
+    if (int rc = check_score_common(e, out, in, (size_t)B * T, nx, (size_t)B * C, "candidate frames")) return rc;
+    std::vector<int> win[4];
+    narrow_tokens(in, (size_t)B * T, win);
+    const std::vector<int> next = frame_rows(nx, (size_t)B * C);
+    ScoreCandIO sc{B, T, C, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), score_dst(out), 0};
     if (int rc = run_score_candidates_any(e, sc)) return rc;
-    float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
-    int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
-    for (int m = 0; m < 4; ++m)
-        for (size_t it = 0; it < N; ++it) {
-            if (lo[m]) memcpy(lo[m] + it * S[m], &logp[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(float));
-            if (ao[m]) memcpy(ao[m] + it * S[m], &arg[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(int32_t));
-        }
     if (shared_slots) *shared_slots = sc.shared_slots;
     return UMGEN_OK;
 }
 
-// umgen_score_clip: every frame of B recorded clips against the frames before it, the growing windows off one pass (engine_frame.hip run_score_clip)
+// umgen_score_clip: every frame of B recorded clips against the frames before it, the growing windows off one pass (engine_score.hip run_score_clip)
 int umgen_score_clip(umgen_engine* e, int32_t B, int32_t L, int32_t T_in, int32_t cond_frames, const int64_t* pose, const int64_t* map,
                      const int64_t* bbox3d, const int64_t* image, umgen_score_out* out, int32_t* shared_frames) {
-    if (!e) return UMGEN_E_INVALID;
-    if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
-    if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
+    const int64_t* in[4] = {pose, map, bbox3d, image};
+    if (int rc = check_score_engine(e, B)) return rc;
     if (L < 2) return e->fail(UMGEN_E_INVALID, "L=%d: a clip has at least two frames", L);
     if (T_in < 1 || T_in >= L) return e->fail(UMGEN_E_INVALID, "T_in=%d out of range [1,%d) (L=%d)", T_in, L, L);
     if (cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
         return e->fail(UMGEN_E_INVALID, "cond_frames=%d out of range [1,%d]", cond_frames, e->cfg.max_cond_frames);
-    if (!out) return e->fail(UMGEN_E_INVALID, "null output struct");
-    if (!pose || !map || !bbox3d || !image) return e->fail(UMGEN_E_INVALID, "null token buffer");
-    if (!head_nll_supported(e->E)) return e->fail(UMGEN_E_UNSUPPORTED, "the scoring head is built for n_embd 96 / 768 / 1536, not %d", e->E);
-    if (int rc = check_scene_tokens(e, (size_t)B * L, pose, map, bbox3d, image)) return rc;
-    const int S[4] = {kNPose, kNMap, kNBox, kNImg}, off[4] = {0, kOffMap, kOffBox, kOffImg};
-    const int64_t* in[4] = {pose, map, bbox3d, image};
+    if (int rc = check_score_common(e, out, in, (size_t)B * L, nullptr, 0, nullptr)) return rc;
     std::vector<int> clip[4];
-    for (int m = 0; m < 4; ++m) {
-        clip[m].resize((size_t)B * L * S[m]);
-        for (size_t i = 0; i < clip[m].size(); ++i) clip[m][i] = (int)in[m][i];
-    }
-    const size_t N = (size_t)B * (L - T_in);
-    std::vector<float> logp(N * kTokPerFrame);
-    std::vector<int> arg(N * kTokPerFrame);
-    ScoreClipIO sc{B, L, T_in, cond_frames, clip[0].data(), clip[1].data(), clip[2].data(), clip[3].data(), logp.data(), arg.data(), 0};
+    narrow_tokens(in, (size_t)B * L, clip);
+    ScoreClipIO sc{B, L, T_in, cond_frames, clip[0].data(), clip[1].data(), clip[2].data(), clip[3].data(), score_dst(out), 0};
     if (int rc = run_score_clip_any(e, sc)) return rc;
-    float* lo[4] = {out->logp_pose, out->logp_map, out->logp_bbox3d, out->logp_image};
-    int32_t* ao[4] = {out->argmax_pose, out->argmax_map, out->argmax_bbox3d, out->argmax_image};
-    for (int m = 0; m < 4; ++m)
-        for (size_t it = 0; it < N; ++it) {
-            if (lo[m]) memcpy(lo[m] + it * S[m], &logp[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(float));
-            if (ao[m]) memcpy(ao[m] + it * S[m], &arg[it * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(int32_t));
-        }
     if (shared_frames) *shared_frames = sc.shared_frames;
     return UMGEN_OK;
 }
@@ -322,19 +287,18 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
     e->tm = umgen_timings{};
     e->overlap_suspended = false;
     const int T_out = T_in + new_frames;
-    const int S[4] = {kNPose, kNMap, kNBox, kNImg};
     const int64_t* in[4] = {pose, map, bbox3d, image};
     int64_t* out[4] = {out_pose, out_map, out_bbox3d, out_image};
     // history: out_tokens and cond_tokens both start as the first T_in frames (UMGen.py:1581-1595)
     std::vector<int> hist[4];   // [B][T_cur][S] "cond_tokens" window (control mode mutates its last bbox3d frame in place)
     for (int m = 0; m < 4; ++m) {
-        hist[m].resize((size_t)B * T_in * S[m]);
+        hist[m].resize((size_t)B * T_in * kModLen[m]);
         for (int b = 0; b < B; ++b)
             for (int t = 0; t < T_in; ++t)
-                for (int i = 0; i < S[m]; ++i) {
-                    const int64_t v = in[m][((size_t)b * T_in + t) * S[m] + i];
-                    hist[m][((size_t)b * T_in + t) * S[m] + i] = (int)v;
-                    out[m][((size_t)b * T_out + t) * S[m] + i] = v;
+                for (int i = 0; i < kModLen[m]; ++i) {
+                    const int64_t v = in[m][((size_t)b * T_in + t) * kModLen[m] + i];
+                    hist[m][((size_t)b * T_in + t) * kModLen[m] + i] = (int)v;
+                    out[m][((size_t)b * T_out + t) * kModLen[m] + i] = v;
                 }
     }
     int T_cur = T_in;
@@ -351,10 +315,10 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
     for (int idx = 0; idx < new_frames; ++idx) {
         if (T_cur > cond_frames) {   // sliding window (UMGen.py:1600-1603)
             for (int m = 0; m < 4; ++m) {
-                std::vector<int> nw((size_t)B * cond_frames * S[m]);
+                std::vector<int> nw((size_t)B * cond_frames * kModLen[m]);
                 for (int b = 0; b < B; ++b)
-                    memcpy(&nw[(size_t)b * cond_frames * S[m]], &hist[m][((size_t)b * T_cur + (T_cur - cond_frames)) * S[m]],
-                           (size_t)cond_frames * S[m] * sizeof(int));
+                    memcpy(&nw[(size_t)b * cond_frames * kModLen[m]], &hist[m][((size_t)b * T_cur + (T_cur - cond_frames)) * kModLen[m]],
+                           (size_t)cond_frames * kModLen[m] * sizeof(int));
                 hist[m].swap(nw);
             }
             T_cur = cond_frames;
@@ -405,21 +369,20 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
         if (fan && shared_slots) *shared_slots = T_cur - 1;
         if (int rc = fan ? run_frame_fan_any(e, io, fan_N) : run_frame_any(e, io)) return rc;
         // append (UMGen.py:1636-1666): control pose tokens are copied verbatim; everything else is what was generated
-        const int off[4] = {0, kOffMap, kOffBox, kOffImg};
         for (int m = 0; m < 4; ++m) {
-            std::vector<int> nw((size_t)B * (T_cur + 1) * S[m]);
+            std::vector<int> nw((size_t)B * (T_cur + 1) * kModLen[m]);
             for (int b = 0; b < B; ++b) {
-                memcpy(&nw[(size_t)b * (T_cur + 1) * S[m]], &hist[m][(size_t)b * T_cur * S[m]], (size_t)T_cur * S[m] * sizeof(int));
-                for (int i = 0; i < S[m]; ++i) {
-                    const int v = frame_out[(size_t)b * kTokPerFrame + off[m] + i];
-                    nw[((size_t)b * (T_cur + 1) + T_cur) * S[m] + i] = v;
-                    out[m][((size_t)b * T_out + T_in + idx) * S[m] + i] = v;
+                memcpy(&nw[(size_t)b * (T_cur + 1) * kModLen[m]], &hist[m][(size_t)b * T_cur * kModLen[m]], (size_t)T_cur * kModLen[m] * sizeof(int));
+                for (int i = 0; i < kModLen[m]; ++i) {
+                    const int v = frame_out[(size_t)b * kTokPerFrame + kModOff[m] + i];
+                    nw[((size_t)b * (T_cur + 1) + T_cur) * kModLen[m] + i] = v;
+                    out[m][((size_t)b * T_out + T_in + idx) * kModLen[m] + i] = v;
                 }
             }
             hist[m].swap(nw);
             if (lp_out[m] && !frame_logp.empty())
                 for (int b = 0; b < B; ++b)
-                    memcpy(lp_out[m] + ((size_t)b * new_frames + idx) * S[m], &frame_logp[(size_t)b * kTokPerFrame + off[m]], (size_t)S[m] * sizeof(float));
+                    memcpy(lp_out[m] + ((size_t)b * new_frames + idx) * kModLen[m], &frame_logp[(size_t)b * kTokPerFrame + kModOff[m]], (size_t)kModLen[m] * sizeof(float));
         }
         T_cur += 1;
     }

@@ -199,8 +199,7 @@ int launch_bg_drain(umgen_engine* e, hipStream_t st) {
 }
 
 int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j) {
-    return e->cfg.precision == UMGEN_PREC_BF16 ? enqueue_step<bf16_t>(e, B, mod, ns, tr, j)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? enqueue_step<f16_t>(e, B, mod, ns, tr, j) : enqueue_step<float>(e, B, mod, ns, tr, j);
+    return with_precision(e, [&](auto t) { return enqueue_step<decltype(t)>(e, B, mod, ns, tr, j); });
 }
 
 }  // namespace umgen

@@ -128,8 +128,8 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
             for (const Range& r : rest) linear_store<T>(e, Wqkv, w.attn.bqkv, E, E, A + r.row0 * E, r.rows, QKV + r.row0 * 3 * E, 3L * E, 0);
             tr.q0 = tr.t0 + Tn - 1;
         }
-        // fan: the B rows-of-one-slot are items that share their scenes' cached slots [0, tr.t0) (cache mode 5 of run_stack); 2: item i also leaves its own
-        // k | v rows in block i, slot tr.t0 (cache mode 6)
+        // fan: the B rows-of-one-slot are items that share their scenes' cached slots [0, tr.t0) (CACHE_SHARED_ITEMS); 2: item i also leaves its own
+        // k | v rows in block i, slot tr.t0 (CACHE_SHARED_ITEMS_APPEND)
         if (fan == 2) launch_attn_temporal_fan_write<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<T*>(tr.cache), tr.Tcap);
         else if (fan) launch_attn_temporal_fan<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<const T*>(tr.cache), tr.Tcap);
         else launch_attn_temporal<T>(e->stream, QKV, A, B, Tn, S, H, tr);
@@ -151,16 +151,11 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
     }
 }
 
-// cache_mode: 0 = one pass over the whole window; 1 = prefix pass (slots [0, w.T), k | v appended to the slot caches);
-// 2 = last-slot pass (slots [w.t0, w.t0 + w.T) against the caches); 3 = whole window like 0, and its k | v rows are left in the slot
-// caches for a longer window that follows; 4 = last-slot pass like 2 that appends its own k | v rows (the window keeps growing);
-// 5 = last-slot pass like 2 of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of e->fan_scenes scenes: item i reads the slots [0, P) of scene
-// e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window); 6 = 5, and item i appends its own k | v rows to
-// block i of the caches (umgen_rollout_fan ahead of a longer window: spread_tcaches then hands every item its scene's slots [0, P))
+// cache_mode: enum CacheMode (engine_state.h).
 // tail: TAIL_AUTO = the final block's last-frame shortcut wherever it applies (below); TAIL_NONE = every block on every slot (umgen_score_clip reads all of
 // them).  warped_all (STACK_MAP, or nullptr): [w.B][w.T][1024][E], the warped map of every slot beside warped_last.
 template <typename T>
-void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode = 0, int tail = TAIL_AUTO, float* warped_all = nullptr) {
+void run_stack(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr) {
     const int S = stack_len(stack);
     launch_embed_stack(e->stream, stack, e->tb, w, e->X, e->mapfeat);
     if (stack != STACK_EGO) launch_warp_map(e->stream, stack, e->tb, w.B, w.T, e->mapfeat, e->pose_diff, e->X,
@@ -168,12 +163,12 @@ void run_stack(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode
     static const bool no_tail = getenv("UMGEN_NO_TAIL") != nullptr;   // measurement: evaluate every block on every frame like the reference
     for (size_t i = 0; i < e->stk[stack].size(); ++i) {
         const TarW& blk = e->stk[stack][i];
-        TemporalRange tr{w.t0, cache_mode ? e->tcache[stack][i] : nullptr, e->cfg.max_cond_frames, (cache_mode == 1 || cache_mode == 3 || cache_mode == 4) ? 1 : 0};
+        TemporalRange tr{w.t0, cache_mode != CACHE_NONE ? e->tcache[stack][i] : nullptr, e->cfg.max_cond_frames, cache_writes(cache_mode) ? 1 : 0};
         // the final block's tail on the last frame only (f-3): whole-window passes with more than one slot (the temporal sub-block still
         // evaluates the k | v rows of every slot, so a pass that fills the slot caches keeps the shortcut)
-        const bool last = i + 1 == e->stk[stack].size() && (cache_mode == 0 || cache_mode == 3) && w.T > 1 && !no_tail && tail == TAIL_AUTO;
+        const bool last = i + 1 == e->stk[stack].size() && cache_whole_window(cache_mode) && w.T > 1 && !no_tail && tail == TAIL_AUTO;
         tar_sub<T>(e, blk.sub[0], w.B, w.T, S, false);
-        tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_mode == 5 ? 1 : (cache_mode == 6 ? 2 : 0));
+        tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_fan_form(cache_mode));
         tar_sub<T>(e, blk.sub[2], w.B, w.T, S, false, TemporalRange{0, nullptr, 0, 0}, last ? 2 : 0);
     }
 }
@@ -234,7 +229,7 @@ void ego_decoder(umgen_engine* e, int n, const long* frame_of, int Tq, const int
 // (UMGen.py:1002), so the 12 decoder blocks run on the last frame only -- identical outputs, 1/T of the work.
 template <typename T>
 void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits,
-             int cache_mode = 0, float* logp = nullptr) {
+             CacheMode cache_mode, float* logp = nullptr) {
     const int B = w.B, Tn = w.T;   // Tn: slots in this pass (the last one is the window's last frame)
     run_stack<T>(e, STACK_EGO, w, cache_mode);
     std::vector<long> last(B);
@@ -250,7 +245,7 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
 // places in e->logits scene by scene in DESCENDING b: scene b's rows lie where item b's go, and every destination of scene b is >= b*N, above every lower scene
 // whose rows are still unread (b == 0, s == 0 is the self-copy that is skipped).  The sampler and its logp then read the rows the replicated call's would.
 template <typename T>
-void run_ego_fan(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, int cache_mode, float* logp) {
+void run_ego_fan(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp) {
     const int B = w.B, Tn = w.T;
     run_stack<T>(e, STACK_EGO, w, cache_mode);
     std::vector<long> last(B);
@@ -324,17 +319,17 @@ int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& eg
     umgen_engine::Prefix& px = e->px;
     px.valid = false;
     px.B = B; px.P = P; px.Tfull = Tnext; px.has_ego = !io.next_has_ctrl_pose;
-    const int S[4] = {kNPose, kNMap, kNBox, kNImg};
     const int* cur[4] = {io.pose, io.map, io.box, io.img};
     std::vector<int>* keep[4] = {&px.pose, &px.map, &px.box, &px.img};
     std::vector<int>* up[4] = {&e->px_up[0], &e->px_up[1], &e->px_up[2], &e->px_up[3]};
     for (int m = 0; m < 4; ++m) {
-        keep[m]->assign((size_t)B * P * S[m], 0);
-        up[m]->assign((size_t)B * Tnext * S[m], 0);
+        const size_t S = kModLen[m];
+        keep[m]->assign(B * P * S, 0);
+        up[m]->assign(B * Tnext * S, 0);
         for (int b = 0; b < B; ++b) {
-            const int* src = cur[m] + ((size_t)b * Tn + off) * S[m];
-            memcpy(keep[m]->data() + (size_t)b * P * S[m], src, (size_t)P * S[m] * sizeof(int));
-            memcpy(up[m]->data() + (size_t)b * Tnext * S[m], src, (size_t)P * S[m] * sizeof(int));
+            const int* src = cur[m] + ((size_t)b * Tn + off) * S;
+            memcpy(keep[m]->data() + b * P * S, src, P * S * sizeof(int));
+            memcpy(up[m]->data() + b * Tnext * S, src, P * S * sizeof(int));
         }
     }
     px.pose_next.assign(ego.begin(), ego.end());
@@ -356,10 +351,10 @@ int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& eg
     HIPCHK(e, hipMemcpyAsync(e->pose_diff, e->px_pdiff.data(), e->px_pdiff.size() * 4, hipMemcpyHostToDevice, bg));
     const WindowTokens ws{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0};
     auto run_pass = [&]() {      // recorded, or launched on e->stream
-        if (px.has_ego) run_stack<T>(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0}, 1);
-        run_stack<T>(e, STACK_MAP, ws, 1);
-        run_stack<T>(e, STACK_BOX, ws, 1);
-        run_stack<T>(e, STACK_TAR, ws, 1);
+        if (px.has_ego) run_stack<T>(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0}, CACHE_FILL_PREFIX);
+        run_stack<T>(e, STACK_MAP, ws, CACHE_FILL_PREFIX);
+        run_stack<T>(e, STACK_BOX, ws, CACHE_FILL_PREFIX);
+        run_stack<T>(e, STACK_TAR, ws, CACHE_FILL_PREFIX);
     };
     if (dbg && dbg->foreground) {      // the reference of tests/test_gpu_bg_pass.py: the stand-alone kernels (bg == the engine's stream here); nothing stays pending
         run_pass();
@@ -436,40 +431,31 @@ int build_tables(umgen_engine* e) {
 
 namespace umgen {
 
-// by-precision dispatchers, in run_frame_any's three-way form: templates on T do not cross files
-void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode, int tail, float* warped_all) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? run_stack<bf16_t>(e, stack, w, cache_mode, tail, warped_all)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_stack<f16_t>(e, stack, w, cache_mode, tail, warped_all) : run_stack<float>(e, stack, w, cache_mode, tail, warped_all);
+// by-precision dispatchers: templates on T do not cross files
+void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail, float* warped_all) {
+    with_precision(e, [&](auto t) { run_stack<decltype(t)>(e, stack, w, cache_mode, tail, warped_all); });
 }
 void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? ego_decoder<bf16_t>(e, n, frame_of, Tq, d_item_T)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? ego_decoder<f16_t>(e, n, frame_of, Tq, d_item_T) : ego_decoder<float>(e, n, frame_of, Tq, d_item_T);
+    with_precision(e, [&](auto t) { ego_decoder<decltype(t)>(e, n, frame_of, Tq, d_item_T); });
 }
-void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
+void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
                  float* logp) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? run_ego<bf16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego<f16_t>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp)
-                                          : run_ego<float>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp);
+    with_precision(e, [&](auto t) { run_ego<decltype(t)>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp); });
 }
-void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, int cache_mode, float* logp) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? run_ego_fan<bf16_t>(e, w, N, sp, frame_idx, cache_mode, logp)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_ego_fan<f16_t>(e, w, N, sp, frame_idx, cache_mode, logp) : run_ego_fan<float>(e, w, N, sp, frame_idx, cache_mode, logp);
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp) {
+    with_precision(e, [&](auto t) { run_ego_fan<decltype(t)>(e, w, N, sp, frame_idx, cache_mode, logp); });
 }
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src) {
-    return e->cfg.precision == UMGEN_PREC_BF16 ? run_prefix_prefill<bf16_t>(e, B, P, src)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? run_prefix_prefill<f16_t>(e, B, P, src) : run_prefix_prefill<float>(e, B, P, src);
+    return with_precision(e, [&](auto t) { return run_prefix_prefill<decltype(t)>(e, B, P, src); });
 }
 int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg) {
-    return e->cfg.precision == UMGEN_PREC_BF16 ? launch_prefix<bf16_t>(e, io, ego, dbg)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? launch_prefix<f16_t>(e, io, ego, dbg) : launch_prefix<float>(e, io, ego, dbg);
+    return with_precision(e, [&](auto t) { return launch_prefix<decltype(t)>(e, io, ego, dbg); });
 }
 void gemv_any(umgen_engine* e, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out, long ldo) {
-    e->cfg.precision == UMGEN_PREC_BF16 ? gemv<bf16_t>(e, x, ldx, ln_w, W, bias, N, K, M, mode, out, ldo)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? gemv<f16_t>(e, x, ldx, ln_w, W, bias, N, K, M, mode, out, ldo) : gemv<float>(e, x, ldx, ln_w, W, bias, N, K, M, mode, out, ldo);
+    with_precision(e, [&](auto t) { gemv<decltype(t)>(e, x, ldx, ln_w, W, bias, N, K, M, mode, out, ldo); });
 }
 int build_tables_any(umgen_engine* e) {
-    return e->cfg.precision == UMGEN_PREC_BF16 ? build_tables<bf16_t>(e)
-    : e->cfg.precision == UMGEN_PREC_FP16 ? build_tables<f16_t>(e) : build_tables<float>(e);
+    return with_precision(e, [&](auto t) { return build_tables<decltype(t)>(e); });
 }
 
 }  // namespace umgen

@@ -80,23 +80,23 @@ struct umgen_engine {
     unsigned long long* d_seeds = nullptr;
     OarState* d_state = nullptr;
     float* d_logp = nullptr;             // [max_batch][2199] log-likelihoods of the frame being generated (umgen_rollout_logp / umgen_frame_logp; SampleArgs::logp)
-    // umgen_score (engine_frame.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
+    // umgen_score (engine_score.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
     int* score_arg = nullptr;
-    // umgen_score_candidates (engine_frame.hip run_score_candidates): the scene of every item (b, c) of the chunk in flight, [max_batch], and the number of
-    // scenes whose slot caches the chunk's last-slot pass reads (run_stack cache mode 5); umgen_rollout_fan's first frame (run_frame_fan) uses both the same way
-    // for its B * N branches (cache modes 5 / 6)
+    // umgen_score_candidates (engine_score.hip run_score_candidates): the scene of every item (b, c) of the chunk in flight, [max_batch], and the number of
+    // scenes whose slot caches the chunk's last-slot pass reads (CACHE_SHARED_ITEMS); umgen_rollout_fan's first frame (run_frame_fan) uses both the same way
+    // for its B * N branches (CACHE_SHARED_ITEMS / CACHE_SHARED_ITEMS_APPEND)
     int* d_item_scene = nullptr;
     int fan_scenes = 0;
-    // umgen_score_clip (engine_frame.hip run_score_clip): allocated by its first call (ensure_score_clip), for max_batch * max_cond_frames items (b, slot) of one
+    // umgen_score_clip (engine_score.hip run_score_clip): allocated by its first call (ensure_score_clip), for max_batch * max_cond_frames items (b, slot) of one
     // window pass.  clip_items [n][2] (scene, slot) and clip_item_T [n] (window length slot + 1); clip_warped [max_batch][max_cond_frames][1024][E], the map
     // stack's warped map of every slot; clip_cond [n][2207][E]; clip_tokens [n][2199], each item's scored frame; clip_xlast [n][E] (the prefix rows' unused
     // last position); clip_part / clip_logp / clip_arg: score_part / score_logp / score_arg for n items.  clip_state: 0 not tried, 1 allocated, -1 no room
     int *clip_items = nullptr, *clip_item_T = nullptr, *clip_tokens = nullptr, *clip_arg = nullptr;
     float *clip_warped = nullptr, *clip_cond = nullptr, *clip_xlast = nullptr, *clip_part = nullptr, *clip_logp = nullptr;
     int clip_state = 0;
-    // umgen_score_detail: allocated by its first call (engine_frame.hip ensure_score_detail).  det_part: the detail sweep's (row, split) records; det_row:
+    // umgen_score_detail: allocated by its first call (engine_score.hip ensure_score_detail).  det_part: the detail sweep's (row, split) records; det_row:
     // lse | target logit | row maximum | sum-exp of one modality's rows, [4][max_batch * 1024]; the results in score_logp's block layout, the lists with room for 16 per row (a call packs its topk)
     float *det_part = nullptr, *det_row = nullptr, *det_mass = nullptr, *det_ent = nullptr, *det_tlp = nullptr;
     int *det_rank = nullptr, *det_tok = nullptr;
@@ -251,6 +251,33 @@ bool ensure_tcache(umgen_engine* e);
 // (8 scenes: 3.53 vs 3.77 s).  UMGEN_ROWS_PER_BLOCK overrides (0 = every workgroup loops over all rows).
 inline int rows_per_block_for(const umgen_engine* e, int M) { return e->rows_per_block >= 0 ? e->rows_per_block : (M <= 6 ? 1 : 2); }
 
+// the four modalities of a frame in the order pose | map | bbox3d | image: content length, and offset in a frame's [2199] row
+constexpr int kModLen[4] = {kNPose, kNMap, kNBox, kNImg}, kModOff[4] = {0, kOffMap, kOffBox, kOffImg};
+
+// f(T{}) for the engine's precision T: templates on T do not cross files, so every file dispatches its own through this
+template <typename F>
+auto with_precision(const umgen_engine* e, F&& f) {
+    return e->cfg.precision == UMGEN_PREC_BF16 ? f(bf16_t{}) : e->cfg.precision == UMGEN_PREC_FP16 ? f(f16_t{}) : f(float{});
+}
+
+// What a pass through a stack (run_stack, w its WindowTokens) does with the per-layer slot caches of temporal k | v rows.  The values are fixed.
+enum CacheMode {
+    CACHE_NONE = 0,                // one pass over the whole window, no slot caches
+    CACHE_FILL_PREFIX = 1,         // prefix pass: slots [0, w.T), their k | v rows appended to the slot caches
+    CACHE_LAST_SLOT = 2,           // last-slot pass: slots [w.t0, w.t0 + w.T) against the caches
+    CACHE_WINDOW_KEEP = 3,         // whole window like CACHE_NONE, and its k | v rows are left in the slot caches for a longer window that follows
+    CACHE_LAST_SLOT_APPEND = 4,    // last-slot pass like CACHE_LAST_SLOT that appends its own k | v rows (the window keeps growing)
+    // last-slot pass of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of e->fan_scenes scenes: item i reads the slots [0, P) of scene
+    // e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window)
+    CACHE_SHARED_ITEMS = 5,
+    // ... and item i appends its own k | v rows to block i of the caches (umgen_rollout_fan ahead of a longer window: spread_tcaches then hands every
+    // item its scene's slots [0, P))
+    CACHE_SHARED_ITEMS_APPEND = 6,
+};
+constexpr bool cache_writes(CacheMode m) { return m == CACHE_FILL_PREFIX || m == CACHE_WINDOW_KEEP || m == CACHE_LAST_SLOT_APPEND; }   // launch_attn_temporal appends
+constexpr bool cache_whole_window(CacheMode m) { return m == CACHE_NONE || m == CACHE_WINDOW_KEEP; }
+constexpr int cache_fan_form(CacheMode m) { return m == CACHE_SHARED_ITEMS ? 1 : (m == CACHE_SHARED_ITEMS_APPEND ? 2 : 0); }           // tar_sub's `fan`
+
 struct FrameIO {
     int B, T;
     const int *pose, *map, *box, *img;          // host window tokens [B][T][S_mod] (box already control-overwritten)
@@ -268,20 +295,23 @@ struct FrameIO {
     const int* given_box = nullptr;              // host [B][660] or nullptr: ... and its boxes (only behind a given map)
 };
 
-// what umgen_score_detail computes beside the scores
+// Where a scoring call leaves its results: per modality [N][S_mod] for the call's N items in its own order (umgen_score_out's layout); any pointer may be null
+struct ScoreDst { float* logp[4]; int* argmax[4]; };
+// what umgen_score_detail computes beside the scores: ScoreDst's layout, the lists with topk entries per position (unused when topk == 0)
 struct ScoreDetailIO {
     int topk; float temperature;
-    int* rank; float *mass_above, *entropy;      // host [2199 B] each, logp's layout
-    int* topk_tok; float* topk_logp;             // host [2199 B][topk]: the same blocks, topk per position (unused when topk == 0)
+    int* rank[4]; float *mass_above[4], *entropy[4];
+    int* topk_tok[4]; float* topk_logp[4];
 };
 // umgen_score's arguments: B scenes' history windows and the frame to score, as host int32 arrays
 struct ScoreIO {
     int B, T;
     const int *pose, *map, *box, *img;          // [B][T][S_mod]
     const int* next;                             // [B][2199]: the scored frame, pose | map | bbox3d | image
-    float* logp;                                 // host [2199 B]: pose [B][3] | map [B][1024] | bbox3d [B][660] | image [B][512]
-    int* argmax;                                 // the same layout
-    const ScoreDetailIO* detail = nullptr;       // umgen_score_detail: what else to compute
+    ScoreDst out;
+    long row0 = 0;                               // scene b's results go to row row0 + b of `out` ...
+    const long* rows = nullptr;                  // ... or, when given, to row rows[b]
+    const ScoreDetailIO* detail = nullptr;       // umgen_score_detail: what else to compute (rows row0 + b)
 };
 
 // umgen_score_candidates' arguments: B scenes' history windows and C candidate next frames of every scene
@@ -289,8 +319,7 @@ struct ScoreCandIO {
     int B, T, C;
     const int *pose, *map, *box, *img;          // [B][T][S_mod]
     const int* next;                             // [B][C][2199]: the candidates, pose | map | bbox3d | image
-    float* logp;                                 // host [B][C][2199], each candidate pose | map | bbox3d | image
-    int* argmax;                                 // the same layout
+    ScoreDst out;                                // candidate (b, c) at row b*C + c
     int shared_slots;                            // out: T - 1 when the history slots ran once per scene, 0 on the replicated path
 };
 
@@ -298,8 +327,7 @@ struct ScoreCandIO {
 struct ScoreClipIO {
     int B, L, T_in, cond;
     const int *pose, *map, *box, *img;          // [B][L][S_mod]
-    float* logp;                                 // host [B][L - T_in][2199], each frame pose | map | bbox3d | image
-    int* argmax;                                 // the same layout
+    ScoreDst out;                                // frame f of clip b at row b*(L - T_in) + f - T_in
     int shared_frames;                           // out: frames per clip that were read off one window pass, 0 on the per-frame path
 };
 
@@ -317,11 +345,11 @@ enum { TAIL_AUTO = -1, TAIL_NONE = 0 };
 void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);
 
 // ---- engine_stacks.hip: by-precision entry points of the templated compute path ------------------------------------
-void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, int cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
+void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
 void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
-void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, int cache_mode,
+void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
                  float* logp = nullptr);
-void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, int cache_mode, float* logp);
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp);
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
@@ -357,6 +385,7 @@ int launch_bg_drain(umgen_engine* e, hipStream_t st);   // the launch without an
 int run_frame_any(umgen_engine* e, const FrameIO& io);
 // umgen_rollout_fan's first frame: io.B = B * N branches as scenes (branch (b, s) at b*N + s, scene b's window replicated), io.T >= 2, slot caches allocated
 int run_frame_fan_any(umgen_engine* e, const FrameIO& io, int N);
+// ---- engine_score.hip -----------------------------------------------------------------------------------------------
 int run_score_any(umgen_engine* e, const ScoreIO& sc);
 int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc);
 int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc);

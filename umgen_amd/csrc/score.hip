@@ -1,4 +1,4 @@
-// Scoring a GIVEN frame (umgen_score, engine_frame.hip run_score): log p(target) of many rows under one AR head without ever holding their logits.
+// Scoring a GIVEN frame (umgen_score, engine_score.hip run_score): log p(target) of many rows under one AR head without ever holding their logits.
 //   head_nll_kernel     one workgroup = 16 rows x one split of the vocabulary.  Prologue: LayerNorm of the 16 rows (weight only, eps 1e-5, fp32
 //                       two-pass statistics like gemv_ln_kernel), left in LDS -- in the 16-bit modes as the hi + lo 16-bit pairs the matrix cores
 //                       consume (activations stay fp32-accurate, like rows_mfma_kernel: two MFMAs per k-step on the weights as stored), in fp32

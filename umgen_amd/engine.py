@@ -262,30 +262,87 @@ class Engine:
             tbuf["logp"] = lpv
         return outs, tbuf
 
-    def _score_args(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray]):
-        """Shapes and token ranges of a score call, checked before anything reaches the device.  Returns (w [B, T, S], nx [B, S], batched)."""
-        w = {m: _i64(window[m]) for m in MOD_ORDER}
-        nx = {m: _i64(next_frame[m]) for m in MOD_ORDER}
-        batched = w["pose"].ndim == 3
-        for m in MOD_ORDER:
-            if w[m].ndim != (3 if batched else 2) or nx[m].ndim != (2 if batched else 1):
-                raise UMGenError(f"score: window[{m}] has shape {w[m].shape} and next_frame[{m}] {nx[m].shape}; expected [B, T, S] with [B, S], or [T, S] with [S]")
-            if not batched:
-                w[m], nx[m] = w[m][None], nx[m][None]
-        B, T = w["pose"].shape[:2]
+    # -- scoring -------------------------------------------------------------------------------
+    @staticmethod
+    def _window_lead(pose):
+        """(batched, (B, T)) of a window or clip argument, read off its pose array: [B, T, 3], or [T, 3] for one scene"""
+        shape = tuple(np.shape(pose))
+        batched = len(shape) == 3
+        return batched, (shape + (0, 0))[:2] if batched else (1,) + (shape + (0,))[:1]
+
+    def _token_arrays(self, call: str, name: str, arrs: Dict[str, np.ndarray], lead: Tuple[int, ...], batched: bool, int_dtype: bool):
+        """One argument of a scoring call, checked before anything reaches the device: arrs[mod] has shape lead + (S_mod,) (without lead's first axis
+        when the call is not batched), every token lies inside its vocabulary and, with int_dtype, the arrays are of an integer dtype -- tokens are
+        indices: a float array is a caller's mistake, not something to truncate.  Returns mod -> int64 [*lead, S_mod]."""
         vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
+        out = {}
         for m in MOD_ORDER:
-            if w[m].shape != (B, T, CONTENT_LEN[m]):
-                raise UMGenError(f"score: window[{m}] has shape {w[m].shape}, expected {(B, T, CONTENT_LEN[m])}")
-            if nx[m].shape != (B, CONTENT_LEN[m]):
-                raise UMGenError(f"score: next_frame[{m}] has shape {nx[m].shape}, expected {(B, CONTENT_LEN[m])}")
-            for what, a in (("window", w[m]), ("next_frame", nx[m])):
-                bad = np.flatnonzero((a.reshape(-1) < 0) | (a.reshape(-1) >= vocab[m]))
-                if bad.size:
-                    raise UMGenError(f"score: {what}[{m}] token {int(a.reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
+            if int_dtype and np.asarray(arrs[m]).dtype.kind not in "iu":
+                raise UMGenError(f"{call}: {name}[{m}] has dtype {np.asarray(arrs[m]).dtype}, expected an integer type")
+            a = _i64(arrs[m])
+            want = tuple(lead if batched else lead[1:]) + (CONTENT_LEN[m],)
+            if a.shape != want:
+                raise UMGenError(f"{call}: {name}[{m}] has shape {a.shape}, expected {want}")
+            bad = np.flatnonzero((a.reshape(-1) < 0) | (a.reshape(-1) >= vocab[m]))
+            if bad.size:
+                raise UMGenError(f"{call}: {name}[{m}] token {int(a.reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
+            out[m] = a if batched else a[None]
+        return out
+
+    @staticmethod
+    def _score_out(lead: Tuple[int, ...]):
+        """(logp: mod -> float32 [*lead, S_mod] of NaN, argmax: mod -> int32 of -1, the umgen_score_out that points at them)"""
+        logp = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
+        arg = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), -1, np.int32) for m in MOD_ORDER}
+        return logp, arg, _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
+                                        **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+
+    @classmethod
+    def _score_result(cls, logp, arg, batched: bool, total: bool = False, **extra) -> dict:
+        """What a scoring call returns: "logp", "argmax" (int64), with total the ranking key "total", and the call's own entries; without the B
+        axis for un-batched inputs."""
+        pick = (lambda a: a) if batched else (lambda a: a[0])
+        res = {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}}
+        if total:
+            res["total"] = pick(cls._candidate_total(logp))
+        res.update(extra)
+        return res
+
+    def _score_args(self, window: Dict[str, np.ndarray], next_frame: Dict[str, np.ndarray]):
+        """Shapes and token ranges of a score call.  Returns (w [B, T, S], nx [B, S], batched).  (Unlike the two calls below, score does not
+        refuse float token arrays.)"""
+        batched, (B, T) = self._window_lead(window["pose"])
+        w = self._token_arrays("score", "window", window, (B, T), batched, False)
+        nx = self._token_arrays("score", "next_frame", next_frame, (B,), batched, False)
         if T < 1:
             raise UMGenError("score: the window has no history frame")
         return w, nx, batched
+
+    def _candidate_args(self, window: Dict[str, np.ndarray], candidates: Dict[str, np.ndarray]):
+        """Shapes, dtypes and token ranges of a score_candidates call.  Returns (w [B, T, S], cd [B, C, S], batched)."""
+        batched, (B, T) = self._window_lead(window["pose"])
+        Cn = (tuple(np.shape(candidates["pose"])) + (0, 0))[1 if batched else 0]
+        w = self._token_arrays("score_candidates", "window", window, (B, T), batched, True)
+        cd = self._token_arrays("score_candidates", "candidates", candidates, (B, Cn), batched, True)
+        if T < 1:
+            raise UMGenError("score_candidates: the window has no history frame")
+        if Cn < 1:
+            raise UMGenError("score_candidates: no candidate frame")
+        return w, cd, batched
+
+    def _clip_args(self, clip: Dict[str, np.ndarray], input_frames, cond_frames):
+        """Shapes, dtypes, token ranges and frame counts of a score_clip call.  Returns (c [B, L, S], cond_frames, batched)."""
+        batched, (B, L) = self._window_lead(clip["pose"])
+        c = self._token_arrays("score_clip", "clip", clip, (B, L), batched, True)
+        if isinstance(input_frames, bool) or not isinstance(input_frames, (int, np.integer)) or not 1 <= input_frames < L:
+            raise UMGenError(f"score_clip: input_frames={input_frames!r} must be an integer in [1, {L}) for a clip of {L} frames")
+        if cond_frames is None:
+            cond_frames = min(self.max_cond_frames, L - 1)
+        if isinstance(cond_frames, bool) or not isinstance(cond_frames, (int, np.integer)) or not 1 <= cond_frames <= self.max_cond_frames:
+            raise UMGenError(f"score_clip: cond_frames={cond_frames!r} must be an integer in [1, {self.max_cond_frames}] (max_cond_frames)")
+        if B < 1 or B > self.max_batch:
+            raise UMGenError(f"score_clip: {B} clips, the engine holds max_batch={self.max_batch}")
+        return c, int(cond_frames), batched
 
     DETAIL_KEYS = ("rank", "mass_above", "entropy", "topk_tokens", "topk_logp")
 
@@ -323,10 +380,7 @@ class Engine:
         keys, topk, temperature = self._detail_args(detail, topk, temperature)
         w, nx, batched = self._score_args(window, next_frame)
         B, T = w["pose"].shape[:2]
-        logp = {m: np.full((B, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
-        arg = {m: np.full((B, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
-        out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
-                            **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+        logp, arg, out = self._score_out((B,))
         tokens = [_p64(w[m]) for m in MOD_ORDER] + [_p64(nx[m]) for m in MOD_ORDER]
         pick = (lambda a: a) if batched else (lambda a: a[0])
         res = {}
@@ -341,41 +395,8 @@ class Engine:
             self._check(self.lib.umgen_score_detail(self._h, B, T, *tokens, topk, temperature, C.byref(out), C.byref(det)), "score_detail")
             for k in keys:
                 res[k] = {m: pick(bufs[k][m].astype(np.int64) if field[k][1] is np.int32 else bufs[k][m]) for m in MOD_ORDER}
-        res["logp"] = {m: pick(logp[m]) for m in MOD_ORDER}
-        res["argmax"] = {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER}
+        res.update(self._score_result(logp, arg, batched))
         return res
-
-    def _candidate_args(self, window: Dict[str, np.ndarray], candidates: Dict[str, np.ndarray]):
-        """Shapes and token ranges of a score_candidates call, checked before anything reaches the device.  Returns (w [B, T, S], cd [B, C, S], batched)."""
-        for what, d in (("window", window), ("candidates", candidates)):
-            for m in MOD_ORDER:
-                if np.asarray(d[m]).dtype.kind not in "iu":      # tokens are indices: a float array is a caller's mistake, not something to truncate
-                    raise UMGenError(f"score_candidates: {what}[{m}] has dtype {np.asarray(d[m]).dtype}, expected an integer type")
-        w = {m: _i64(window[m]) for m in MOD_ORDER}
-        cd = {m: _i64(candidates[m]) for m in MOD_ORDER}
-        batched = w["pose"].ndim == 3
-        for m in MOD_ORDER:
-            if w[m].ndim != (3 if batched else 2) or cd[m].ndim != (3 if batched else 2):
-                raise UMGenError(f"score_candidates: window[{m}] has shape {w[m].shape} and candidates[{m}] {cd[m].shape}; expected [B, T, S] with [B, C, S], or [T, S] with [C, S]")
-            if not batched:
-                w[m], cd[m] = w[m][None], cd[m][None]
-        B, T = w["pose"].shape[:2]
-        Cn = cd["pose"].shape[1]
-        vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
-        for m in MOD_ORDER:
-            if w[m].shape != (B, T, CONTENT_LEN[m]):
-                raise UMGenError(f"score_candidates: window[{m}] has shape {w[m].shape}, expected {(B, T, CONTENT_LEN[m])}")
-            if cd[m].shape != (B, Cn, CONTENT_LEN[m]):
-                raise UMGenError(f"score_candidates: candidates[{m}] has shape {cd[m].shape}, expected {(B, Cn, CONTENT_LEN[m])}")
-            for what, a in (("window", w[m]), ("candidates", cd[m])):
-                bad = np.flatnonzero((a.reshape(-1) < 0) | (a.reshape(-1) >= vocab[m]))
-                if bad.size:
-                    raise UMGenError(f"score_candidates: {what}[{m}] token {int(a.reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
-        if T < 1:
-            raise UMGenError("score_candidates: the window has no history frame")
-        if Cn < 1:
-            raise UMGenError("score_candidates: no candidate frame")
-        return w, cd, batched
 
     @staticmethod
     def _candidate_total(logp: Dict[str, np.ndarray]) -> np.ndarray:
@@ -393,52 +414,17 @@ class Engine:
         w, cd, batched = self._candidate_args(window, candidates)
         B, T = w["pose"].shape[:2]
         Cn = cd["pose"].shape[1]
-        logp = {m: np.full((B, Cn, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
-        arg = {m: np.full((B, Cn, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
-        out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
-                            **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+        logp, arg, out = self._score_out((B, Cn))
         tokens = [_p64(w[m]) for m in MOD_ORDER] + [_p64(cd[m]) for m in MOD_ORDER]
         shared = C.c_int32(-1)
         self._check(self.lib.umgen_score_candidates(self._h, B, T, Cn, *tokens, C.byref(out), C.byref(shared)), "score_candidates")
-        pick = (lambda a: a) if batched else (lambda a: a[0])
-        return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER},
-                "total": pick(self._candidate_total(logp)), "shared_slots": int(shared.value)}
+        return self._score_result(logp, arg, batched, total=True, shared_slots=int(shared.value))
 
     @staticmethod
     def clip_windows(L: int, input_frames: int, cond_frames: int):
         """The window rule of score_clip (and of a rollout, UMGen.py:1597-1603), stated once: [(f, start, n), ...] for every scored frame f in
         [input_frames, L) -- frame f is scored against the n = min(f, cond_frames) frames clip[start : start + n], start = f - n."""
         return [(f, f - min(f, cond_frames), min(f, cond_frames)) for f in range(input_frames, L)]
-
-    def _clip_args(self, clip: Dict[str, np.ndarray], input_frames, cond_frames):
-        """Shapes, token ranges and frame counts of a score_clip call, checked before anything reaches the device.  Returns (c [B, L, S], cond_frames, batched)."""
-        for m in MOD_ORDER:
-            if np.asarray(clip[m]).dtype.kind not in "iu":      # tokens are indices: a float array is a caller's mistake, not something to truncate
-                raise UMGenError(f"score_clip: clip[{m}] has dtype {np.asarray(clip[m]).dtype}, expected an integer type")
-        c = {m: _i64(clip[m]) for m in MOD_ORDER}
-        batched = c["pose"].ndim == 3
-        for m in MOD_ORDER:
-            if c[m].ndim != (3 if batched else 2):
-                raise UMGenError(f"score_clip: clip[{m}] has shape {c[m].shape}; expected [B, L, S] for every modality, or [L, S]")
-            if not batched:
-                c[m] = c[m][None]
-        B, L = c["pose"].shape[:2]
-        vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
-        for m in MOD_ORDER:
-            if c[m].shape != (B, L, CONTENT_LEN[m]):
-                raise UMGenError(f"score_clip: clip[{m}] has shape {c[m].shape}, expected {(B, L, CONTENT_LEN[m])}")
-            bad = np.flatnonzero((c[m].reshape(-1) < 0) | (c[m].reshape(-1) >= vocab[m]))
-            if bad.size:
-                raise UMGenError(f"score_clip: clip[{m}] token {int(c[m].reshape(-1)[bad[0]])} at flat index {int(bad[0])} is outside [0, {vocab[m]})")
-        if isinstance(input_frames, bool) or not isinstance(input_frames, (int, np.integer)) or not 1 <= input_frames < L:
-            raise UMGenError(f"score_clip: input_frames={input_frames!r} must be an integer in [1, {L}) for a clip of {L} frames")
-        if cond_frames is None:
-            cond_frames = min(self.max_cond_frames, L - 1)
-        if isinstance(cond_frames, bool) or not isinstance(cond_frames, (int, np.integer)) or not 1 <= cond_frames <= self.max_cond_frames:
-            raise UMGenError(f"score_clip: cond_frames={cond_frames!r} must be an integer in [1, {self.max_cond_frames}] (max_cond_frames)")
-        if B < 1 or B > self.max_batch:
-            raise UMGenError(f"score_clip: {B} clips, the engine holds max_batch={self.max_batch}")
-        return c, int(cond_frames), batched
 
     def score_clip(self, clip: Dict[str, np.ndarray], input_frames: int, cond_frames=None) -> dict:
         """Per-token log-likelihoods of every frame of a recorded clip, each against the frames before it under the rollout's window rule
@@ -453,16 +439,11 @@ class Engine:
         c, cond_frames, batched = self._clip_args(clip, input_frames, cond_frames)
         B, L = c["pose"].shape[:2]
         F = L - int(input_frames)
-        logp = {m: np.full((B, F, CONTENT_LEN[m]), np.nan, np.float32) for m in MOD_ORDER}
-        arg = {m: np.full((B, F, CONTENT_LEN[m]), -1, np.int32) for m in MOD_ORDER}
-        out = _lib.ScoreOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER},
-                            **{f"argmax_{m}": arg[m].ctypes.data_as(C.POINTER(C.c_int32)) for m in MOD_ORDER})
+        logp, arg, out = self._score_out((B, F))
         shared = C.c_int32(-1)
         self._check(self.lib.umgen_score_clip(self._h, B, L, int(input_frames), cond_frames, *[_p64(c[m]) for m in MOD_ORDER], C.byref(out), C.byref(shared)),
                     "score_clip")
-        pick = (lambda a: a) if batched else (lambda a: a[0])
-        return {"logp": {m: pick(logp[m]) for m in MOD_ORDER}, "argmax": {m: pick(arg[m].astype(np.int64)) for m in MOD_ORDER},
-                "total": pick(self._candidate_total(logp)), "frames": np.arange(int(input_frames), L, dtype=np.int64), "shared_frames": int(shared.value)}
+        return self._score_result(logp, arg, batched, total=True, frames=np.arange(int(input_frames), L, dtype=np.int64), shared_frames=int(shared.value))
 
     def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True) -> np.ndarray:
         """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L).
