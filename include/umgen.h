@@ -273,6 +273,26 @@ int umgen_score_candidates(umgen_engine *e, int32_t B, int32_t T, int32_t C,
                            umgen_score_out *out,   /* every array [B][C][S_mod]; any pointer may be NULL */
                            int32_t *shared_slots); /* NULL, or receives T - 1 when the history slots were evaluated once per scene, 0 on the replicated path */
 
+/* Ranking futures of several frames: C candidate futures of K frames per scene against ONE history of T frames.  With seq(b, c) = history[b] ++
+ * future[b][c], f = T + k and n_k = min(T + k, cond_frames), entry (b, c, k) of every output is bit for bit what
+ *     umgen_score(e, 1, n_k, seq(b, c)[f - n_k : f], seq(b, c)[f])
+ * returns on the same engine -- umgen_rollout's window rule with the given frames in place of generated ones -- in every precision, whichever path ran and
+ * however the B * C items were chunked.  At frame k the window holds h_k = max(0, n_k - k) history frames; slots 0 .. h_k - 2 of the map / bbox3d / TAR
+ * stacks (slot h_k - 1 carries the pose of future frame 0 through the pose shift) and slots 0 .. h_k - 1 of the ego stack are the same for every candidate
+ * of a scene, and the causal temporal attention never lets them see one.  They are evaluated once per scene -- and only when the window's first frame
+ * moved: while the window grows the slot caches already hold them -- and the items, in chunks of at most max_batch, run their tail of k + 1 slots (ego: k)
+ * against the scene's caches, then the ego decoder, the BlockOAR pass and the heads.  A frame with no shared slot (h_k < 2), a tail longer than the tail
+ * kernel holds (16 slots; 8 when it needs four heads per workgroup), slot caches that do not fit in device memory, or UMGEN_SCORE_FUTURES_SHARE=0 in the
+ * environment (read per call) evaluate umgen_score's own pass on per-item windows -- the same bits; shared_slots[k] is then 0.
+ * B <= max_batch, T >= 1, 1 <= cond_frames <= max_cond_frames, C >= 1, K >= 1; B * C may exceed max_batch and T may exceed cond_frames.  Tokens are
+ * range-checked like umgen_score's; `out` must not be NULL, any pointer in it may be.  K == 1 with T <= cond_frames gives umgen_score_candidates' bytes.
+ * Like umgen_score, the call settles a pending background pass and leaves nothing an overlapped rollout could reuse in the slot caches. */
+int umgen_score_futures(umgen_engine *e, int32_t B, int32_t T, int32_t C, int32_t K, int32_t cond_frames,
+                        const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,                 /* [B][T][S_mod]    */
+                        const int64_t *fut_pose, const int64_t *fut_map, const int64_t *fut_bbox3d, const int64_t *fut_image, /* [B][C][K][S_mod] */
+                        umgen_score_out *out,    /* every array [B][C][K][S_mod]; any pointer may be NULL, out itself not */
+                        int32_t *shared_slots);  /* NULL, or [K]: per future frame the history slots evaluated once per scene, 0 = replicated path */
+
 /* Scoring a recorded clip: the teacher-forced counterpart of umgen_rollout.  For B clips of L frames, every frame f with T_in <= f < L is scored against
  * the n_f = min(f, cond_frames) frames before it -- umgen_rollout's window rule (UMGen.py:1597-1603) with the recorded frames in place of generated ones.
  * Entry (b, f - T_in) of every output is bit for bit what

@@ -10,7 +10,11 @@ Engine.score with the window replicated C times (the same numbers, bit for bit),
 is stored under "candidates" in out.json, whose other entries are kept.
 --clip measures only umgen_score_clip: one scene, a clip of L = 21 frames, input_frames 1, cond_frames 20, an engine of one scene; Engine.score_clip
 against the loop of 20 Engine.score calls on the growing windows (the same numbers, bit for bit) and against itself with UMGEN_SCORE_CLIP_SHARE=0, 5
-alternating rounds behind one warm-up call of each kind, and one profiled call's stage split; stored under "clip" in out.json."""
+alternating rounds behind one warm-up call of each kind, and one profiled call's stage split; stored under "clip" in out.json.
+--futures C K measures only umgen_score_futures: one scene, 20 history frames, cond_frames 20, C candidate futures of K frames, an engine of 8 scenes;
+Engine.score_futures against the loop of C * K Engine.score calls on the same engine (the same numbers, bit for bit) and against itself with
+UMGEN_SCORE_FUTURES_SHARE=0, 5 alternating rounds behind one warm-up call of each kind, the bytes compared, the shared_slots and one profiled call's
+ego / stacks / BlockOAR+heads split; stored under "futures" in out.json."""
 import json
 import os
 import statistics
@@ -35,6 +39,11 @@ if "--candidates" in sys.argv[1:]:
     CAND = int(sys.argv[k + 1])
     args.remove(sys.argv[k + 1])
 CLIP = "--clip" in sys.argv[1:]
+FUT = None
+if "--futures" in sys.argv[1:]:
+    k = sys.argv.index("--futures")
+    FUT = (int(sys.argv[k + 1]), int(sys.argv[k + 2]))
+    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and i not in (k + 1, k + 2)]
 REPS = 5
 
 
@@ -152,6 +161,72 @@ def clip_bench(out, L=21, cond=20):
     with open(out, "w") as f:
         f.write(json.dumps(res) + "\n")
 
+
+def futures_bench(out, Cn, K, T=20, cond=20):
+    """one scene's history against Cn futures of K frames (the frames behind the other synthetic scenes' histories): the futures call, the loop of
+    Engine.score calls a user writes without it, and the futures call with nothing shared"""
+    cfg = large_config()
+    e = Engine(cfg, precision="bf16", max_batch=8, max_cond_frames=cond)
+    e.load_state_dict(synthetic_items(cfg, seed=0))
+    e.finalize()
+    sc = [synthetic_scene(i, n_frames=T + K) for i in range(8)]
+    w = {m: sc[0][m][0, :T] for m in MOD_ORDER}
+    fut = {m: np.stack([sc[i % 8][m][0, T:] for i in range(Cn)]) for m in MOD_ORDER}
+    windows = Engine.future_windows(T, K, cond)
+    got = {}
+
+    def loop():
+        res = []
+        for c in range(Cn):
+            seq = {m: np.concatenate([w[m], fut[m][c]]) for m in MOD_ORDER}
+            res.append([e.score({m: seq[m][s:s + n] for m in MOD_ORDER}, {m: seq[m][T + k] for m in MOD_ORDER}) for k, s, n, _ in windows])
+        got["l"] = res
+
+    def unshared():
+        os.environ["UMGEN_SCORE_FUTURES_SHARE"] = "0"
+        try:
+            got["u"] = e.score_futures(w, fut, cond)
+        finally:
+            del os.environ["UMGEN_SCORE_FUTURES_SHARE"]
+    kinds = ((lambda: got.__setitem__("f", e.score_futures(w, fut, cond)), []), (loop, []), (unshared, []))
+    for fn, _ in kinds:
+        fn()
+    for _ in range(REPS):
+        for fn, ts in kinds:
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+    tf, tl, tu = (ts for _, ts in kinds)
+    same = all(got["f"][kind][m][c, k].tobytes() == got["l"][c][k][kind][m].tobytes() == got["u"][kind][m][c, k].tobytes()
+               for kind in ("logp", "argmax") for m in MOD_ORDER for c in range(Cn) for k in range(K))
+    med = statistics.median
+    r = {"candidates": Cn, "future_frames": K, "history_frames": T, "cond_frames": cond, "reps": REPS,
+         "score_futures_ms": med(tf), "score_futures_all_ms": tf, "score_futures_spread_ms": max(tf) - min(tf),
+         "score_loop_ms": med(tl), "score_loop_all_ms": tl, "score_loop_spread_ms": max(tl) - min(tl), "loop_over_futures": med(tl) / med(tf),
+         "unshared_futures_ms": med(tu), "unshared_futures_all_ms": tu, "unshared_futures_spread_ms": max(tu) - min(tu), "unshared_over_futures": med(tu) / med(tf),
+         "shared_slots": got["f"]["shared_slots"].tolist(), "unshared_shared_slots": got["u"]["shared_slots"].tolist(),
+         "bytes_compared": int(sum(got["f"][kind][m].nbytes for kind in ("logp", "argmax") for m in MOD_ORDER)), "same_bytes": same,
+         "best": int(np.argmax(got["f"]["cum_total"])), "cum_total": got["f"]["cum_total"].tolist()}
+    e.set_profiling(True)      # one profiled call: the stage split (the stream is drained at every stage boundary, per-launch events serialise the stacks)
+    t0 = time.perf_counter()
+    e.score_futures(w, fut, cond)
+    r["profiled_call_ms"] = (time.perf_counter() - t0) * 1e3
+    r["profiled_timings"] = {k: v for k, v in e.timings().items() if k in ("total_ms", "ego_ms", "tar_ms", "oar_ms", "gemm_ms", "gemm_launches", "attn_ms", "attn_launches")}
+    e.set_profiling(False)
+    e.close()
+    res = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            res = json.loads(f.read())
+    res["futures"] = r
+    print(json.dumps(r))
+    with open(out, "w") as f:
+        f.write(json.dumps(res) + "\n")
+
+
+if FUT:
+    futures_bench(args[0] if args else os.path.join(ROOT, "profiles", "score_bench.json"), *FUT)
+    sys.exit(0)
 
 if CLIP:
     clip_bench(args[0] if args else os.path.join(ROOT, "profiles", "score_bench.json"))

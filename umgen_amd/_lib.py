@@ -16,19 +16,19 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.so")
 SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "engine_score.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
            "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip", "debug_vq.hip"]
-EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp", "umgen_rollout_fan",
+EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_futures", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp", "umgen_rollout_fan",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
            "umgen_vqenc_create", "umgen_vqenc_load_tensor", "umgen_vqenc_finalize", "umgen_vqenc_encode", "umgen_vqenc_last_error", "umgen_vqenc_destroy",
-           "umgen_dbg_linear", "umgen_dbg_linear_vt", "umgen_dbg_gemm", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_temporal_range", "umgen_dbg_attn_temporal_fan", "umgen_dbg_attn_temporal_fan_write", "umgen_dbg_tcache_spread", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_gemm_vt_bench", "umgen_dbg_gemm_stamps", "umgen_dbg_oar_step", "umgen_dbg_oar_cache", "umgen_dbg_oar_epoch", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
+           "umgen_dbg_linear", "umgen_dbg_linear_vt", "umgen_dbg_gemm", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_temporal_range", "umgen_dbg_attn_temporal_fan", "umgen_dbg_attn_temporal_fan_write", "umgen_dbg_attn_temporal_fan_tail", "umgen_dbg_tcache_spread", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_gemm_vt_bench", "umgen_dbg_gemm_stamps", "umgen_dbg_oar_step", "umgen_dbg_oar_cache", "umgen_dbg_oar_epoch", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
            "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
            "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer", "umgen_dbg_guard_selftest",
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
            "umgen_dbg_embed_warp_slots", "umgen_dbg_cond_rows_slots", "umgen_dbg_ego_queries_slots",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego", "umgen_dbg_token_steps_logp", "umgen_dbg_sample_ego_logp",
            "umgen_dbg_head_nll", "umgen_dbg_head_nll_split", "umgen_dbg_head_detail", "umgen_dbg_logits_detail",
-           "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache",
+           "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache", "umgen_dbg_score_futures_passes",
            "umgen_dbg_vq_quantize", "umgen_dbg_vq_quant_tile", "umgen_dbg_vq_im2col", "umgen_dbg_vq_im2col_s2", "umgen_dbg_vq_upsample", "umgen_dbg_vq_from_nchw", "umgen_dbg_vq_to_nchw",
            "umgen_dbg_vq_group_norm", "umgen_dbg_vq_softmax"]
 
@@ -279,6 +279,7 @@ def load_library() -> C.CDLL:
     lib.umgen_score.argtypes = [vp, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut)]
     lib.umgen_score_detail.argtypes = lib.umgen_score.argtypes[:-1] + [i32, C.c_float, C.POINTER(ScoreOut), C.POINTER(ScoreDetailOut)]
     lib.umgen_score_candidates.argtypes = [vp, i32, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
+    lib.umgen_score_futures.argtypes = [vp, i32, i32, i32, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
     lib.umgen_score_clip.argtypes = [vp, i32, i32, i32, i32, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
     lib.umgen_set_profiling.argtypes = [vp, i32]
     lib.umgen_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -301,6 +302,7 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_attn_temporal_range.argtypes = [i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.umgen_dbg_attn_temporal_fan.argtypes = [i32, vp, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, vp]
     lib.umgen_dbg_attn_temporal_fan_write.argtypes = [i32, vp, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.umgen_dbg_attn_temporal_fan_tail.argtypes = [i32, vp, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, vp, vp]
     lib.umgen_dbg_tcache_spread.argtypes = [vp, i32, i32, i32, i32, i32, C.c_long]
     lib.umgen_dbg_attn_decode.argtypes = [i32, fp, vp, i32, i32, i32, fp]
     lib.umgen_dbg_gemv.argtypes = [i32, fp, fp, vp, fp, i32, i32, i32, i32, fp]
@@ -348,6 +350,7 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_bg_drain.argtypes = [vp]
     lib.umgen_dbg_bg_end.argtypes = [vp]
     lib.umgen_dbg_tcache.argtypes = [vp, i32, i32, vp, i32]
+    lib.umgen_dbg_score_futures_passes.argtypes = [vp]
     lib.umgen_dbg_vq_quantize.argtypes = [fp, i32, fp, i32, i32, C.c_long, i64p, fp]
     lib.umgen_dbg_vq_quant_tile.argtypes = [i32]
     lib.umgen_dbg_vq_im2col.argtypes = [fp, i32, i32, i32, i32, i32, fp, C.c_long]

@@ -683,6 +683,38 @@ template void launch_attn_temporal_fan_write<float>(hipStream_t, const float*, f
 template void launch_attn_temporal_fan_write<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, const int*, int, int, int, int, bf16_t*, int);
 template void launch_attn_temporal_fan_write<f16_t>(hipStream_t, const f16_t*, f16_t*, int, const int*, int, int, int, int, f16_t*, int);
 
+// Tails of Wt slots over the shared slots [0, P) (attn_body.h attn_temporal_fan_tail_kernel).  Heads per workgroup: the most of 4 / 2 / 1 that divide H, hold a
+// whole tail in one round (Wt <= kFanItems) and keep the staged rows inside the LDS the temporal kernel requests (73728 B); 0: no form holds this tail
+int attn_temporal_fan_tail_heads(int H, int P, int Wt) {
+    if (H < 1 || P < 1 || Wt < 1) return 0;
+    for (int HG : {4, 2, 1})
+        if (H % HG == 0 && Wt <= kFanItems(HG) && (size_t)(2 * P + 3 * kFanItems(HG)) * HG * kHeadDim * sizeof(float) <= (size_t)kTmax * 3 * 4 * kHeadDim * sizeof(float))
+            return HG;
+    return 0;
+}
+template <typename T>
+int launch_attn_temporal_fan_tail(hipStream_t s, const T* qkv, T* y, int N, int Wt, const int* scene_of_item, int B, int S, int H, int P, int q0, const T* cache,
+                                  int Tcap) {
+    if (BgRecorder* rec = g_bg_rec) { rec->failed = "temporal attention over shared caches"; return -1; }
+    const int HG = attn_temporal_fan_tail_heads(H, P, Wt);
+    if (!HG || q0 >= P + Wt) return -1;      // (refused before any launch: the caller takes the replicated path)
+    if (N < 1 || B < 1) return 0;
+    const size_t shm = (size_t)(2 * P + 3 * kFanItems(HG)) * HG * kHeadDim * sizeof(float);
+    const dim3 grid((unsigned)((long)B * S * (H / HG))), block(kFanItems(HG) * HG * 4);
+    auto launch = [&](auto kernel) {
+        if (shm > ((size_t)48 << 10) && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
+            return;      // (the refusal stays behind as the thread's last error: the engine fails the call, the test hook returns it)
+        hipLaunchKernelGGL(kernel, grid, block, shm, s, qkv, y, scene_of_item, N, Wt, S, H, P, q0, cache, Tcap);
+    };
+    if (HG == 4) launch(attn_temporal_fan_tail_kernel<T, 4>);
+    else if (HG == 2) launch(attn_temporal_fan_tail_kernel<T, 2>);
+    else launch(attn_temporal_fan_tail_kernel<T, 1>);
+    return 0;
+}
+template int launch_attn_temporal_fan_tail<float>(hipStream_t, const float*, float*, int, int, const int*, int, int, int, int, int, const float*, int);
+template int launch_attn_temporal_fan_tail<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, int, int, const int*, int, int, int, int, int, const bf16_t*, int);
+template int launch_attn_temporal_fan_tail<f16_t>(hipStream_t, const f16_t*, f16_t*, int, int, const int*, int, int, int, int, int, const f16_t*, int);
+
 // One scene of the spread behind a fan frame (umgen_rollout_fan): slots [0, P) of block `b` of a slot cache [blocks][Tcap][S][2E] -- `n16` 16-byte
 // vectors from the block's start, a block being `blk16` vectors -- to the blocks b*N + s, s = 0 .. N-1; a block's slots >= P are not touched.
 // The source block b is itself the destination of item b of scene b / N, so a cache is spread scene by scene in DESCENDING b, one launch each in

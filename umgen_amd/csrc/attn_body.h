@@ -463,4 +463,105 @@ __global__ __launch_bounds__(kFanItems(HG) * HG * 4) void attn_temporal_fan_kern
     }
 }
 
+// Temporal attention of item TAILS over one scene's slot cache (umgen_score_futures: future frame k of every candidate brings k + 1 slots of its own behind
+// the history slots its scene's candidates share).  qkv [N][Wt][S][3E] holds the slots [P, P + Wt) of N items, scene_of_item and cache as above.  A workgroup
+// owns one (scene, position, group of HG heads), stages the P cached k | v rows into LDS once and serves the scene's items in rounds of WHOLE items,
+// kFanItems(HG) / Wt of them per round: the round's q | k | v rows sit behind the cached rows as [item][tail slot][3][W], lane = (item, tail slot j, head,
+// 12-wide head-dim part).  Query (i, j) runs over the cached keys 0 .. P - 1 and then item i's own rows 0 .. j -- the keys 0 .. P + j of its window -- with
+// attn_temporal_body's operations in its order, so y [N][Wt][S][E] has the bits of that kernel's launch with t0 = P, Tn = Wt, write = 0 on per-item copies of
+// the cache, and those of attn_temporal_fan_kernel for Wt == 1.  Tail slots below q0 (TemporalRange::q0) have no query: their q rows are not read, their y
+// rows not written.  The trip count is per lane; the four lanes of a quad belong to one query, so the DPP adds always see their partners.
+// Wt <= kFanItems(HG); LDS (2 P + 3 kFanItems) * HG * 48 floats as above; the cache is read only, and only its slots < P.
+template <typename T, int HG>
+__global__ __launch_bounds__(kFanItems(HG) * HG * 4) void attn_temporal_fan_tail_kernel(const T* __restrict__ qkv, T* __restrict__ y,
+                                                                                        const int* __restrict__ scene_of_item, int N, int Wt, int S, int H, int P,
+                                                                                        int q0, const T* __restrict__ cache, int Tcap) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char dyn_lds[];
+    constexpr int W = HG * kHeadDim, G = kFanItems(HG), NT = G * HG * 4, chunks_per_seg = W / 8;
+    float* const ck = reinterpret_cast<float*>(dyn_lds);   // [P][2][W]: k | v of the cached slots
+    float* const own = ck + P * 2 * W;                     // [G][3][W]: q | k | v of the round's items, row = item * Wt + tail slot
+    const int tid = (int)threadIdx.x;
+    const long blk = (long)blockIdx.x;
+    const int hg = (int)(blk % (H / HG));
+    const long bs = blk / (H / HG);          // b*S + s
+    const int s = (int)(bs % S);
+    const int b = (int)(bs / S);
+    const int E = H * kHeadDim;
+    int first = 0, cnt = 0;                  // the scene's items [first, first + cnt)
+    for (int i = 0; i < N; ++i)
+        if (scene_of_item[i] == b) {
+            if (!cnt) first = i;
+            ++cnt;
+        }
+    if (!cnt) return;
+    for (int c = tid; c < P * 2 * chunks_per_seg; c += NT) {
+        const int cc = c % chunks_per_seg, seg = (c / chunks_per_seg) & 1, t = c / (2 * chunks_per_seg);
+        float v8[8];
+        load8(cache + (((long)b * Tcap + t) * S + s) * 2L * E + (long)seg * E + hg * W + cc * 8, v8);
+        float* d = ck + ((t * 2 + seg) * W + cc * 8);
+        *reinterpret_cast<float4*>(d) = make_float4(v8[0], v8[1], v8[2], v8[3]);
+        *reinterpret_cast<float4*>(d + 4) = make_float4(v8[4], v8[5], v8[6], v8[7]);
+    }
+    // 4 lanes per (row of the round, head): lane part p owns head-dim slice [12p, 12p+12); row rl is tail slot j of the round's item il
+    const int per = G / Wt;                  // whole items per round (Wt <= G: the launcher)
+    const int part = tid & 3, rl = (tid >> 2) % G, hl = tid / (4 * G);
+    const int il = rl / Wt, j = rl - il * Wt;
+    for (int i0 = 0; i0 < cnt; i0 += per) {
+        const int ni = min(per, cnt - i0);
+        if (i0) __syncthreads();             // the previous round's rows are read until here
+        for (int c = tid; c < ni * Wt * 3 * chunks_per_seg; c += NT) {
+            const int cc = c % chunks_per_seg, seg = (c / chunks_per_seg) % 3, r = c / (3 * chunks_per_seg);
+            if (seg == 0 && P + r % Wt < q0) continue;      // no query below q0 (the q rows may not exist)
+            float v8[8];
+            load8(qkv + (((long)(first + i0) * Wt + r) * S + s) * 3L * E + (long)seg * E + hg * W + cc * 8, v8);
+            float* d = own + ((r * 3 + seg) * W + cc * 8);
+            *reinterpret_cast<float4*>(d) = make_float4(v8[0], v8[1], v8[2], v8[3]);
+            *reinterpret_cast<float4*>(d + 4) = make_float4(v8[4], v8[5], v8[6], v8[7]);
+        }
+        __syncthreads();
+        if (il >= ni || P + j < q0) continue;                // (whole quads: the DPP adds below stay inside a query's 4 lanes)
+        float q[12], o[12];
+        const float* qp = own + (rl * 3 + 0) * W + hl * kHeadDim + part * 12;
+#pragma unroll
+        for (int d = 0; d < 12; d += 4) {
+            const float4 q4 = *reinterpret_cast<const float4*>(qp + d);
+            q[d] = q4.x; q[d + 1] = q4.y; q[d + 2] = q4.z; q[d + 3] = q4.w;
+            o[d] = 0.f; o[d + 1] = 0.f; o[d + 2] = 0.f; o[d + 3] = 0.f;
+        }
+        float m = -INFINITY, l = 0.f;
+        const float* const tail = own + (il * Wt * 3 + 1) * W;      // k row of the item's tail slot 0
+        for (int tk = 0; tk <= P + j; ++tk) {
+            const float* kp = (tk < P ? ck + (tk * 2) * W : tail + (tk - P) * 3 * W) + hl * kHeadDim + part * 12;
+            const float* vp = kp + W;
+            float a = 0.f;
+#pragma unroll
+            for (int d = 0; d < 12; d += 4) {
+                const float4 k4 = *reinterpret_cast<const float4*>(kp + d);
+                a = fmaf(q[d], k4.x, a); a = fmaf(q[d + 1], k4.y, a); a = fmaf(q[d + 2], k4.z, a); a = fmaf(q[d + 3], k4.w, a);
+            }
+            a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0xB1, 0xf, 0xf, true));
+            a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x4E, 0xf, 0xf, true));
+            a *= kScale;
+            const float mn = fmaxf(m, a);
+            const float alpha = sizeof(T) == 2 ? __expf(m - mn) : expf(m - mn);
+            const float p = sizeof(T) == 2 ? __expf(a - mn) : expf(a - mn);
+            m = mn;
+            l = l * alpha + p;
+#pragma unroll
+            for (int d = 0; d < 12; d += 4) {
+                const float4 v4 = *reinterpret_cast<const float4*>(vp + d);
+                o[d] = fmaf(p, v4.x, o[d] * alpha); o[d + 1] = fmaf(p, v4.y, o[d + 1] * alpha);
+                o[d + 2] = fmaf(p, v4.z, o[d + 2] * alpha); o[d + 3] = fmaf(p, v4.w, o[d + 3] * alpha);
+            }
+        }
+        const float inv = 1.0f / l;
+        T* yp = y + (((long)(first + i0) * Wt + rl) * S + s) * (long)E + (hg * HG + hl) * kHeadDim + part * 12;
+#pragma unroll
+        for (int d = 0; d < 12; d += 4) {
+            float t4[4] = {o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv};
+            store4(yp + d, t4);
+        }
+    }
+}
+
 }  // namespace umgen

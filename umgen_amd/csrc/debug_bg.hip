@@ -151,4 +151,7 @@ int umgen_dbg_tcache(umgen_engine* e, int32_t stack, int32_t block, void* host, 
     return UMGEN_OK;
 }
 
+// Test hook: how many per-scene history passes the engine's last umgen_score_futures call launched (0: every frame took the replicated path)
+int umgen_dbg_score_futures_passes(umgen_engine* e) { return e ? e->fut_history_passes : UMGEN_E_INVALID; }
+
 }  // extern "C"

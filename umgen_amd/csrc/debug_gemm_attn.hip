@@ -274,6 +274,39 @@ int umgen_dbg_attn_temporal_fan_write(int prec, const void* qkv, int N, const in
     return down(y, dY, Rn * E * es);
 }
 
+// ONE launch_attn_temporal_fan_tail call (kernels.h): qkv [N][Wt][S][3E] holds the slots [P, P + Wt) of N items, item i reads the k | v rows of slots [0, P)
+// from block scene_of_item[i] of cache [B][Tcap][S][2E]; only tail slots >= q0 have a query.  cache and y [N][Wt][S][E] are in / out, as for
+// umgen_dbg_attn_temporal_fan.  A tail no form of the kernel holds is refused with UMGEN_E_UNSUPPORTED before any buffer is made or anything is launched.
+int umgen_dbg_attn_temporal_fan_tail(int prec, const void* qkv, int N, int Wt, const int32_t* scene_of_item, int B, int S, int H, int P, int q0, int Tcap,
+                                     void* cache, void* y) {
+    if (prec < 0 || prec > 2 || !qkv || !y || !cache || !scene_of_item || N < 1 || Wt < 1 || B < 1 || S < 1 || H < 1 || P < 1 || q0 < 0 || q0 >= P + Wt || Tcap < P)
+        return UMGEN_E_INVALID;
+    if (!attn_temporal_fan_tail_heads(H, P, Wt)) return UMGEN_E_UNSUPPORTED;
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < N; ++i) {
+        const int sc = scene_of_item[i];
+        if (sc < 0 || sc >= B || (seen[sc] && scene_of_item[i - 1] != sc)) return UMGEN_E_INVALID;
+        seen[sc] = 1;
+    }
+    const int E = H * kHeadDim;
+    const size_t es = prec ? 2 : 4, Rn = (size_t)N * Wt * S, csz = (size_t)B * Tcap * S * 2 * E * es;
+    Scratch s;
+    const void* dQ = s.in(qkv, Rn * 3 * E * es);
+    const int* dS = s.in(scene_of_item, (size_t)N * 4);
+    void* dY = s.inout(y, Rn * E * es);
+    void* dC = s.inout(cache, csz);
+    if (s.rc) return s.rc;
+    int refused = 0;
+    by_prec(prec, [&](auto t) {
+        typedef decltype(t) TT;
+        refused = launch_attn_temporal_fan_tail<TT>(nullptr, (const TT*)dQ, (TT*)dY, N, Wt, dS, B, S, H, P, q0, (const TT*)dC, Tcap);
+    });
+    if (refused) return UMGEN_E_UNSUPPORTED;
+    if (int rc = s.finish()) return rc;
+    if (down(cache, dC, csz)) return UMGEN_E_HIP;
+    return down(y, dY, Rn * E * es);
+}
+
 // ONE launch_tcache_spread call (kernels.h) on cache [blocks][Tcap][row_bytes] (in / out), blocks >= B * N: slots [0, P) of block b < B to the blocks b*N + s
 int umgen_dbg_tcache_spread(void* cache, int blocks, int B, int N, int P, int Tcap, long row_bytes) {
     if (!cache || B < 1 || N < 1 || P < 1 || P > Tcap || row_bytes < 16 || row_bytes % 16 || (long)B * N > blocks) return UMGEN_E_INVALID;

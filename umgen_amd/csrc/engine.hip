@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan (UMGen.inference).  Creation, weights, the compute path, the frame itself and the scoring passes are in
+// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan (UMGen.inference).  Creation, weights, the compute path, the frame itself and the scoring passes are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip, engine_frame.hip and engine_score.hip.
 #include "engine_state.h"
 
@@ -132,9 +132,9 @@ int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* 
                             out_bbox3d, out_image, nullptr);
 }
 
-// ---- umgen_score(_detail), umgen_score_candidates, umgen_score_clip: the passes of engine_score.hip behind the argument checks ----
+// ---- umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip: the passes of engine_score.hip behind the argument checks ----
 
-// What the three calls check alike, in their common order: the engine and B first; then, behind what only the call itself takes, the output struct,
+// What these calls check alike, in their common order: the engine and B first; then, behind what only the call itself takes, the output struct,
 // the token buffers -- a history of `frames` frames and, with next, n_next frames to score that an error names next_what -- the head, and every token
 static int check_score_engine(umgen_engine* e, int32_t B) {
     if (!e) return UMGEN_E_INVALID;
@@ -237,6 +237,27 @@ int umgen_score_candidates(umgen_engine* e, int32_t B, int32_t T, int32_t C, con
     if (int rc = run_score_candidates_any(e, sc)) return rc;
     if (shared_slots) *shared_slots = sc.shared_slots;
     return UMGEN_OK;
+}
+
+// umgen_score_futures: C candidate futures of K frames per scene against one history, frame by frame under the rollout's window rule (engine_score.hip
+// run_score_futures)
+int umgen_score_futures(umgen_engine* e, int32_t B, int32_t T, int32_t C, int32_t K, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                        const int64_t* bbox3d, const int64_t* image, const int64_t* fut_pose, const int64_t* fut_map, const int64_t* fut_bbox3d,
+                        const int64_t* fut_image, umgen_score_out* out, int32_t* shared_slots) {
+    const int64_t *in[4] = {pose, map, bbox3d, image}, *nx[4] = {fut_pose, fut_map, fut_bbox3d, fut_image};
+    if (int rc = check_score_engine(e, B)) return rc;
+    if (T < 1) return e->fail(UMGEN_E_INVALID, "T=%d: at least one history frame", T);
+    if (cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
+        return e->fail(UMGEN_E_INVALID, "cond_frames=%d out of range [1,%d]", cond_frames, e->cfg.max_cond_frames);
+    if (C < 1) return e->fail(UMGEN_E_INVALID, "C=%d: at least one candidate per scene", C);
+    if (K < 1) return e->fail(UMGEN_E_INVALID, "K=%d: at least one future frame per candidate", K);
+    if (int rc = check_score_common(e, out, in, (size_t)B * T, nx, (size_t)B * C * K, "future frames")) return rc;
+    std::vector<int> win[4], fut[4];
+    narrow_tokens(in, (size_t)B * T, win);
+    narrow_tokens(nx, (size_t)B * C * K, fut);
+    const ScoreFutIO sc{B, T, C, K, cond_frames, win[0].data(), win[1].data(), win[2].data(), win[3].data(),
+                        {fut[0].data(), fut[1].data(), fut[2].data(), fut[3].data()}, score_dst(out), shared_slots};
+    return run_score_futures_any(e, sc);
 }
 
 // umgen_score_clip: every frame of B recorded clips against the frames before it, the growing windows off one pass (engine_score.hip run_score_clip)

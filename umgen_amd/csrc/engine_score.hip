@@ -1,6 +1,7 @@
 // Scoring given frames, from run_frame's own stages (engine_frame.h): run_score<T>, the pass of umgen_score and umgen_score_detail, run_score_candidates<T>,
-// which scores several next frames per scene on one pass over the history, run_score_clip<T>, which scores every frame of a recorded clip, the growing
-// windows off one pass, and run_score_any / run_score_candidates_any / run_score_clip_any, which pick the precision and clean up behind a failed call.
+// which scores several next frames per scene on one pass over the history, run_score_futures<T>, which does so for futures of several frames (item tails
+// behind the shared slots), run_score_clip<T>, which scores every frame of a recorded clip, the growing windows off one pass, and run_score_any /
+// run_score_candidates_any / run_score_futures_any / run_score_clip_any, which pick the precision and clean up behind a failed call.
 #include "engine_frame.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -241,6 +242,177 @@ int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
     return finish_call(e, "scoring pass");
 }
 
+// Where future frame k of umgen_score_futures sits: its window is frames [start, start + n) of history ++ future (umgen_rollout's window rule), the first h of
+// them history frames; slots [0, P) of the map / box / TAR stacks are the scene's (the shift hands slot h - 1 the pose of future frame 0)
+struct FutureFrame { int start, n, h, P; };
+FutureFrame future_frame(const ScoreFutIO& sc, int k) {
+    const int f = sc.T + k, n = std::min(f, sc.cond), h = std::max(0, n - k);
+    return FutureFrame{f - n, n, h, h - 1};
+}
+// can frame k take the shared path: a shared slot, and tails the kernel holds in the three stacks (k + 1 slots behind P) and in the ego stack (k behind h)
+bool future_frame_shares(const umgen_engine* e, const ScoreFutIO& sc, int k) {
+    const FutureFrame w = future_frame(sc, k);
+    return w.P >= 1 && attn_temporal_fan_tail_heads(e->H, w.P, k + 1) && (k == 0 || attn_temporal_fan_tail_heads(e->H, w.h, k));
+}
+
+// The windows and targets of items [i0, i0 + n) -- item i is candidate (i / C, i % C) -- at future frame k: win[m] [n][w.n][S_mod], next [n][2199], rows[i] the
+// row of sc.out that takes item i's results
+struct FutureChunk { std::vector<int> win[4], next; std::vector<long> rows; };
+void future_chunk(const ScoreFutIO& sc, int k, const FutureFrame& w, long i0, int n, FutureChunk& ch) {
+    const int* hist[4] = {sc.pose, sc.map, sc.box, sc.img};
+    ch.next.resize((size_t)n * kTokPerFrame);
+    ch.rows.resize(n);
+    for (int m = 0; m < 4; ++m) {
+        const size_t len = kModLen[m];
+        ch.win[m].resize((size_t)n * w.n * len);
+        for (int i = 0; i < n; ++i) {
+            const long it = i0 + i, b = it / sc.C;
+            int* dst = &ch.win[m][(size_t)i * w.n * len];
+            if (w.h) memcpy(dst, hist[m] + ((size_t)b * sc.T + w.start) * len, (size_t)w.h * len * sizeof(int));
+            const int k0 = w.h ? 0 : w.start - sc.T;      // first future frame inside the window
+            memcpy(dst + (size_t)w.h * len, sc.fut[m] + ((size_t)it * sc.K + k0) * len, (size_t)(w.n - w.h) * len * sizeof(int));
+            memcpy(&ch.next[(size_t)i * kTokPerFrame + kModOff[m]], sc.fut[m] + ((size_t)it * sc.K + k) * len, len * sizeof(int));
+        }
+    }
+    for (int i = 0; i < n; ++i) ch.rows[i] = (i0 + i) * sc.K + k;
+}
+
+// frames [k0, k1) of every candidate, each item against its own window: run_score in chunks of at most max_batch items
+template <typename T>
+int score_futures_replicated(umgen_engine* e, const ScoreFutIO& sc, int k0, int k1) {
+    const long N = (long)sc.B * sc.C;
+    const int Bm = e->cfg.max_batch;
+    FutureChunk ch;
+    for (int k = k0; k < k1; ++k) {
+        const FutureFrame w = future_frame(sc, k);
+        for (long i0 = 0; i0 < N; i0 += Bm) {
+            const int n = (int)std::min<long>(Bm, N - i0);
+            future_chunk(sc, k, w, i0, n, ch);
+            const ScoreIO one{n, w.n, ch.win[0].data(), ch.win[1].data(), ch.win[2].data(), ch.win[3].data(), ch.next.data(), sc.out, 0, ch.rows.data()};
+            if (int rc = run_score<T>(e, one)) return rc;
+        }
+    }
+    return 0;
+}
+
+// Frames [0, Ks) of umgen_score_futures on shared history slots.  At frame k the per-scene pass (the ego stack over the window's h history slots, unshifted, and
+// history_slots_once over slots [0, P) of the other three) runs only when the window's first frame moved: while the window grows the caches already hold exactly
+// those slots.  Then the items, in chunks of at most max_batch, run their tails against the scenes' caches (CACHE_SHARED_ITEMS_TAIL): k slots of the ego stack
+// behind h, the decoder and head_ego on the item's last slot (k == 0: the scene's own rows, as in run_score_candidates), k + 1 slots of the other stacks behind
+// P, the conditioning rows, the BlockOAR pass and the heads -- run_score's kernels and row arithmetic over other row sets.
+template <typename T>
+int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
+    const int B = sc.B, C = sc.C, Bm = e->cfg.max_batch, pv = e->cfg.pose_vocab;
+    const long N = (long)B * C;
+    const int* hist_src[4] = {sc.pose, sc.map, sc.box, sc.img};
+    FrameCtx ctx = begin_call(e, kNoSampling);
+    RestoreStream restore{e, ctx.fg};
+    const FrameIO io{B, std::min(sc.T, sc.cond), sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
+    e->px.valid = false;                 // the passes below overwrite the slot caches and the stacks' workspaces
+    if (int rc = settle_background_pass(e, io, ctx)) return rc;
+    hipStream_t const st = ctx.st;
+    HIPCHK(e, hipMemsetAsync(e->d_counters, 0, 8 * sizeof(int), st));      // (what upload_frame_inputs clears ahead of the ego sampler)
+    ctx.seeds.assign(B, 0ull);
+    HIPCHK(e, hipMemcpyAsync(e->d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+    StageClock clock{e, st};
+    e->fan_scenes = B;
+    // host staging (the asynchronous copies read it until the next synchronisation: a chunk ends with one, and nothing is rewritten before it)
+    std::vector<int> hist[4], cand_pose, item_scene, pshift, am;
+    std::vector<float> pdiff, lp;
+    std::vector<long> frame_of;
+    FutureChunk ch;
+    int prev_start = -1;
+    for (int k = 0; k < Ks; ++k) {
+        const FutureFrame w = future_frame(sc, k);
+        const int Wt = k + 1;
+        if (k == 0 || w.start != prev_start) {
+            prev_start = w.start;
+            ++e->fut_history_passes;
+            for (int m = 0; m < 4; ++m) {      // the scenes' history frames inside the window, [B][h][S_mod]
+                const size_t len = kModLen[m];
+                hist[m].resize((size_t)B * w.h * len);
+                for (int b = 0; b < B; ++b) memcpy(&hist[m][(size_t)b * w.h * len], hist_src[m] + ((size_t)b * sc.T + w.start) * len, (size_t)w.h * len * sizeof(int));
+            }
+            HIPCHK(e, hipMemcpyAsync(e->d_pose, hist[0].data(), hist[0].size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_map, hist[1].data(), hist[1].size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_box, hist[2].data(), hist[2].size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_img, hist[3].data(), hist[3].size() * 4, hipMemcpyHostToDevice, st));
+            clock.stage(nullptr);            // the uploads
+            const WindowTokens we{e->d_pose, e->d_map, e->d_box, e->d_img, B, w.h, w.h, 0};
+            // k == 0: the whole window is history -- the ego net once per scene, its three head_ego rows in e->logits [3 B][pose_vocab], and the ego stack's
+            // k | v rows kept for the longer windows that follow; later: the ego stack's shared slots alone
+            if (k == 0) run_ego_any(e, we, ctx.sp, 0, false, nullptr, Ks > 1 ? CACHE_WINDOW_KEEP : CACHE_NONE);
+            else run_stack_any(e, STACK_EGO, we, CACHE_FILL_PREFIX);
+            clock.stage(&e->tm.ego_ms);
+            if (int rc = history_slots_once(e, st, hist[0].data(), B, w.h, ctx.pshift, ctx.pdiff)) return rc;
+            clock.stage(&e->tm.tar_ms);
+        }
+        for (long i0 = 0; i0 < N; i0 += Bm) {
+            const int n = (int)std::min<long>(Bm, N - i0);
+            future_chunk(sc, k, w, i0, n, ch);
+            cand_pose.resize((size_t)n * 3);
+            item_scene.resize(n);
+            for (int i = 0; i < n; ++i) {
+                item_scene[i] = (int)((i0 + i) / C);
+                for (int a = 0; a < 3; ++a) cand_pose[(size_t)i * 3 + a] = ch.next[(size_t)i * kTokPerFrame + a];
+            }
+            HIPCHK(e, hipMemcpyAsync(e->d_map, ch.win[1].data(), ch.win[1].size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_box, ch.win[2].data(), ch.win[2].size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_img, ch.win[3].data(), ch.win[3].size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->d_tokens, ch.next.data(), (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
+            if (k == 0) {
+                // the pose of future frame 0: a lookup in the scene's rows (the bits depend on the row and the target only)
+                for (int i = 0; i < n; ++i)
+                    launch_logits_nll(st, e->logits + (long)item_scene[i] * 3 * pv, pv, pv, 3, e->d_tokens + (long)i * kTokPerFrame, kNPose, kTokPerFrame,
+                                      e->score_logp + (long)i * 3, e->score_arg + (long)i * 3, nullptr, nullptr);
+            } else {
+                // the ego net reads the unshifted window: the item's k future slots behind the scene's h, the decoder and head_ego on its last slot
+                HIPCHK(e, hipMemcpyAsync(e->d_pose, ch.win[0].data(), ch.win[0].size() * 4, hipMemcpyHostToDevice, st));
+                run_stack_any(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, n, k, w.n, w.h}, CACHE_SHARED_ITEMS_TAIL);
+                frame_of.resize(n);
+                for (int i = 0; i < n; ++i) frame_of[i] = (long)i * k + (k - 1);
+                ego_decoder_any(e, n, frame_of.data(), w.n, nullptr);
+                launch_logits_nll(st, e->logits, pv, pv, 3 * n, e->d_tokens, kNPose, kTokPerFrame, e->score_logp, e->score_arg, nullptr, nullptr);
+                clock.stage(&e->tm.ego_ms);
+            }
+            if (int rc = upload_pose_shift(e, st, ch.win[0].data(), cand_pose.data(), n, w.n, pshift, pdiff)) return rc;      // slot n - 1: the pose of future frame k
+            stacks_with_cond_rows(e, st, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, Wt, w.n, w.P}, CACHE_SHARED_ITEMS_TAIL);
+            clock.stage(&e->tm.tar_ms);
+            if (int rc = run_prefix_prefill_any(e, n, kSeq)) return rc;
+            if (int rc = score_heads<T>(e, st, n, nullptr)) return rc;
+            lp.resize((size_t)n * kTokPerFrame);
+            am.resize((size_t)n * kTokPerFrame);
+            HIPCHK(e, hipMemcpyAsync(lp.data(), e->score_logp, (size_t)n * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(e, hipMemcpyAsync(am.data(), e->score_arg, (size_t)n * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(e, hipStreamSynchronize(st));
+            clock.stage(&e->tm.oar_ms);
+            scatter_blocks(sc.out.logp, n, lp.data(), 0, ch.rows.data());
+            scatter_blocks(sc.out.argmax, n, am.data(), 0, ch.rows.data());
+        }
+    }
+    if (e->profiling) fold_launch_events(e);
+    return finish_call(e, "scoring pass");
+}
+
+// umgen_score_futures: C candidate futures of K frames per scene against one history, every frame under umgen_rollout's window rule.  The leading frames whose
+// window still holds a shared history slot and whose tails the kernel holds take score_futures_shared; the frames behind them, and everything when the slot
+// caches do not fit or UMGEN_SCORE_FUTURES_SHARE=0, are run_score itself on per-item windows.  Either way entry (b, c, k) has the bits of umgen_score on its own
+// window.  (P_k never grows and the tails only do, so the frames that share are a prefix of the K.)
+template <typename T>
+int run_score_futures(umgen_engine* e, const ScoreFutIO& sc) {
+    const char* she = getenv("UMGEN_SCORE_FUTURES_SHARE");      // (read per call: the tests compare both forms in one process)
+    int Ks = 0;
+    e->fut_history_passes = 0;
+    if (!(she && she[0] == '0') && future_frame_shares(e, sc, 0) && ensure_tcache(e))
+        while (Ks < sc.K && future_frame_shares(e, sc, Ks)) ++Ks;
+    if (sc.shared_slots)
+        for (int k = 0; k < sc.K; ++k) sc.shared_slots[k] = k < Ks ? future_frame(sc, k).P : 0;
+    if (Ks)
+        if (int rc = score_futures_shared<T>(e, sc, Ks)) return rc;
+    return score_futures_replicated<T>(e, sc, Ks, sc.K);
+}
+
 // device buffers of umgen_score_clip's shared pass, on its first call (like ensure_score_detail); no room is not an error: the call takes the per-frame path
 bool ensure_score_clip(umgen_engine* e) {
     if (e->clip_state) return e->clip_state > 0;
@@ -404,5 +576,6 @@ namespace umgen {
 int run_score_any(umgen_engine* e, const ScoreIO& sc) { return run_pass(e, [&](auto t) { return run_score<decltype(t)>(e, sc); }); }
 int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc) { return run_pass(e, [&](auto t) { return run_score_candidates<decltype(t)>(e, sc); }); }
 int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc) { return run_pass(e, [&](auto t) { return run_score_clip<decltype(t)>(e, sc); }); }
+int run_score_futures_any(umgen_engine* e, const ScoreFutIO& sc) { return run_pass(e, [&](auto t) { return run_score_futures<decltype(t)>(e, sc); }); }
 
 }  // namespace umgen

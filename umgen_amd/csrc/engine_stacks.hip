@@ -129,9 +129,14 @@ void tar_sub(umgen_engine* e, const SubW& w, int B, int Tn, int S, bool temporal
             tr.q0 = tr.t0 + Tn - 1;
         }
         // fan: the B rows-of-one-slot are items that share their scenes' cached slots [0, tr.t0) (CACHE_SHARED_ITEMS); 2: item i also leaves its own
-        // k | v rows in block i, slot tr.t0 (CACHE_SHARED_ITEMS_APPEND)
+        // k | v rows in block i, slot tr.t0 (CACHE_SHARED_ITEMS_APPEND); 3: the items bring Tn slots [tr.t0, tr.t0 + Tn) each (CACHE_SHARED_ITEMS_TAIL; the
+        // caller has asked attn_temporal_fan_tail_heads, so a refusal here is a refused launch like any other)
         if (fan == 2) launch_attn_temporal_fan_write<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<T*>(tr.cache), tr.Tcap);
-        else if (fan) launch_attn_temporal_fan<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<const T*>(tr.cache), tr.Tcap);
+        else if (fan == 3) {
+            if (launch_attn_temporal_fan_tail<T>(e->stream, QKV, A, B, Tn, e->d_item_scene, e->fan_scenes, S, H, tr.t0, tr.q0, reinterpret_cast<const T*>(tr.cache), tr.Tcap) &&
+                e->launch_status == hipSuccess)
+                e->launch_status = hipErrorInvalidConfiguration;
+        } else if (fan) launch_attn_temporal_fan<T>(e->stream, QKV, A, B, e->d_item_scene, e->fan_scenes, S, H, tr.t0, reinterpret_cast<const T*>(tr.cache), tr.Tcap);
         else launch_attn_temporal<T>(e->stream, QKV, A, B, Tn, S, H, tr);
     } else if (tail == 0) {
         launch_layernorm<T>(e->stream, e->X, E, R, E, w.ln_a, A);
@@ -166,7 +171,7 @@ void run_stack(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cach
         TemporalRange tr{w.t0, cache_mode != CACHE_NONE ? e->tcache[stack][i] : nullptr, e->cfg.max_cond_frames, cache_writes(cache_mode) ? 1 : 0};
         // the final block's tail on the last frame only (f-3): whole-window passes with more than one slot (the temporal sub-block still
         // evaluates the k | v rows of every slot, so a pass that fills the slot caches keeps the shortcut)
-        const bool last = i + 1 == e->stk[stack].size() && cache_whole_window(cache_mode) && w.T > 1 && !no_tail && tail == TAIL_AUTO;
+        const bool last = i + 1 == e->stk[stack].size() && cache_last_frame_shortcut(cache_mode) && w.T > 1 && !no_tail && tail == TAIL_AUTO;
         tar_sub<T>(e, blk.sub[0], w.B, w.T, S, false);
         tar_sub<T>(e, blk.sub[1], w.B, w.T, S, true, tr, last ? 1 : 0, cache_fan_form(cache_mode));
         tar_sub<T>(e, blk.sub[2], w.B, w.T, S, false, TemporalRange{0, nullptr, 0, 0}, last ? 2 : 0);

@@ -86,9 +86,11 @@ struct umgen_engine {
     int* score_arg = nullptr;
     // umgen_score_candidates (engine_score.hip run_score_candidates): the scene of every item (b, c) of the chunk in flight, [max_batch], and the number of
     // scenes whose slot caches the chunk's last-slot pass reads (CACHE_SHARED_ITEMS); umgen_rollout_fan's first frame (run_frame_fan) uses both the same way
-    // for its B * N branches (CACHE_SHARED_ITEMS / CACHE_SHARED_ITEMS_APPEND)
+    // for its B * N branches (CACHE_SHARED_ITEMS / CACHE_SHARED_ITEMS_APPEND), umgen_score_futures for its B * C items (CACHE_SHARED_ITEMS_TAIL)
     int* d_item_scene = nullptr;
     int fan_scenes = 0;
+    // umgen_score_futures (engine_score.hip run_score_futures): per-scene history passes of the last call (read by the test hook umgen_dbg_score_futures_passes)
+    int fut_history_passes = 0;
     // umgen_score_clip (engine_score.hip run_score_clip): allocated by its first call (ensure_score_clip), for max_batch * max_cond_frames items (b, slot) of one
     // window pass.  clip_items [n][2] (scene, slot) and clip_item_T [n] (window length slot + 1); clip_warped [max_batch][max_cond_frames][1024][E], the map
     // stack's warped map of every slot; clip_cond [n][2207][E]; clip_tokens [n][2199], each item's scored frame; clip_xlast [n][E] (the prefix rows' unused
@@ -273,10 +275,17 @@ enum CacheMode {
     // ... and item i appends its own k | v rows to block i of the caches (umgen_rollout_fan ahead of a longer window: spread_tcaches then hands every
     // item its scene's slots [0, P))
     CACHE_SHARED_ITEMS_APPEND = 6,
+    // tail pass of w.B ITEMS that share the caches of e->fan_scenes scenes like CACHE_SHARED_ITEMS, with w.T >= 1 slots [w.t0, w.t0 + w.T) of their own each
+    // (umgen_score_futures: future frame k of a candidate brings k + 1 slots); nothing is written to the caches.  The final block's last-frame shortcut
+    // applies to the tail (w.T > 1), as it does to a whole window
+    CACHE_SHARED_ITEMS_TAIL = 7,
 };
 constexpr bool cache_writes(CacheMode m) { return m == CACHE_FILL_PREFIX || m == CACHE_WINDOW_KEEP || m == CACHE_LAST_SLOT_APPEND; }   // launch_attn_temporal appends
 constexpr bool cache_whole_window(CacheMode m) { return m == CACHE_NONE || m == CACHE_WINDOW_KEEP; }
-constexpr int cache_fan_form(CacheMode m) { return m == CACHE_SHARED_ITEMS ? 1 : (m == CACHE_SHARED_ITEMS_APPEND ? 2 : 0); }           // tar_sub's `fan`
+constexpr bool cache_last_frame_shortcut(CacheMode m) { return cache_whole_window(m) || m == CACHE_SHARED_ITEMS_TAIL; }                // run_stack's `last`
+constexpr int cache_fan_form(CacheMode m) {                                                                                             // tar_sub's `fan`
+    return m == CACHE_SHARED_ITEMS ? 1 : (m == CACHE_SHARED_ITEMS_APPEND ? 2 : (m == CACHE_SHARED_ITEMS_TAIL ? 3 : 0));
+}
 
 struct FrameIO {
     int B, T;
@@ -321,6 +330,16 @@ struct ScoreCandIO {
     const int* next;                             // [B][C][2199]: the candidates, pose | map | bbox3d | image
     ScoreDst out;                                // candidate (b, c) at row b*C + c
     int shared_slots;                            // out: T - 1 when the history slots ran once per scene, 0 on the replicated path
+};
+
+// umgen_score_futures' arguments: B scenes' histories of T frames and C candidate futures of K frames per scene; future frame k of candidate (b, c) is scored
+// against the last min(T + k, cond) frames of history[b] ++ future[b][c]
+struct ScoreFutIO {
+    int B, T, C, K, cond;
+    const int *pose, *map, *box, *img;          // [B][T][S_mod]
+    const int* fut[4];                           // pose | map | bbox3d | image, each [B][C][K][S_mod]
+    ScoreDst out;                                // frame k of candidate (b, c) at row (b*C + c)*K + k
+    int* shared_slots;                           // out, [K]: per future frame the history slots that ran once per scene, 0 on the replicated path
 };
 
 // umgen_score_clip's arguments: B recorded clips of L frames; every frame f in [T_in, L) is scored against the min(f, cond) frames before it
@@ -389,5 +408,6 @@ int run_frame_fan_any(umgen_engine* e, const FrameIO& io, int N);
 int run_score_any(umgen_engine* e, const ScoreIO& sc);
 int run_score_candidates_any(umgen_engine* e, ScoreCandIO& sc);
 int run_score_clip_any(umgen_engine* e, ScoreClipIO& sc);
+int run_score_futures_any(umgen_engine* e, const ScoreFutIO& sc);
 
 }  // namespace umgen

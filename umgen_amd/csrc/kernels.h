@@ -73,7 +73,15 @@ template <typename T> void launch_attn_temporal_fan(hipStream_t s, const T* qkv,
 // every block are only read, no other byte of the cache is written.
 template <typename T> void launch_attn_temporal_fan_write(hipStream_t s, const T* qkv, T* y, int N, const int* scene_of_item, int B, int S, int H, int P,
                                                           T* cache, int Tcap);
-// Behind it: slots [0, P) of the scene blocks b < B of cache [>= B*N blocks][Tcap][row_bytes] to the blocks b*N + s, s < N, in 16-byte vectors; slots >= P of
+// Item TAILS of Wt slots behind the shared slots (umgen_score_futures): qkv [N][Wt][S][3E] holds the slots [P, P + Wt) of every item, scene_of_item and cache as
+// for launch_attn_temporal_fan; y [N][Wt][S][E] has the bits of launch_attn_temporal with t0 = P, Tn = Wt, write = 0 on a per-item copy of the cache (Wt == 1:
+// those of launch_attn_temporal_fan).  q0 as TemporalRange::q0: tail slots below it have no query, their q rows are not read and their y rows not written.
+// attn_temporal_fan_tail_heads: heads per workgroup of the form that holds this tail, 0 when none does (Wt > 16, Wt > 8 with H % 4 == 0 only through the
+// 2-head form, P beyond the LDS request); the launcher then returns -1 WITHOUT launching, else 0.
+int attn_temporal_fan_tail_heads(int H, int P, int Wt);
+template <typename T> int launch_attn_temporal_fan_tail(hipStream_t s, const T* qkv, T* y, int N, int Wt, const int* scene_of_item, int B, int S, int H, int P,
+                                                        int q0, const T* cache, int Tcap);
+// Behind launch_attn_temporal_fan_write: slots [0, P) of the scene blocks b < B of cache [>= B*N blocks][Tcap][row_bytes] to the blocks b*N + s, s < N, in 16-byte vectors; slots >= P of
 // every block stay.  Scene by scene in descending b on the stream (block b is both scene b's source and item b's destination).  row_bytes % 16 == 0.
 void launch_tcache_spread(hipStream_t s, void* cache, int B, int N, int P, int Tcap, size_t row_bytes);
 

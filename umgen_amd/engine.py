@@ -421,6 +421,62 @@ class Engine:
         return self._score_result(logp, arg, batched, total=True, shared_slots=int(shared.value))
 
     @staticmethod
+    def future_windows(T: int, K: int, cond_frames: int):
+        """The window rule of score_futures, stated once: [(k, start, n, shared), ...] for the future frames k in [0, K) of a candidate.  Over the
+        concatenated sequence history ++ future, frame T + k is scored against its n = min(T + k, cond_frames) frames seq[start : start + n],
+        start = T + k - n (clip_windows' rule).  h = max(0, n - k) of them are history frames, and shared = max(0, h - 1) is the number of window
+        slots of the map / bbox3d / TAR stacks that every candidate of a scene has in common (slot h - 1 carries the pose of future frame 0): what
+        "shared_slots" reports for a frame on the shared path."""
+        out = []
+        for k in range(K):
+            n = min(T + k, cond_frames)
+            out.append((k, T + k - n, n, max(0, max(0, n - k) - 1)))
+        return out
+
+    def _future_args(self, window: Dict[str, np.ndarray], futures: Dict[str, np.ndarray], cond_frames):
+        """Shapes, dtypes, token ranges and counts of a score_futures call.  Returns (w [B, T, S], fu [B, C, K, S], cond_frames, batched)."""
+        batched, (B, T) = self._window_lead(window["pose"])
+        Cn, Kn = (tuple(np.shape(futures["pose"])) + (0, 0, 0))[1 if batched else 0:][:2]
+        w = self._token_arrays("score_futures", "window", window, (B, T), batched, True)
+        fu = self._token_arrays("score_futures", "futures", futures, (B, Cn, Kn), batched, True)
+        if T < 1:
+            raise UMGenError("score_futures: the window has no history frame")
+        if Cn < 1:
+            raise UMGenError("score_futures: no candidate future")
+        if Kn < 1:
+            raise UMGenError("score_futures: no future frame")
+        if cond_frames is None:
+            cond_frames = self.max_cond_frames
+        if isinstance(cond_frames, bool) or not isinstance(cond_frames, (int, np.integer)) or not 1 <= cond_frames <= self.max_cond_frames:
+            raise UMGenError(f"score_futures: cond_frames={cond_frames!r} must be an integer in [1, {self.max_cond_frames}] (max_cond_frames)")
+        if B < 1 or B > self.max_batch:
+            raise UMGenError(f"score_futures: {B} scenes, the engine holds max_batch={self.max_batch}")
+        return w, fu, int(cond_frames), batched
+
+    def score_futures(self, window: Dict[str, np.ndarray], futures: Dict[str, np.ndarray], cond_frames=None) -> dict:
+        """Per-token log-likelihoods of C candidate futures of K frames per scene against one history (umgen_score_futures: the history slots a
+        scene's candidates share run once per scene, every candidate only its own tail of slots, the BlockOAR pass and the heads).
+        window: mod -> [B, T, S_mod] (or [T, S_mod]); futures: mod -> [B, C, K, S_mod] (or [C, K, S_mod]), integer dtypes; cond_frames (default
+        max_cond_frames) caps every frame's window as a rollout's does (future_windows).
+        Returns {"logp": {mod: float32 [B, C, K, S_mod]}, "argmax": {mod: int64 [B, C, K, S_mod]}, "total": float64 [B, C, K], "cum_total": float64
+        [B, C], "shared_slots": int64 [K]} (without the B axis for un-batched inputs).  Entry (b, c, k) has the bits of score on the window
+        future_windows names inside window[b] ++ futures[b, c] and frame futures[b, c, k]; "total" is the sum of logp over the 2199 content
+        positions of a frame, "cum_total" its sum over the K frames, the trajectory's ranking key; "shared_slots"[k] is the number of history
+        slots evaluated once per scene at frame k, 0 when that frame ran every candidate's whole window (no shared slot left, a tail longer than
+        the kernel holds, slot caches that do not fit, UMGEN_SCORE_FUTURES_SHARE=0)."""
+        w, fu, cond_frames, batched = self._future_args(window, futures, cond_frames)
+        B, T = w["pose"].shape[:2]
+        Cn, Kn = fu["pose"].shape[1:3]
+        logp, arg, out = self._score_out((B, Cn, Kn))
+        tokens = [_p64(w[m]) for m in MOD_ORDER] + [_p64(fu[m]) for m in MOD_ORDER]
+        shared = np.full(Kn, -1, np.int32)
+        self._check(self.lib.umgen_score_futures(self._h, B, T, Cn, Kn, cond_frames, *tokens, C.byref(out), shared.ctypes.data_as(C.POINTER(C.c_int32))),
+                    "score_futures")
+        res = self._score_result(logp, arg, batched, total=True, shared_slots=shared.astype(np.int64))
+        res["cum_total"] = res["total"].sum(axis=-1)
+        return res
+
+    @staticmethod
     def clip_windows(L: int, input_frames: int, cond_frames: int):
         """The window rule of score_clip (and of a rollout, UMGen.py:1597-1603), stated once: [(f, start, n), ...] for every scored frame f in
         [input_frames, L) -- frame f is scored against the n = min(f, cond_frames) frames clip[start : start + n], start = f - n."""

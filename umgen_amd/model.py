@@ -266,6 +266,52 @@ class UMGen(nn.Module):
         res["best"] = np.argmax(res["total"], axis=-1).astype(np.int64)
         return res
 
+    @staticmethod
+    def _future_split(cond: Dict[str, np.ndarray], fut: Dict[str, np.ndarray], includes_history: Optional[bool]):
+        """What `score_futures` hands the engine as futures, mod -> [B, C, K, S]: ``fut`` itself, or -- for the output of
+        ``inference(num_samples=N)``, [B, N, T_in + K, S] with every branch's first T_in frames the conditioning clip -- the branches' new frames.
+        includes_history None decides by looking: more frames than the clip, and every modality's leading frames equal to it.  Pure numpy, raises
+        UMGenError on bad shapes."""
+        for m in MOD_ORDER:
+            if cond[m].ndim != 3 or fut[m].ndim != 4 or cond[m].shape[0] != fut[m].shape[0] or fut[m].shape[:3] != fut["pose"].shape[:3]:
+                raise UMGenError(f"score_futures: input_cond_tokens[{m}] {cond[m].shape} / futures[{m}] {fut[m].shape}: expected [B, T, S] and [B, C, K, S] "
+                                 "(or [B, N, T + K, S], an inference(num_samples=N) output)")
+        T, L = cond["pose"].shape[1], fut["pose"].shape[2]
+        same = L > T and all(fut[m].shape[3:] == cond[m].shape[2:] and np.array_equal(fut[m][:, :, :T], np.broadcast_to(cond[m][:, None], fut[m][:, :, :T].shape))
+                             for m in MOD_ORDER)
+        if includes_history is None:
+            includes_history = same
+        elif includes_history and not same:
+            raise UMGenError(f"score_futures: includes_history=True, but the first {T} frames of every branch are not the conditioning clip")
+        return {m: np.ascontiguousarray(fut[m][:, :, T:]) for m in MOD_ORDER} if includes_history else fut
+
+    @torch.no_grad()
+    def score_futures(self, input_cond_tokens: Dict[str, torch.Tensor], futures: Dict[str, torch.Tensor], cond_frames: int = -1,
+                      includes_history: Optional[bool] = None) -> Dict[str, dict]:
+        """Ranks C candidate futures of K frames per scene: ``futures[m]`` [B, C, K, S_mod] behind the history ``input_cond_tokens[m]`` [B, T, S_mod],
+        every future frame scored against the frames before it, at most ``cond_frames`` of them (-1: the engine's window of 20) -- `inference`'s
+        window rule with the given frames in place of generated ones (Engine.score_futures: what a scene's candidates share of the history runs
+        once per scene).  The output of ``inference(num_samples=N)``, [B, N, T + K, S_mod], is accepted as it is: the history is its first T
+        frames, the futures are the branches' new frames (``includes_history``: None looks, True insists, False takes every frame as future).
+        Returns Engine.score_futures' dict -- "logp", "argmax", "total" (float64 [B, C, K]), "cum_total" (float64 [B, C], the ranking key),
+        "shared_slots" -- plus "nll": mod -> float64 [B, C, K], the mean negative log-likelihood per frame, and "best": int64 [B], the candidate
+        with the highest cum_total."""
+        if not self._loaded:
+            raise UMGenError("load_state_dict() has not provided every tensor the model reads")
+        np_ = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
+        cond = {m: np_(input_cond_tokens[m]) for m in MOD_ORDER}
+        fut = self._future_split(cond, {m: np_(futures[m]) for m in MOD_ORDER}, includes_history)
+        cap = min(20, self.rcfg.max_frame_len)
+        if isinstance(cond_frames, bool) or not isinstance(cond_frames, (int, np.integer)) or not (cond_frames == -1 or 1 <= cond_frames <= cap):
+            raise UMGenError(f"score_futures: cond_frames={cond_frames!r} must be -1 or an integer in [1, {cap}] (window cap)")
+        B = cond["pose"].shape[0]
+        if B > self._engine_args["max_batch"]:
+            self._recreate(max_batch=B)
+        res = self.engine.score_futures(cond, fut, cap if cond_frames == -1 else int(cond_frames))
+        res["nll"] = {m: -res["logp"][m].astype(np.float64).mean(axis=-1) for m in MOD_ORDER}
+        res["best"] = np.argmax(res["cum_total"], axis=-1).astype(np.int64)
+        return res
+
     @torch.no_grad()
     def score_clip(self, tokens: Dict[str, torch.Tensor], input_cond_frames: int = 1, cond_frames: int = 20) -> Dict[str, dict]:
         """The validation loss of the model over a recorded clip: ``tokens[m]`` [B, L, S_mod] (torch or numpy); every frame from
