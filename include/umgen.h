@@ -258,6 +258,46 @@ int umgen_score_detail(umgen_engine *e, int32_t B, int32_t T, const int64_t *pos
                        const int64_t *next_pose, const int64_t *next_map, const int64_t *next_bbox3d, const int64_t *next_image, int32_t topk,
                        float temperature, umgen_score_out *out, umgen_score_detail_out *detail);
 
+/* ---- rollout diagnostics: umgen_score_detail's quantities for every GENERATED token, from the decode step that sampled it ------------------
+ * umgen_rollout_detail is umgen_rollout_fan, umgen_frame_detail is umgen_frame_logp, plus `topk` and `detail`; with detail == NULL or all its
+ * pointers NULL they are exactly those calls (which are these with detail = NULL), and tokens and lp are the same bits whether or not detail is
+ * asked.  N == 1 is the plain rollout.  Per content token of every NEW frame, with v the fp32 logit row [0, vocab) the sampler of that decode
+ * step read -- the plain AR head's row (head_ego for the pose), never head_tar_bbox3d -- m its maximum, S = sum exp(v - m), and t = v[tok] for
+ * the token umgen_rollout_logp scores (the token the step settled on BEFORE the rule constraint; the forced token under teacher forcing):
+ *     rank        number of n with v[n] > t, strictly.  For a token of the main draw rank < top_k (top-k sampler) holds exactly: it is the row the
+ *                 sampler drew from.  A token resampled from the TAR head (control / pad-avoid) is ranked on the AR row and may lie outside
+ *     mass_above  A / Z, A = sum over v[n] > t of exp((v[n] - m) / tau), Z = the same sum over all n, tau = sampling->temperature (finite)
+ *     entropy     log S - U / S, U = sum exp(v - m)(v - m): the entropy of softmax(v) in nats at temperature 1
+ *     topk_tok    the `topk` (0 .. UMGEN_SCORE_TOPK_MAX) largest logits' tokens, descending, equal logits by ascending index
+ *     topk_logp   (v[topk_tok[i]] - m) - log S, formed like lp's value: where the scored token is listed its entry has the bits of lp's.
+ *                 -1 / -inf past a vocabulary smaller than topk
+ * Every sum runs in lp's fixed order, so a position's outputs are a function of (row, vocab, topk, tau, token) alone: not of B, the scene's place
+ * in the batch or the decode path.  Where no head ran -- exactly where lp is NaN: the pose under ctrl_pose, every given map / bbox3d position --
+ * rank and topk_tok are -1 and the floats NaN.  Rule constraint: like lp, a blanked slot returns pad tokens and keeps the diagnostics of the
+ * tokens that were DRAWN; scoring the returned frame with umgen_score_detail conditions on the pads and is a different quantity there.
+ * Shapes: rollout [B][N][new_frames][S_mod] (lists [..][S_mod][topk]), frame [S_mod] (lists [S_mod][topk]).  Any pointer may be NULL; top-K
+ * pointers with topk == 0, topk outside [0, UMGEN_SCORE_TOPK_MAX] and a non-finite temperature are refused (UMGEN_E_INVALID) when detail is asked.
+ * Cost: no extra pass over the model and no extra launch; the sampler kernel of a step sweeps its row twice more and runs topk arg-max rounds. */
+typedef struct umgen_gen_detail_out {
+    int32_t *rank_pose, *rank_map, *rank_bbox3d, *rank_image;
+    float *mass_above_pose, *mass_above_map, *mass_above_bbox3d, *mass_above_image;
+    float *entropy_pose, *entropy_map, *entropy_bbox3d, *entropy_image;
+    int32_t *topk_tok_pose, *topk_tok_map, *topk_tok_bbox3d, *topk_tok_image;
+    float *topk_logp_pose, *topk_logp_map, *topk_logp_bbox3d, *topk_logp_image;
+} umgen_gen_detail_out;
+int umgen_rollout_detail(umgen_engine *e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames,
+                         const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                         int32_t T_ctl, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                         const int64_t *given_map, const int64_t *given_bbox3d,
+                         const umgen_sampling *sampling,
+                         int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image,
+                         const umgen_logp_out *lp, int32_t *shared_slots, int32_t topk, const umgen_gen_detail_out *detail);
+int umgen_frame_detail(umgen_engine *e, int32_t T, const int64_t *pose, const int64_t *map, const int64_t *bbox3d,
+                       const int64_t *image, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                       const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
+                       int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp,
+                       int32_t topk, const umgen_gen_detail_out *detail);
+
 /* Ranking futures: C given next frames per scene against ONE history.  Entry (b, c) of every output is bit for bit what
  *     umgen_score(e, 1, T, window b, candidate (b, c))
  * returns on the same engine, in every precision, whichever path ran and however the B * C items were chunked.  Only the last history slot of the map /

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.
 SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "engine_score.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
            "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip", "debug_vq.hip"]
 EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_futures", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp", "umgen_rollout_fan",
+           "umgen_rollout_detail", "umgen_frame_detail",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
@@ -27,6 +28,7 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
            "umgen_dbg_embed_warp_slots", "umgen_dbg_cond_rows_slots", "umgen_dbg_ego_queries_slots",
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego", "umgen_dbg_token_steps_logp", "umgen_dbg_sample_ego_logp",
+           "umgen_dbg_token_steps_detail", "umgen_dbg_sample_ego_detail",
            "umgen_dbg_head_nll", "umgen_dbg_head_nll_split", "umgen_dbg_head_detail", "umgen_dbg_logits_detail",
            "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache", "umgen_dbg_score_futures_passes",
            "umgen_dbg_vq_quantize", "umgen_dbg_vq_quant_tile", "umgen_dbg_vq_im2col", "umgen_dbg_vq_im2col_s2", "umgen_dbg_vq_upsample", "umgen_dbg_vq_from_nchw", "umgen_dbg_vq_to_nchw",
@@ -83,6 +85,12 @@ class ScoreDetailOut(C.Structure):
     """umgen_score_detail_out (include/umgen.h): rank, mass_above, entropy [B][S_mod] and topk_tok, topk_logp [B][S_mod][topk] per modality; any pointer may be NULL"""
     _fields_ = [(f"{k}_{m}", C.POINTER(t)) for k, t in (("rank", C.c_int32), ("mass_above", C.c_float), ("entropy", C.c_float),
                                                         ("topk_tok", C.c_int32), ("topk_logp", C.c_float)) for m in ("pose", "map", "bbox3d", "image")]
+
+
+class GenDetailOut(C.Structure):
+    """umgen_gen_detail_out (include/umgen.h): ScoreDetailOut's fields for generated frames, [B][N][new_frames][S_mod] (x topk) (rollout) or [S_mod] (x topk)
+    (frame); any pointer may be NULL"""
+    _fields_ = list(ScoreDetailOut._fields_)
 
 
 class LogpOut(C.Structure):
@@ -276,6 +284,8 @@ def load_library() -> C.CDLL:
     lib.umgen_rollout_logp.argtypes = lib.umgen_rollout.argtypes + [C.POINTER(LogpOut)]
     lib.umgen_frame_logp.argtypes = lib.umgen_frame.argtypes + [C.POINTER(LogpOut)]
     lib.umgen_rollout_fan.argtypes = [vp, i32, i32] + lib.umgen_rollout.argtypes[2:] + [C.POINTER(LogpOut), C.POINTER(C.c_int32)]
+    lib.umgen_rollout_detail.argtypes = lib.umgen_rollout_fan.argtypes + [i32, C.POINTER(GenDetailOut)]
+    lib.umgen_frame_detail.argtypes = lib.umgen_frame_logp.argtypes + [i32, C.POINTER(GenDetailOut)]
     lib.umgen_score.argtypes = [vp, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut)]
     lib.umgen_score_detail.argtypes = lib.umgen_score.argtypes[:-1] + [i32, C.c_float, C.POINTER(ScoreOut), C.POINTER(ScoreDetailOut)]
     lib.umgen_score_candidates.argtypes = [vp, i32, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
@@ -338,6 +348,8 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_sample_ego.argtypes = [fp, i32, C.POINTER(DbgSamplerParams), C.POINTER(C.c_uint64), i32, i32p, i32, i32p]
     lib.umgen_dbg_token_steps_logp.argtypes = [tp, C.POINTER(DbgSteps), fp]
     lib.umgen_dbg_sample_ego_logp.argtypes = lib.umgen_dbg_sample_ego.argtypes + [fp]
+    lib.umgen_dbg_token_steps_detail.argtypes = lib.umgen_dbg_token_steps_logp.argtypes + [i32, i32p, fp, fp, i32p, fp]
+    lib.umgen_dbg_sample_ego_detail.argtypes = lib.umgen_dbg_sample_ego_logp.argtypes + [i32, i32p, fp, fp, i32p, fp]
     lib.umgen_dbg_head_nll.argtypes = [i32, i32, i32, i32, fp, C.c_long, fp, vp, i32p, fp, i32p, fp, fp]
     lib.umgen_dbg_head_nll_split.argtypes = [i32]
     lib.umgen_dbg_head_detail.argtypes = [i32, i32, i32, i32, fp, C.c_long, fp, vp, i32p, i32, C.c_float, i32p, fp, fp, i32p, fp]

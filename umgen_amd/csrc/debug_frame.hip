@@ -50,7 +50,42 @@ EmbedTables tables_in(Scratch& s, const umgen_dbg_tables& t) {
     tb.grid_posi = s.in(t.grid_posi, (size_t)kNMap * E * 2);
     return tb;
 }
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp);
+// The five arrays of a detail hook: on the host [n] and [n][topk] (in / out: a position no sampled step reaches keeps what it was handed), on the
+// device in the kernels' layout -- the lists kDetailTopK apart, the entries behind topk all bits set, and checked to come back that way
+struct DetailHook {
+    int topk;
+    size_t n;
+    int32_t* rank; float *mass_above, *entropy; int32_t* topk_tok; float* topk_logp;
+    DetailOut d{};
+    std::vector<uint32_t> wt, wl;
+    bool sane() const { return rank && mass_above && entropy && topk >= 0 && topk <= kDetailTopK && (topk == 0 || (topk_tok && topk_logp)); }
+    void widen(const void* host, std::vector<uint32_t>& w) const {
+        w.assign(n * kDetailTopK, 0xffffffffu);
+        for (size_t i = 0; i < n; ++i) memcpy(&w[i * kDetailTopK], (const uint32_t*)host + i * topk, (size_t)topk * 4);
+    }
+    void to_device(Scratch& s) {
+        d.rank = s.inout(rank, n * 4); d.mass_above = s.inout(mass_above, n * 4); d.entropy = s.inout(entropy, n * 4);
+        if (!topk) return;
+        widen(topk_tok, wt); widen(topk_logp, wl);
+        d.topk_tok = s.inout(wt.data(), wt.size() * 4); d.topk_logp = s.inout(wl.data(), wl.size() * 4);
+    }
+    int narrow(void* host, const void* dev, std::vector<uint32_t>& w) const {
+        if (down(w.data(), dev, w.size() * 4)) return UMGEN_E_HIP;
+        for (size_t i = 0; i < n; ++i) {
+            memcpy((uint32_t*)host + i * topk, &w[i * kDetailTopK], (size_t)topk * 4);
+            for (int k = topk; k < kDetailTopK; ++k)
+                if (w[i * kDetailTopK + k] != 0xffffffffu) return UMGEN_E_STATE;
+        }
+        return UMGEN_OK;
+    }
+    int to_host() {
+        if (down(rank, d.rank, n * 4) || down(mass_above, d.mass_above, n * 4) || down(entropy, d.entropy, n * 4)) return UMGEN_E_HIP;
+        if (!topk) return UMGEN_OK;
+        if (int rc = narrow(topk_tok, d.topk_tok, wt)) return rc;
+        return narrow(topk_logp, d.topk_logp, wl);
+    }
+};
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh = nullptr);
 
 // the body of umgen_dbg_embed_warp and umgen_dbg_embed_warp_slots (warped_all: nullptr, or the host buffer of launch_warp_map's output of that name)
 int embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B, int T, int Tfull,
@@ -251,11 +286,19 @@ int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
 int umgen_dbg_token_steps_logp(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp) {
     return logp ? token_steps(t, a, logp) : UMGEN_E_INVALID;
 }
+// ... and with OarState::want_detail = 1, detail_topk = topk and SampleArgs::detail = rank, mass_above, entropy [B][2199], topk_tok, topk_logp [B][2199][topk]
+// (in / out like logp; the lists may be NULL when topk == 0)
+int umgen_dbg_token_steps_detail(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, int topk, int32_t* rank, float* mass_above,
+                                 float* entropy, int32_t* topk_tok, float* topk_logp) {
+    if (!logp || !a || a->B < 1) return UMGEN_E_INVALID;
+    DetailHook dh{topk, (size_t)a->B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
+    return dh.sane() ? token_steps(t, a, logp, &dh) : UMGEN_E_INVALID;
+}
 
 }  // extern "C"
 
 namespace {
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp) {
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh) {
     if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
     // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
     if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
@@ -284,6 +327,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     OarState s0{};
     s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
     s0.epoch = a->epoch0; s0.sp = a->sp; s0.want_logp = logp ? 1 : 0;
+    s0.want_detail = dh ? 1 : 0; s0.detail_topk = dh ? dh->topk : 0;
     Scratch s;
     SampleArgs sa{};
     sa.tb = tables_in(s, *t);
@@ -296,6 +340,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     sa.x_next = s.out(xn * 4); sa.tokens = s.inout(a->tokens, tn * 4); sa.counters = s.inout(a->counters, 8 * 4);
     sa.n_boxes = s.inout(a->n_boxes, (size_t)B * 4); sa.boxes = s.inout(a->boxes, bn * 8);
     if (logp) sa.logp = s.inout(logp, tn * 4);
+    if (dh) { dh->to_device(s); sa.detail = dh->d; }
     if (s.rc) return s.rc;
     for (int i = 0; i < n; ++i) {
         const int j = a->j0 + i, mod = kind_of_pos(j, a->given_end);
@@ -316,6 +361,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     if (!s.intact()) return UMGEN_E_STATE;
     if (down(a->tokens, sa.tokens, tn * 4) || down(a->counters, sa.counters, 8 * 4) || down(a->n_boxes, sa.n_boxes, (size_t)B * 4)) return UMGEN_E_HIP;
     if (logp && down(logp, sa.logp, tn * 4)) return UMGEN_E_HIP;
+    if (dh) { if (int rc = dh->to_host()) return rc; }
     return down(a->boxes, sa.boxes, bn * 8);
 }
 }  // namespace
@@ -325,11 +371,11 @@ extern "C" {
 // launch_sample_ego: logits [3 B][V] -> out_tokens [B][3]; the draw of row (b, jq) is rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN); forced
 // [B][2199] (or NULL) overrides with its pose tokens.  logp [B][2199] (in / out, or NULL): entry [b][jq] receives the log-likelihood of pose token jq
 // of scene b on its row
-int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
-                              int32_t* out_tokens, float* logp) {
+static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                           int32_t* out_tokens, float* logp, DetailHook* dh) {
     if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
         return UMGEN_E_INVALID;
-    for (int b = 0; logp && forced && b < B; ++b)      // the scored token indexes the row
+    for (int b = 0; (logp || dh) && forced && b < B; ++b)      // the scored token indexes the row
         if (!in_range(forced + (size_t)b * kTokPerFrame, kNPose, V)) return UMGEN_E_INVALID;
     const size_t ln = (size_t)B * 3 * V, tn = (size_t)B * kTokPerFrame, osz = (size_t)B * 3 * 4;
     Scratch s;
@@ -338,15 +384,29 @@ int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* s
     const int* dF = s.in(forced, tn * 4);
     int *dOv = s.raw(4), *dT = s.out(osz);
     float* dLp = logp ? (float*)s.inout(logp, tn * 4) : nullptr;
+    if (dh) dh->to_device(s);
     if (s.rc) return s.rc;
     if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
-    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, dLp);
+    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, dLp, dh ? &dh->d : nullptr, dh ? dh->topk : 0);
     if (int rc = finish()) return rc;
     int ovf = 0;
     if (down(&ovf, dOv, 4)) return UMGEN_E_HIP;
     if (!s.intact() || ovf != 0) return UMGEN_E_STATE;      // (the overflow word is unused since the exhaustive tie walk: it must stay 0)
     if (logp && down(logp, dLp, tn * 4)) return UMGEN_E_HIP;
+    if (dh) { if (int rc = dh->to_host()) return rc; }
     return down(out_tokens, dT, osz);
+}
+int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                              int32_t* out_tokens, float* logp) {
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, logp, nullptr);
+}
+// the same with the diagnostics of the three pose tokens: rank, mass_above, entropy [B][2199], topk_tok, topk_logp [B][2199][topk] (in / out, entries [b][jq])
+int umgen_dbg_sample_ego_detail(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                                int32_t* out_tokens, float* logp, int topk, int32_t* rank, float* mass_above, float* entropy, int32_t* topk_tok,
+                                float* topk_logp) {
+    if (B < 1) return UMGEN_E_INVALID;
+    DetailHook dh{topk, (size_t)B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
+    return dh.sane() ? sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, logp, &dh) : UMGEN_E_INVALID;
 }
 int umgen_dbg_sample_ego(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                          int32_t* out_tokens) {

@@ -1,5 +1,5 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan (UMGen.inference).  Creation, weights, the compute path, the frame itself and the scoring passes are in
+// umgen_frame(_logp, _detail), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail (UMGen.inference).  Creation, weights, the compute path, the frame itself and the scoring passes are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip, engine_frame.hip and engine_score.hip.
 #include "engine_state.h"
 
@@ -63,14 +63,67 @@ static int check_scene_tokens(umgen_engine* e, size_t frames, const int64_t* pos
 
 static bool wants_logp(const umgen_logp_out* lp) { return lp && (lp->logp_pose || lp->logp_map || lp->logp_bbox3d || lp->logp_image); }
 
-int umgen_frame_logp(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+// umgen_gen_detail_out behind its checks: a frame's host buffers in the device layout (FrameDetail) and their way into the caller's arrays
+struct GenDetail {
+    int topk = 0;
+    int* rank[4] = {}; float *mass_above[4] = {}, *entropy[4] = {};
+    int* topk_tok[4] = {}; float* topk_logp[4] = {};
+    bool on = false;
+    std::vector<int> f_rank, f_tok;
+    std::vector<float> f_mass, f_ent, f_tlp;
+    FrameDetail fd{};
+
+    // refuses what umgen_score_detail refuses; a NULL or all-NULL struct asks for nothing and is not checked further
+    int init(umgen_engine* e, const umgen_gen_detail_out* d, int32_t k, const umgen_sampling* s, size_t B) {
+        if (!d) return 0;
+        int* const r[4] = {d->rank_pose, d->rank_map, d->rank_bbox3d, d->rank_image};
+        float* const ma[4] = {d->mass_above_pose, d->mass_above_map, d->mass_above_bbox3d, d->mass_above_image};
+        float* const en[4] = {d->entropy_pose, d->entropy_map, d->entropy_bbox3d, d->entropy_image};
+        int* const tt[4] = {d->topk_tok_pose, d->topk_tok_map, d->topk_tok_bbox3d, d->topk_tok_image};
+        float* const tl[4] = {d->topk_logp_pose, d->topk_logp_map, d->topk_logp_bbox3d, d->topk_logp_image};
+        bool lists = false;
+        for (int m = 0; m < 4; ++m) {
+            rank[m] = r[m]; mass_above[m] = ma[m]; entropy[m] = en[m]; topk_tok[m] = tt[m]; topk_logp[m] = tl[m];
+            lists = lists || tt[m] || tl[m];
+            on = on || r[m] || ma[m] || en[m] || tt[m] || tl[m];
+        }
+        if (!on) return 0;
+        if (k < 0 || k > UMGEN_SCORE_TOPK_MAX) return e->fail(UMGEN_E_INVALID, "topk=%d out of range [0,%d]", k, UMGEN_SCORE_TOPK_MAX);
+        if (lists && k == 0) return e->fail(UMGEN_E_INVALID, "top-K outputs requested with topk = 0");
+        if (!(s->temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0 and finite");
+        topk = lists ? k : 0;      // (lists nobody receives are not formed)
+        const size_t n = B * kTokPerFrame;
+        f_rank.resize(n); f_mass.resize(n); f_ent.resize(n);
+        f_tok.resize(topk ? n * kDetailTopK : 0); f_tlp.resize(topk ? n * kDetailTopK : 0);
+        fd = FrameDetail{topk, f_rank.data(), f_mass.data(), f_ent.data(), f_tok.data(), f_tlp.data()};
+        return 0;
+    }
+    const FrameDetail* frame() const { return on ? &fd : nullptr; }
+    // scene b of the frame just generated -> item `item` of the caller's arrays ([items][S_mod], the lists [items][S_mod][topk])
+    void deliver(size_t b, size_t item) const {
+        for (int m = 0; on && m < 4; ++m) {
+            const size_t src = b * kTokPerFrame + kModOff[m], dst = item * kModLen[m], len = (size_t)kModLen[m];
+            if (rank[m]) memcpy(rank[m] + dst, &f_rank[src], len * sizeof(int));
+            if (mass_above[m]) memcpy(mass_above[m] + dst, &f_mass[src], len * sizeof(float));
+            if (entropy[m]) memcpy(entropy[m] + dst, &f_ent[src], len * sizeof(float));
+            for (size_t i = 0; i < len && topk; ++i) {
+                if (topk_tok[m]) memcpy(topk_tok[m] + (dst + i) * topk, &f_tok[(src + i) * kDetailTopK], (size_t)topk * sizeof(int));
+                if (topk_logp[m]) memcpy(topk_logp[m] + (dst + i) * topk, &f_tlp[(src + i) * kDetailTopK], (size_t)topk * sizeof(float));
+            }
+        }
+    }
+};
+
+int umgen_frame_detail(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
                      const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
-                     int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
-                     const umgen_logp_out* lp) {
+                       int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                       const umgen_logp_out* lp, int32_t topk, const umgen_gen_detail_out* detail) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
     if (int rc = check_sampling(e, sampling)) return rc;
+    GenDetail gd;
+    if (int rc = gd.init(e, detail, topk, sampling, 1)) return rc;
     if (!pose || !map || !bbox3d || !image || !out_pose || !out_map || !out_bbox3d || !out_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
     if (int rc = check_scene_tokens(e, (size_t)T, pose, map, bbox3d, image)) return rc;
     if (ctrl_pose) { if (int rc = check_tokens(e, "control pose", ctrl_pose, 3, e->cfg.pose_vocab, false)) return rc; }
@@ -111,7 +164,9 @@ int umgen_frame_logp(umgen_engine* e, int32_t T, const int64_t* pose, const int6
     }
     std::vector<float> flp(wants_logp(lp) ? (size_t)kTokPerFrame : 0);
     if (!flp.empty()) io.out_logp = flp.data();
+    io.out_detail = gd.frame();
     if (int rc = run_frame_any(e, io)) return rc;
+    gd.deliver(0, 0);
     for (int i = 0; i < kNPose; ++i) out_pose[i] = out[i];
     for (int i = 0; i < kNMap; ++i) out_map[i] = out[kOffMap + i];
     for (int i = 0; i < kNBox; ++i) out_bbox3d[i] = out[kOffBox + i];
@@ -123,6 +178,14 @@ int umgen_frame_logp(umgen_engine* e, int32_t T, const int64_t* pose, const int6
         if (lp->logp_image) memcpy(lp->logp_image, &flp[kOffImg], kNImg * sizeof(float));
     }
     return UMGEN_OK;
+}
+
+int umgen_frame_logp(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                     const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
+                     int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                     const umgen_logp_out* lp) {
+    return umgen_frame_detail(e, T, pose, map, bbox3d, image, ctrl_pose, ctrl_bbox3d, control_test, sampling, frame_idx, trace, out_pose, out_map,
+                              out_bbox3d, out_image, lp, 0, nullptr);
 }
 
 int umgen_frame(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
@@ -285,13 +348,15 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
                           const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
                           const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
                           const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
-                          const umgen_logp_out* lp, int32_t fan_N, int32_t* shared_slots) {
+                          const umgen_logp_out* lp, int32_t fan_N, int32_t* shared_slots, int32_t topk, const umgen_gen_detail_out* detail) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
     if (T_in < 1 || new_frames < 0 || cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
         return e->fail(UMGEN_E_INVALID, "T_in=%d new_frames=%d cond_frames=%d (max %d)", T_in, new_frames, cond_frames, e->cfg.max_cond_frames);
     if (int rc = check_sampling(e, sampling)) return rc;
+    GenDetail gd;      // the frame's diagnostics, scattered to [B][new_frames][S_mod] below
+    if (int rc = gd.init(e, detail, topk, sampling, (size_t)B)) return rc;
     if (!pose || !map || !bbox3d || !image || !out_pose || !out_map || !out_bbox3d || !out_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
     if (int rc = check_scene_tokens(e, (size_t)B * T_in, pose, map, bbox3d, image)) return rc;
     if ((ctrl_pose || ctrl_bbox3d) && T_ctl < 1) return e->fail(UMGEN_E_INVALID, "control tokens given with T_ctl=%d", T_ctl);
@@ -385,6 +450,7 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
         io.given_map = gm.empty() ? nullptr : gm.data();
         io.given_box = gb.empty() ? nullptr : gb.data();
         io.out_logp = frame_logp.empty() ? nullptr : frame_logp.data();
+        io.out_detail = gd.frame();
         const char* fse = getenv("UMGEN_FAN_SHARE");      // (read per call: the tests compare both forms in one process)
         const bool fan = idx == 0 && fan_N >= 2 && T_cur >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
         if (fan && shared_slots) *shared_slots = T_cur - 1;
@@ -405,6 +471,7 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
                 for (int b = 0; b < B; ++b)
                     memcpy(lp_out[m] + ((size_t)b * new_frames + idx) * kModLen[m], &frame_logp[(size_t)b * kTokPerFrame + kModOff[m]], (size_t)kModLen[m] * sizeof(float));
         }
+        for (int b = 0; b < B; ++b) gd.deliver((size_t)b, (size_t)b * new_frames + idx);
         T_cur += 1;
     }
     return UMGEN_OK;
@@ -416,15 +483,17 @@ int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_fra
                        const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
                        const umgen_logp_out* lp) {
     return rollout_driver(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr);
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr, 0, nullptr);
 }
 
 // umgen_rollout_fan: N sampled futures per scene.  The branches are the scenes of an ordinary rollout of B * N scenes on replicated inputs -- the driver above,
 // whose first frame shares the history between a scene's branches (engine_frame.hip run_frame_fan); outputs [B][N][..] are that rollout's [B * N][..].
-int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
-                      const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
-                      const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
-                      int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots) {
+// umgen_rollout_detail: the same with the diagnostics of every generated token ([B][N][..] likewise)
+int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                         const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                         const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                         int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
+                         const umgen_gen_detail_out* detail) {
     if (!e) return UMGEN_E_INVALID;
     if (shared_slots) *shared_slots = 0;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
@@ -433,7 +502,7 @@ int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32
     if ((int64_t)B * N > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B*N=%lld (B=%d, N=%d) exceeds max_batch=%d", (long long)B * N, B, N, e->cfg.max_batch);
     if (N == 1)
         return rollout_driver(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                              sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr);
+                              sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr, topk, detail);
     // what the replication below reads; the driver checks everything again, and everything else, on the replicated arrays
     if (T_in < 1 || new_frames < 0 || cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
         return e->fail(UMGEN_E_INVALID, "T_in=%d new_frames=%d cond_frames=%d (max %d)", T_in, new_frames, cond_frames, e->cfg.max_cond_frames);
@@ -454,7 +523,15 @@ int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32
                                gb = replicate(given_bbox3d, (size_t)T_ctl * kNBox);
     return rollout_driver(e, B * N, T_in, new_frames, cond_frames, rp.data(), rm.data(), rb.data(), ri.data(), T_ctl, ctrl_pose ? cp.data() : nullptr,
                           ctrl_bbox3d ? cb.data() : nullptr, control_test, given_map ? gm.data() : nullptr, given_bbox3d ? gb.data() : nullptr, sampling, out_pose,
-                          out_map, out_bbox3d, out_image, lp, N, shared_slots);
+                          out_map, out_bbox3d, out_image, lp, N, shared_slots, topk, detail);
+}
+
+int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                      const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                      const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                      int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots) {
+    return umgen_rollout_detail(e, B, N, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map,
+                                given_bbox3d, sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, 0, nullptr);
 }
 
 int umgen_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,

@@ -154,6 +154,16 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     HIPCHK(e, hipMemsetAsync(e->d_nboxes, 0, (size_t)B * sizeof(int), st));
     // log-likelihoods of the new frame: NaN (all bits set) wherever no head is evaluated -- a given pose, given map / bbox3d positions
     if (io.out_logp) HIPCHK(e, hipMemsetAsync(e->d_logp, 0xFF, (size_t)B * kTokPerFrame * sizeof(float), st));
+    if (io.out_detail) {      // the same for the diagnostics: all bits set is -1 for rank and tokens, NaN for the floats
+        const size_t n = (size_t)B * kTokPerFrame * 4;
+        HIPCHK(e, hipMemsetAsync(e->d_detail.rank, 0xFF, n, st));
+        HIPCHK(e, hipMemsetAsync(e->d_detail.mass_above, 0xFF, n, st));
+        HIPCHK(e, hipMemsetAsync(e->d_detail.entropy, 0xFF, n, st));
+        if (io.out_detail->topk > 0) {
+            HIPCHK(e, hipMemsetAsync(e->d_detail.topk_tok, 0xFF, n * kDetailTopK, st));
+            HIPCHK(e, hipMemsetAsync(e->d_detail.topk_logp, 0xFF, n * kDetailTopK, st));
+        }
+    }
     return 0;
 }
 
@@ -172,7 +182,8 @@ int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if (io.ctrl_pose) {
         for (int i = 0; i < B * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, io.out_logp ? e->d_logp : nullptr);
+        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, io.out_logp ? e->d_logp : nullptr,
+                    io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0);
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }
@@ -309,7 +320,8 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipMemset(e->eng_gloc, 0, e->eng_gloc_bytes));
         e->eng_epoch = 16u;
     }
-    ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, io.out_logp ? 1 : 0};
+    ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, io.out_logp ? 1 : 0, io.out_detail ? 1 : 0,
+                      io.out_detail ? io.out_detail->topk : 0};
     e->eng_epoch += (unsigned)(kImgEos + 1) * kEpochPerStep;
     HIPCHK(e, hipMemcpyAsync(e->d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     ctx.n_lanes = (sizeof(T) == 2 && !tr) ? e->lane_count(B) : 1;      // decode lanes: every lane steps its own copy of the state
@@ -542,6 +554,16 @@ int drain_and_download(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     HIPCHK(e, hipEventRecord(e->ev[3], st));
     HIPCHK(e, hipMemcpyAsync(io.out_tokens, e->d_tokens, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
     if (io.out_logp) HIPCHK(e, hipMemcpyAsync(io.out_logp, e->d_logp, (size_t)B * kTokPerFrame * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (const FrameDetail* d = io.out_detail) {
+        const size_t n = (size_t)B * kTokPerFrame * 4;
+        HIPCHK(e, hipMemcpyAsync(d->rank, e->d_detail.rank, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(d->mass_above, e->d_detail.mass_above, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(d->entropy, e->d_detail.entropy, n, hipMemcpyDeviceToHost, st));
+        if (d->topk > 0) {
+            HIPCHK(e, hipMemcpyAsync(d->topk_tok, e->d_detail.topk_tok, n * kDetailTopK, hipMemcpyDeviceToHost, st));
+            HIPCHK(e, hipMemcpyAsync(d->topk_logp, e->d_detail.topk_logp, n * kDetailTopK, hipMemcpyDeviceToHost, st));
+        }
+    }
     HIPCHK(e, hipMemcpyAsync(ctx.counters, e->d_counters, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (eng) HIPCHK(e, hipMemcpyAsync(&ctx.eng_err, wide ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
@@ -710,7 +732,8 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     if (io.ctrl_pose) {
         for (int i = 0; i < BN * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, io.out_logp ? e->d_logp : nullptr);
+        run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, io.out_logp ? e->d_logp : nullptr,
+                        io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0);
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)BN * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }

@@ -475,6 +475,12 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dalloc(e, &e->d_seeds, Bm)) return rc;
     if (int rc = dalloc(e, &e->d_state, (size_t)1)) return rc;
     if (int rc = dalloc(e, &e->d_logp, Bm * kTokPerFrame)) return rc;
+    // (with the engine, like d_logp: the step graphs captured later hold these pointers)
+    if (int rc = dalloc(e, &e->d_detail.rank, Bm * kTokPerFrame)) return rc;
+    if (int rc = dalloc(e, &e->d_detail.mass_above, Bm * kTokPerFrame)) return rc;
+    if (int rc = dalloc(e, &e->d_detail.entropy, Bm * kTokPerFrame)) return rc;
+    if (int rc = dalloc(e, &e->d_detail.topk_tok, Bm * kTokPerFrame * kDetailTopK)) return rc;
+    if (int rc = dalloc(e, &e->d_detail.topk_logp, Bm * kTokPerFrame * kDetailTopK)) return rc;
     return 0;
 }
 

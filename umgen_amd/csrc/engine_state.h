@@ -80,6 +80,7 @@ struct umgen_engine {
     unsigned long long* d_seeds = nullptr;
     OarState* d_state = nullptr;
     float* d_logp = nullptr;             // [max_batch][2199] log-likelihoods of the frame being generated (umgen_rollout_logp / umgen_frame_logp; SampleArgs::logp)
+    DetailOut d_detail{};                // [max_batch][2199] (x kDetailTopK) diagnostics of the frame being generated (umgen_rollout_detail / umgen_frame_detail; SampleArgs::detail)
     // umgen_score (engine_score.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
@@ -287,6 +288,13 @@ constexpr int cache_fan_form(CacheMode m) {                                     
     return m == CACHE_SHARED_ITEMS ? 1 : (m == CACHE_SHARED_ITEMS_APPEND ? 2 : (m == CACHE_SHARED_ITEMS_TAIL ? 3 : 0));
 }
 
+// host buffers of a frame's diagnostics in the device layout (DetailOut, frame.h): [B][2199], the lists [B][2199][kDetailTopK] with the first topk entries
+// of a position written
+struct FrameDetail {
+    int topk;
+    int* rank; float *mass_above, *entropy;
+    int* topk_tok; float* topk_logp;
+};
 struct FrameIO {
     int B, T;
     const int *pose, *map, *box, *img;          // host window tokens [B][T][S_mod] (box already control-overwritten)
@@ -297,6 +305,7 @@ struct FrameIO {
     const umgen_trace* trace;                    // B == 1 only
     int* out_tokens;                             // host [B][2199]
     float* out_logp = nullptr;                   // host [B][2199] or nullptr: log-likelihood of every content token of the new frame (NaN where no head ran)
+    const FrameDetail* out_detail = nullptr;     // or nullptr: the diagnostics of every content token of the new frame (-1 / NaN where no head ran)
     int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
     bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
     bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed
@@ -367,8 +376,9 @@ void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vect
 void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
 void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
-                 float* logp = nullptr);
-void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp);
+                 float* logp = nullptr, const DetailOut* detail = nullptr, int detail_topk = 0);
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp,
+                     const DetailOut* detail = nullptr, int detail_topk = 0);
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
@@ -392,6 +402,7 @@ struct DecView {
     unsigned long long* d_seeds;
     OarState* d_state;
     float* d_logp;
+    DetailOut d_detail;
 };
 // ---- engine_decode.hip ----------------------------------------------------------------------------------------------
 DecView current_view(const umgen_engine* e);

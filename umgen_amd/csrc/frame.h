@@ -53,8 +53,26 @@ struct OarState {
     int done;        // blocks of the step's last kernel that have finished (the last one advances `step`)
     unsigned epoch;  // base of the decode engine's hand-off tags for this step (advanced with `step`, oar_engine.hip)
     SamplerParams sp;
-    int want_logp;   // the call asked for per-token log-likelihoods: sample_token_kernel also writes SampleArgs::logp (last member: older initialisers leave it 0)
+    int want_logp;   // the call asked for per-token log-likelihoods: sample_token_kernel also writes SampleArgs::logp (older initialisers leave it 0)
+    // the call asked for per-token diagnostics: sample_token_kernel also writes SampleArgs::detail, the detail_topk <= kDetailTopK most likely tokens among them.
+    // At the end of the struct (the decode engines read step and epoch at the offsets they know; older initialisers leave both 0)
+    int want_detail;
+    int detail_topk;
 };
+
+// Diagnostics of a generated token (umgen_rollout_detail / umgen_frame_detail, block_detail in frame.hip), device buffers: rank, mass_above, entropy
+// [B][2199]; topk_tok, topk_logp [B][2199][kDetailTopK] -- a call that lists K < kDetailTopK tokens writes the first K entries of a position.
+constexpr int kDetailTopK = 16;   // == UMGEN_SCORE_TOPK_MAX
+struct DetailOut {
+    int* rank;
+    float *mass_above, *entropy;
+    int* topk_tok;
+    float* topk_logp;
+};
+inline DetailOut detail_at(const DetailOut& d, long scene) {   // the buffers of scene `scene` on (decode lanes, like d_tokens)
+    const long o = scene * kTokPerFrame;
+    return d.rank ? DetailOut{d.rank + o, d.mass_above + o, d.entropy + o, d.topk_tok + o * kDetailTopK, d.topk_logp + o * kDetailTopK} : d;
+}
 
 // everything the per-token sampler kernel touches
 struct SampleArgs {
@@ -78,6 +96,7 @@ struct SampleArgs {
     int* counters;             // [8] per-frame event counters (pad_avoid, control, rule_checked, rule_collision, rule_blanked, sampled != forced,
                                //     -, 7: unused since round 5 -- more than 64 ties at the k-th logit are sampled by an exhaustive walk, frame.hip)
     float* logp;               // [B][2199] or nullptr: log softmax(AR row over [0, vocab))[token the step settled on], written when st->want_logp
+    DetailOut detail;          // the same token's diagnostics on the same row, written when st->want_detail
 };
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);
@@ -107,7 +126,8 @@ void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerP
 void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts, int max_n, int* out, int n_sets);
 // logp: nullptr, or [B][2199] -- entry [b][jq] receives log softmax(head_ego row)[pose token jq of scene b]
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow, float* logp = nullptr);
+                       const int* forced, int* out_tokens, int B, int* overflow, float* logp = nullptr, const DetailOut* detail = nullptr,
+                       int detail_topk = 0);   // detail (or nullptr): entry [b][jq] receives the diagnostics of pose token jq on its head_ego row
 // ego query rows: egoe[j] + spe[j] + tpe[T-1]; item_T [B] on the device (or nullptr): item i's own window length instead of T
 void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x, const int* item_T = nullptr);
 

@@ -613,6 +613,95 @@ __device__ float block_logp(const float* __restrict__ row, int V, int tok) {
     return sub_rn(sub_rn(row[tok], mx), logf(total));
 }
 
+// The diagnostics of umgen_score_detail for the row a sampler drew from, for the samplers' 256-thread block (all threads call; thread 0 writes
+// entry `at` of the buffers): with t = row[tok], m the row maximum and S = sum exp(v - m),
+//   rank = #{n : v[n] > t};  mass_above = A / Z, A = sum over v > t of exp((v - m) / tau), Z = the same over all;
+//   entropy = log S - U / S, U = sum exp(v - m)(v - m);  the K <= kDetailTopK largest logits, descending, equal logits by ascending index, with
+//   (v - m) - log S formed like block_logp's value -- where tok is listed its entry has block_logp's bits; -1 / -inf past a vocabulary < K.
+// m and S are block_logp's own operations in block_logp's order, and A, Z, U follow the same order (a thread's columns tid + 256 i ascending,
+// wave_sum's lanes, waves 0..3, separately rounded), so a row's outputs are a function of (row, V, K, tau, tok) alone.  Columns >= V are never read.
+// The list: K rounds of a block arg-max over the values the threads hold, each thread marking what it gave up in a 32-bit mask (one bit per
+// column it owns); a thread rescans its columns only after it won a round.  The rounds alternate between two sets of exchange words, so one
+// barrier per round is enough.  V <= 8192 like the samplers.
+__device__ void block_detail(const float* __restrict__ row, int V, int tok, int K, float tau, const DetailOut& o, long at) {
+    __shared__ float red[6][4];
+    __shared__ float win_v[2][4];
+    __shared__ int win_i[2][4];
+    constexpr int kNone = 0x7fffffff;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float v[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int idx = tid + 256 * i;
+        v[i] = idx < V ? row[idx] : -INFINITY;
+    }
+    const float t = row[tok];
+    float mx = v[0];
+#pragma unroll
+    for (int i = 1; i < 32; ++i) mx = fmaxf(mx, v[i]);
+    mx = wave_max(mx);
+    if (lane == 0) red[0][wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    const float inv_tau = 1.0f / tau;
+    float s = 0.f, A = 0.f, Z = 0.f, U = 0.f, cnt = 0.f;      // (cnt: a count <= 8192, exact in fp32 in any order)
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+        if (tid + 256 * i < V) {
+            const float c = sub_rn(v[i], mx), e1 = exp_det(c), ez = exp_det(mul_rn(c, inv_tau));
+            s = add_rn(s, e1);
+            U = add_rn(U, mul_rn(e1, c));
+            Z = add_rn(Z, ez);
+            if (v[i] > t) { A = add_rn(A, ez); cnt += 1.f; }
+        }
+    s = wave_sum(s); A = wave_sum(A); Z = wave_sum(Z); U = wave_sum(U); cnt = wave_sum(cnt);
+    if (lane == 0) { red[1][wave] = s; red[2][wave] = A; red[3][wave] = Z; red[4][wave] = U; red[5][wave] = cnt; }
+    __syncthreads();
+    const float S = add_rn(add_rn(add_rn(red[1][0], red[1][1]), red[1][2]), red[1][3]);
+    const float logS = logf(S);
+    if (tid == 0) {
+        const float At = add_rn(add_rn(add_rn(red[2][0], red[2][1]), red[2][2]), red[2][3]);
+        const float Zt = add_rn(add_rn(add_rn(red[3][0], red[3][1]), red[3][2]), red[3][3]);
+        const float Ut = add_rn(add_rn(add_rn(red[4][0], red[4][1]), red[4][2]), red[4][3]);
+        o.rank[at] = (int)(red[5][0] + red[5][1] + red[5][2] + red[5][3]);
+        o.mass_above[at] = At / Zt;
+        o.entropy[at] = sub_rn(logS, Ut / S);
+    }
+    unsigned gone = 0u;              // bit i: column tid + 256 i is already listed
+    bool rescan = true;
+    float bv = -INFINITY;
+    int bi = kNone;
+#pragma unroll 1
+    for (int r = 0; r < min(K, kDetailTopK); ++r) {
+        if (rescan) {                // this thread's best column still unlisted: the first of the largest (ascending i = ascending index)
+            bv = -INFINITY; bi = kNone;
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                const int idx = tid + 256 * i;
+                if (idx < V && !((gone >> i) & 1u) && (bi == kNone || v[i] > bv)) { bv = v[i]; bi = idx; }
+            }
+            rescan = false;
+        }
+        const float wv = wave_max(bv);
+        const int wi = wave_min_i32(bv == wv ? bi : kNone);      // (a thread with nothing left holds kNone)
+        if (lane == 0) { win_v[r & 1][wave] = wv; win_i[r & 1][wave] = wi; }
+        __syncthreads();
+        float gv = win_v[r & 1][0];
+        int gi = win_i[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float cv = win_v[r & 1][w];
+            const int ci = win_i[r & 1][w];
+            if (ci != kNone && (gi == kNone || cv > gv || (cv == gv && ci < gi))) { gv = cv; gi = ci; }
+        }
+        if (gi != kNone && (gi & 255) == tid) { gone |= 1u << (gi >> 8); rescan = true; }
+        if (tid == 0) {
+            o.topk_tok[at * kDetailTopK + r] = gi == kNone ? -1 : gi;
+            o.topk_logp[at * kDetailTopK + r] = gi == kNone ? -INFINITY : sub_rn(sub_rn(gv, mx), logS);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     __shared__ SamplerLds sh;
     __shared__ float cor[64][8];
@@ -620,6 +709,7 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     const int b = blockIdx.x, j = a.st->step, frame = a.st->frame_idx, E = a.tb.E;
     const SamplerParams sp = a.st->sp;
     const bool use_forced = a.st->use_forced != 0, use_control = a.st->use_control != 0, want_logp = a.st->want_logp != 0;
+    const bool want_detail = a.st->want_detail != 0;
     const int pos1 = j + 1;   // the reference's 1-based curr_seq_len
     const unsigned long long seed = a.seeds[b];
     const CondRow crow = load_cond_row(a, b, j);
@@ -656,6 +746,11 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
         const float lp = block_logp(lg, a.vocab, use_forced ? a.forced[(long)b * kTokPerFrame + off + k] : tok);
         if (threadIdx.x == 0) a.logp[(long)b * kTokPerFrame + off + k] = lp;
     }
+    // ... and its diagnostics on the same row -- rank, mass above at the call's temperature, entropy, the most likely tokens (OarState::want_detail,
+    // off unless the call asked: nothing of it runs on the default path)
+    if (want_detail)
+        block_detail(lg, a.vocab, use_forced ? a.forced[(long)b * kTokPerFrame + off + k] : tok, a.st->detail_topk, sp.temperature, a.detail,
+                     (long)b * kTokPerFrame + off + k);
     if (a.mod == 2) {
         if (sp.rule_constrain && !use_forced && tok != kBoxPad && (pos1 - 1032) % kSlotLen == 0) {   // UMGen.py:1116-1123
             if (threadIdx.x == 0) {
@@ -707,7 +802,7 @@ void launch_sample_token(hipStream_t s, const SampleArgs& a, int B) { hipLaunchK
 __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict__ logits, int vocab, SamplerParams sp,
                                                          const unsigned long long* __restrict__ seeds, int frame_idx,
                                                          const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow,
-                                                         float* __restrict__ logp) {
+                                                         float* __restrict__ logp, DetailOut detail, int detail_topk) {
     __shared__ SamplerLds sh;
     const int b = blockIdx.x / 3, jq = blockIdx.x % 3;
     int tok = block_sample(sp, logits + (long)blockIdx.x * vocab, vocab, sp.top_k, sp.p,
@@ -718,10 +813,12 @@ __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict
         const float lp = block_logp(logits + (long)blockIdx.x * vocab, vocab, tok);
         if (threadIdx.x == 0) logp[(long)b * kTokPerFrame + jq] = lp;
     }
+    if (detail.rank) block_detail(logits + (long)blockIdx.x * vocab, vocab, tok, detail_topk, sp.temperature, detail, (long)b * kTokPerFrame + jq);
 }
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow, float* logp) {
-    hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow, logp);
+                       const int* forced, int* out_tokens, int B, int* overflow, float* logp, const DetailOut* detail, int detail_topk) {
+    hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow, logp,
+                       detail ? *detail : DetailOut{}, detail_topk);
 }
 
 // test hook (debug_gemm_attn.hip): the top-k sampler on n independent logit rows with given uniforms

@@ -116,10 +116,38 @@ class Engine:
         logp = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
         return logp, _lib.LogpOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
 
+    _GEN_DETAIL_FIELDS = {"rank": ("rank", np.int32, -1), "mass_above": ("mass_above", np.float32, np.nan), "entropy": ("entropy", np.float32, np.nan),
+                          "topk_tokens": ("topk_tok", np.int32, -1), "topk_logp": ("topk_logp", np.float32, np.nan)}
+
+    @classmethod
+    def _gen_detail_args(cls, call: str, topk, sampling: RolloutConfig) -> int:
+        """topk of a rollout / frame that returns diagnostics, checked before anything reaches the device"""
+        if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)) or not 0 <= topk <= _lib.SCORE_TOPK_MAX:
+            raise UMGenError(f"{call}: topk={topk!r} is outside [0, {_lib.SCORE_TOPK_MAX}]")
+        if not np.isfinite(float(sampling.sfmx_temp)):
+            raise UMGenError(f"{call}: diagnostics need a finite sampling temperature, not {sampling.sfmx_temp}")
+        return int(topk)
+
+    @classmethod
+    def _gen_detail_out(cls, lead: Tuple[int, ...], topk: int):
+        """(key -> mod -> array [*lead, S_mod] (lists [*lead, S_mod, topk]) filled with "no head ran": -1 / NaN, the umgen_gen_detail_out that points at them);
+        the keys are Engine.score(detail=True)'s, the lists only with topk > 0"""
+        keys = [k for k in cls.DETAIL_KEYS if topk > 0 or not k.startswith("topk_")]
+        f = cls._GEN_DETAIL_FIELDS
+        bufs = {k: {m: np.full(tuple(lead) + (CONTENT_LEN[m],) + ((topk,) if k.startswith("topk_") else ()), f[k][2], f[k][1]) for m in MOD_ORDER} for k in keys}
+        out = _lib.GenDetailOut(**{f"{f[k][0]}_{m}": bufs[k][m].ctypes.data_as(C.POINTER(C.c_int32 if f[k][1] is np.int32 else C.c_float))
+                                   for k in keys for m in MOD_ORDER})
+        return bufs, out
+
+    @staticmethod
+    def _gen_detail_result(bufs):
+        return {k: {m: (a.astype(np.int64) if a.dtype == np.int32 else a) for m, a in d.items()} for k, d in bufs.items()}
+
     def rollout(self, tokens: Dict[str, np.ndarray], new_frames: int, cond_frames: int = 20,
                 input_cond_frames: int = -1, init_tokens: Optional[Dict[str, np.ndarray]] = None,
                 control_test: bool = False, seeds: Optional[Sequence[int]] = None,
-                sampling: Optional[RolloutConfig] = None, return_logp: bool = False, samples: Optional[int] = None):
+                sampling: Optional[RolloutConfig] = None, return_logp: bool = False, samples: Optional[int] = None,
+                return_detail: bool = False, topk: int = 0):
         """tokens: mod -> int64 [B, T, S_mod].  Returns mod -> int64 [B, input_cond_frames + new_frames, S_mod].
         samples=N (umgen_rollout_fan): N sampled futures of every scene off one pass over its history.  seeds: [B, N] or flat B*N (default 0), branch
         (b, s) at b*N + s; init_tokens stay per scene, a scene's branches share them.  Returns mod -> int64 [B, N, input_cond_frames + new_frames, S_mod],
@@ -128,7 +156,14 @@ class Engine:
         samples=None is the plain call.
         return_logp: returns (tokens, mod -> float32 [B, new_frames, S_mod]) -- the log-likelihood of every generated token under the plain AR
         heads at temperature 1 (umgen_rollout_logp, include/umgen.h: Engine.score's measure, taken from the decode steps that sampled the
-        token); NaN where no head ran (a controlled pose, given map / bbox3d tokens).  The tokens are the same either way."""
+        token); NaN where no head ran (a controlled pose, given map / bbox3d tokens).  The tokens are the same either way.
+        return_detail (with topk <= 16): the result gains, as its last element, the diagnostics of every generated token (umgen_rollout_detail) keyed like
+        score(detail=True)'s: "rank" int64, "mass_above" (at the rollout's own temperature), "entropy", and with topk > 0 "topk_tokens" int64 [.., S_mod, topk]
+        and "topk_logp"; each mod -> [B, new_frames, S_mod] ([B, N, new_frames, S_mod] with samples).  They are taken from the fp32 row the decode step
+        sampled from, for the token logp scores; -1 / NaN where logp is NaN.  Tokens and logp are the same bits with or without them."""
+        if return_detail or topk:
+            topk = self._gen_detail_args("rollout", topk, sampling or self.cfg)
+            return_detail = True
         if new_frames < 0:
             raise UMGenError(f"new_frames={new_frames}")
         if input_cond_frames == -1:
@@ -187,13 +222,20 @@ class Engine:
         args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
-        if samples is not None:
+        if samples is not None or return_detail:
             logp, lp = self._logp_out(lead + (new_frames,)) if return_logp else (None, None)
             shared = C.c_int32(-1)
-            self._check(self.lib.umgen_rollout_fan(self._h, B, samples, *args[2:], C.byref(lp) if lp is not None else None, C.byref(shared)), "rollout")
+            lpp = C.byref(lp) if lp is not None else None
+            if return_detail:
+                dbufs, det = self._gen_detail_out(lead + (new_frames,), topk)
+                self._check(self.lib.umgen_rollout_detail(self._h, B, samples or 1, *args[2:], lpp, C.byref(shared), topk, C.byref(det)), "rollout")
+            else:
+                self._check(self.lib.umgen_rollout_fan(self._h, B, samples, *args[2:], lpp, C.byref(shared)), "rollout")
             del keep
-            self.last_shared_slots = int(shared.value)
-            return (outs, logp) if return_logp else outs
+            if samples is not None:
+                self.last_shared_slots = int(shared.value)
+            res = (outs,) + ((logp,) if return_logp else ()) + ((self._gen_detail_result(dbufs),) if return_detail else ())
+            return res if len(res) > 1 else outs
         if not return_logp:
             self._check(self.lib.umgen_rollout(*args), "rollout")
             del keep
@@ -206,12 +248,17 @@ class Engine:
     def frame(self, window: Dict[str, np.ndarray], frame_idx: int = 0, ctrl: Optional[Dict[str, np.ndarray]] = None,
               control_test: bool = False, seed: int = 0, sampling: Optional[RolloutConfig] = None,
               forced: Optional[Dict[str, np.ndarray]] = None, trace: bool = False, given: Optional[Dict[str, np.ndarray]] = None,
-              logp: bool = False):
+              logp: bool = False, detail: bool = False, topk: int = 0):
         """One frame of one scene.  window: mod -> [T, S_mod].  Returns (tokens dict, trace dict or None).
         given: {"map": [1024]} or {"map": ..., "bbox3d": [660]}: the frame's GIVEN tokens (init_tokens of `rollout` for one frame).
         logp: the trace dict (created if need be) gains "logp": mod -> float32 [S_mod], `rollout(return_logp=True)` for this frame; under
-        `forced` the values are those of the forced tokens: a step-by-step `score`."""
+        `forced` the values are those of the forced tokens: a step-by-step `score`.
+        detail (with topk <= 16): the trace dict gains "detail", `rollout(return_detail=True, topk=topk)` for this frame: key -> mod -> [S_mod] (lists
+        [S_mod, topk])."""
         cfg = self.cfg
+        if detail or topk:
+            topk = self._gen_detail_args("frame", topk, sampling or cfg)
+            detail = True
         w = {m: _i64(window[m]) for m in MOD_ORDER}
         T = w["pose"].shape[0]
         outs = {m: np.empty((CONTENT_LEN[m],), dtype=np.int64) for m in MOD_ORDER}
@@ -246,8 +293,12 @@ class Engine:
         args = (self._h, T, _p64(w["pose"]), _p64(w["map"]), _p64(w["bbox3d"]), _p64(w["image"]), _p64(cp), _p64(cb),
                 int(control_test), C.byref(smp), frame_idx, C.byref(tr) if tr is not None else None,
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
-        lpv = None
-        if logp:
+        lpv = dbufs = None
+        if detail:
+            lpv, lp = self._logp_out(()) if logp else (None, None)
+            dbufs, det = self._gen_detail_out((), topk)
+            self._check(self.lib.umgen_frame_detail(*args, C.byref(lp) if lp is not None else None, topk, C.byref(det)), "frame")
+        elif logp:
             lpv, lp = self._logp_out(())
             self._check(self.lib.umgen_frame_logp(*args, C.byref(lp)), "frame")
         else:
@@ -260,6 +311,9 @@ class Engine:
         if lpv is not None:
             tbuf = tbuf if tbuf is not None else {}
             tbuf["logp"] = lpv
+        if dbufs is not None:
+            tbuf = tbuf if tbuf is not None else {}
+            tbuf["detail"] = self._gen_detail_result(dbufs)
         return outs, tbuf
 
     # -- scoring -------------------------------------------------------------------------------

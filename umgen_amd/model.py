@@ -138,13 +138,17 @@ class UMGen(nn.Module):
                   input_cond_tokens: Optional[Dict[str, torch.Tensor]] = None,
                   init_tokens: Optional[Dict[str, torch.Tensor]] = None, cond_on_tar: bool = False,
                   test_map_affine: bool = False, max_objects=100, control_test=False, return_logp: bool = False,
-                  num_samples: Optional[int] = None, **kwargs):
+                  num_samples: Optional[int] = None, return_detail: bool = False, topk: int = 0, **kwargs):
         """UMGen.inference (UMGen.py:1542-1671).  ``cond_on_par`` / ``infer_from_gt`` are swallowed like the reference.
         return_logp (extension): returns (tokens, mod -> torch.float32 [B, new_frames, S_mod]), the log-likelihood of every generated token
         (Engine.rollout's return_logp; NaN on controlled / given positions), beside the tokens it returns today.
         num_samples=N (extension): N sampled futures of every scene off one pass over its history (Engine.rollout's samples).  Returns mod -> torch.int64
         [B, N, T, S_mod]; with return_logp (tokens, logp) where logp holds mod -> torch.float32 [B, N, new_frames, S_mod] and "total", torch.float64
-        [B, N, new_frames]: the host sum over a frame's finite entries, the ranking key for best-of-N.  seeds: [B, N] or flat B*N (default seed + i)."""
+        [B, N, new_frames]: the host sum over a frame's finite entries, the ranking key for best-of-N.  seeds: [B, N] or flat B*N (default seed + i).
+        return_detail=True, topk=K (extension): the result gains, as its last element, Engine.rollout's detail dict -- rank, mass_above, entropy and the K most
+        likely tokens of every generated token, from the decode step that sampled it -- as key -> mod -> torch tensor; combines with return_logp and num_samples."""
+        return_detail = bool(return_detail) or bool(topk)
+        as_torch = lambda d: {k: {m: torch.from_numpy(v) for m, v in per.items()} for k, per in d.items()}      # noqa: E731
         if pred_task != "pose_map_bbox3d_image":
             raise UMGenError(f"pred_task={pred_task!r}: only 'pose_map_bbox3d_image' (the evaluation task) is implemented")
         if not self._loaded:
@@ -165,20 +169,32 @@ class UMGen(nn.Module):
                 self._recreate(max_batch=B * N)
             seeds = kwargs.get("seeds", [self.seed + i for i in range(B * N)])
             out = self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames, init_tokens=init,
-                                      control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp), samples=N)
-            if not return_logp:
+                                      control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp), samples=N,
+                                      return_detail=return_detail, topk=topk)
+            if not return_logp and not return_detail:
                 return {m: torch.from_numpy(v) for m, v in out.items()}
-            lp = {m: torch.from_numpy(v) for m, v in out[1].items()}
-            lp["total"] = torch.from_numpy(sum(np.where(np.isfinite(v), v, 0).astype(np.float64).sum(axis=-1) for v in out[1].values()))
-            return {m: torch.from_numpy(v) for m, v in out[0].items()}, lp
+            res = [{m: torch.from_numpy(v) for m, v in out[0].items()}]
+            if return_logp:
+                lp = {m: torch.from_numpy(v) for m, v in out[1].items()}
+                lp["total"] = torch.from_numpy(sum(np.where(np.isfinite(v), v, 0).astype(np.float64).sum(axis=-1) for v in out[1].values()))
+                res.append(lp)
+            if return_detail:
+                res.append(as_torch(out[-1]))
+            return tuple(res)
         if B > self._engine_args["max_batch"]:      # extension over the reference (B = 1): several scenes per call
             self._recreate(max_batch=B)
         seeds = kwargs.get("seeds", [self.seed + i for i in range(B)])
         out = self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames,
-                                  init_tokens=init, control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp))
-        if not return_logp:
+                                  init_tokens=init, control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp),
+                                  return_detail=return_detail, topk=topk)
+        if not return_logp and not return_detail:
             return out
-        return out[0], {m: torch.from_numpy(v) for m, v in out[1].items()}
+        res = [out[0]]
+        if return_logp:
+            res.append({m: torch.from_numpy(v) for m, v in out[1].items()})
+        if return_detail:
+            res.append(as_torch(out[-1]))
+        return tuple(res)
 
     @staticmethod
     def _score_window(cond: Dict[str, np.ndarray], tgt: Dict[str, np.ndarray], input_cond_frames: int, t: Optional[int], cap: int):
