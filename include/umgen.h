@@ -204,6 +204,8 @@ int umgen_frame_logp(umgen_engine *e, int32_t T, const int64_t *pose, const int6
  *   - pose/map/bbox3d/image [B][T_in][S_mod]; ctrl_* / given_* NULL or [B][T_ctl][S_mod]: a scene's branches share them; sampling->seeds [B*N] (NULL: 0),
  *     branch (b, s) at b*N + s; out_* [B][N][T_in + new_frames][S_mod]; lp NULL or arrays [B][N][new_frames][S_mod].
  *   - B >= 1, N >= 1, B*N <= max_batch; everything else is checked like umgen_rollout's arguments.  N == 1 is umgen_rollout_logp itself.
+ *     Every argument is checked once, on the arrays as the caller passed them: an error message that names a token "at flat index i" indexes the caller's
+ *     [B][T_in][S_mod] (or [B][T_ctl][S_mod]) array, for every N.
  *   - What is saved: in the FIRST frame, with n0 = min(T_in, cond_frames) window slots, the ego net and slots 0 .. n0-2 of the map / box / TAR stacks run
  *     once per scene, and only slot n0-1 -- the one the pose shift hands the branch's own new pose -- runs per branch, against the scene's slot caches.
  *     When the window then grows (n0 + 1 <= cond_frames) every branch's slot caches are completed from its scene's, so later frames push one slot per

@@ -214,6 +214,14 @@ def test_refused_calls_leave_the_engine_usable():
                                ("NULL output", (sc, 2, 3, 2, 2, None), "null"), ("token >= vocab", (bad, 2, 3, 2, 2), "8192")):
         rc, msg, _ = raw_call(e, *args)
         assert rc == -1 and needle in msg, (what, rc, msg)
+    # B = 2, N = 2, a map token outside the vocabulary in scene 1: the message names the index in the caller's [2][T_in][1024] array (not in a replicated
+    # one, where scene 1 starts at item 2), and the call is refused before any device work: no frame is counted, nothing is written
+    bad = dict(sc, map=sc["map"].copy())
+    bad["map"][1, 1, 9] = e.cfg.map_vocab_size
+    frames = e.timings()["frames"]
+    rc, msg, out = raw_call(e, bad, 2, 2, 2, 2)
+    assert rc == -1 and f"map token {e.cfg.map_vocab_size} at flat index {(1 * 2 + 1) * 1024 + 9} " in msg, (rc, msg)
+    assert e.timings()["frames"] == frames and all(not out[m].any() for m in MOD_ORDER)
     with pytest.raises(UMGenError):
         e.rollout(sc, 2, cond_frames=3, input_cond_frames=2, samples=4)
     rc, msg, out = raw_call(e, sc, 2, 3, 2, 2)      # a NULL umgen_logp_out is fine

@@ -48,7 +48,7 @@ int umgen_dbg_bg_begin(umgen_engine* e, int32_t T, int32_t cond_cap, const int32
     HIPCHK(e, hipStreamSynchronize(e->stream));
     (void)hipGetLastError();
     FrameIO io{};
-    io.B = 1; io.T = T; io.pose = pose; io.map = map; io.box = bbox3d; io.img = image; io.cond_cap = cond_cap; io.next_follows = true;
+    io.B = 1; io.T = T; io.win = TokenView{{pose, map, bbox3d, image}, T}; io.cond_cap = cond_cap; io.next_follows = true;
     const BgPassDebug dbg{foreground ? 1 : 0, chunk, margin_ticks};
     const std::vector<int> ego(ego3, ego3 + 3);
     e->bg_pending = false;

@@ -1,12 +1,55 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp, _detail), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail (UMGen.inference).  Creation, weights, the compute path, the frame itself and the scoring passes are in
-// engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip, engine_frame.hip and engine_score.hip.
+// umgen_frame(_logp, _detail), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver
+// umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail (UMGen.inference).  Every call narrows its int64 tokens once (narrow_tokens) and
+// hands them on as a TokenView (token_windows.h); the output structs become [4] arrays through MOD4; the driver keeps one conditioning sequence and
+// gathers a frame's window from it, and a frame's control / given tokens are one plan_frame, for the driver and for umgen_frame alike.  Creation,
+// weights, the compute path, the frame itself and the scoring passes are in engine_setup.hip, engine_weights.hip, engine_stacks.hip,
+// engine_decode.hip, engine_frame.hip and engine_score.hip.
 #include "engine_state.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
 #pragma clang fp contract(off)
 
 namespace umgen { thread_local BgRecorder* g_bg_rec = nullptr; }      // bg_queue.h: installed around the recording of a background pass
+
+// ---- helpers of the C ABI below that are templates (or hold one): they need C++ linkage ----
+
+// One group `f` of an output struct of include/umgen.h -- umgen_logp_out, umgen_score_out, umgen_score_detail_out, umgen_gen_detail_out: every group is
+// f_pose | f_map | f_bbox3d | f_image -- as a [4] array in the modality order; a null struct gives null pointers
+#define MOD4(s, f) {(s) ? (s)->f##_pose : nullptr, (s) ? (s)->f##_map : nullptr, (s) ? (s)->f##_bbox3d : nullptr, (s) ? (s)->f##_image : nullptr}
+
+template <typename D>      // umgen_score_detail_out or umgen_gen_detail_out: one layout
+static ScoreDetailIO detail_io(const D* d, int topk, float temperature) {
+    return ScoreDetailIO{topk, temperature, MOD4(d, rank), MOD4(d, mass_above), MOD4(d, entropy), MOD4(d, topk_tok), MOD4(d, topk_logp)};
+}
+
+// What one frame takes from the control arrays (ctrl_*) and the given arrays (given_*), each NULL or [scenes][T_ctl][S_mod], at their frame idx, for `items`
+// branches of N per scene (item i reads scene i / N): the controlled pose cp [items][3], the given map gm and boxes gb [items][S_mod], and with control boxes
+// the mask cs [items][60] of the controlled slots -- their tokens, all but -1 = free, overwrite item i's last conditioning frame at box_last + i * box_stride
+// (UMGen.py:1458-1473).  Empty where the frame takes nothing.  The frame's asynchronous uploads read these until its synchronisation
+struct FramePlan {
+    std::vector<int> cp, gm, gb;
+    std::vector<unsigned char> cs;
+    template <typename V> static const V* ptr(const std::vector<V>& v) { return v.empty() ? nullptr : v.data(); }
+};
+static void plan_frame(int items, int N, int T_ctl, int idx, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, const int64_t* given_map,
+                       const int64_t* given_bbox3d, int* box_last, size_t box_stride, FramePlan& p) {
+    const auto at = [&](const int64_t* a, int i, int len) { return a + ((size_t)(i / N) * T_ctl + idx) * len; };
+    const auto take = [&](const int64_t* a, int len, std::vector<int>& out) {
+        out.resize(a ? (size_t)items * len : 0);
+        for (int i = 0; a && i < items; ++i)
+            for (int k = 0; k < len; ++k) out[(size_t)i * len + k] = (int)at(a, i, len)[k];
+    };
+    take(ctrl_pose, kNPose, p.cp);
+    take(given_map, kNMap, p.gm);
+    take(given_bbox3d, kNBox, p.gb);
+    p.cs.assign(ctrl_bbox3d ? (size_t)items * kSlots : 0, 0);
+    for (int i = 0; ctrl_bbox3d && i < items; ++i)
+        for (int k = 0; k < kNBox; ++k) {
+            const int64_t v = at(ctrl_bbox3d, i, kNBox)[k];
+            if (v != -1) { box_last[i * box_stride + k] = (int)v; p.cs[(size_t)i * kSlots + k / kSlotLen] = 1; }
+        }
+}
 
 // =============================================================================================================
 // C ABI
@@ -62,12 +105,23 @@ static int check_scene_tokens(umgen_engine* e, size_t frames, const int64_t* pos
 }
 
 static bool wants_logp(const umgen_logp_out* lp) { return lp && (lp->logp_pose || lp->logp_map || lp->logp_bbox3d || lp->logp_image); }
+static ScoreDst score_dst(const umgen_score_out* o) { return ScoreDst{MOD4(o, logp), MOD4(o, argmax)}; }
+static bool wants_lists(const ScoreDetailIO& d) {
+    bool lists = false;
+    for (int m = 0; m < 4; ++m) lists = lists || d.topk_tok[m] || d.topk_logp[m];
+    return lists;
+}
+// what umgen_score_detail and the generation calls refuse of a detail request
+static int check_detail_request(umgen_engine* e, const ScoreDetailIO& d) {
+    if (d.topk < 0 || d.topk > UMGEN_SCORE_TOPK_MAX) return e->fail(UMGEN_E_INVALID, "topk=%d out of range [0,%d]", d.topk, UMGEN_SCORE_TOPK_MAX);
+    if (!(d.temperature > 0.f) || !(d.temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0 and finite");
+    if (wants_lists(d) && d.topk == 0) return e->fail(UMGEN_E_INVALID, "top-K outputs requested with topk = 0");
+    return 0;
+}
 
 // umgen_gen_detail_out behind its checks: a frame's host buffers in the device layout (FrameDetail) and their way into the caller's arrays
 struct GenDetail {
-    int topk = 0;
-    int* rank[4] = {}; float *mass_above[4] = {}, *entropy[4] = {};
-    int* topk_tok[4] = {}; float* topk_logp[4] = {};
+    ScoreDetailIO dst{};      // the caller's arrays; topk is 0 when nobody receives a list (lists nobody receives are not formed)
     bool on = false;
     std::vector<int> f_rank, f_tok;
     std::vector<float> f_mass, f_ent, f_tlp;
@@ -75,40 +129,29 @@ struct GenDetail {
 
     // refuses what umgen_score_detail refuses; a NULL or all-NULL struct asks for nothing and is not checked further
     int init(umgen_engine* e, const umgen_gen_detail_out* d, int32_t k, const umgen_sampling* s, size_t B) {
-        if (!d) return 0;
-        int* const r[4] = {d->rank_pose, d->rank_map, d->rank_bbox3d, d->rank_image};
-        float* const ma[4] = {d->mass_above_pose, d->mass_above_map, d->mass_above_bbox3d, d->mass_above_image};
-        float* const en[4] = {d->entropy_pose, d->entropy_map, d->entropy_bbox3d, d->entropy_image};
-        int* const tt[4] = {d->topk_tok_pose, d->topk_tok_map, d->topk_tok_bbox3d, d->topk_tok_image};
-        float* const tl[4] = {d->topk_logp_pose, d->topk_logp_map, d->topk_logp_bbox3d, d->topk_logp_image};
-        bool lists = false;
-        for (int m = 0; m < 4; ++m) {
-            rank[m] = r[m]; mass_above[m] = ma[m]; entropy[m] = en[m]; topk_tok[m] = tt[m]; topk_logp[m] = tl[m];
-            lists = lists || tt[m] || tl[m];
-            on = on || r[m] || ma[m] || en[m] || tt[m] || tl[m];
-        }
+        dst = detail_io(d, k, s->temperature);
+        for (int m = 0; m < 4; ++m) on = on || dst.rank[m] || dst.mass_above[m] || dst.entropy[m] || dst.topk_tok[m] || dst.topk_logp[m];
         if (!on) return 0;
-        if (k < 0 || k > UMGEN_SCORE_TOPK_MAX) return e->fail(UMGEN_E_INVALID, "topk=%d out of range [0,%d]", k, UMGEN_SCORE_TOPK_MAX);
-        if (lists && k == 0) return e->fail(UMGEN_E_INVALID, "top-K outputs requested with topk = 0");
-        if (!(s->temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0 and finite");
-        topk = lists ? k : 0;      // (lists nobody receives are not formed)
+        if (int rc = check_detail_request(e, dst)) return rc;
+        if (!wants_lists(dst)) dst.topk = 0;
         const size_t n = B * kTokPerFrame;
         f_rank.resize(n); f_mass.resize(n); f_ent.resize(n);
-        f_tok.resize(topk ? n * kDetailTopK : 0); f_tlp.resize(topk ? n * kDetailTopK : 0);
-        fd = FrameDetail{topk, f_rank.data(), f_mass.data(), f_ent.data(), f_tok.data(), f_tlp.data()};
+        f_tok.resize(dst.topk ? n * kDetailTopK : 0); f_tlp.resize(dst.topk ? n * kDetailTopK : 0);
+        fd = FrameDetail{dst.topk, f_rank.data(), f_mass.data(), f_ent.data(), f_tok.data(), f_tlp.data()};
         return 0;
     }
     const FrameDetail* frame() const { return on ? &fd : nullptr; }
     // scene b of the frame just generated -> item `item` of the caller's arrays ([items][S_mod], the lists [items][S_mod][topk])
     void deliver(size_t b, size_t item) const {
+        const size_t topk = (size_t)dst.topk;
         for (int m = 0; on && m < 4; ++m) {
-            const size_t src = b * kTokPerFrame + kModOff[m], dst = item * kModLen[m], len = (size_t)kModLen[m];
-            if (rank[m]) memcpy(rank[m] + dst, &f_rank[src], len * sizeof(int));
-            if (mass_above[m]) memcpy(mass_above[m] + dst, &f_mass[src], len * sizeof(float));
-            if (entropy[m]) memcpy(entropy[m] + dst, &f_ent[src], len * sizeof(float));
+            const size_t src = b * kTokPerFrame + kModOff[m], at = item * kModLen[m], len = (size_t)kModLen[m];
+            if (dst.rank[m]) memcpy(dst.rank[m] + at, &f_rank[src], len * sizeof(int));
+            if (dst.mass_above[m]) memcpy(dst.mass_above[m] + at, &f_mass[src], len * sizeof(float));
+            if (dst.entropy[m]) memcpy(dst.entropy[m] + at, &f_ent[src], len * sizeof(float));
             for (size_t i = 0; i < len && topk; ++i) {
-                if (topk_tok[m]) memcpy(topk_tok[m] + (dst + i) * topk, &f_tok[(src + i) * kDetailTopK], (size_t)topk * sizeof(int));
-                if (topk_logp[m]) memcpy(topk_logp[m] + (dst + i) * topk, &f_tlp[(src + i) * kDetailTopK], (size_t)topk * sizeof(float));
+                if (dst.topk_tok[m]) memcpy(dst.topk_tok[m] + (at + i) * topk, &f_tok[(src + i) * kDetailTopK], topk * sizeof(int));
+                if (dst.topk_logp[m]) memcpy(dst.topk_logp[m] + (at + i) * topk, &f_tlp[(src + i) * kDetailTopK], topk * sizeof(float));
             }
         }
     }
@@ -129,53 +172,35 @@ int umgen_frame_detail(umgen_engine* e, int32_t T, const int64_t* pose, const in
     if (ctrl_pose) { if (int rc = check_tokens(e, "control pose", ctrl_pose, 3, e->cfg.pose_vocab, false)) return rc; }
     if (ctrl_bbox3d) { if (int rc = check_tokens(e, "control bbox3d", ctrl_bbox3d, kNBox, e->cfg.bbox3d_vocab, true)) return rc; }
     if (ctrl_bbox3d && !control_test) return e->fail(UMGEN_E_UNSUPPORTED, "init_tokens['bbox3d'] without control_test is not a supported reference path");
-    std::vector<int> p((size_t)T * 3), m((size_t)T * kNMap), bx((size_t)T * kNBox), im((size_t)T * kNImg);
-    for (size_t i = 0; i < p.size(); ++i) p[i] = (int)pose[i];
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (int)map[i];
-    for (size_t i = 0; i < bx.size(); ++i) bx[i] = (int)bbox3d[i];
-    for (size_t i = 0; i < im.size(); ++i) im[i] = (int)image[i];
-    std::vector<int> cp;
-    std::vector<unsigned char> cs;
-    if (ctrl_pose) { cp.resize(3); for (int i = 0; i < 3; ++i) cp[i] = (int)ctrl_pose[i]; }
-    if (ctrl_bbox3d && control_test) {   // UMGen.py:1458-1473
-        cs.assign(kSlots, 0);
-        for (int i = 0; i < kNBox; ++i)
-            if (ctrl_bbox3d[i] != -1) { bx[(size_t)(T - 1) * kNBox + i] = (int)ctrl_bbox3d[i]; cs[i / kSlotLen] = 1; }
-    }
-    std::vector<int> out(kTokPerFrame);
-    FrameIO io{1, T, p.data(), m.data(), bx.data(), im.data(), ctrl_pose ? cp.data() : nullptr, cs.empty() ? nullptr : cs.data(),
-               frame_idx, sampling, trace, out.data()};
     // the frame's GIVEN tokens (umgen_rollout's given_* for one frame: the predefined-token prefix of infer_oar_net, UMGen.py:1184-1201)
-    std::vector<int> gm, gb;
-    if (trace && trace->given_bbox3d && !trace->given_map)
+    const int64_t* const given_map = trace ? trace->given_map : nullptr;
+    const int64_t* const given_bbox3d = trace ? trace->given_bbox3d : nullptr;
+    if (given_bbox3d && !given_map)
         return e->fail(UMGEN_E_UNSUPPORTED, "given bbox3d tokens without a given map: the reference would put them on the map's positions (UMGen.py:1190-1201)");
-    if (trace && trace->given_map) {
+    if (given_map) {
         if (control_test) return e->fail(UMGEN_E_UNSUPPORTED, "given tokens and control_test exclude each other");
-        if (int rc = check_tokens(e, "given map", trace->given_map, kNMap, e->cfg.map_vocab, false)) return rc;
-        gm.resize(kNMap);
-        for (int i = 0; i < kNMap; ++i) gm[i] = (int)trace->given_map[i];
-        io.given_map = gm.data();
-        if (trace->given_bbox3d) {
-            if (int rc = check_tokens(e, "given bbox3d", trace->given_bbox3d, kNBox, e->cfg.bbox3d_vocab, false)) return rc;
-            gb.resize(kNBox);
-            for (int i = 0; i < kNBox; ++i) gb[i] = (int)trace->given_bbox3d[i];
-            io.given_box = gb.data();
-        }
+        if (int rc = check_tokens(e, "given map", given_map, kNMap, e->cfg.map_vocab, false)) return rc;
+        if (given_bbox3d) { if (int rc = check_tokens(e, "given bbox3d", given_bbox3d, kNBox, e->cfg.bbox3d_vocab, false)) return rc; }
     }
+    const int64_t* const in[4] = {pose, map, bbox3d, image};
+    int64_t* const outp[4] = {out_pose, out_map, out_bbox3d, out_image};
+    float* const lp_out[4] = MOD4(lp, logp);
+    TokenSeqs win;
+    narrow_tokens(in, 1, T, win);
+    FramePlan plan;      // the rollout's plan for one scene and one frame of control / given tokens (the boxes overwrite window slot T - 1)
+    plan_frame(1, 1, 1, 0, ctrl_pose, ctrl_bbox3d, given_map, given_bbox3d, win.at(2, 0, T - 1), 0, plan);
+    std::vector<int> out(kTokPerFrame);
     std::vector<float> flp(wants_logp(lp) ? (size_t)kTokPerFrame : 0);
-    if (!flp.empty()) io.out_logp = flp.data();
+    FrameIO io{1, T, win.view(), FramePlan::ptr(plan.cp), FramePlan::ptr(plan.cs), frame_idx, sampling, trace, out.data()};
+    io.given_map = FramePlan::ptr(plan.gm);
+    io.given_box = FramePlan::ptr(plan.gb);
+    io.out_logp = flp.empty() ? nullptr : flp.data();
     io.out_detail = gd.frame();
     if (int rc = run_frame_any(e, io)) return rc;
     gd.deliver(0, 0);
-    for (int i = 0; i < kNPose; ++i) out_pose[i] = out[i];
-    for (int i = 0; i < kNMap; ++i) out_map[i] = out[kOffMap + i];
-    for (int i = 0; i < kNBox; ++i) out_bbox3d[i] = out[kOffBox + i];
-    for (int i = 0; i < kNImg; ++i) out_image[i] = out[kOffImg + i];
-    if (!flp.empty()) {
-        if (lp->logp_pose) memcpy(lp->logp_pose, &flp[0], kNPose * sizeof(float));
-        if (lp->logp_map) memcpy(lp->logp_map, &flp[kOffMap], kNMap * sizeof(float));
-        if (lp->logp_bbox3d) memcpy(lp->logp_bbox3d, &flp[kOffBox], kNBox * sizeof(float));
-        if (lp->logp_image) memcpy(lp->logp_image, &flp[kOffImg], kNImg * sizeof(float));
+    for (int m = 0; m < 4; ++m) {
+        for (int i = 0; i < kModLen[m]; ++i) outp[m][i] = out[kModOff[m] + i];
+        if (lp_out[m] && !flp.empty()) memcpy(lp_out[m], &flp[kModOff[m]], kModLen[m] * sizeof(float));
     }
     return UMGEN_OK;
 }
@@ -221,24 +246,13 @@ static int check_window_length(umgen_engine* e, int32_t T) {
     return T < 1 || T > e->cfg.max_cond_frames ? e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames) : 0;
 }
 
-// int64 tokens [frames][S_mod] of every modality as int32
-static void narrow_tokens(const int64_t* const in[4], size_t frames, std::vector<int> out[4]) {
-    for (int m = 0; m < 4; ++m) {
-        out[m].resize(frames * kModLen[m]);
-        for (size_t i = 0; i < out[m].size(); ++i) out[m][i] = (int)in[m][i];
-    }
-}
-// n frames, [n][S_mod] per modality, as int32 rows [n][2199] pose | map | bbox3d | image
-static std::vector<int> frame_rows(const int64_t* const in[4], size_t n) {
+// n frames, int64 [n][S_mod] per modality, as int32 rows [n][2199] pose | map | bbox3d | image
+static std::vector<int> narrow_frame_rows(const int64_t* const in[4], size_t n) {
+    TokenSeqs t;
+    narrow_tokens(in, n, 1, t);
     std::vector<int> rows(n * kTokPerFrame);
-    for (int m = 0; m < 4; ++m)
-        for (size_t it = 0; it < n; ++it)
-            for (int i = 0; i < kModLen[m]; ++i) rows[it * kTokPerFrame + kModOff[m] + i] = (int)in[m][it * kModLen[m] + i];
+    frame_rows(t.view(), n, [](size_t i) { return i; }, [](size_t) { return 0; }, rows.data());
     return rows;
-}
-static ScoreDst score_dst(const umgen_score_out* o) {
-    if (!o) return ScoreDst{};
-    return ScoreDst{{o->logp_pose, o->logp_map, o->logp_bbox3d, o->logp_image}, {o->argmax_pose, o->argmax_map, o->argmax_bbox3d, o->argmax_image}};
 }
 
 // umgen_score and umgen_score_detail: log p of a given next frame per content position (the reference's loss terms, UMGen.py:539-582) for B scenes, and
@@ -249,24 +263,13 @@ static int score_call(umgen_engine* e, int32_t B, int32_t T, const int64_t* pose
     const int64_t *in[4] = {pose, map, bbox3d, image}, *nx[4] = {next_pose, next_map, next_bbox3d, next_image};
     if (int rc = check_score_engine(e, B)) return rc;
     if (int rc = check_window_length(e, T)) return rc;
-    if (d) {
-        if (topk < 0 || topk > UMGEN_SCORE_TOPK_MAX) return e->fail(UMGEN_E_INVALID, "topk=%d out of range [0,%d]", topk, UMGEN_SCORE_TOPK_MAX);
-        if (!(temperature > 0.f) || !(temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0 and finite");
-        const bool lists = d->topk_tok_pose || d->topk_tok_map || d->topk_tok_bbox3d || d->topk_tok_image || d->topk_logp_pose || d->topk_logp_map ||
-                           d->topk_logp_bbox3d || d->topk_logp_image;
-        if (lists && topk == 0) return e->fail(UMGEN_E_INVALID, "top-K outputs requested with topk = 0");
-    }
+    const ScoreDetailIO dio = detail_io(d, topk, temperature);
+    if (d) { if (int rc = check_detail_request(e, dio)) return rc; }
     if (int rc = check_score_common(e, out || d, in, (size_t)B * T, nx, (size_t)B, "next frame")) return rc;
-    std::vector<int> win[4];
-    narrow_tokens(in, (size_t)B * T, win);
-    const std::vector<int> next = frame_rows(nx, (size_t)B);
-    ScoreIO sc{B, T, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), score_dst(out)};
-    const ScoreDetailIO dio = !d ? ScoreDetailIO{}
-                                 : ScoreDetailIO{topk, temperature, {d->rank_pose, d->rank_map, d->rank_bbox3d, d->rank_image},
-                                                 {d->mass_above_pose, d->mass_above_map, d->mass_above_bbox3d, d->mass_above_image},
-                                                 {d->entropy_pose, d->entropy_map, d->entropy_bbox3d, d->entropy_image},
-                                                 {d->topk_tok_pose, d->topk_tok_map, d->topk_tok_bbox3d, d->topk_tok_image},
-                                                 {d->topk_logp_pose, d->topk_logp_map, d->topk_logp_bbox3d, d->topk_logp_image}};
+    TokenSeqs win;
+    narrow_tokens(in, B, T, win);
+    const std::vector<int> next = narrow_frame_rows(nx, (size_t)B);
+    ScoreIO sc{B, T, win.view(), next.data(), score_dst(out)};
     if (d) sc.detail = &dio;
     return run_score_any(e, sc);
 }
@@ -293,10 +296,10 @@ int umgen_score_candidates(umgen_engine* e, int32_t B, int32_t T, int32_t C, con
     if (int rc = check_window_length(e, T)) return rc;
     if (C < 1) return e->fail(UMGEN_E_INVALID, "C=%d: at least one candidate per scene", C);
     if (int rc = check_score_common(e, out, in, (size_t)B * T, nx, (size_t)B * C, "candidate frames")) return rc;
-    std::vector<int> win[4];
-    narrow_tokens(in, (size_t)B * T, win);
-    const std::vector<int> next = frame_rows(nx, (size_t)B * C);
-    ScoreCandIO sc{B, T, C, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), score_dst(out), 0};
+    TokenSeqs win;
+    narrow_tokens(in, B, T, win);
+    const std::vector<int> next = narrow_frame_rows(nx, (size_t)B * C);
+    ScoreCandIO sc{B, T, C, win.view(), next.data(), score_dst(out), 0};
     if (int rc = run_score_candidates_any(e, sc)) return rc;
     if (shared_slots) *shared_slots = sc.shared_slots;
     return UMGEN_OK;
@@ -315,11 +318,10 @@ int umgen_score_futures(umgen_engine* e, int32_t B, int32_t T, int32_t C, int32_
     if (C < 1) return e->fail(UMGEN_E_INVALID, "C=%d: at least one candidate per scene", C);
     if (K < 1) return e->fail(UMGEN_E_INVALID, "K=%d: at least one future frame per candidate", K);
     if (int rc = check_score_common(e, out, in, (size_t)B * T, nx, (size_t)B * C * K, "future frames")) return rc;
-    std::vector<int> win[4], fut[4];
-    narrow_tokens(in, (size_t)B * T, win);
-    narrow_tokens(nx, (size_t)B * C * K, fut);
-    const ScoreFutIO sc{B, T, C, K, cond_frames, win[0].data(), win[1].data(), win[2].data(), win[3].data(),
-                        {fut[0].data(), fut[1].data(), fut[2].data(), fut[3].data()}, score_dst(out), shared_slots};
+    TokenSeqs win, fut;
+    narrow_tokens(in, B, T, win);
+    narrow_tokens(nx, (size_t)B * C, K, fut);
+    const ScoreFutIO sc{B, T, C, K, cond_frames, win.view(), fut.view(), score_dst(out), shared_slots};
     return run_score_futures_any(e, sc);
 }
 
@@ -333,32 +335,27 @@ int umgen_score_clip(umgen_engine* e, int32_t B, int32_t L, int32_t T_in, int32_
     if (cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
         return e->fail(UMGEN_E_INVALID, "cond_frames=%d out of range [1,%d]", cond_frames, e->cfg.max_cond_frames);
     if (int rc = check_score_common(e, out, in, (size_t)B * L, nullptr, 0, nullptr)) return rc;
-    std::vector<int> clip[4];
-    narrow_tokens(in, (size_t)B * L, clip);
-    ScoreClipIO sc{B, L, T_in, cond_frames, clip[0].data(), clip[1].data(), clip[2].data(), clip[3].data(), score_dst(out), 0};
+    TokenSeqs clip;
+    narrow_tokens(in, B, L, clip);
+    ScoreClipIO sc{B, L, T_in, cond_frames, clip.view(), score_dst(out), 0};
     if (int rc = run_score_clip_any(e, sc)) return rc;
     if (shared_frames) *shared_frames = sc.shared_frames;
     return UMGEN_OK;
 }
 
-// UMGen.inference (UMGen.py:1542-1671).  fan_N >= 2 (umgen_rollout_fan): the B scenes are B / fan_N recorded scenes of fan_N branches each, branch (b, s) at
-// b*fan_N + s with scene b's arrays replicated -- the first frame then runs its history once per scene (run_frame_fan) when its window has at least two slots,
-// the slot caches fit and UMGEN_FAN_SHARE is not 0, and *shared_slots reports the slots that were shared.
-static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose,
-                          const int64_t* map, const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose,
-                          const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
-                          const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
-                          const umgen_logp_out* lp, int32_t fan_N, int32_t* shared_slots, int32_t topk, const umgen_gen_detail_out* detail) {
-    if (!e) return UMGEN_E_INVALID;
+// What every rollout call refuses, in this order, on the caller's arrays: B scenes, whatever the number of branches
+static int check_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* const in[4], int32_t T_ctl,
+                         const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
+                         const umgen_sampling* sampling, int64_t* const out[4], GenDetail& gd, size_t branches, int32_t topk, const umgen_gen_detail_out* detail) {
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
     if (T_in < 1 || new_frames < 0 || cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
         return e->fail(UMGEN_E_INVALID, "T_in=%d new_frames=%d cond_frames=%d (max %d)", T_in, new_frames, cond_frames, e->cfg.max_cond_frames);
     if (int rc = check_sampling(e, sampling)) return rc;
-    GenDetail gd;      // the frame's diagnostics, scattered to [B][new_frames][S_mod] below
-    if (int rc = gd.init(e, detail, topk, sampling, (size_t)B)) return rc;
-    if (!pose || !map || !bbox3d || !image || !out_pose || !out_map || !out_bbox3d || !out_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
-    if (int rc = check_scene_tokens(e, (size_t)B * T_in, pose, map, bbox3d, image)) return rc;
+    if (int rc = gd.init(e, detail, topk, sampling, branches)) return rc;
+    for (int m = 0; m < 4; ++m)
+        if (!in[m] || !out[m]) return e->fail(UMGEN_E_INVALID, "null token buffer");
+    if (int rc = check_scene_tokens(e, (size_t)B * T_in, in[0], in[1], in[2], in[3])) return rc;
     if ((ctrl_pose || ctrl_bbox3d) && T_ctl < 1) return e->fail(UMGEN_E_INVALID, "control tokens given with T_ctl=%d", T_ctl);
     if (ctrl_pose) { if (int rc = check_tokens(e, "control pose", ctrl_pose, (size_t)B * T_ctl * 3, e->cfg.pose_vocab, false)) return rc; }
     if (ctrl_bbox3d) { if (int rc = check_tokens(e, "control bbox3d", ctrl_bbox3d, (size_t)B * T_ctl * kNBox, e->cfg.bbox3d_vocab, true)) return rc; }
@@ -370,109 +367,72 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_
     if (given_bbox3d && (ctrl_bbox3d || control_test)) return e->fail(UMGEN_E_INVALID, "given bbox3d tokens and bbox3d control exclude each other");
     if (given_map) { if (int rc = check_tokens(e, "given map", given_map, (size_t)B * T_ctl * kNMap, e->cfg.map_vocab, false)) return rc; }
     if (given_bbox3d) { if (int rc = check_tokens(e, "given bbox3d", given_bbox3d, (size_t)B * T_ctl * kNBox, e->cfg.bbox3d_vocab, false)) return rc; }
+    return 0;
+}
+
+// UMGen.inference (UMGen.py:1542-1671) for B scenes of N branches each: branch i = (b, s) at b*N + s reads scene i / N of the caller's arrays and has its own
+// seed, so every output is [B][N][..] = [B * N][..].  The driver keeps ONE int32 conditioning sequence per modality, seq [B * N][T_in + new_frames][S_mod]: filled
+// from the input once, every new frame written behind it, and frame f = T_in + idx conditioned on the window cond_window(f, cond_frames) of it.  Control boxes
+// overwrite frame f - 1 of seq in place, so the overwrite stays in later windows ("cond_tokens", UMGen.py:1465-1467); out_* receive the inputs and what was
+// generated, never the overwrite.  Control and given tokens apply while idx < T_ctl (get_mod_tokens returns None past the end, and the pose tokens take
+// control mode with them, UMGen.py:1605-1619).  N >= 2 (umgen_rollout_fan): the first frame runs its history once per scene (run_frame_fan) when its window has
+// at least two slots, the slot caches fit and UMGEN_FAN_SHARE is not 0, and *shared_slots reports the slots that were shared.
+static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                          const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                          const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                          int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
+                          const umgen_gen_detail_out* detail) {
+    if (!e) return UMGEN_E_INVALID;
+    const int64_t* const in[4] = {pose, map, bbox3d, image};
+    int64_t* const out[4] = {out_pose, out_map, out_bbox3d, out_image};
+    float* const lp_out[4] = MOD4(lp, logp);
+    const int BN = B * N, T_out = T_in + new_frames;
+    GenDetail gd;      // a frame's diagnostics and log-likelihoods are scattered to [B * N][new_frames][S_mod] below
+    if (int rc = check_rollout(e, B, T_in, new_frames, cond_frames, in, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d, sampling, out, gd,
+                               (size_t)BN, topk, detail))
+        return rc;
     e->tm = umgen_timings{};
     e->overlap_suspended = false;
-    const int T_out = T_in + new_frames;
-    const int64_t* in[4] = {pose, map, bbox3d, image};
-    int64_t* out[4] = {out_pose, out_map, out_bbox3d, out_image};
-    // history: out_tokens and cond_tokens both start as the first T_in frames (UMGen.py:1581-1595)
-    std::vector<int> hist[4];   // [B][T_cur][S] "cond_tokens" window (control mode mutates its last bbox3d frame in place)
-    for (int m = 0; m < 4; ++m) {
-        hist[m].resize((size_t)B * T_in * kModLen[m]);
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < T_in; ++t)
-                for (int i = 0; i < kModLen[m]; ++i) {
-                    const int64_t v = in[m][((size_t)b * T_in + t) * kModLen[m] + i];
-                    hist[m][((size_t)b * T_in + t) * kModLen[m] + i] = (int)v;
-                    out[m][((size_t)b * T_out + t) * kModLen[m] + i] = v;
-                }
-    }
-    int T_cur = T_in;
-    // Control tokens (UMGen.py:1605-1619, 1438-1473).  With pose tokens the rollout leaves control mode for good once they are used
-    // up (init_tokens = None, control_test = False); bbox3d tokens alone (agents controlled, ego inferred by the ego net) simply stop
-    // applying after their last frame (get_mod_tokens returns None past the end).
-    bool have_ctl = (ctrl_pose != nullptr) && T_ctl > 0;
-    bool have_box = (ctrl_bbox3d != nullptr) && T_ctl > 0;
-    bool have_given = (given_map != nullptr) && T_ctl > 0;   // like every init_tokens entry: None past its last frame (get_mod_tokens), and gone
-                                                              // for good with the pose tokens (UMGen.py:1613-1619)
-    std::vector<int> frame_out((size_t)B * kTokPerFrame);
-    std::vector<float> frame_logp(wants_logp(lp) ? (size_t)B * kTokPerFrame : 0);      // the frame's log-likelihoods, scattered to [B][new_frames][S_mod] below
-    float* const lp_out[4] = {lp ? lp->logp_pose : nullptr, lp ? lp->logp_map : nullptr, lp ? lp->logp_bbox3d : nullptr, lp ? lp->logp_image : nullptr};
+    TokenSeqs seq, win;      // (win: the frame's asynchronous uploads read it until the frame's synchronisation)
+    seq.resize(BN, T_out);
+    for (int m = 0; m < 4; ++m)      // out_tokens and cond_tokens both start as the first T_in frames (UMGen.py:1581-1595)
+        for (int i = 0; i < BN; ++i) {
+            const size_t len = (size_t)T_in * kModLen[m];
+            const int64_t* src = in[m] + (size_t)(i / N) * len;
+            for (size_t k = 0; k < len; ++k) { out[m][(size_t)i * T_out * kModLen[m] + k] = src[k]; seq.at(m, i, 0)[k] = (int)src[k]; }
+        }
+    std::vector<int> frame_out((size_t)BN * kTokPerFrame);
+    std::vector<float> frame_logp(wants_logp(lp) ? (size_t)BN * kTokPerFrame : 0);
     for (int idx = 0; idx < new_frames; ++idx) {
-        if (T_cur > cond_frames) {   // sliding window (UMGen.py:1600-1603)
-            for (int m = 0; m < 4; ++m) {
-                std::vector<int> nw((size_t)B * cond_frames * kModLen[m]);
-                for (int b = 0; b < B; ++b)
-                    memcpy(&nw[(size_t)b * cond_frames * kModLen[m]], &hist[m][((size_t)b * T_cur + (T_cur - cond_frames)) * kModLen[m]],
-                           (size_t)cond_frames * kModLen[m] * sizeof(int));
-                hist[m].swap(nw);
-            }
-            T_cur = cond_frames;
-        }
-        if (have_ctl && idx >= T_ctl) { have_ctl = false; have_box = false; have_given = false; control_test = 0; }   // control tokens exhausted (UMGen.py:1613-1619)
-        if (have_box && idx >= T_ctl) have_box = false;
-        if (have_given && idx >= T_ctl) have_given = false;
-        std::vector<int> gm, gb;
-        if (have_given) {
-            gm.resize((size_t)B * kNMap);
-            for (int b = 0; b < B; ++b)
-                for (int i = 0; i < kNMap; ++i) gm[(size_t)b * kNMap + i] = (int)given_map[((size_t)b * T_ctl + idx) * kNMap + i];
-            if (given_bbox3d) {
-                gb.resize((size_t)B * kNBox);
-                for (int b = 0; b < B; ++b)
-                    for (int i = 0; i < kNBox; ++i) gb[(size_t)b * kNBox + i] = (int)given_bbox3d[((size_t)b * T_ctl + idx) * kNBox + i];
-            }
-        }
-        std::vector<int> cp;
-        std::vector<unsigned char> cs;
-        if (have_ctl) {
-            cp.resize((size_t)B * 3);
-            for (int b = 0; b < B; ++b)
-                for (int a = 0; a < 3; ++a) cp[b * 3 + a] = (int)ctrl_pose[((size_t)b * T_ctl + idx) * 3 + a];
-        }
-        if (have_box) {
-            if (control_test) {
-                cs.assign((size_t)B * kSlots, 0);
-                for (int b = 0; b < B; ++b)
-                    for (int i = 0; i < kNBox; ++i) {
-                        const int64_t v = ctrl_bbox3d[((size_t)b * T_ctl + idx) * kNBox + i];
-                        if (v != -1) { hist[2][((size_t)b * T_cur + (T_cur - 1)) * kNBox + i] = (int)v; cs[(size_t)b * kSlots + i / kSlotLen] = 1; }
-                    }
-            } else {
-                return e->fail(UMGEN_E_UNSUPPORTED, "init_tokens['bbox3d'] without control_test is not a supported reference path");
-            }
-        }
-        FrameIO io{B, T_cur, hist[0].data(), hist[1].data(), hist[2].data(), hist[3].data(), have_ctl ? cp.data() : nullptr,
-                   cs.empty() ? nullptr : cs.data(), idx, sampling, nullptr, frame_out.data()};
+        const int f = T_in + idx;
+        const CondWindow w = cond_window(f, cond_frames);
+        const bool ctl = idx < T_ctl;
+        if (ctl && ctrl_bbox3d && !control_test) return e->fail(UMGEN_E_UNSUPPORTED, "init_tokens['bbox3d'] without control_test is not a supported reference path");
+        FramePlan plan;
+        plan_frame(BN, N, T_ctl, idx, ctl ? ctrl_pose : nullptr, ctl ? ctrl_bbox3d : nullptr, ctl ? given_map : nullptr, ctl && given_map ? given_bbox3d : nullptr,
+                   seq.at(2, 0, f - 1), (size_t)T_out * kNBox, plan);
+        gather_windows(seq.view(), BN, w.start, w.n, win);
+        FrameIO io{BN, w.n, win.view(), FramePlan::ptr(plan.cp), FramePlan::ptr(plan.cs), idx, sampling, nullptr, frame_out.data()};
         io.cond_cap = cond_frames;
         io.next_follows = idx + 1 < new_frames;
-        io.next_has_ctrl_pose = have_ctl && idx + 1 < T_ctl;
-        io.given_map = gm.empty() ? nullptr : gm.data();
-        io.given_box = gb.empty() ? nullptr : gb.data();
+        io.next_has_ctrl_pose = ctrl_pose && idx + 1 < T_ctl;
+        io.given_map = FramePlan::ptr(plan.gm);
+        io.given_box = FramePlan::ptr(plan.gb);
         io.out_logp = frame_logp.empty() ? nullptr : frame_logp.data();
         io.out_detail = gd.frame();
         const char* fse = getenv("UMGEN_FAN_SHARE");      // (read per call: the tests compare both forms in one process)
-        const bool fan = idx == 0 && fan_N >= 2 && T_cur >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
-        if (fan && shared_slots) *shared_slots = T_cur - 1;
-        if (int rc = fan ? run_frame_fan_any(e, io, fan_N) : run_frame_any(e, io)) return rc;
-        // append (UMGen.py:1636-1666): control pose tokens are copied verbatim; everything else is what was generated
-        for (int m = 0; m < 4; ++m) {
-            std::vector<int> nw((size_t)B * (T_cur + 1) * kModLen[m]);
-            for (int b = 0; b < B; ++b) {
-                memcpy(&nw[(size_t)b * (T_cur + 1) * kModLen[m]], &hist[m][(size_t)b * T_cur * kModLen[m]], (size_t)T_cur * kModLen[m] * sizeof(int));
-                for (int i = 0; i < kModLen[m]; ++i) {
-                    const int v = frame_out[(size_t)b * kTokPerFrame + kModOff[m] + i];
-                    nw[((size_t)b * (T_cur + 1) + T_cur) * kModLen[m] + i] = v;
-                    out[m][((size_t)b * T_out + T_in + idx) * kModLen[m] + i] = v;
-                }
+        const bool fan = idx == 0 && N >= 2 && w.n >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
+        if (fan && shared_slots) *shared_slots = w.n - 1;
+        if (int rc = fan ? run_frame_fan_any(e, io, N) : run_frame_any(e, io)) return rc;
+        // the new frame (UMGen.py:1636-1666): control pose tokens are copied verbatim; everything else is what was generated
+        for (int m = 0; m < 4; ++m)
+            for (int i = 0; i < BN; ++i) {
+                const size_t src = (size_t)i * kTokPerFrame + kModOff[m], len = (size_t)kModLen[m];
+                memcpy(seq.at(m, i, f), &frame_out[src], len * sizeof(int));
+                for (size_t k = 0; k < len; ++k) out[m][((size_t)i * T_out + f) * len + k] = frame_out[src + k];
+                if (lp_out[m] && !frame_logp.empty()) memcpy(lp_out[m] + ((size_t)i * new_frames + idx) * len, &frame_logp[src], len * sizeof(float));
             }
-            hist[m].swap(nw);
-            if (lp_out[m] && !frame_logp.empty())
-                for (int b = 0; b < B; ++b)
-                    memcpy(lp_out[m] + ((size_t)b * new_frames + idx) * kModLen[m], &frame_logp[(size_t)b * kTokPerFrame + kModOff[m]], (size_t)kModLen[m] * sizeof(float));
-        }
-        for (int b = 0; b < B; ++b) gd.deliver((size_t)b, (size_t)b * new_frames + idx);
-        T_cur += 1;
+        for (int i = 0; i < BN; ++i) gd.deliver((size_t)i, (size_t)i * new_frames + idx);
     }
     return UMGEN_OK;
 }
@@ -482,12 +442,12 @@ int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_fra
                        const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
                        const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
                        const umgen_logp_out* lp) {
-    return rollout_driver(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr, 0, nullptr);
+    return rollout_driver(e, B, 1, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, nullptr, 0, nullptr);
 }
 
-// umgen_rollout_fan: N sampled futures per scene.  The branches are the scenes of an ordinary rollout of B * N scenes on replicated inputs -- the driver above,
-// whose first frame shares the history between a scene's branches (engine_frame.hip run_frame_fan); outputs [B][N][..] are that rollout's [B * N][..].
+// umgen_rollout_fan: N sampled futures per scene, the driver above with N branches per scene, whose first frame shares the history between a scene's branches
+// (engine_frame.hip run_frame_fan).  Every argument is checked once, on the caller's arrays: an error that names a flat index names it there.
 // umgen_rollout_detail: the same with the diagnostics of every generated token ([B][N][..] likewise)
 int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
                          const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
@@ -500,30 +460,8 @@ int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, in
     if (B < 1) return e->fail(UMGEN_E_INVALID, "B=%d: at least one scene", B);
     if (N < 1) return e->fail(UMGEN_E_INVALID, "N=%d: at least one sample per scene", N);
     if ((int64_t)B * N > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B*N=%lld (B=%d, N=%d) exceeds max_batch=%d", (long long)B * N, B, N, e->cfg.max_batch);
-    if (N == 1)
-        return rollout_driver(e, B, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                              sampling, out_pose, out_map, out_bbox3d, out_image, lp, 0, nullptr, topk, detail);
-    // what the replication below reads; the driver checks everything again, and everything else, on the replicated arrays
-    if (T_in < 1 || new_frames < 0 || cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
-        return e->fail(UMGEN_E_INVALID, "T_in=%d new_frames=%d cond_frames=%d (max %d)", T_in, new_frames, cond_frames, e->cfg.max_cond_frames);
-    if (!pose || !map || !bbox3d || !image || !out_pose || !out_map || !out_bbox3d || !out_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
-    if ((ctrl_pose || ctrl_bbox3d) && T_ctl < 1) return e->fail(UMGEN_E_INVALID, "control tokens given with T_ctl=%d", T_ctl);
-    if ((given_map || given_bbox3d) && T_ctl < 1) return e->fail(UMGEN_E_INVALID, "given tokens with T_ctl=%d", T_ctl);
-    auto replicate = [&](const int64_t* a, size_t per_scene) {      // [B][per_scene] -> [B][N][per_scene]
-        std::vector<int64_t> r;
-        if (!a) return r;
-        r.resize((size_t)B * N * per_scene);
-        for (int b = 0; b < B; ++b)
-            for (int s = 0; s < N; ++s) memcpy(&r[((size_t)b * N + s) * per_scene], a + (size_t)b * per_scene, per_scene * sizeof(int64_t));
-        return r;
-    };
-    const std::vector<int64_t> rp = replicate(pose, (size_t)T_in * kNPose), rm = replicate(map, (size_t)T_in * kNMap), rb = replicate(bbox3d, (size_t)T_in * kNBox),
-                               ri = replicate(image, (size_t)T_in * kNImg), cp = replicate(ctrl_pose, (size_t)T_ctl * kNPose),
-                               cb = replicate(ctrl_bbox3d, (size_t)T_ctl * kNBox), gm = replicate(given_map, (size_t)T_ctl * kNMap),
-                               gb = replicate(given_bbox3d, (size_t)T_ctl * kNBox);
-    return rollout_driver(e, B * N, T_in, new_frames, cond_frames, rp.data(), rm.data(), rb.data(), ri.data(), T_ctl, ctrl_pose ? cp.data() : nullptr,
-                          ctrl_bbox3d ? cb.data() : nullptr, control_test, given_map ? gm.data() : nullptr, given_bbox3d ? gb.data() : nullptr, sampling, out_pose,
-                          out_map, out_bbox3d, out_image, lp, N, shared_slots, topk, detail);
+    return rollout_driver(e, B, N, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail);
 }
 
 int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,

@@ -41,6 +41,9 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx);
 int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx);
 int run_stacks(umgen_engine* e, const FrameIO& io, FrameCtx& ctx);
 
+// `rows` frames of v -- rows * S_mod tokens from the start of every modality -- into d_pose (with_pose; callers whose pose goes through the shift
+// leave it out), d_map, d_box and d_img.  The copies are asynchronous: what v points at outlives the call's next synchronisation of st
+int upload_tokens(umgen_engine* e, hipStream_t st, const TokenView& v, size_t rows, bool with_pose = true);
 // decode_pose_shift of B windows [B][Tn][3] and the new frames' poses ego [B][3] into d_pose_shift and pose_diff; the copies are asynchronous, so
 // pshift and pdiff outlive the call's next synchronisation of st
 int upload_pose_shift(umgen_engine* e, hipStream_t st, const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);

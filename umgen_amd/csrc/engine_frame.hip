@@ -1,7 +1,8 @@
 // One frame, UMGen._inference: run_frame<T> as a sequence of stages -- background pass, uploads, ego net and pose shift, decode state, the
 // stacks, first input and prefix pass, the lane loop or the single-stream step loop, drain, download, checks, bookkeeping -- run_frame_fan<T>,
 // the first frame of umgen_rollout_fan with the history once per scene, and run_frame_any / run_frame_fan_any, which pick the precision and
-// clean up behind a failed call.  The scoring passes (engine_score.hip) are built from the stages engine_frame.h declares.
+// clean up behind a failed call.  The scoring passes (engine_score.hip) are built from the stages engine_frame.h declares.  A frame's host tokens
+// are FrameIO::win, a TokenView (token_windows.h); every upload of the four token arrays is upload_tokens.
 #include "engine_frame.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -14,13 +15,12 @@ bool prefix_matches(const umgen_engine* e, const FrameIO& io) {
     const umgen_engine::Prefix& px = e->px;
     if (!px.valid || io.trace || io.B != px.B || io.T != px.Tfull || px.P != io.T - 1 || px.P < 1) return false;
     if (!io.ctrl_pose && !px.has_ego) return false;
-    const int* cur[4] = {io.pose, io.map, io.box, io.img};
-    const std::vector<int>* old[4] = {&px.pose, &px.map, &px.box, &px.img};
+    const TokenView old = px.win.view();
     for (int m = 0; m < 4; ++m)
         for (int b = 0; b < io.B; ++b)
-            if (memcmp(cur[m] + (size_t)b * io.T * kModLen[m], old[m]->data() + (size_t)b * px.P * kModLen[m], (size_t)px.P * kModLen[m] * sizeof(int))) return false;
+            if (memcmp(io.win.at(m, b, 0), old.at(m, b, 0), (size_t)px.P * kModLen[m] * sizeof(int))) return false;
     for (int b = 0; b < io.B; ++b)   // the last frame's pose tokens were already baked into shifted slot P-1
-        if (memcmp(io.pose + ((size_t)b * io.T + px.P) * kNPose, &px.pose_next[(size_t)b * 3], 3 * sizeof(int))) return false;
+        if (memcmp(io.win.at(0, b, px.P), &px.pose_next[(size_t)b * 3], 3 * sizeof(int))) return false;
     return true;
 }
 
@@ -35,10 +35,7 @@ bool grows_into_cache(umgen_engine* e, const FrameIO& io) {
 void remember_window(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego) {
     umgen_engine::Prefix& px = e->px;
     px.B = io.B; px.P = io.T; px.Tfull = io.T + 1; px.has_ego = !io.ctrl_pose;
-    px.pose.assign(io.pose, io.pose + (size_t)io.B * io.T * kNPose);
-    px.map.assign(io.map, io.map + (size_t)io.B * io.T * kNMap);
-    px.box.assign(io.box, io.box + (size_t)io.B * io.T * kNBox);
-    px.img.assign(io.img, io.img + (size_t)io.B * io.T * kNImg);
+    gather_windows(io.win, io.B, 0, io.T, px.win);
     px.pose_next.assign(ego.begin(), ego.end());   // slot T-1 was evaluated with the new frame's pose (the shift of UMGen.py:1445-1452)
     px.valid = true;
 }
@@ -60,6 +57,12 @@ int finish_call(umgen_engine* e, const char* what) {
     const hipError_t le = e->launch_status != hipSuccess ? e->launch_status : hipGetLastError();
     e->launch_status = hipSuccess;
     if (le != hipSuccess) return e->fail(UMGEN_E_HIP, "a kernel launch of this %s was refused: %s", what, hipGetErrorString(le));
+    return 0;
+}
+
+int upload_tokens(umgen_engine* e, hipStream_t st, const TokenView& v, size_t rows, bool with_pose) {
+    int* const dev[4] = {e->d_pose, e->d_map, e->d_box, e->d_img};
+    for (int m = with_pose ? 0 : 1; m < 4; ++m) HIPCHK(e, hipMemcpyAsync(dev[m], v.mod[m], rows * kModLen[m] * 4, hipMemcpyHostToDevice, st));
     return 0;
 }
 
@@ -135,10 +138,7 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     const int B = io.B, Tn = io.T;
     const umgen_trace* tr = io.trace;
     hipStream_t const st = ctx.st;
-    HIPCHK(e, hipMemcpyAsync(e->d_pose, io.pose, (size_t)B * Tn * 3 * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(e->d_map, io.map, (size_t)B * Tn * kNMap * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(e->d_box, io.box, (size_t)B * Tn * kNBox * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(e->d_img, io.img, (size_t)B * Tn * kNImg * 4, hipMemcpyHostToDevice, st));
+    if (int rc = upload_tokens(e, st, io.win, (size_t)B * Tn)) return rc;
     ctx.seeds.resize(B);
     for (int b = 0; b < B; ++b) ctx.seeds[b] = io.smp->seeds ? io.smp->seeds[b] : 0ull;
     HIPCHK(e, hipMemcpyAsync(e->d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
@@ -188,7 +188,7 @@ int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipStreamSynchronize(st));
     }
     HIPCHK(e, hipEventRecord(e->ev[1], st));
-    return upload_pose_shift(e, st, io.pose, ctx.ego.data(), B, Tn, ctx.pshift, ctx.pdiff);
+    return upload_pose_shift(e, st, io.win.pose(), ctx.ego.data(), B, Tn, ctx.pshift, ctx.pdiff);
 }
 
 int run_stacks(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
@@ -289,7 +289,7 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     ctx.prevbox.resize((size_t)B * kNBox);
     for (int b = 0; b < B; ++b) {
         for (int a = 0; a < 3; ++a) ctx.tok0[(size_t)b * kTokPerFrame + a] = ctx.ego[b * 3 + a];
-        memcpy(&ctx.prevbox[(size_t)b * kNBox], io.box + ((size_t)b * Tn + (Tn - 1)) * kNBox, kNBox * sizeof(int));
+        memcpy(&ctx.prevbox[(size_t)b * kNBox], io.win.at(2, b, Tn - 1), kNBox * sizeof(int));
         if (io.given_map) memcpy(&ctx.tok0[(size_t)b * kTokPerFrame + kOffMap], io.given_map + (size_t)b * kNMap, kNMap * sizeof(int));
         if (io.given_box) memcpy(&ctx.tok0[(size_t)b * kTokPerFrame + kOffBox], io.given_box + (size_t)b * kNBox, kNBox * sizeof(int));
     }
@@ -714,16 +714,11 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     if (int rc = upload_frame_inputs(e, io, ctx)) return rc;      // seeds, counters and logp of the B * N branches; the token arrays follow below
     hipStream_t const st = ctx.st;
     // the scenes' windows [B][T][S_mod] (branch (b, 0) holds scene b's) for the passes that run once per scene
-    const int* src[4] = {io.pose, io.map, io.box, io.img};
-    int* dev[4] = {e->d_pose, e->d_map, e->d_box, e->d_img};
-    std::vector<int> win[4], item_scene(BN), hshift;
+    TokenSeqs win;
+    std::vector<int> item_scene(BN), hshift;
     std::vector<float> hdiff;
-    for (int m = 0; m < 4; ++m) {
-        const size_t len = (size_t)Tn * kModLen[m];      // of one window
-        win[m].resize(B * len);
-        for (int b = 0; b < B; ++b) memcpy(&win[m][b * len], src[m] + (size_t)b * N * len, len * sizeof(int));
-        HIPCHK(e, hipMemcpyAsync(dev[m], win[m].data(), win[m].size() * 4, hipMemcpyHostToDevice, st));
-    }
+    gather_windows(io.win, B, [N](size_t b) { return b * N; }, [](size_t) { return 0; }, Tn, win);
+    if (int rc = upload_tokens(e, st, win.view(), (size_t)B * Tn)) return rc;
     ctx.fg_write = grows_into_cache(e, io);      // (io.trace is null: a fan frame is a rollout's)
     ctx.t0 = 0; ctx.Tc = Tn; ctx.cmode = ctx.fg_write ? CACHE_WINDOW_KEEP : CACHE_NONE;
     // Step 1: the ego net once per scene, a pose per branch
@@ -741,10 +736,10 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     if (int rc = init_decode_state<T>(e, io, ctx)) return rc;
     // Step 2a: slots [0, T - 1) of the three stacks once per scene, their temporal k | v rows into the scenes' blocks of the slot caches (slot T - 1 of the
     // shifted pose is not read)
-    if (int rc = history_slots_once(e, st, win[0].data(), B, Tn, hshift, hdiff)) return rc;
+    if (int rc = history_slots_once(e, st, win.view().pose(), B, Tn, hshift, hdiff)) return rc;
     // Step 2b: slot T - 1 of every branch -- its own pose in the shift, its own window rows -- against its scene's caches, and the conditioning rows
-    if (int rc = upload_pose_shift(e, st, io.pose, ctx.ego.data(), BN, Tn, ctx.pshift, ctx.pdiff)) return rc;
-    for (int m = 0; m < 4; ++m) HIPCHK(e, hipMemcpyAsync(dev[m], src[m], (size_t)BN * Tn * kModLen[m] * 4, hipMemcpyHostToDevice, st));
+    if (int rc = upload_pose_shift(e, st, io.win.pose(), ctx.ego.data(), BN, Tn, ctx.pshift, ctx.pdiff)) return rc;
+    if (int rc = upload_tokens(e, st, io.win, (size_t)BN * Tn)) return rc;
     for (int i = 0; i < BN; ++i) item_scene[i] = i / N;
     HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)BN * 4, hipMemcpyHostToDevice, st));
     e->fan_scenes = B;

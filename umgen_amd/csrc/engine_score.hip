@@ -1,7 +1,9 @@
 // Scoring given frames, from run_frame's own stages (engine_frame.h): run_score<T>, the pass of umgen_score and umgen_score_detail, run_score_candidates<T>,
 // which scores several next frames per scene on one pass over the history, run_score_futures<T>, which does so for futures of several frames (item tails
 // behind the shared slots), run_score_clip<T>, which scores every frame of a recorded clip, the growing windows off one pass, and run_score_any /
-// run_score_candidates_any / run_score_futures_any / run_score_clip_any, which pick the precision and clean up behind a failed call.
+// run_score_candidates_any / run_score_futures_any / run_score_clip_any, which pick the precision and clean up behind a failed call.  Every pass cuts
+// its items' windows out of the call's TokenView with gather_windows / copy_frames and packs the scored frames with frame_rows (token_windows.h) into
+// staging that lives until the chunk's synchronisation, and uploads it with upload_tokens (engine_frame.h).
 #include "engine_frame.h"
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
@@ -111,7 +113,7 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
     const size_t rows = (size_t)B * kTokPerFrame;
     const ScoreDetailIO* dt = sc.detail;
     if (dt) { if (int rc = ensure_score_detail(e)) return rc; }
-    const FrameIO io{B, sc.T, sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
+    const FrameIO io{B, sc.T, sc.win, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
     e->px.valid = false;                 // (before the stage below asks whether an earlier pass covers this window: the score is always a whole-window pass)
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
@@ -166,32 +168,25 @@ template <typename T>
 int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
     const int B = sc.B, Tn = sc.T, C = sc.C, P = sc.T - 1, Bm = e->cfg.max_batch;
     const long N = (long)B * C;
-    const int* win[4] = {sc.pose, sc.map, sc.box, sc.img};
     const char* she = getenv("UMGEN_SCORE_SHARE");      // (read per call: the tests compare both forms in one process)
     const bool share = Tn >= 2 && !(she && she[0] == '0') && ensure_tcache(e);
     sc.shared_slots = share ? P : 0;
     // host staging of a chunk (the asynchronous copies read it until the chunk's synchronisation)
-    std::vector<int> rep[4], cand_pose, item_scene, pshift, am;
+    TokenSeqs rep;                                       // the windows of a chunk's items [i0, i0 + n): [n][T][S_mod], item i scene i / C
+    std::vector<int> cand_pose, item_scene, pshift, am;
     std::vector<float> pdiff, lp;
-    auto replicate = [&](long i0, int n) {               // the windows of items [i0, i0 + n): [n][T][S_mod]
-        for (int m = 0; m < 4; ++m) {
-            const size_t len = (size_t)Tn * kModLen[m];
-            rep[m].resize(n * len);
-            for (int i = 0; i < n; ++i) memcpy(&rep[m][i * len], win[m] + (size_t)((i0 + i) / C) * len, len * sizeof(int));
-        }
-    };
     if (!share) {
         for (long i0 = 0; i0 < N; i0 += Bm) {
             const int n = (int)std::min<long>(Bm, N - i0);
-            replicate(i0, n);
-            const ScoreIO one{n, Tn, rep[0].data(), rep[1].data(), rep[2].data(), rep[3].data(), sc.next + (size_t)i0 * kTokPerFrame, sc.out, i0};
+            gather_fan_windows(sc.win, i0, n, C, 0, Tn, rep);
+            const ScoreIO one{n, Tn, rep.view(), sc.next + (size_t)i0 * kTokPerFrame, sc.out, i0};
             if (int rc = run_score<T>(e, one)) return rc;
         }
         return 0;
     }
     FrameCtx ctx = begin_call(e, kNoSampling);
     RestoreStream restore{e, ctx.fg};
-    const FrameIO io{B, Tn, sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
+    const FrameIO io{B, Tn, sc.win, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
     e->px.valid = false;                 // the passes below overwrite the slot caches and the stacks' workspaces
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
@@ -202,23 +197,21 @@ int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
     run_ego_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, ctx.sp, 0, false, nullptr, CACHE_NONE);
     clock.stage(&e->tm.ego_ms);
     // ... and slots [0, T - 1) of the three stacks
-    if (int rc = history_slots_once(e, st, sc.pose, B, Tn, ctx.pshift, ctx.pdiff)) return rc;
+    if (int rc = history_slots_once(e, st, sc.win.pose(), B, Tn, ctx.pshift, ctx.pdiff)) return rc;
     clock.stage(&e->tm.tar_ms);
     e->fan_scenes = B;
     for (long i0 = 0; i0 < N; i0 += Bm) {
         const int n = (int)std::min<long>(Bm, N - i0);
         const int* next = sc.next + (size_t)i0 * kTokPerFrame;
-        replicate(i0, n);
+        gather_fan_windows(sc.win, i0, n, C, 0, Tn, rep);
         cand_pose.resize((size_t)n * 3);
         item_scene.resize(n);
         for (int i = 0; i < n; ++i) {
             item_scene[i] = (int)((i0 + i) / C);
             for (int a = 0; a < 3; ++a) cand_pose[(size_t)i * 3 + a] = next[(size_t)i * kTokPerFrame + a];
         }
-        if (int rc = upload_pose_shift(e, st, rep[0].data(), cand_pose.data(), n, Tn, pshift, pdiff)) return rc;      // slot T - 1 of item (b, c): the candidate's pose
-        HIPCHK(e, hipMemcpyAsync(e->d_map, rep[1].data(), rep[1].size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(e, hipMemcpyAsync(e->d_box, rep[2].data(), rep[2].size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(e, hipMemcpyAsync(e->d_img, rep[3].data(), rep[3].size() * 4, hipMemcpyHostToDevice, st));
+        if (int rc = upload_pose_shift(e, st, rep.view().pose(), cand_pose.data(), n, Tn, pshift, pdiff)) return rc;      // slot T - 1 of item (b, c): the candidate's pose
+        if (int rc = upload_tokens(e, st, rep.view(), (size_t)n * Tn, false)) return rc;
         HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
         HIPCHK(e, hipMemcpyAsync(e->d_tokens, next, (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
         // a candidate's pose: a lookup in its scene's rows (the bits depend on the row and the target only)
@@ -246,8 +239,9 @@ int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
 // them history frames; slots [0, P) of the map / box / TAR stacks are the scene's (the shift hands slot h - 1 the pose of future frame 0)
 struct FutureFrame { int start, n, h, P; };
 FutureFrame future_frame(const ScoreFutIO& sc, int k) {
-    const int f = sc.T + k, n = std::min(f, sc.cond), h = std::max(0, n - k);
-    return FutureFrame{f - n, n, h, h - 1};
+    const CondWindow w = cond_window(sc.T + k, sc.cond);
+    const int h = std::max(0, w.n - k);
+    return FutureFrame{w.start, w.n, h, h - 1};
 }
 // can frame k take the shared path: a shared slot, and tails the kernel holds in the three stacks (k + 1 slots behind P) and in the ego stack (k behind h)
 bool future_frame_shares(const umgen_engine* e, const ScoreFutIO& sc, int k) {
@@ -257,23 +251,17 @@ bool future_frame_shares(const umgen_engine* e, const ScoreFutIO& sc, int k) {
 
 // The windows and targets of items [i0, i0 + n) -- item i is candidate (i / C, i % C) -- at future frame k: win[m] [n][w.n][S_mod], next [n][2199], rows[i] the
 // row of sc.out that takes item i's results
-struct FutureChunk { std::vector<int> win[4], next; std::vector<long> rows; };
+struct FutureChunk { TokenSeqs win; std::vector<int> next; std::vector<long> rows; };
 void future_chunk(const ScoreFutIO& sc, int k, const FutureFrame& w, long i0, int n, FutureChunk& ch) {
-    const int* hist[4] = {sc.pose, sc.map, sc.box, sc.img};
+    const int C = sc.C, k0 = w.h ? 0 : w.start - sc.T;      // k0: first future frame inside the window
+    const auto scene = [i0, C](size_t i) { return (i0 + i) / C; };
+    const auto item = [i0](size_t i) { return i0 + i; };
+    ch.win.resize(n, w.n);
+    copy_frames(sc.win, n, scene, [&w](size_t) { return w.start; }, w.h, ch.win, 0);
+    copy_frames(sc.fut, n, item, [k0](size_t) { return k0; }, w.n - w.h, ch.win, w.h);
     ch.next.resize((size_t)n * kTokPerFrame);
+    frame_rows(sc.fut, n, item, [k](size_t) { return k; }, ch.next.data());
     ch.rows.resize(n);
-    for (int m = 0; m < 4; ++m) {
-        const size_t len = kModLen[m];
-        ch.win[m].resize((size_t)n * w.n * len);
-        for (int i = 0; i < n; ++i) {
-            const long it = i0 + i, b = it / sc.C;
-            int* dst = &ch.win[m][(size_t)i * w.n * len];
-            if (w.h) memcpy(dst, hist[m] + ((size_t)b * sc.T + w.start) * len, (size_t)w.h * len * sizeof(int));
-            const int k0 = w.h ? 0 : w.start - sc.T;      // first future frame inside the window
-            memcpy(dst + (size_t)w.h * len, sc.fut[m] + ((size_t)it * sc.K + k0) * len, (size_t)(w.n - w.h) * len * sizeof(int));
-            memcpy(&ch.next[(size_t)i * kTokPerFrame + kModOff[m]], sc.fut[m] + ((size_t)it * sc.K + k) * len, len * sizeof(int));
-        }
-    }
     for (int i = 0; i < n; ++i) ch.rows[i] = (i0 + i) * sc.K + k;
 }
 
@@ -288,7 +276,7 @@ int score_futures_replicated(umgen_engine* e, const ScoreFutIO& sc, int k0, int 
         for (long i0 = 0; i0 < N; i0 += Bm) {
             const int n = (int)std::min<long>(Bm, N - i0);
             future_chunk(sc, k, w, i0, n, ch);
-            const ScoreIO one{n, w.n, ch.win[0].data(), ch.win[1].data(), ch.win[2].data(), ch.win[3].data(), ch.next.data(), sc.out, 0, ch.rows.data()};
+            const ScoreIO one{n, w.n, ch.win.view(), ch.next.data(), sc.out, 0, ch.rows.data()};
             if (int rc = run_score<T>(e, one)) return rc;
         }
     }
@@ -304,10 +292,9 @@ template <typename T>
 int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
     const int B = sc.B, C = sc.C, Bm = e->cfg.max_batch, pv = e->cfg.pose_vocab;
     const long N = (long)B * C;
-    const int* hist_src[4] = {sc.pose, sc.map, sc.box, sc.img};
     FrameCtx ctx = begin_call(e, kNoSampling);
     RestoreStream restore{e, ctx.fg};
-    const FrameIO io{B, std::min(sc.T, sc.cond), sc.pose, sc.map, sc.box, sc.img, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
+    const FrameIO io{B, std::min(sc.T, sc.cond), sc.win, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
     e->px.valid = false;                 // the passes below overwrite the slot caches and the stacks' workspaces
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
@@ -317,7 +304,8 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
     StageClock clock{e, st};
     e->fan_scenes = B;
     // host staging (the asynchronous copies read it until the next synchronisation: a chunk ends with one, and nothing is rewritten before it)
-    std::vector<int> hist[4], cand_pose, item_scene, pshift, am;
+    TokenSeqs hist;                      // the scenes' history frames inside the window, [B][h][S_mod]
+    std::vector<int> cand_pose, item_scene, pshift, am;
     std::vector<float> pdiff, lp;
     std::vector<long> frame_of;
     FutureChunk ch;
@@ -328,15 +316,8 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
         if (k == 0 || w.start != prev_start) {
             prev_start = w.start;
             ++e->fut_history_passes;
-            for (int m = 0; m < 4; ++m) {      // the scenes' history frames inside the window, [B][h][S_mod]
-                const size_t len = kModLen[m];
-                hist[m].resize((size_t)B * w.h * len);
-                for (int b = 0; b < B; ++b) memcpy(&hist[m][(size_t)b * w.h * len], hist_src[m] + ((size_t)b * sc.T + w.start) * len, (size_t)w.h * len * sizeof(int));
-            }
-            HIPCHK(e, hipMemcpyAsync(e->d_pose, hist[0].data(), hist[0].size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(e, hipMemcpyAsync(e->d_map, hist[1].data(), hist[1].size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(e, hipMemcpyAsync(e->d_box, hist[2].data(), hist[2].size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(e, hipMemcpyAsync(e->d_img, hist[3].data(), hist[3].size() * 4, hipMemcpyHostToDevice, st));
+            gather_windows(sc.win, B, w.start, w.h, hist);
+            if (int rc = upload_tokens(e, st, hist.view(), (size_t)B * w.h)) return rc;
             clock.stage(nullptr);            // the uploads
             const WindowTokens we{e->d_pose, e->d_map, e->d_box, e->d_img, B, w.h, w.h, 0};
             // k == 0: the whole window is history -- the ego net once per scene, its three head_ego rows in e->logits [3 B][pose_vocab], and the ego stack's
@@ -344,7 +325,7 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
             if (k == 0) run_ego_any(e, we, ctx.sp, 0, false, nullptr, Ks > 1 ? CACHE_WINDOW_KEEP : CACHE_NONE);
             else run_stack_any(e, STACK_EGO, we, CACHE_FILL_PREFIX);
             clock.stage(&e->tm.ego_ms);
-            if (int rc = history_slots_once(e, st, hist[0].data(), B, w.h, ctx.pshift, ctx.pdiff)) return rc;
+            if (int rc = history_slots_once(e, st, hist.view().pose(), B, w.h, ctx.pshift, ctx.pdiff)) return rc;
             clock.stage(&e->tm.tar_ms);
         }
         for (long i0 = 0; i0 < N; i0 += Bm) {
@@ -356,9 +337,7 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
                 item_scene[i] = (int)((i0 + i) / C);
                 for (int a = 0; a < 3; ++a) cand_pose[(size_t)i * 3 + a] = ch.next[(size_t)i * kTokPerFrame + a];
             }
-            HIPCHK(e, hipMemcpyAsync(e->d_map, ch.win[1].data(), ch.win[1].size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(e, hipMemcpyAsync(e->d_box, ch.win[2].data(), ch.win[2].size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(e, hipMemcpyAsync(e->d_img, ch.win[3].data(), ch.win[3].size() * 4, hipMemcpyHostToDevice, st));
+            if (int rc = upload_tokens(e, st, ch.win.view(), (size_t)n * w.n, false)) return rc;
             HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
             HIPCHK(e, hipMemcpyAsync(e->d_tokens, ch.next.data(), (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
             if (k == 0) {
@@ -368,7 +347,7 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
                                       e->score_logp + (long)i * 3, e->score_arg + (long)i * 3, nullptr, nullptr);
             } else {
                 // the ego net reads the unshifted window: the item's k future slots behind the scene's h, the decoder and head_ego on its last slot
-                HIPCHK(e, hipMemcpyAsync(e->d_pose, ch.win[0].data(), ch.win[0].size() * 4, hipMemcpyHostToDevice, st));
+                HIPCHK(e, hipMemcpyAsync(e->d_pose, ch.win.view().pose(), ch.win.mod[0].size() * 4, hipMemcpyHostToDevice, st));
                 run_stack_any(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, n, k, w.n, w.h}, CACHE_SHARED_ITEMS_TAIL);
                 frame_of.resize(n);
                 for (int i = 0; i < n; ++i) frame_of[i] = (long)i * k + (k - 1);
@@ -376,7 +355,7 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
                 launch_logits_nll(st, e->logits, pv, pv, 3 * n, e->d_tokens, kNPose, kTokPerFrame, e->score_logp, e->score_arg, nullptr, nullptr);
                 clock.stage(&e->tm.ego_ms);
             }
-            if (int rc = upload_pose_shift(e, st, ch.win[0].data(), cand_pose.data(), n, w.n, pshift, pdiff)) return rc;      // slot n - 1: the pose of future frame k
+            if (int rc = upload_pose_shift(e, st, ch.win.view().pose(), cand_pose.data(), n, w.n, pshift, pdiff)) return rc;      // slot n - 1: the pose of future frame k
             stacks_with_cond_rows(e, st, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, Wt, w.n, w.P}, CACHE_SHARED_ITEMS_TAIL);
             clock.stage(&e->tm.tar_ms);
             if (int rc = run_prefix_prefill_any(e, n, kSeq)) return rc;
@@ -434,11 +413,6 @@ bool ensure_score_clip(umgen_engine* e) {
     return true;
 }
 
-// frame f of clip b as one [2199] row pose | map | bbox3d | image
-void clip_frame_row(const ScoreClipIO& sc, int b, int f, int* dst) {
-    const int* src[4] = {sc.pose, sc.map, sc.box, sc.img};
-    for (int m = 0; m < 4; ++m) memcpy(dst + kModOff[m], src[m] + ((size_t)b * sc.L + f) * kModLen[m], (size_t)kModLen[m] * sizeof(int));
-}
 // the row of sc.out [B][L - T_in][S_mod] that takes frame f of clip b
 long clip_out_row(const ScoreClipIO& sc, int b, int f) { return (long)b * (sc.L - sc.T_in) + (f - sc.T_in); }
 
@@ -446,25 +420,22 @@ long clip_out_row(const ScoreClipIO& sc, int b, int f) { return (long)b * (sc.L 
 template <typename T>
 int score_clip_frames(umgen_engine* e, const ScoreClipIO& sc, int f0, int f1) {
     const int B = sc.B, Bm = e->cfg.max_batch;
-    const int* src[4] = {sc.pose, sc.map, sc.box, sc.img};
-    std::vector<int> win[4], next;
+    TokenSeqs win;
+    std::vector<int> next;
     std::vector<long> rows;
     const long N = (long)(f1 - f0) * B;
-    for (long i0 = 0; i0 < N;) {
-        const int Tn = std::min(f0 + (int)(i0 / B), sc.cond);
+    for (long i0 = 0; i0 < N;) {      // item i0 + i: frame f0 + (i0 + i) / B of clip (i0 + i) % B
+        const auto frame = [=](size_t i) { return f0 + (int)((i0 + i) / B); };
+        const auto clip = [=](size_t i) { return (int)((i0 + i) % B); };
+        const int Tn = cond_window(frame(0), sc.cond).n;
         int n = 0;
-        while (n < Bm && i0 + n < N && std::min(f0 + (int)((i0 + n) / B), sc.cond) == Tn) ++n;
+        while (n < Bm && i0 + n < N && cond_window(frame(n), sc.cond).n == Tn) ++n;
         rows.resize(n);
+        for (int i = 0; i < n; ++i) rows[i] = clip_out_row(sc, clip(i), frame(i));
+        gather_windows(sc.clip, n, clip, [&](size_t i) { return frame(i) - Tn; }, Tn, win);
         next.resize((size_t)n * kTokPerFrame);
-        for (int m = 0; m < 4; ++m) win[m].resize((size_t)n * Tn * kModLen[m]);
-        for (int i = 0; i < n; ++i) {
-            const int f = f0 + (int)((i0 + i) / B), b = (int)((i0 + i) % B);
-            rows[i] = clip_out_row(sc, b, f);
-            for (int m = 0; m < 4; ++m)
-                memcpy(&win[m][(size_t)i * Tn * kModLen[m]], src[m] + ((size_t)b * sc.L + (f - Tn)) * kModLen[m], (size_t)Tn * kModLen[m] * sizeof(int));
-            clip_frame_row(sc, b, f, &next[(size_t)i * kTokPerFrame]);
-        }
-        const ScoreIO one{n, Tn, win[0].data(), win[1].data(), win[2].data(), win[3].data(), next.data(), sc.out, 0, rows.data()};
+        frame_rows(sc.clip, n, clip, frame, next.data());
+        const ScoreIO one{n, Tn, win.view(), next.data(), sc.out, 0, rows.data()};
         if (int rc = run_score<T>(e, one)) return rc;
         i0 += n;
     }
@@ -478,26 +449,23 @@ int score_clip_frames(umgen_engine* e, const ScoreClipIO& sc, int f0, int f1) {
 // arithmetic of run_score, launched over other row sets.
 template <typename T>
 int score_clip_shared(umgen_engine* e, const ScoreClipIO& sc, int P, int G) {
-    const int E = e->E, B = sc.B, L = sc.L, Bm = e->cfg.max_batch, n = B * G, pv = e->cfg.pose_vocab;
+    const int E = e->E, B = sc.B, Bm = e->cfg.max_batch, n = B * G, pv = e->cfg.pose_vocab;
     FrameCtx ctx = begin_call(e, kNoSampling);
     RestoreStream restore{e, ctx.fg};
     // the window [0, P) of every clip, [B][P][S_mod], and frame P's pose, which the shift hands to slot P - 1
-    const int* src[4] = {sc.pose, sc.map, sc.box, sc.img};
-    std::vector<int> win[4], pose_P((size_t)B * 3), items((size_t)n * 2), item_T(n), next((size_t)n * kTokPerFrame);
+    TokenSeqs win;
+    std::vector<int> pose_P((size_t)B * 3), items((size_t)n * 2), item_T(n), next((size_t)n * kTokPerFrame);
     std::vector<long> rows(n);
-    for (int m = 0; m < 4; ++m) {
-        win[m].resize((size_t)B * P * kModLen[m]);
-        for (int b = 0; b < B; ++b) memcpy(&win[m][(size_t)b * P * kModLen[m]], src[m] + (size_t)b * L * kModLen[m], (size_t)P * kModLen[m] * sizeof(int));
-    }
+    gather_windows(sc.clip, B, 0, P, win);
     for (int b = 0; b < B; ++b) {
-        memcpy(&pose_P[(size_t)b * 3], sc.pose + ((size_t)b * L + P) * 3, 3 * sizeof(int));
+        memcpy(&pose_P[(size_t)b * 3], sc.clip.at(0, b, P), 3 * sizeof(int));
         for (int g = 0; g < G; ++g) {      // item (b, g): slot t = T_in - 1 + g scores frame t + 1
             const int i = b * G + g, t = sc.T_in - 1 + g;
             items[2 * i] = b; items[2 * i + 1] = t; item_T[i] = t + 1; rows[i] = clip_out_row(sc, b, t + 1);
-            clip_frame_row(sc, b, t + 1, &next[(size_t)i * kTokPerFrame]);
         }
     }
-    const FrameIO io{B, P, win[0].data(), win[1].data(), win[2].data(), win[3].data(), nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
+    frame_rows(sc.clip, n, [G](size_t i) { return i / G; }, [&](size_t i) { return sc.T_in + (int)(i % G); }, next.data());
+    const FrameIO io{B, P, win.view(), nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
     e->px.valid = false;                 // the passes below overwrite the stacks' workspaces; nothing of them is for a later rollout
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
@@ -519,7 +487,7 @@ int score_clip_shared(umgen_engine* e, const ScoreClipIO& sc, int P, int G) {
     }
     clock.stage(&e->tm.ego_ms);
     // one pose shift for the window: slot t carries the pose of frame t + 1, slot P - 1 that of frame P
-    if (int rc = upload_pose_shift(e, st, win[0].data(), pose_P.data(), B, P, ctx.pshift, ctx.pdiff)) return rc;
+    if (int rc = upload_pose_shift(e, st, win.view().pose(), pose_P.data(), B, P, ctx.pshift, ctx.pdiff)) return rc;
     const WindowTokens ws{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, P, 0};
     run_stack_any(e, STACK_MAP, ws, CACHE_NONE, TAIL_NONE, e->clip_warped);
     launch_cond_rows_slots(st, STACK_MAP, P, E, e->X, e->ln_map_tar, e->clip_warped, e->clip_items, n, e->clip_cond);

@@ -1,7 +1,8 @@
 // The templated compute path on whole windows: GEMM / attention launch helpers, the BlockTAR sub-block and the four stacks, the ego
-// decoder, the given-token prefix as one pass, the recorder / launcher of the next frame's background pass, and the GMLP tables.
+// decoder, the given-token prefix as one pass, the recorder / launcher of the next frame's background pass (its known slots one gather_windows of
+// the frame's TokenView, token_windows.h, kept in px.win and staged in px_up), and the GMLP tables.
 // Other files enter through the *_any dispatchers at the end.
-#include "engine_state.h"
+#include "engine_frame.h"      // (upload_tokens)
 
 // host arithmetic stays unfused in every engine file, as it was while they were one file behind the numpy-faithful helpers (engine_weights.hip)
 #pragma clang fp contract(off)
@@ -325,34 +326,25 @@ int launch_prefix(umgen_engine* e, const FrameIO& io, const std::vector<int>& eg
     umgen_engine::Prefix& px = e->px;
     px.valid = false;
     px.B = B; px.P = P; px.Tfull = Tnext; px.has_ego = !io.next_has_ctrl_pose;
-    const int* cur[4] = {io.pose, io.map, io.box, io.img};
-    std::vector<int>* keep[4] = {&px.pose, &px.map, &px.box, &px.img};
-    std::vector<int>* up[4] = {&e->px_up[0], &e->px_up[1], &e->px_up[2], &e->px_up[3]};
+    // the known slots [B][P][S_mod], kept for prefix_matches, and as the first P of Tnext slots in the upload: slot P is zero but for the new pose
+    TokenSeqs& up = e->px_up;
+    gather_windows(io.win, B, off, P, px.win);
+    up.resize(B, Tnext);
     for (int m = 0; m < 4; ++m) {
-        const size_t S = kModLen[m];
-        keep[m]->assign(B * P * S, 0);
-        up[m]->assign(B * Tnext * S, 0);
-        for (int b = 0; b < B; ++b) {
-            const int* src = cur[m] + ((size_t)b * Tn + off) * S;
-            memcpy(keep[m]->data() + b * P * S, src, P * S * sizeof(int));
-            memcpy(up[m]->data() + b * Tnext * S, src, P * S * sizeof(int));
-        }
+        std::fill(up.mod[m].begin(), up.mod[m].end(), 0);
+        for (int b = 0; b < B; ++b) memcpy(up.at(m, b, 0), px.win.at(m, b, 0), (size_t)P * kModLen[m] * sizeof(int));
     }
     px.pose_next.assign(ego.begin(), ego.end());
-    for (int b = 0; b < B; ++b)
-        for (int a = 0; a < 3; ++a) (*up[0])[((size_t)b * Tnext + P) * 3 + a] = ego[b * 3 + a];
+    for (int b = 0; b < B; ++b) memcpy(up.at(0, b, P), &ego[(size_t)b * 3], 3 * sizeof(int));
     std::vector<int> zero((size_t)B * 3, 0);
-    decode_pose_shift(up[0]->data(), zero.data(), B, Tnext, e->px_pshift, e->px_pdiff);   // slot P (unknown) is not touched by this pass
+    decode_pose_shift(up.mod[0].data(), zero.data(), B, Tnext, e->px_pshift, e->px_pdiff);   // slot P (unknown) is not touched by this pass
 
     hipStream_t fg = e->stream, bg = e->bg_engine ? e->stream : e->bg_stream;
     if (!e->bg_engine) {
         HIPCHK(e, hipEventRecord(e->ev_tar_done, fg));
         HIPCHK(e, hipStreamWaitEvent(bg, e->ev_tar_done, 0));
     }
-    HIPCHK(e, hipMemcpyAsync(e->d_pose, up[0]->data(), up[0]->size() * 4, hipMemcpyHostToDevice, bg));
-    HIPCHK(e, hipMemcpyAsync(e->d_map, up[1]->data(), up[1]->size() * 4, hipMemcpyHostToDevice, bg));
-    HIPCHK(e, hipMemcpyAsync(e->d_box, up[2]->data(), up[2]->size() * 4, hipMemcpyHostToDevice, bg));
-    HIPCHK(e, hipMemcpyAsync(e->d_img, up[3]->data(), up[3]->size() * 4, hipMemcpyHostToDevice, bg));
+    if (int rc = upload_tokens(e, bg, up.view(), (size_t)B * Tnext)) return rc;
     HIPCHK(e, hipMemcpyAsync(e->d_pose_shift, e->px_pshift.data(), e->px_pshift.size() * 4, hipMemcpyHostToDevice, bg));
     HIPCHK(e, hipMemcpyAsync(e->pose_diff, e->px_pdiff.data(), e->px_pdiff.size() * 4, hipMemcpyHostToDevice, bg));
     const WindowTokens ws{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, Tnext, 0};

@@ -1,5 +1,6 @@
 // State of the host engine, shared by the engine_*.hip files: the weight table and struct umgen_engine (one block of members per mechanism),
-// the per-frame call arguments (FrameIO), a decode lane's view of the engine (DecView), and the declarations of the functions that cross files.
+// the per-frame call arguments (FrameIO) and the scoring calls' (ScoreIO ...), which carry their host tokens as a TokenView (token_windows.h),
+// a decode lane's view of the engine (DecView), and the declarations of the functions that cross files.
 // No code that launches or decides anything lives here.
 #pragma once
 
@@ -21,6 +22,7 @@
 #include "bg_queue.h"
 #include "frame.h"
 #include "kernels.h"
+#include "token_windows.h"
 
 using namespace umgen;
 
@@ -144,10 +146,11 @@ struct umgen_engine {
     struct Prefix {
         bool valid = false, has_ego = false;
         int B = 0, P = 0, Tfull = 0;
-        std::vector<int> pose, map, box, img;   // slots 0..P-1 of the window the pass was computed for, [B][P][S_mod]
+        TokenSeqs win;                          // slots 0..P-1 of the window the pass was computed for, [B][P][S_mod]
         std::vector<int> pose_next;             // [B][3] pose tokens the new frame must carry (they sit in shifted slot P-1)
     } px;
-    std::vector<int> px_up[4], px_pshift;   // host staging of the background pass's uploads (must outlive the async copies)
+    TokenSeqs px_up;                        // host staging of the background pass's uploads (must outlive the async copies)
+    std::vector<int> px_pshift;
     std::vector<float> px_pdiff;
     // timing
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -254,8 +257,8 @@ bool ensure_tcache(umgen_engine* e);
 // (8 scenes: 3.53 vs 3.77 s).  UMGEN_ROWS_PER_BLOCK overrides (0 = every workgroup loops over all rows).
 inline int rows_per_block_for(const umgen_engine* e, int M) { return e->rows_per_block >= 0 ? e->rows_per_block : (M <= 6 ? 1 : 2); }
 
-// the four modalities of a frame in the order pose | map | bbox3d | image: content length, and offset in a frame's [2199] row
-constexpr int kModLen[4] = {kNPose, kNMap, kNBox, kNImg}, kModOff[4] = {0, kOffMap, kOffBox, kOffImg};
+static_assert(kModLen[0] == kNPose && kModLen[1] == kNMap && kModLen[2] == kNBox && kModLen[3] == kNImg && kModOff[1] == kOffMap && kModOff[2] == kOffBox &&
+                  kModOff[3] == kOffImg && kFrameRowLen == kTokPerFrame, "token_windows.h states the frame layout of frame.h");
 
 // f(T{}) for the engine's precision T: templates on T do not cross files, so every file dispatches its own through this
 template <typename F>
@@ -297,7 +300,7 @@ struct FrameDetail {
 };
 struct FrameIO {
     int B, T;
-    const int *pose, *map, *box, *img;          // host window tokens [B][T][S_mod] (box already control-overwritten)
+    TokenView win;                               // host window tokens [B][T][S_mod] (box already control-overwritten)
     const int* ctrl_pose;                        // host [B][3] or nullptr: pose given (init_tokens["pose"])
     const unsigned char* control_slot;           // host [B][60] or nullptr
     int frame_idx;
@@ -324,7 +327,7 @@ struct ScoreDetailIO {
 // umgen_score's arguments: B scenes' history windows and the frame to score, as host int32 arrays
 struct ScoreIO {
     int B, T;
-    const int *pose, *map, *box, *img;          // [B][T][S_mod]
+    TokenView win;                               // [B][T][S_mod]
     const int* next;                             // [B][2199]: the scored frame, pose | map | bbox3d | image
     ScoreDst out;
     long row0 = 0;                               // scene b's results go to row row0 + b of `out` ...
@@ -335,7 +338,7 @@ struct ScoreIO {
 // umgen_score_candidates' arguments: B scenes' history windows and C candidate next frames of every scene
 struct ScoreCandIO {
     int B, T, C;
-    const int *pose, *map, *box, *img;          // [B][T][S_mod]
+    TokenView win;                               // [B][T][S_mod]
     const int* next;                             // [B][C][2199]: the candidates, pose | map | bbox3d | image
     ScoreDst out;                                // candidate (b, c) at row b*C + c
     int shared_slots;                            // out: T - 1 when the history slots ran once per scene, 0 on the replicated path
@@ -345,8 +348,8 @@ struct ScoreCandIO {
 // against the last min(T + k, cond) frames of history[b] ++ future[b][c]
 struct ScoreFutIO {
     int B, T, C, K, cond;
-    const int *pose, *map, *box, *img;          // [B][T][S_mod]
-    const int* fut[4];                           // pose | map | bbox3d | image, each [B][C][K][S_mod]
+    TokenView win;                               // [B][T][S_mod]
+    TokenView fut;                               // [B * C][K][S_mod]
     ScoreDst out;                                // frame k of candidate (b, c) at row (b*C + c)*K + k
     int* shared_slots;                           // out, [K]: per future frame the history slots that ran once per scene, 0 on the replicated path
 };
@@ -354,7 +357,7 @@ struct ScoreFutIO {
 // umgen_score_clip's arguments: B recorded clips of L frames; every frame f in [T_in, L) is scored against the min(f, cond) frames before it
 struct ScoreClipIO {
     int B, L, T_in, cond;
-    const int *pose, *map, *box, *img;          // [B][L][S_mod]
+    TokenView clip;                              // [B][L][S_mod]
     ScoreDst out;                                // frame f of clip b at row b*(L - T_in) + f - T_in
     int shared_frames;                           // out: frames per clip that were read off one window pass, 0 on the per-frame path
 };

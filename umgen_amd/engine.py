@@ -116,8 +116,24 @@ class Engine:
         logp = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
         return logp, _lib.LogpOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
 
-    _GEN_DETAIL_FIELDS = {"rank": ("rank", np.int32, -1), "mass_above": ("mass_above", np.float32, np.nan), "entropy": ("entropy", np.float32, np.nan),
-                          "topk_tokens": ("topk_tok", np.int32, -1), "topk_logp": ("topk_logp", np.float32, np.nan)}
+    # the diagnostics of score(detail=...) and of rollout / frame (return_detail): key -> (field stem of the C struct, dtype); the "topk_" keys are lists
+    _DETAIL_FIELDS = {"rank": ("rank", np.int32), "mass_above": ("mass_above", np.float32), "entropy": ("entropy", np.float32),
+                      "topk_tokens": ("topk_tok", np.int32), "topk_logp": ("topk_logp", np.float32)}
+    DETAIL_KEYS = tuple(_DETAIL_FIELDS)
+
+    @classmethod
+    def _detail_out(cls, struct, keys, lead: Tuple[int, ...], topk: int, fill):
+        """(key -> mod -> array [*lead, S_mod] (lists [*lead, S_mod, topk]) filled with fill[dtype], the `struct` -- _lib.ScoreDetailOut or GenDetailOut --
+        that points at them)"""
+        f = cls._DETAIL_FIELDS
+        bufs = {k: {m: np.full(tuple(lead) + (CONTENT_LEN[m],) + ((topk,) if k.startswith("topk_") else ()), fill[f[k][1]], f[k][1]) for m in MOD_ORDER} for k in keys}
+        out = struct(**{f"{f[k][0]}_{m}": bufs[k][m].ctypes.data_as(C.POINTER(C.c_int32 if f[k][1] is np.int32 else C.c_float)) for k in keys for m in MOD_ORDER})
+        return bufs, out
+
+    @staticmethod
+    def _detail_result(bufs, pick=lambda a: a):
+        """the buffers as a call returns them: int32 as int64, through pick (a scoring call without the B axis drops it)"""
+        return {k: {m: pick(a.astype(np.int64) if a.dtype == np.int32 else a) for m, a in d.items()} for k, d in bufs.items()}
 
     @classmethod
     def _gen_detail_args(cls, call: str, topk, sampling: RolloutConfig) -> int:
@@ -133,15 +149,44 @@ class Engine:
         """(key -> mod -> array [*lead, S_mod] (lists [*lead, S_mod, topk]) filled with "no head ran": -1 / NaN, the umgen_gen_detail_out that points at them);
         the keys are Engine.score(detail=True)'s, the lists only with topk > 0"""
         keys = [k for k in cls.DETAIL_KEYS if topk > 0 or not k.startswith("topk_")]
-        f = cls._GEN_DETAIL_FIELDS
-        bufs = {k: {m: np.full(tuple(lead) + (CONTENT_LEN[m],) + ((topk,) if k.startswith("topk_") else ()), f[k][2], f[k][1]) for m in MOD_ORDER} for k in keys}
-        out = _lib.GenDetailOut(**{f"{f[k][0]}_{m}": bufs[k][m].ctypes.data_as(C.POINTER(C.c_int32 if f[k][1] is np.int32 else C.c_float))
-                                   for k in keys for m in MOD_ORDER})
-        return bufs, out
+        return cls._detail_out(_lib.GenDetailOut, keys, lead, topk, {np.int32: -1, np.float32: np.nan})
 
     @staticmethod
-    def _gen_detail_result(bufs):
-        return {k: {m: (a.astype(np.int64) if a.dtype == np.int32 else a) for m, a in d.items()} for k, d in bufs.items()}
+    def _init_token_args(init_tokens: Optional[Dict[str, np.ndarray]], control_test: bool, B: int):
+        """init_tokens of a rollout as the arrays of the C call: (T_ctl, control pose, control bbox3d, given map, given bbox3d), int64 [B, T_ctl, S_mod] or
+        None.  bbox3d tokens are GIVEN behind a given map without control_test, control tokens otherwise."""
+        cp = cb = gm = gb = None
+        T_ctl = 0
+        if init_tokens is not None:
+            # init_tokens["image"] is dropped by the reference before the decode loop ("to avoid image token as init tokens",
+            # UMGen.py:1512-1520) but still copied into the output (1640-1651): not a generation path -- refused rather than imitated
+            extra = [k for k, v in init_tokens.items() if v is not None and k not in ("pose", "bbox3d", "map")]
+            if extra:
+                raise UMGenError(f"init_tokens for {extra} are not supported (pose / bbox3d control tokens, given map / map + bbox3d tokens)")
+        if init_tokens is not None and init_tokens.get("pose") is not None:
+            cp = _i64(init_tokens["pose"])
+            if cp.ndim != 3 or cp.shape[0] != B or cp.shape[2] != CONTENT_LEN["pose"]:
+                raise UMGenError(f"init_tokens['pose'] has shape {cp.shape}, expected ({B}, T_ctl, {CONTENT_LEN['pose']})")
+            T_ctl = cp.shape[1]
+        if init_tokens is not None and init_tokens.get("map") is not None:      # the map of every new frame is GIVEN (UMGen.py:1184-1201)
+            gm = _i64(init_tokens["map"])
+            if gm.ndim != 3 or gm.shape[0] != B or gm.shape[2] != CONTENT_LEN["map"] or (T_ctl and gm.shape[1] != T_ctl):
+                raise UMGenError(f"init_tokens['map'] has shape {gm.shape}, expected ({B}, {T_ctl or 'T'}, {CONTENT_LEN['map']})")
+            T_ctl = gm.shape[1]
+        if init_tokens is not None and init_tokens.get("bbox3d") is not None and not control_test and gm is not None:
+            gb = _i64(init_tokens["bbox3d"])                                     # boxes given too (behind a given map)
+            if gb.shape != (B, T_ctl, CONTENT_LEN["bbox3d"]):
+                raise UMGenError(f"init_tokens['bbox3d'] has shape {gb.shape}, expected {(B, T_ctl, CONTENT_LEN['bbox3d'])}")
+        elif init_tokens is not None and init_tokens.get("bbox3d") is not None:   # with or without pose tokens (UMGen.py:1458-1473)
+            cb = _i64(init_tokens["bbox3d"])
+            if cp is None:
+                # (umgen_rollout takes ONE T_ctl for every control / given array: a given map and control boxes must cover the same frames)
+                if cb.ndim != 3 or cb.shape[0] != B or cb.shape[2] != CONTENT_LEN["bbox3d"] or (T_ctl and cb.shape[1] != T_ctl):
+                    raise UMGenError(f"init_tokens['bbox3d'] has shape {cb.shape}, expected ({B}, {T_ctl or 'T_ctl'}, {CONTENT_LEN['bbox3d']})")
+                T_ctl = cb.shape[1]
+            elif cb.shape != (B, T_ctl, CONTENT_LEN["bbox3d"]):
+                raise UMGenError(f"init_tokens['bbox3d'] has shape {cb.shape}, expected {(B, T_ctl, CONTENT_LEN['bbox3d'])}")
+        return T_ctl, cp, cb, gm, gb
 
     def rollout(self, tokens: Dict[str, np.ndarray], new_frames: int, cond_frames: int = 20,
                 input_cond_frames: int = -1, init_tokens: Optional[Dict[str, np.ndarray]] = None,
@@ -187,37 +232,7 @@ class Engine:
                 raise UMGenError(f"rollout: seeds has dtype {sd.dtype}, expected an integer type")
             seeds = sd.reshape(-1)
         outs = {m: np.empty(lead + (T_in + new_frames, CONTENT_LEN[m]), dtype=np.int64) for m in MOD_ORDER}
-        cp = cb = gm = gb = None
-        T_ctl = 0
-        if init_tokens is not None:
-            # init_tokens["image"] is dropped by the reference before the decode loop ("to avoid image token as init tokens",
-            # UMGen.py:1512-1520) but still copied into the output (1640-1651): not a generation path -- refused rather than imitated
-            extra = [k for k, v in init_tokens.items() if v is not None and k not in ("pose", "bbox3d", "map")]
-            if extra:
-                raise UMGenError(f"init_tokens for {extra} are not supported (pose / bbox3d control tokens, given map / map + bbox3d tokens)")
-        if init_tokens is not None and init_tokens.get("pose") is not None:
-            cp = _i64(init_tokens["pose"])
-            if cp.ndim != 3 or cp.shape[0] != B or cp.shape[2] != CONTENT_LEN["pose"]:
-                raise UMGenError(f"init_tokens['pose'] has shape {cp.shape}, expected ({B}, T_ctl, {CONTENT_LEN['pose']})")
-            T_ctl = cp.shape[1]
-        if init_tokens is not None and init_tokens.get("map") is not None:      # the map of every new frame is GIVEN (UMGen.py:1184-1201)
-            gm = _i64(init_tokens["map"])
-            if gm.ndim != 3 or gm.shape[0] != B or gm.shape[2] != CONTENT_LEN["map"] or (T_ctl and gm.shape[1] != T_ctl):
-                raise UMGenError(f"init_tokens['map'] has shape {gm.shape}, expected ({B}, {T_ctl or 'T'}, {CONTENT_LEN['map']})")
-            T_ctl = gm.shape[1]
-        if init_tokens is not None and init_tokens.get("bbox3d") is not None and not control_test and gm is not None:
-            gb = _i64(init_tokens["bbox3d"])                                     # boxes given too (behind a given map)
-            if gb.shape != (B, T_ctl, CONTENT_LEN["bbox3d"]):
-                raise UMGenError(f"init_tokens['bbox3d'] has shape {gb.shape}, expected {(B, T_ctl, CONTENT_LEN['bbox3d'])}")
-        elif init_tokens is not None and init_tokens.get("bbox3d") is not None:   # with or without pose tokens (UMGen.py:1458-1473)
-            cb = _i64(init_tokens["bbox3d"])
-            if cp is None:
-                # (umgen_rollout takes ONE T_ctl for every control / given array: a given map and control boxes must cover the same frames)
-                if cb.ndim != 3 or cb.shape[0] != B or cb.shape[2] != CONTENT_LEN["bbox3d"] or (T_ctl and cb.shape[1] != T_ctl):
-                    raise UMGenError(f"init_tokens['bbox3d'] has shape {cb.shape}, expected ({B}, {T_ctl or 'T_ctl'}, {CONTENT_LEN['bbox3d']})")
-                T_ctl = cb.shape[1]
-            elif cb.shape != (B, T_ctl, CONTENT_LEN["bbox3d"]):
-                raise UMGenError(f"init_tokens['bbox3d'] has shape {cb.shape}, expected {(B, T_ctl, CONTENT_LEN['bbox3d'])}")
+        T_ctl, cp, cb, gm, gb = self._init_token_args(init_tokens, control_test, B)
         smp, keep = self._sampling(sampling or self.cfg, seeds if seeds is not None else [0] * B)
         args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
@@ -234,7 +249,7 @@ class Engine:
             del keep
             if samples is not None:
                 self.last_shared_slots = int(shared.value)
-            res = (outs,) + ((logp,) if return_logp else ()) + ((self._gen_detail_result(dbufs),) if return_detail else ())
+            res = (outs,) + ((logp,) if return_logp else ()) + ((self._detail_result(dbufs),) if return_detail else ())
             return res if len(res) > 1 else outs
         if not return_logp:
             self._check(self.lib.umgen_rollout(*args), "rollout")
@@ -313,7 +328,7 @@ class Engine:
             tbuf["logp"] = lpv
         if dbufs is not None:
             tbuf = tbuf if tbuf is not None else {}
-            tbuf["detail"] = self._gen_detail_result(dbufs)
+            tbuf["detail"] = self._detail_result(dbufs)
         return outs, tbuf
 
     # -- scoring -------------------------------------------------------------------------------
@@ -398,8 +413,6 @@ class Engine:
             raise UMGenError(f"score_clip: {B} clips, the engine holds max_batch={self.max_batch}")
         return c, int(cond_frames), batched
 
-    DETAIL_KEYS = ("rank", "mass_above", "entropy", "topk_tokens", "topk_logp")
-
     @classmethod
     def _detail_args(cls, detail, topk, temperature):
         """What a score call asks for beyond the scores, checked before anything reaches the device.  Returns (keys or None, topk, temperature)."""
@@ -441,14 +454,9 @@ class Engine:
         if keys is None:
             self._check(self.lib.umgen_score(self._h, B, T, *tokens, C.byref(out)), "score")
         else:
-            field = {"rank": ("rank", np.int32, ()), "mass_above": ("mass_above", np.float32, ()), "entropy": ("entropy", np.float32, ()),
-                     "topk_tokens": ("topk_tok", np.int32, (topk,)), "topk_logp": ("topk_logp", np.float32, (topk,))}
-            bufs = {k: {m: np.zeros((B, CONTENT_LEN[m]) + field[k][2], field[k][1]) for m in MOD_ORDER} for k in keys}
-            det = _lib.ScoreDetailOut(**{f"{field[k][0]}_{m}": bufs[k][m].ctypes.data_as(C.POINTER(C.c_int32 if field[k][1] is np.int32 else C.c_float))
-                                         for k in keys for m in MOD_ORDER})
+            bufs, det = self._detail_out(_lib.ScoreDetailOut, keys, (B,), topk, {np.int32: 0, np.float32: 0.0})
             self._check(self.lib.umgen_score_detail(self._h, B, T, *tokens, topk, temperature, C.byref(out), C.byref(det)), "score_detail")
-            for k in keys:
-                res[k] = {m: pick(bufs[k][m].astype(np.int64) if field[k][1] is np.int32 else bufs[k][m]) for m in MOD_ORDER}
+            res = self._detail_result(bufs, pick)
         res.update(self._score_result(logp, arg, batched))
         return res
 
