@@ -11,7 +11,7 @@ layer's new row and n_layers x LAYER_BAR on x (every layer adds at most its own 
 the residual): reference, weights and cache layout are right independently of the engines.
 
 The preloaded history is shaped per (scene, head, layer) from the fp64 query of that layer, pattern (h + b + l) % 5: 0 the newest cached key
-dominates the softmax, 1 a key on a seam of the engine's key partition dominates (xcd_seam / wide_seam restate the partition), 2 every cached
+dominates the softmax, 1 a key on a seam of the engine's key partition dominates (xcd_seam / wide_seam / rows_seam restate the partition), 2 every cached
 score equal, 3 random, 4 every cached key ~20 nats below the new token's own key (which the engines take from the q|k|v exchange, not from
 the cache).  Row L starts as NaN bits, rows (L, L + 64] hold 7.0: the engines load them (clamped at the last cache row) and must mask them.
 Every preloaded row but row L must come back bit for bit.
@@ -30,6 +30,12 @@ same cases, and the bars -- 3 x measured rounded up to one digit, and never abov
 dropped key at L = 2206, 1 / 2207 of a head's weight, would fit under the bar):
   XCD-resident engine, 12 layers   4.5e-5 | 2.6e-6   ENGINE_BAR 1e-4 | 8e-6   five launches per layer 2.7e-6 | 3.1e-6 (bar 12 x LAYER_BAR)
   chip-wide engine, 4 layers       1.5e-6 | 1.6e-6   WIDE_BAR   5e-6 | 5e-6   five launches per layer 2.0e-6 | 1.7e-6 (bar 4 x LAYER_BAR)
+  batched decode layer, 4 layers (use_engine 2; families rows, E = 768, and rows96, E = 96; the cases and tests are in tests/test_gpu_batched_step.py):
+    rows                           2.8e-5 | 3.9e-6   ROWS_STEP_BAR 9e-5 | 2e-5   five launches per layer 1.7e-6 | 1.4e-6 (bar 4 x LAYER_BAR)
+    rows96                         1.8e-5 | 3.6e-6   ROWS_STEP_BAR 6e-5 | 2e-5
+  In bf16 the batched layer feeds all four GEMMs of a layer with hi + lo pairs (2^-17 per activation, decode_batched.hip split8), like the XCD-resident
+  engine's MLP below; 1.4e-5 .. 2.8e-5 over all cases whatever L or B is.  Its wrong references at (1, 2206): a key dropped from the all-equal heads
+  1.8e-3 | 1.7e-3, no lo part 1.5e-2 | 1.7e-3 (asserted to be >= 4 x the bar on the CPU, test_bar_sees_a_dropped_key_and_a_lost_lo_part).
 FINDING: in bf16 the XCD-resident engine is 17 x further from fp64 than the five-launch path and than its own fp16 instantiation, and 3 x its
 measured error (1.4e-4) is above 1e-4, so the bar stays at the cap, 2.2 x measured.  The error is the MLP's: c_fc and the mlp c_proj run on the
 matrix cores with the fp32 activation split into hi + lo parts of the operand type (oar_engine.hip ln_split / split16), which keeps 16 mantissa
@@ -67,8 +73,20 @@ MANY_CASES = sorted({(B, L) for B in (1, 2) for L in XCD_POS} | set(MANY_B))
 WIDE_CASES = sorted({(1, L) for L in WIDE_POS} | {(2, 64), (2, 1919), (2, 2303)})
 GUARD = 64                                            # finite rows preloaded behind row L
 EPOCH_WRAP = 0xE0000000                               # engine_frame.hip / engine_decode.hip: an epoch above it drains, clears and restarts at tag 16
+# the batched decode layer (tests/test_gpu_batched_step.py): no cached key, one, a full lane-group row and one past it, exactly one pass round and a
+# second that holds the token's own key alone, exactly one flight batch, a second with the own key alone and one more, the middle of a frame, the last
+# position of a frame, the last cache row
+ROWS_POS = [0, 1, 15, 16, 63, 64, 65, 255, 256, 257, 1100, 2206, 2303]
+# every position at 1 and 2 scenes; each of the four column-block instantiations full and ragged (L <= 257: a case uploads B x layers cache blocks)
+ROWS_B = [(15, 65), (16, 256), (17, 257), (32, 64), (33, 63), (48, 16), (49, 15), (64, 65)]
+ROWS_CASES = sorted({(B, L) for B in (1, 2) for L in ROWS_POS} | set(ROWS_B))
+ROWS96_CASES = [(B, L) for B in (1, 17) for L in (0, 64, 257)]    # K = 96: three k-steps, waves 3 .. 7 of rows_mfma_kernel idle in the E-wide GEMMs
+ROWS_STEP_BAR = {"rows": {1: 9e-5, 2: 2e-5}, "rows96": {1: 6e-5, 2: 2e-5}}      # on x and on the new rows (the table in the file header)
 
-FAMILY = {"xcd": types.SimpleNamespace(E=768, H=16, layers=12, use=1), "wide": types.SimpleNamespace(E=1536, H=32, layers=4, use=3)}
+FAMILY = {"xcd": types.SimpleNamespace(E=768, H=16, layers=12, use=1), "wide": types.SimpleNamespace(E=1536, H=32, layers=4, use=3),
+          # 4 layers: the first reads rows_to_frag's output, two read the previous ROWS_RESID's fragment copy, the last one's copy only the head would read
+          "rows": types.SimpleNamespace(E=768, H=16, layers=4, use=2), "rows96": types.SimpleNamespace(E=96, H=2, layers=4, use=2)}
+CASES = {"xcd": MANY_CASES, "wide": WIDE_CASES, "rows": ROWS_CASES, "rows96": ROWS96_CASES}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -118,7 +136,27 @@ def wide_seam(L, b, h, l):
     return seam([[q * spn - 1, spn - 1], [q * spn, spn], [lo, spn - 1], [hi - 1, spn]][b % 4], L)
 
 
-SEAM = {"xcd": xcd_seam, "wide": wide_seam}
+def rows_partition(L):
+    """attn_decode_batched_kernel (decode_batched.hip) over the L + 1 keys: key k is lane group k % 16 of wave (k // 16) % 4 in pass k // 64, and
+    a wave requests 4 passes (a flight batch, 256 keys) before it uses the first; loads past the last key clamp to the token's own row.
+    -> (flight batches, [(k_lo, k_hi)] of the 16-key wave passes that are requested, index 4 * pass + wave; k_lo >= k_hi: only clamped loads)"""
+    nk = L + 1
+    nflight = (((nk + 63) // 64) + 3) // 4
+    return nflight, [(16 * (w + 4 * p), min(nk, 16 * (w + 4 * p) + 16)) for p in range(4 * nflight) for w in range(4)]
+
+
+def rows_seam(L, b, h, l):
+    """the scene (with the head's and the layer's turn among the seam heads) picks the edge: the last / first key of a 16-key wave pass, of a 64-key
+    pass round, of a 256-key flight batch (which pass, round or batch: by head and layer), key 0"""
+    nflight, passes = rows_partition(L)
+    live = [p for p in passes if p[0] < p[1]]
+    lo, hi = live[(h + 3 * l) % len(live)]
+    r = (h + 3 * l) % ((L + 64) // 64)                 # a pass round with keys
+    f = (h + 3 * l) % nflight
+    return seam([[hi - 1, 15], [lo, 16], [64 * r + 63, 63], [64 * r, 64], [256 * f + 255, 255], [256 * f, 256], [0]][(b + h // 5 + 2 * l) % 7], L)
+
+
+SEAM = {"xcd": xcd_seam, "wide": wide_seam, "rows": rows_seam, "rows96": rows_seam}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -285,12 +323,16 @@ def env(**kv):
 def create(which, prec, max_batch=None, max_cond_frames=4, **over):
     """many: the XCD-resident engine for every batch size up to 33 (8 groups; 12 layers: the production tail sharing, 4 tail layers on two groups
     each; UMGEN_BG_ENGINE=0 keeps a fresh one-scene handle of this kind on 8 groups); one: one scene per call, so the kernel instance with background
-    workers on 4 groups; wide: the chip-wide engine for up to two scenes.  max_cond_frames / over (tiny_config fields): a longer window (tests/test_gpu_bg_pass.py)"""
+    workers on 4 groups; wide: the chip-wide engine for up to two scenes; rows / rows96: the batched decode layer for every batch size
+    (UMGEN_DECODE_BATCHED=1) up to 64 / 17 scenes; rows5: the rows family's layers as five launches per layer for up to 17 scenes.
+    max_cond_frames / over (tiny_config fields): a longer window (tests/test_gpu_bg_pass.py)"""
     from umgen_amd.engine import Engine
-    fam = "wide" if which == "wide" else "xcd"
-    switches = {"many": dict(UMGEN_DECODE_BATCHED=0, UMGEN_BG_ENGINE=0), "one": {}, "wide": dict(UMGEN_DECODE_WIDE=2)}[which]
+    fam = {"wide": "wide", "rows": "rows", "rows96": "rows96", "rows5": "rows"}.get(which, "xcd")
+    switches = {"many": dict(UMGEN_DECODE_BATCHED=0, UMGEN_BG_ENGINE=0), "one": {}, "wide": dict(UMGEN_DECODE_WIDE=2),
+                "rows": dict(UMGEN_DECODE_BATCHED=1), "rows96": dict(UMGEN_DECODE_BATCHED=1), "rows5": dict(UMGEN_DECODE_BATCHED=0, UMGEN_BG_ENGINE=0)}[which]
     with env(**switches):
-        e = Engine(config(fam, **over), precision=PREC_NAME[prec], max_batch=max_batch or {"many": 33, "one": 1, "wide": 2}[which], max_cond_frames=max_cond_frames)
+        e = Engine(config(fam, **over), precision=PREC_NAME[prec],
+                   max_batch=max_batch or {"many": 33, "one": 1, "wide": 2, "rows": 64, "rows96": 17, "rows5": 17}[which], max_cond_frames=max_cond_frames)
     e.load_state_dict(state_items(fam, prec, **over))
     e.finalize()
     e.fam, e.prec = fam, prec
@@ -544,7 +586,8 @@ def test_epoch_wrap_in_the_middle_of_a_rollout(B):
 @pytest.mark.gpu
 def test_step_hook_refuses_a_path_the_step_would_not_take():
     """umgen_dbg_oar_step never runs another path than the one asked for: 24 scenes take the batched decode layer by default, so neither
-    the engine nor five launches per layer; no chip-wide engine at E = 768; the cache hook checks its ranges"""
+    the engine nor five launches per layer, and 23 do not, so not the batched layer (use_engine 2); no chip-wide engine at E = 768; the cache
+    hook checks its ranges; with UMGEN_DECODE_BATCHED=0 no batch size takes the batched layer; fp32 has no 16-bit path at all"""
     from umgen_amd.engine import Engine, UMGenError
     from umgen_amd.weights import synthetic_state_dict
     cfg = tiny_config(n_embd=768, n_head=16, rule_constrain=False)
@@ -559,6 +602,12 @@ def test_step_hook_refuses_a_path_the_step_would_not_take():
         with pytest.raises(UMGenError, match="chip-wide"):
             e.dbg_oar_step(x[:1], 0, 3)
         e.dbg_oar_step(x[:23], 0, 1)
+        with pytest.raises(UMGenError, match="do not take the batched decode layer"):
+            e.dbg_oar_step(x[:23], 0, 2)
+        out, frag = e.dbg_oar_step(x, 0, 2, return_frag=True)
+        assert np.all(np.isfinite(out)) and np.array_equal(out.view(np.uint32), frag.view(np.uint32))
+        with pytest.raises(UMGenError, match="use_engine 2"):            # no other path keeps a fragment-major copy of x
+            e.dbg_oar_step(x[:23], 0, 1, return_frag=True)
         for layer, scene, row0, n in ((2, 0, 0, 1), (0, 24, 0, 1), (0, 0, -1, 1), (0, 0, 0, 0), (0, 0, LMAX - 1, 2)):
             with pytest.raises(UMGenError):
                 e.dbg_oar_cache_get(layer, scene, row0, n)
@@ -568,6 +617,24 @@ def test_step_hook_refuses_a_path_the_step_would_not_take():
         assert not e.dbg_oar_cache_get(1, 22, LMAX - 3, 3).any() and not e.dbg_oar_cache_get(1, 23, LMAX - 6, 3).any()
     finally:
         e.close()
+    # UMGEN_DECODE_BATCHED=0: no batch size takes the batched decode layer; fp32 has neither engines nor the batched layer
+    with env(UMGEN_DECODE_BATCHED=0):
+        e = Engine(cfg, precision="bf16", max_batch=24, max_cond_frames=4)
+    e32 = Engine(tiny_config(rule_constrain=False), precision="fp32", max_batch=1, max_cond_frames=2)
+    try:
+        e.load_state_dict(synthetic_state_dict(cfg, seed=1))
+        e.finalize()
+        for B in (1, 23, 24):
+            with pytest.raises(UMGenError, match="do not take the batched decode layer"):
+                e.dbg_oar_step(x[:B], 0, 2)
+        e.dbg_oar_step(x, 0, 0)
+        e32.load_state_dict(synthetic_state_dict(tiny_config(rule_constrain=False), seed=1))
+        e32.finalize()
+        with pytest.raises(UMGenError, match="16-bit engines only"):
+            e32.dbg_oar_step(np.zeros((1, 96), np.float32), 0, 2)
+    finally:
+        e.close()
+        e32.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -600,14 +667,48 @@ def test_stack_restatement_matches_oracle():
     assert err <= 2e-6, f"restatement vs oracle: {err:.3e}"
 
 
+def rows_partition_claims():
+    """what the comment at ROWS_POS says of rows_partition, and rows_seam's keys: cached keys on the edge that the scene's turn names"""
+    def live(L):
+        return [p for p in rows_partition(L)[1] if p[0] < p[1]]
+    assert live(0) == [(0, 1)] and live(1) == [(0, 2)]                              # the own key alone | one cached key
+    assert live(15) == [(0, 16)] and live(16) == [(0, 16), (16, 17)]                # a full lane-group row | one key past it
+    assert len(live(63)) == 4 and live(63)[-1] == (48, 64)                          # exactly one pass round
+    assert live(64)[4:] == [(64, 65)] and live(65)[4:] == [(64, 66)]                # the second round: the own key alone | with one cached key
+    assert rows_partition(255)[0] == 1 and len(live(255)) == 16 and live(255)[-1] == (240, 256)     # exactly one flight batch
+    assert rows_partition(256)[0] == 2 and live(256)[16:] == [(256, 257)]           # the second flight batch: the own key alone
+    assert rows_partition(257)[0] == 2 and live(257)[16:] == [(256, 258)]
+    assert [rows_partition(L)[0] for L in (1100, 2206, 2303)] == [5, 9, 9]
+    assert len(live(2303)) == 144 == len(rows_partition(2303)[1]) and live(2303)[-1] == (2288, LMAX)        # the last cache row fills the last flight batch
+    for L in ROWS_POS:
+        nflight, passes = rows_partition(L)
+        assert len(passes) == 16 * nflight and all(passes[k // 16][0] <= k < passes[k // 16][1] for k in range(L + 1))
+        assert sum(hi - lo for lo, hi in live(L)) == L + 1
+    residue = [(16, 15), (16, 0), (64, 63), (64, 0), (256, 255), (256, 0), (1 << 30, 0)]        # by edge kind: k % 16 == 15, ...
+    for L in ROWS_POS[1:]:
+        edges = {k for lo, hi in live(L) for k in (lo, hi - 1)} | {L - 1}
+        for b in range(7):
+            for h in range(16):
+                for l in range(4):
+                    k = rows_seam(L, b, h, l)
+                    mod, r = residue[(b + h // 5 + 2 * l) % 7]
+                    assert k in edges and 0 <= k < L and (k % mod == r or k == L - 1), (L, b, h, l, k)
+    # at one scene the seam heads of the four layers take every kind of edge, and at L = 2206 none of them falls back to key L - 1
+    assert {(h // 5 + 2 * l) % 7 for l in range(4) for h in range(16) if pattern(0, h, l) == 1} == set(range(7))
+    assert all(rows_seam(2206, 0, h, l) != 2205 for l in range(4) for h in range(16) if pattern(0, h, l) == 1)
+
+
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("fam", ["xcd", "wide"])
+@pytest.mark.parametrize("fam", ["xcd", "wide", "rows", "rows96"])
 def test_case_premises_hold_on_the_reference(fam, prec):
     """every case's patterns (dominant newest / seam / own key, all-equal scores) are there in the reference's own scores, the seam keys are
     cached keys on a boundary of the partition, and the position lists hit what the file header says of the partitions"""
-    for B, L in (MANY_CASES if fam == "xcd" else WIDE_CASES):
+    for B, L in CASES[fam]:
         plan(fam, prec, B, L)                          # (asserts the premises)
     plan.cache_clear()
+    if fam in ("rows", "rows96"):
+        rows_partition_claims()
+        return
     n0, w = xcd_partition(15)
     assert n0 == 16 and all(lo >= hi for lo, hi in w[8:])                           # empty second half
     assert [xcd_partition(L)[1][8] for L in (16, 32)] == [(16, 17), (32, 33)]       # one-key second half: the token's own

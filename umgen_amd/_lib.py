@@ -22,7 +22,7 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
            "umgen_vqenc_create", "umgen_vqenc_load_tensor", "umgen_vqenc_finalize", "umgen_vqenc_encode", "umgen_vqenc_last_error", "umgen_vqenc_destroy",
-           "umgen_dbg_linear", "umgen_dbg_linear_vt", "umgen_dbg_gemm", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_temporal_range", "umgen_dbg_attn_temporal_fan", "umgen_dbg_attn_temporal_fan_write", "umgen_dbg_attn_temporal_fan_tail", "umgen_dbg_tcache_spread", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_gemm_vt_bench", "umgen_dbg_gemm_stamps", "umgen_dbg_oar_step", "umgen_dbg_oar_cache", "umgen_dbg_oar_epoch", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
+           "umgen_dbg_linear", "umgen_dbg_linear_vt", "umgen_dbg_gemm", "umgen_dbg_attn_spatial", "umgen_dbg_attn_temporal", "umgen_dbg_attn_temporal_range", "umgen_dbg_attn_temporal_fan", "umgen_dbg_attn_temporal_fan_write", "umgen_dbg_attn_temporal_fan_tail", "umgen_dbg_tcache_spread", "umgen_dbg_attn_decode", "umgen_dbg_gemv", "umgen_dbg_gemm_bench", "umgen_dbg_gemm_vt_bench", "umgen_dbg_gemm_stamps", "umgen_dbg_oar_step", "umgen_dbg_oar_step_frag", "umgen_dbg_oar_cache", "umgen_dbg_oar_epoch", "umgen_dbg_sample_topk", "umgen_dbg_batched_layer_bench",
            "umgen_dbg_rows", "umgen_dbg_attn_decode_batched", "umgen_dbg_sample", "umgen_dbg_collision",
            "umgen_dbg_gemv_modes", "umgen_dbg_gemv_resid", "umgen_dbg_attn_partial", "umgen_dbg_decode_layer", "umgen_dbg_guard_selftest",
            "umgen_dbg_embed_warp", "umgen_dbg_layernorm", "umgen_dbg_cond_rows", "umgen_dbg_first_input", "umgen_dbg_ego_queries",
@@ -320,6 +320,7 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_gemm_vt_bench.argtypes = [i32, i32, i32, i32, i32, i32, fp]
     lib.umgen_dbg_gemm_stamps.argtypes = [C.POINTER(C.c_ulonglong)]
     lib.umgen_dbg_oar_step.argtypes = [vp, i32, i32, fp, fp, i32, i32]
+    lib.umgen_dbg_oar_step_frag.argtypes = [vp, i32, i32, fp, fp, fp, i32, i32]
     lib.umgen_dbg_oar_cache.argtypes = [vp, i32, i32, i32, i32, vp, i32]
     lib.umgen_dbg_oar_epoch.argtypes = [vp, C.c_uint32]
     lib.umgen_dbg_sample_topk.argtypes = [fp, i32, i32, i32, C.c_float, fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

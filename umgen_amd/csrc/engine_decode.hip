@@ -210,19 +210,26 @@ int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace*
 extern "C" {
 
 // Test hook: ONE decode step through the BlockOAR layers (no head, no sampler) on caller-provided inputs, either as the five-launch
-// layer form (use_engine 0), the XCD-resident engine (1) or the chip-wide engine (3).  The K/V rows of position L are appended to the cache: a
-// test drives L = 0, 1, 2, ... or sets the history with umgen_dbg_oar_cache.  A path that oar_layers would not take for this B is refused.
-int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in, float* x_out, int32_t use_engine, int32_t unmasked) {
+// layer form (use_engine 0), the XCD-resident engine (1), the batched decode layer (2) or the chip-wide engine (3).  The K/V rows of position L are
+// appended to the cache: a test drives L = 0, 1, 2, ... or sets the history with umgen_dbg_oar_cache.  A path that oar_layers would not take for this
+// B is refused: 2 runs exactly when use_batched(B) holds on this handle, 0 / 1 / 3 exactly when it does not.
+// x_frag (umgen_dbg_oar_step_frag; use_engine 2 only): the fragment-major copy of x behind the step -- e->xfrag, the buffer the head's launch
+// would stream (enqueue_step) -- downloaded as it is and put into rows [B][E] on the host with frag_index.
+static int oar_step_hook(umgen_engine* e, int32_t B, int32_t L, const float* x_in, float* x_out, float* x_frag, int32_t use_engine, int32_t unmasked) {
     if (!e || !x_in || !x_out) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (e->cfg.precision == UMGEN_PREC_FP32) return e->fail(UMGEN_E_UNSUPPORTED, "16-bit engines only");
     if (B < 1 || B > e->cfg.max_batch || L < 0 || L >= e->Lmax) return e->fail(UMGEN_E_INVALID, "B=%d L=%d", B, L);
-    if (use_engine != 0 && use_engine != 1 && use_engine != 3) return e->fail(UMGEN_E_INVALID, "use_engine %d (0: five launches per layer, 1: XCD-resident engine, 3: chip-wide engine)", use_engine);
+    if (use_engine < 0 || use_engine > 3)
+        return e->fail(UMGEN_E_INVALID, "use_engine %d (0: five launches per layer, 1: XCD-resident engine, 2: batched decode layer, 3: chip-wide engine)", use_engine);
+    if (x_frag && use_engine != 2) return e->fail(UMGEN_E_INVALID, "only the batched decode layer (use_engine 2) keeps a fragment-major copy of x");
     if (use_engine == 1 && !e->eng_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "decode engine not available on this engine");
     if (use_engine == 3 && !e->wide_enabled) return e->fail(UMGEN_E_UNSUPPORTED, "chip-wide decode engine not available on this engine");
     // the step runs on the path that was asked for or not at all: oar_layers decides by B, and a test must not measure another path's arithmetic
     hipStream_t const st = (unmasked && e->full_stream) ? e->full_stream : e->stream;
-    if (e->use_batched(B))
+    if (use_engine == 2 && !e->use_batched(B))
+        return e->fail(UMGEN_E_UNSUPPORTED, "%d scenes do not take the batched decode layer on this engine (UMGEN_DECODE_BATCHED)", B);
+    if (use_engine != 2 && e->use_batched(B))
         return e->fail(UMGEN_E_UNSUPPORTED, "%d scenes take the batched decode layer on this engine (UMGEN_DECODE_BATCHED), not %s", B,
                        use_engine == 0 ? "five launches per layer" : "a decode engine");
     if (use_engine == 3 && !e->use_wide(B)) return e->fail(UMGEN_E_UNSUPPORTED, "the chip-wide decode engine takes at most 4 scenes per call, not %d", B);
@@ -252,14 +259,29 @@ int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in,
     e->wide_enabled = wide_keep;
     if (lrc) return lrc;
     HIPCHK(e, hipMemcpyAsync(x_out, e->xdec, (size_t)B * e->E * 4, hipMemcpyDeviceToHost, st));
+    std::vector<float> hfrag(x_frag ? (size_t)kRowsMaxM * e->E : 0);
+    if (x_frag) HIPCHK(e, hipMemcpyAsync(hfrag.data(), e->xfrag, hfrag.size() * 4, hipMemcpyDeviceToHost, st));
     unsigned eng_err = 0;
-    if (use_engine) HIPCHK(e, hipMemcpyAsync(&eng_err, use_engine == 3 ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (use_engine == 1 || use_engine == 3)
+        HIPCHK(e, hipMemcpyAsync(&eng_err, use_engine == 3 ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
+    if (x_frag)
+        for (int m = 0; m < B; ++m)
+            for (int k = 0; k < e->E; ++k) x_frag[(size_t)m * e->E + k] = hfrag[frag_index(m, k)];
     if (eng_err) {      // clear the word of the engine that ran (the other engine's may not exist: ADVICE r5)
         (void)hipMemset(use_engine == 3 ? e->wide_err : e->eng_err, 0, sizeof(unsigned));
         return e->fail(UMGEN_E_HIP, "decode engine gave up waiting for hand-off tag 0x%08x", eng_err);
     }
     return UMGEN_OK;
+}
+
+int umgen_dbg_oar_step(umgen_engine* e, int32_t B, int32_t L, const float* x_in, float* x_out, int32_t use_engine, int32_t unmasked) {
+    return oar_step_hook(e, B, L, x_in, x_out, nullptr, use_engine, unmasked);
+}
+
+// the same step with the second output x_frag [B][E] (may be null)
+int umgen_dbg_oar_step_frag(umgen_engine* e, int32_t B, int32_t L, const float* x_in, float* x_out, float* x_frag, int32_t use_engine, int32_t unmasked) {
+    return oar_step_hook(e, B, L, x_in, x_out, x_frag, use_engine, unmasked);
 }
 
 // Test hook: rows [row0, row0 + n_rows) of every (K / V, head) of one (layer, scene) block of the decode K/V cache, device [layer][scene][2][H][Lmax][48],

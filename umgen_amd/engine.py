@@ -563,13 +563,20 @@ class Engine:
                     "score_clip")
         return self._score_result(logp, arg, batched, total=True, frames=np.arange(int(input_frames), L, dtype=np.int64), shared_frames=int(shared.value))
 
-    def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True) -> np.ndarray:
+    def dbg_oar_step(self, x: np.ndarray, L: int, use_engine, unmasked: bool = True, return_frag: bool = False):
         """Test hook: one decode step through the BlockOAR layers for x [B, n_embd] at KV length L (appends K/V row L).
-        use_engine goes through int() as it is: 0 / False five launches per layer, 1 / True the XCD-resident engine, 3 the chip-wide engine.
-        A path that a decode step of B scenes would not take on this engine is refused (UMGenError), never replaced by another."""
+        use_engine goes through int() as it is: 0 / False five launches per layer, 1 / True the XCD-resident engine, 2 the batched decode
+        layer, 3 the chip-wide engine.  A path that a decode step of B scenes would not take on this engine is refused (UMGenError), never
+        replaced by another: 2 runs exactly at the batch sizes the batched layer takes (UMGEN_DECODE_BATCHED), 0 / 1 / 3 at the others.
+        return_frag (use_engine 2 only): -> (x out, the fragment-major copy of x behind the step -- the buffer the head's launch would stream --
+        as rows [B, n_embd])."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         out = np.empty_like(x)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        if return_frag:
+            frag = np.empty_like(x)
+            self._check(self.lib.umgen_dbg_oar_step_frag(self._h, x.shape[0], L, fp(x), fp(out), fp(frag), int(use_engine), int(unmasked)), "dbg_oar_step")
+            return out, frag
         self._check(self.lib.umgen_dbg_oar_step(self._h, x.shape[0], L, fp(x), fp(out), int(use_engine), int(unmasked)), "dbg_oar_step")
         return out
 
