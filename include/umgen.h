@@ -300,6 +300,54 @@ int umgen_frame_detail(umgen_engine *e, int32_t T, const int64_t *pose, const in
                        int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp,
                        int32_t topk, const umgen_gen_detail_out *detail);
 
+/* ---- constrained sampling: per-class logit bias and token bans inside the samplers of every decode step -----------------------------------
+ * umgen_rollout_biased is umgen_rollout_detail, umgen_frame_biased is umgen_frame_detail, plus `bias` and `lz`; with bias NULL or all its tables
+ * NULL, and lz NULL, they are exactly those calls (which are these with bias = lz = NULL): no existing call changes its bits.
+ * A bias table belongs to a token class (host float32; entries finite, or -inf = a ban):
+ *     pose    [3][pose_vocab]       row of component jq
+ *     map     [map_vocab]           the one row
+ *     bbox3d  [11][bbox3d_vocab]    row of attribute a = k % 11, k the position in the 660; a == 10 is the category token
+ *     image   [img_vocab]           the one row
+ * Wherever a sampler would read a logit row v of such a position -- the AR head's row (head_ego's for the pose), or the head_tar_bbox3d row of a
+ * control or pad-avoid resample -- it reads w[n] = v[n] + r[n] instead: one fp32 add, round to nearest, -inf where r[n] is -inf; r the class row
+ * of the position.  Everything else is unchanged and runs on w: the top-k threshold with ties kept, temperature, the nucleus, the control
+ * resample's masked index vocab - 1, the RNG draw kinds, the pad-avoid trigger, the rule constraint, teacher forcing.  A biased call returns, bit
+ * for bit, what the unbiased samplers return on the rows w.  Consequences:
+ *   - Bans hold for draws: a banned token is never the result of a draw, for any uniform (an inverse-CDF walk that finds no prefix sum above its
+ *     target ends on its last ALLOWED entry).
+ *   - Bans do not hold for non-draws: the rule constraint blanks a slot to pad whatever the tables say; forced, controlled and given tokens are
+ *     written as given.
+ *   - lp (umgen_logp_out) and the diagnostics (umgen_gen_detail_out) stay in the model's measure: computed on v, never on w, for the token the step
+ *     settled on.  lp is finite for every drawn token (r > -inf there and v is finite).  rank < top_k for a token of the main draw is guaranteed
+ *     only WITHOUT a bias on its class: under a bias the top-k support is that of w.
+ *   - logz (umgen_logz_out, float32, the shapes of umgen_logp_out): per sampled position logz = lse(w) - lse(v) over [0, vocab) of the AR row -- the
+ *     log of sum_n softmax(v)[n] exp(r[n]); for a table of bans the log of the model's mass on the allowed set, <= 0.  Each lse is max + log sum
+ *     exp(row - max) in lp's fixed order, so the bits are a function of (row, class row, vocab) alone; an all-zero table gives exactly +0.0.  +0.0 at
+ *     sampled positions of a class without a table; NaN exactly where lp is NaN; for a TAR-resampled token still the AR row's value, like lp.
+ *     What it is for: under an UNTRUNCATED sampler at temperature 1 (top-k >= vocab / nucleus keeping everything) the proposal's log-density of a
+ *     drawn token is lp + r[tok] - logz, so logz - r[tok], summed over a frame, is the log importance weight of a constrained sample against the
+ *     model.  The renormalisation of a truncated sampler and the composite density of the resample flow are not part of it.
+ *   - Refused with UMGEN_E_INVALID before anything reaches the device, the message naming class, row and index: a NaN or +inf entry; a row without an
+ *     allowed entry; a bbox3d row whose only allowed entry is vocab - 1 when the call has control slots (control_test with ctrl_bbox3d: the control
+ *     resample masks that index); a table of a class whose vocabulary exceeds 8192.
+ *   - One set of tables per call: scenes, fan-out branches and frames share it.  lz without a bias is allowed (+0.0 / NaN).
+ * The scoring entry points take no bias: they describe the model, not a sampler. */
+typedef struct umgen_logit_bias { const float *pose, *map, *bbox3d, *image; } umgen_logit_bias;   /* host; any may be NULL = no bias for that class */
+typedef struct umgen_logz_out   { float *logz_pose, *logz_map, *logz_bbox3d, *logz_image; } umgen_logz_out; /* shapes of umgen_logp_out */
+int umgen_rollout_biased(umgen_engine *e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames,
+                         const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                         int32_t T_ctl, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                         const int64_t *given_map, const int64_t *given_bbox3d,
+                         const umgen_sampling *sampling,
+                         int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image,
+                         const umgen_logp_out *lp, int32_t *shared_slots, int32_t topk, const umgen_gen_detail_out *detail,
+                         const umgen_logit_bias *bias, const umgen_logz_out *lz);
+int umgen_frame_biased(umgen_engine *e, int32_t T, const int64_t *pose, const int64_t *map, const int64_t *bbox3d,
+                       const int64_t *image, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                       const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
+                       int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp,
+                       int32_t topk, const umgen_gen_detail_out *detail, const umgen_logit_bias *bias, const umgen_logz_out *lz);
+
 /* Ranking futures: C given next frames per scene against ONE history.  Entry (b, c) of every output is bit for bit what
  *     umgen_score(e, 1, T, window b, candidate (b, c))
  * returns on the same engine, in every precision, whichever path ran and however the B * C items were chunked.  Only the last history slot of the map /

@@ -1,0 +1,146 @@
+"""Logit-bias tables for constrained generation (``Engine.rollout(logit_bias=...)``, include/umgen.h: umgen_rollout_biased).  Host only.
+
+A set of tables is a dict class -> float32 array: "pose" [3, 1024], "map" [1024 codes], "bbox3d" [11, 1028], "image" [codes]; finite entries
+shift a token's logit inside the sampler of every decode step, ``-inf`` bans the token.  The builders return such dicts with one class each;
+``merge`` adds them up (``-inf`` wins), so a scenario reads
+
+    tables = merge(ban_categories(["pedestrian"]), pose_limits(dx=(0.0, 1.5)))
+    tokens, logz = engine.rollout(clip, 10, logit_bias=tables, return_logz=True)
+
+The vocabulary sizes default to UMGen_Large's (config.py); pass ``vocab=`` for another model.
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import scene_io
+
+CLASSES = ("pose", "map", "bbox3d", "image")
+ROWS = {"pose": 3, "map": 1, "bbox3d": 11, "image": 1}           # rows of a class's table: pose component, bbox3d attribute (10: the category token)
+DEFAULT_VOCAB = {"pose": 1024, "map": 8192, "bbox3d": 1028, "image": 8192}
+CATEGORY_ATTR = 10
+CATEGORY_TOKEN0 = 1024                                            # category token = 1024 + index of scene_io.CATEGORIES
+
+Tables = Dict[str, np.ndarray]
+
+
+def table_shape(mod: str, vocab: int) -> Tuple[int, ...]:
+    """the shape of class ``mod``'s table in the C call: [rows, vocab], or [vocab] for the one-row classes"""
+    return (ROWS[mod], vocab) if ROWS[mod] > 1 else (vocab,)
+
+
+def _vocab(mod: str, vocab: Optional[int]) -> int:
+    if mod not in ROWS:
+        raise ValueError(f"unknown token class {mod!r} (one of {CLASSES})")
+    return int(DEFAULT_VOCAB[mod] if vocab is None else vocab)
+
+
+def _rows(mod: str, attr) -> Sequence[int]:
+    """the table rows a builder writes: every row for attr None, else the given row(s)"""
+    if attr is None:
+        return range(ROWS[mod])
+    rows = [int(attr)] if np.isscalar(attr) else [int(a) for a in attr]
+    for r in rows:
+        if not 0 <= r < ROWS[mod]:
+            raise ValueError(f"attr={r} is outside the {ROWS[mod]} rows of class {mod!r}")
+    return rows
+
+
+def _check_rows(mod: str, t: np.ndarray) -> None:
+    t2 = t.reshape(ROWS[mod], -1)
+    if np.isnan(t2).any() or np.isposinf(t2).any():
+        raise ValueError(f"{mod}: bias entries are finite or -inf")
+    empty = np.flatnonzero(np.isneginf(t2).all(axis=1))
+    if empty.size:
+        raise ValueError(f"{mod}: row {int(empty[0])} has no allowed token left")
+
+
+def bias(mod: str, values, attr=None, vocab: Optional[int] = None) -> Tables:
+    """values [vocab] added to the logits of class ``mod`` -- in row(s) ``attr`` (pose component / bbox3d attribute), every row when None"""
+    V = _vocab(mod, vocab)
+    v = np.asarray(values, dtype=np.float32)
+    if v.shape != (V,):
+        raise ValueError(f"bias({mod!r}): values have shape {v.shape}, expected {(V,)}")
+    t = np.zeros((ROWS[mod], V), np.float32)
+    for r in _rows(mod, attr):
+        t[r] = v
+    _check_rows(mod, t)
+    return {mod: t.reshape(table_shape(mod, V))}
+
+
+def ban(mod: str, tokens: Iterable[int], attr=None, vocab: Optional[int] = None) -> Tables:
+    """``tokens`` of class ``mod`` are never drawn (in row(s) ``attr``, every row when None)"""
+    V = _vocab(mod, vocab)
+    idx = np.asarray(list(tokens), dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= V):
+        raise ValueError(f"ban({mod!r}): token outside [0, {V})")
+    v = np.zeros(V, np.float32)
+    v[idx] = -np.inf
+    return bias(mod, v, attr, V)
+
+
+def allow_only(mod: str, tokens: Iterable[int], attr=None, vocab: Optional[int] = None) -> Tables:
+    """only ``tokens`` of class ``mod`` may be drawn (in row(s) ``attr``, every row when None); an empty set raises"""
+    V = _vocab(mod, vocab)
+    idx = np.asarray(list(tokens), dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= V):
+        raise ValueError(f"allow_only({mod!r}): token outside [0, {V})")
+    v = np.full(V, -np.inf, np.float32)
+    v[idx] = 0.0
+    return bias(mod, v, attr, V)
+
+
+def merge(*tables: Optional[Tables]) -> Tables:
+    """the sum of several sets of tables, class by class: finite entries add, -inf wins; a row left without an allowed token raises"""
+    out: Tables = {}
+    for tb in tables:
+        for mod, t in (tb or {}).items():
+            if mod not in ROWS:
+                raise ValueError(f"unknown token class {mod!r} (one of {CLASSES})")
+            t = np.asarray(t, dtype=np.float32)
+            if t.ndim == 1 and ROWS[mod] > 1:
+                t = np.broadcast_to(t, (ROWS[mod], t.shape[0]))
+            if mod in out:
+                if out[mod].reshape(ROWS[mod], -1).shape != t.reshape(ROWS[mod], -1).shape:
+                    raise ValueError(f"merge: tables of class {mod!r} have shapes {out[mod].shape} and {t.shape}")
+                with np.errstate(invalid="ignore"):
+                    s = out[mod].reshape(ROWS[mod], -1) + t.reshape(ROWS[mod], -1)
+                out[mod] = s.reshape(table_shape(mod, s.shape[1])).astype(np.float32)
+            else:
+                out[mod] = np.array(t, dtype=np.float32).reshape(table_shape(mod, t.reshape(ROWS[mod], -1).shape[1]))
+            _check_rows(mod, out[mod])
+    return out
+
+
+def ban_categories(names: Iterable[str], vocab: Optional[int] = None) -> Tables:
+    """no generated agent of these categories (scene_io.CATEGORIES): their category tokens 1024 + index are banned at attribute 10"""
+    toks = []
+    for n in names:
+        if n not in scene_io.CATEGORIES:
+            raise ValueError(f"unknown category {n!r} (one of {scene_io.CATEGORIES})")
+        toks.append(CATEGORY_TOKEN0 + scene_io.CATEGORIES.index(n))
+    return ban("bbox3d", toks, attr=CATEGORY_ATTR, vocab=vocab)
+
+
+def pose_limits(dx: Optional[Tuple[float, float]] = None, dy: Optional[Tuple[float, float]] = None,
+                dheading: Optional[Tuple[float, float]] = None, vocab: Optional[int] = None) -> Tables:
+    """Keep the ego step inside an envelope, in the units scene_io.decode_ego returns: per component (lo, hi) or None = free; the pose tokens whose
+    decoded value lies outside [lo, hi] are banned.  Derived by decoding every token of every component, so there is no second copy of the bins."""
+    V = _vocab("pose", vocab)
+    toks = np.repeat(np.arange(V, dtype=np.int64)[:, None], 3, axis=1)
+    val = scene_io.decode_ego_numpy(toks).reshape(V, 3)
+    t = np.zeros((3, V), np.float32)
+    for c, (name, lim) in enumerate((("dx", dx), ("dy", dy), ("dheading", dheading))):
+        if lim is None:
+            continue
+        lo, hi = float(lim[0]), float(lim[1])
+        if not lo <= hi:
+            raise ValueError(f"pose_limits: {name}=({lo}, {hi}) is empty")
+        t[c, (val[:, c] < lo) | (val[:, c] > hi)] = -np.inf
+    try:
+        _check_rows("pose", t)
+    except ValueError:
+        raise ValueError("pose_limits: no pose token decodes into the envelope of one component") from None
+    return {"pose": t}

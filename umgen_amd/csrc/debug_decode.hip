@@ -88,6 +88,34 @@ int umgen_dbg_sample(int method, const float* logits, int n, int V, int k, float
     return down(tokens, dT, (size_t)n * 4);
 }
 
+// block_sample on the rows w = logits + bias (bias [n][V]: every row its own, entries finite or -inf with one allowed entry that is not mask_idx),
+// formed on the device in a scratch row per block like the samplers of a biased call form them -> tokens[n]
+int umgen_dbg_sample_biased(int method, const float* logits, const float* bias, int n, int V, int k, float p, float temp, int mask_idx, const float* u,
+                            int32_t* tokens) {
+    if ((method != 0 && method != 1) || !logits || !bias || !u || !tokens || V < 1 || V > 8192 || n < 1 || k < 1 || mask_idx < -1 || mask_idx >= V)
+        return UMGEN_E_INVALID;
+    for (int i = 0; i < n; ++i) {
+        int allowed = 0;
+        for (int c = 0; c < V; ++c) {
+            const float v = bias[(size_t)i * V + c];
+            if (v != v || v == INFINITY) return UMGEN_E_INVALID;
+            allowed += (v != -INFINITY && c != mask_idx);
+        }
+        if (!allowed) return UMGEN_E_INVALID;
+    }
+    Scratch s;
+    const float *dL = s.in(logits, (size_t)n * V * 4), *dB = s.in(bias, (size_t)n * V * 4), *dU = s.in(u, (size_t)n * 4);
+    float* dW = s.out((size_t)n * kBiasRowLen * 4);
+    int *dO = s.raw(4), *dT = s.out((size_t)n * 4);
+    if (s.rc) return s.rc;
+    if (hipMemset(dO, 0, 4) != hipSuccess) return UMGEN_E_HIP;
+    SamplerParams sp{};
+    sp.method = method; sp.top_k = sp.top_k_map = sp.topk_image = k; sp.p = sp.p_map = p; sp.temperature = temp;
+    launch_sample_dbg_biased(nullptr, dL, dB, dW, V, sp, k, p, dU, mask_idx, dT, dO, n);
+    if (int rc = s.finish()) return rc;
+    return down(tokens, dT, (size_t)n * 4);
+}
+
 // check_collision_dev (frame.hip) on n_sets box sets: boxes [n_sets][max_n][10] fp64, set i = its first counts[i] boxes -> out[i] 0 / 1
 int umgen_dbg_collision(const double* boxes, const int32_t* counts, int n_sets, int max_n, int32_t* out) {
     if (n_sets < 1 || max_n < 1 || max_n > 64 || !boxes || !counts || !out) return UMGEN_E_INVALID;     // the sampler's corner table holds 64 boxes

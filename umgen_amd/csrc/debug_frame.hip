@@ -85,7 +85,12 @@ struct DetailHook {
         return narrow(topk_logp, d.topk_logp, wl);
     }
 };
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh = nullptr);
+// what a biased token-step hook adds: the class tables on the host (any may be NULL: no bias for that class) and logz [B][2199] (in / out, or NULL)
+struct BiasHook {
+    const float *map, *box /*[11][n_box]*/, *img;
+    float* logz;
+};
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh = nullptr, const BiasHook* bh = nullptr);
 
 // the body of umgen_dbg_embed_warp and umgen_dbg_embed_warp_slots (warped_all: nullptr, or the host buffer of launch_warp_map's output of that name)
 int embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B, int T, int Tfull,
@@ -294,11 +299,41 @@ int umgen_dbg_token_steps_detail(const umgen_dbg_tables* t, const umgen_dbg_step
     DetailHook dh{topk, (size_t)a->B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
     return dh.sane() ? token_steps(t, a, logp, &dh) : UMGEN_E_INVALID;
 }
+// ... and with the logit-bias tables of a biased call: bias_map [n_map], bias_box [11][n_box], bias_img [n_img] (any may be NULL; entries finite or -inf,
+// every row with an allowed entry) set the classes' bits of OarState::bias_classes, SampleArgs::bias follows the step's mod, bias_rows is the hook's
+// scratch; logz [B][2199] (in / out, or NULL) sets want_logz.  logp may be NULL
+int umgen_dbg_token_steps_biased(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, const float* bias_map, const float* bias_box,
+                                 const float* bias_img, float* logz) {
+    const BiasHook bh{bias_map, bias_box, bias_img, logz};
+    return token_steps(t, a, logp, nullptr, &bh);
+}
+// ... together with umgen_dbg_token_steps_detail's diagnostics (they stay on the unbiased row)
+int umgen_dbg_token_steps_biased_detail(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, const float* bias_map, const float* bias_box,
+                                        const float* bias_img, float* logz, int topk, int32_t* rank, float* mass_above, float* entropy, int32_t* topk_tok,
+                                        float* topk_logp) {
+    if (!logp || !a || a->B < 1) return UMGEN_E_INVALID;
+    const BiasHook bh{bias_map, bias_box, bias_img, logz};
+    DetailHook dh{topk, (size_t)a->B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
+    return dh.sane() ? token_steps(t, a, logp, &dh, &bh) : UMGEN_E_INVALID;
+}
 
 }  // extern "C"
 
 namespace {
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh) {
+// every row of a bias table: finite or -inf entries, one of them allowed
+bool bias_rows_sane(const float* tab, int rows, int V) {
+    for (int r = 0; tab && r < rows; ++r) {
+        int allowed = 0;
+        for (int n = 0; n < V; ++n) {
+            const float v = tab[(size_t)r * V + n];
+            if (v != v || v == INFINITY) return false;
+            allowed += v != -INFINITY;
+        }
+        if (!allowed) return false;
+    }
+    return true;
+}
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh, const BiasHook* bh) {
     if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
     // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
     if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
@@ -328,6 +363,11 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
     s0.epoch = a->epoch0; s0.sp = a->sp; s0.want_logp = logp ? 1 : 0;
     s0.want_detail = dh ? 1 : 0; s0.detail_topk = dh ? dh->topk : 0;
+    if (bh) {
+        if (!bias_rows_sane(bh->map, 1, t->n_map) || !bias_rows_sane(bh->box, kSlotLen, t->n_box) || !bias_rows_sane(bh->img, 1, t->n_img)) return UMGEN_E_INVALID;
+        s0.bias_classes = (bh->map ? 1 << kBiasMap : 0) | (bh->box ? 1 << kBiasBox : 0) | (bh->img ? 1 << kBiasImg : 0);
+        s0.want_logz = bh->logz ? 1 : 0;
+    }
     Scratch s;
     SampleArgs sa{};
     sa.tb = tables_in(s, *t);
@@ -341,6 +381,13 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     sa.n_boxes = s.inout(a->n_boxes, (size_t)B * 4); sa.boxes = s.inout(a->boxes, bn * 8);
     if (logp) sa.logp = s.inout(logp, tn * 4);
     if (dh) { dh->to_device(s); sa.detail = dh->d; }
+    const float* dBias[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (bh) {
+        dBias[kBiasMap] = s.in(bh->map, (size_t)t->n_map * 4); dBias[kBiasBox] = s.in(bh->box, (size_t)kSlotLen * t->n_box * 4);
+        dBias[kBiasImg] = s.in(bh->img, (size_t)t->n_img * 4);
+        sa.bias_rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
+        if (bh->logz) sa.logz = s.inout(bh->logz, tn * 4);
+    }
     if (s.rc) return s.rc;
     for (int i = 0; i < n; ++i) {
         const int j = a->j0 + i, mod = kind_of_pos(j, a->given_end);
@@ -351,6 +398,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
             if (up(dLg, a->logits + (size_t)i * ln, ln * 4)) return UMGEN_E_HIP;
             sa.mod = mod;
             sa.vocab = mod == 1 ? t->n_map : (mod == 2 ? t->n_box : t->n_img);
+            sa.bias = dBias[mod];
             launch_sample_token(nullptr, sa, B);
         }
         if (int rc = finish()) return rc;
@@ -361,6 +409,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     if (!s.intact()) return UMGEN_E_STATE;
     if (down(a->tokens, sa.tokens, tn * 4) || down(a->counters, sa.counters, 8 * 4) || down(a->n_boxes, sa.n_boxes, (size_t)B * 4)) return UMGEN_E_HIP;
     if (logp && down(logp, sa.logp, tn * 4)) return UMGEN_E_HIP;
+    if (bh && bh->logz && down(bh->logz, sa.logz, tn * 4)) return UMGEN_E_HIP;
     if (dh) { if (int rc = dh->to_host()) return rc; }
     return down(a->boxes, sa.boxes, bn * 8);
 }
@@ -372,7 +421,8 @@ extern "C" {
 // [B][2199] (or NULL) overrides with its pose tokens.  logp [B][2199] (in / out, or NULL): entry [b][jq] receives the log-likelihood of pose token jq
 // of scene b on its row
 static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
-                           int32_t* out_tokens, float* logp, DetailHook* dh) {
+                           int32_t* out_tokens, float* logp, DetailHook* dh, const float* bias = nullptr, float* logz = nullptr) {
+    if (bias && !bias_rows_sane(bias, 3, V)) return UMGEN_E_INVALID;
     if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
         return UMGEN_E_INVALID;
     for (int b = 0; (logp || dh) && forced && b < B; ++b)      // the scored token indexes the row
@@ -385,16 +435,26 @@ static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, 
     int *dOv = s.raw(4), *dT = s.out(osz);
     float* dLp = logp ? (float*)s.inout(logp, tn * 4) : nullptr;
     if (dh) dh->to_device(s);
+    EgoBias eb{};
+    eb.bias = s.in(bias, (size_t)3 * V * 4);
+    if (bias) eb.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
+    if (logz) eb.logz = s.inout(logz, tn * 4);
     if (s.rc) return s.rc;
     if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
-    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, dLp, dh ? &dh->d : nullptr, dh ? dh->topk : 0);
+    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, dLp, dh ? &dh->d : nullptr, dh ? dh->topk : 0, eb);
     if (int rc = finish()) return rc;
     int ovf = 0;
     if (down(&ovf, dOv, 4)) return UMGEN_E_HIP;
     if (!s.intact() || ovf != 0) return UMGEN_E_STATE;      // (the overflow word is unused since the exhaustive tie walk: it must stay 0)
     if (logp && down(logp, dLp, tn * 4)) return UMGEN_E_HIP;
+    if (logz && down(logz, eb.logz, tn * 4)) return UMGEN_E_HIP;
     if (dh) { if (int rc = dh->to_host()) return rc; }
     return down(out_tokens, dT, osz);
+}
+// the same with a pose bias table bias [3][V] (or NULL) and logz [B][2199] (in / out, or NULL): entries [b][jq]
+int umgen_dbg_sample_ego_biased(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                                int32_t* out_tokens, const float* bias, float* logp, float* logz) {
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, logp, nullptr, bias, logz);
 }
 int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                               int32_t* out_tokens, float* logp) {

@@ -1,6 +1,6 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
-// umgen_frame(_logp, _detail), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver
-// umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail (UMGen.inference).  Every call narrows its int64 tokens once (narrow_tokens) and
+// umgen_frame(_logp, _detail, _biased), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver
+// umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail / umgen_rollout_biased (UMGen.inference).  Every call narrows its int64 tokens once (narrow_tokens) and
 // hands them on as a TokenView (token_windows.h); the output structs become [4] arrays through MOD4; the driver keeps one conditioning sequence and
 // gathers a frame's window from it, and a frame's control / given tokens are one plan_frame, for the driver and for umgen_frame alike.  Creation,
 // weights, the compute path, the frame itself and the scoring passes are in engine_setup.hip, engine_weights.hip, engine_stacks.hip,
@@ -157,10 +157,54 @@ struct GenDetail {
     }
 };
 
-int umgen_frame_detail(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
-                     const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
+static bool wants_logz(const umgen_logz_out* lz) { return lz && (lz->logz_pose || lz->logz_map || lz->logz_bbox3d || lz->logz_image); }
+
+// The logit-bias tables of a call (umgen_logit_bias) behind their checks, before anything reaches the device: entries are finite or -inf (a ban), every
+// row keeps an allowed entry, and with control slots a bbox3d row must allow more than vocab - 1 (the control resample masks that index).  -> the bit
+// per class with a table (OarState::bias_classes); host receives the tables in d_bias' layout (absent classes stay 0 and are never read)
+static int check_bias(umgen_engine* e, const umgen_logit_bias* bias, bool control_slots, std::vector<float>& host, int* classes) {
+    *classes = 0;
+    if (!bias) return 0;
+    const float* const tab[4] = {bias->pose, bias->map, bias->bbox3d, bias->image};
+    const char* const name[4] = {"pose", "map", "bbox3d", "image"};
+    const int rows[4] = {3, 1, kSlotLen, 1}, vocab[4] = {e->cfg.pose_vocab, e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
+    for (int c = 0; c < 4; ++c) {
+        if (!tab[c]) continue;
+        if (vocab[c] > kBiasRowLen)
+            return e->fail(UMGEN_E_INVALID, "logit bias: class %s has a vocabulary of %d, the samplers' scratch row holds %d", name[c], vocab[c], kBiasRowLen);
+        for (int r = 0; r < rows[c]; ++r) {
+            const float* row = tab[c] + (size_t)r * vocab[c];
+            int allowed = 0, last = -1;
+            for (int n = 0; n < vocab[c]; ++n) {
+                const float v = row[n];
+                if (v != v || v == INFINITY)
+                    return e->fail(UMGEN_E_INVALID, "logit bias: class %s row %d index %d is %s (entries are finite or -inf)", name[c], r, n, v != v ? "NaN" : "+inf");
+                if (v != -INFINITY) { ++allowed; last = n; }
+            }
+            if (!allowed) return e->fail(UMGEN_E_INVALID, "logit bias: class %s row %d bans every token (index 0 .. %d are all -inf)", name[c], r, vocab[c] - 1);
+            if (c == kBiasBox && control_slots && allowed == 1 && last == vocab[c] - 1)
+                return e->fail(UMGEN_E_INVALID, "logit bias: class %s row %d allows only index %d, which the control resample of a controlled slot masks", name[c], r, last);
+        }
+        *classes |= 1 << c;
+    }
+    if (!*classes) return 0;
+    host.assign(e->bias_floats(), 0.f);
+    for (int c = 0; c < 4; ++c)
+        if (tab[c]) memcpy(host.data() + e->bias_offset(c), tab[c], (size_t)rows[c] * vocab[c] * sizeof(float));
+    return 0;
+}
+// ... and onto the device, on the engine's stream and finished before the call's first frame starts (a frame may run on another stream of the engine)
+static int upload_bias(umgen_engine* e, const std::vector<float>& host) {
+    if (host.empty()) return 0;
+    HIPCHK(e, hipMemcpyAsync(e->d_bias, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int umgen_frame_biased(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                       const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
                        int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
-                       const umgen_logp_out* lp, int32_t topk, const umgen_gen_detail_out* detail) {
+                       const umgen_logp_out* lp, int32_t topk, const umgen_gen_detail_out* detail, const umgen_logit_bias* bias, const umgen_logz_out* lz) {
     if (!e) return UMGEN_E_INVALID;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
@@ -182,9 +226,14 @@ int umgen_frame_detail(umgen_engine* e, int32_t T, const int64_t* pose, const in
         if (int rc = check_tokens(e, "given map", given_map, kNMap, e->cfg.map_vocab, false)) return rc;
         if (given_bbox3d) { if (int rc = check_tokens(e, "given bbox3d", given_bbox3d, kNBox, e->cfg.bbox3d_vocab, false)) return rc; }
     }
+    std::vector<float> bias_host;
+    int bias_classes = 0;
+    if (int rc = check_bias(e, bias, ctrl_bbox3d && control_test, bias_host, &bias_classes)) return rc;
+    if (int rc = upload_bias(e, bias_host)) return rc;
     const int64_t* const in[4] = {pose, map, bbox3d, image};
     int64_t* const outp[4] = {out_pose, out_map, out_bbox3d, out_image};
     float* const lp_out[4] = MOD4(lp, logp);
+    float* const lz_out[4] = MOD4(lz, logz);
     TokenSeqs win;
     narrow_tokens(in, 1, T, win);
     FramePlan plan;      // the rollout's plan for one scene and one frame of control / given tokens (the boxes overwrite window slot T - 1)
@@ -194,15 +243,27 @@ int umgen_frame_detail(umgen_engine* e, int32_t T, const int64_t* pose, const in
     FrameIO io{1, T, win.view(), FramePlan::ptr(plan.cp), FramePlan::ptr(plan.cs), frame_idx, sampling, trace, out.data()};
     io.given_map = FramePlan::ptr(plan.gm);
     io.given_box = FramePlan::ptr(plan.gb);
+    std::vector<float> flz(wants_logz(lz) ? (size_t)kTokPerFrame : 0);
     io.out_logp = flp.empty() ? nullptr : flp.data();
     io.out_detail = gd.frame();
+    io.bias_classes = bias_classes;
+    io.out_logz = flz.empty() ? nullptr : flz.data();
     if (int rc = run_frame_any(e, io)) return rc;
     gd.deliver(0, 0);
     for (int m = 0; m < 4; ++m) {
         for (int i = 0; i < kModLen[m]; ++i) outp[m][i] = out[kModOff[m] + i];
         if (lp_out[m] && !flp.empty()) memcpy(lp_out[m], &flp[kModOff[m]], kModLen[m] * sizeof(float));
+        if (lz_out[m] && !flz.empty()) memcpy(lz_out[m], &flz[kModOff[m]], kModLen[m] * sizeof(float));
     }
     return UMGEN_OK;
+}
+
+int umgen_frame_detail(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
+                       const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const umgen_sampling* sampling,
+                       int32_t frame_idx, const umgen_trace* trace, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
+                       const umgen_logp_out* lp, int32_t topk, const umgen_gen_detail_out* detail) {
+    return umgen_frame_biased(e, T, pose, map, bbox3d, image, ctrl_pose, ctrl_bbox3d, control_test, sampling, frame_idx, trace, out_pose, out_map,
+                              out_bbox3d, out_image, lp, topk, detail, nullptr, nullptr);
 }
 
 int umgen_frame_logp(umgen_engine* e, int32_t T, const int64_t* pose, const int64_t* map, const int64_t* bbox3d, const int64_t* image,
@@ -381,16 +442,21 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
                           const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
                           const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
                           int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
-                          const umgen_gen_detail_out* detail) {
+                          const umgen_gen_detail_out* detail, const umgen_logit_bias* bias, const umgen_logz_out* lz) {
     if (!e) return UMGEN_E_INVALID;
     const int64_t* const in[4] = {pose, map, bbox3d, image};
     int64_t* const out[4] = {out_pose, out_map, out_bbox3d, out_image};
     float* const lp_out[4] = MOD4(lp, logp);
+    float* const lz_out[4] = MOD4(lz, logz);
     const int BN = B * N, T_out = T_in + new_frames;
     GenDetail gd;      // a frame's diagnostics and log-likelihoods are scattered to [B * N][new_frames][S_mod] below
     if (int rc = check_rollout(e, B, T_in, new_frames, cond_frames, in, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d, sampling, out, gd,
                                (size_t)BN, topk, detail))
         return rc;
+    std::vector<float> bias_host;      // one set of tables per call: scenes, branches and frames share it
+    int bias_classes = 0;
+    if (int rc = check_bias(e, bias, ctrl_bbox3d && control_test, bias_host, &bias_classes)) return rc;
+    if (int rc = upload_bias(e, bias_host)) return rc;
     e->tm = umgen_timings{};
     e->overlap_suspended = false;
     TokenSeqs seq, win;      // (win: the frame's asynchronous uploads read it until the frame's synchronisation)
@@ -403,6 +469,7 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
         }
     std::vector<int> frame_out((size_t)BN * kTokPerFrame);
     std::vector<float> frame_logp(wants_logp(lp) ? (size_t)BN * kTokPerFrame : 0);
+    std::vector<float> frame_logz(wants_logz(lz) ? (size_t)BN * kTokPerFrame : 0);
     for (int idx = 0; idx < new_frames; ++idx) {
         const int f = T_in + idx;
         const CondWindow w = cond_window(f, cond_frames);
@@ -420,6 +487,8 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
         io.given_box = FramePlan::ptr(plan.gb);
         io.out_logp = frame_logp.empty() ? nullptr : frame_logp.data();
         io.out_detail = gd.frame();
+        io.bias_classes = bias_classes;
+        io.out_logz = frame_logz.empty() ? nullptr : frame_logz.data();
         const char* fse = getenv("UMGEN_FAN_SHARE");      // (read per call: the tests compare both forms in one process)
         const bool fan = idx == 0 && N >= 2 && w.n >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
         if (fan && shared_slots) *shared_slots = w.n - 1;
@@ -431,6 +500,7 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
                 memcpy(seq.at(m, i, f), &frame_out[src], len * sizeof(int));
                 for (size_t k = 0; k < len; ++k) out[m][((size_t)i * T_out + f) * len + k] = frame_out[src + k];
                 if (lp_out[m] && !frame_logp.empty()) memcpy(lp_out[m] + ((size_t)i * new_frames + idx) * len, &frame_logp[src], len * sizeof(float));
+                if (lz_out[m] && !frame_logz.empty()) memcpy(lz_out[m] + ((size_t)i * new_frames + idx) * len, &frame_logz[src], len * sizeof(float));
             }
         for (int i = 0; i < BN; ++i) gd.deliver((size_t)i, (size_t)i * new_frames + idx);
     }
@@ -443,17 +513,18 @@ int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_fra
                        const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map, int64_t* out_bbox3d, int64_t* out_image,
                        const umgen_logp_out* lp) {
     return rollout_driver(e, B, 1, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, nullptr, 0, nullptr);
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
 // umgen_rollout_fan: N sampled futures per scene, the driver above with N branches per scene, whose first frame shares the history between a scene's branches
 // (engine_frame.hip run_frame_fan).  Every argument is checked once, on the caller's arrays: an error that names a flat index names it there.
 // umgen_rollout_detail: the same with the diagnostics of every generated token ([B][N][..] likewise)
-int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+// umgen_rollout_biased: the same with the call's logit-bias tables and logz of every sampled position
+int umgen_rollout_biased(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
                          const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
                          const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
                          int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
-                         const umgen_gen_detail_out* detail) {
+                         const umgen_gen_detail_out* detail, const umgen_logit_bias* bias, const umgen_logz_out* lz) {
     if (!e) return UMGEN_E_INVALID;
     if (shared_slots) *shared_slots = 0;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
@@ -461,7 +532,16 @@ int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, in
     if (N < 1) return e->fail(UMGEN_E_INVALID, "N=%d: at least one sample per scene", N);
     if ((int64_t)B * N > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B*N=%lld (B=%d, N=%d) exceeds max_batch=%d", (long long)B * N, B, N, e->cfg.max_batch);
     return rollout_driver(e, B, N, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail);
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail, bias, lz);
+}
+
+int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                         const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                         const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                         int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
+                         const umgen_gen_detail_out* detail) {
+    return umgen_rollout_biased(e, B, N, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map,
+                                given_bbox3d, sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail, nullptr, nullptr);
 }
 
 int umgen_rollout_fan(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,

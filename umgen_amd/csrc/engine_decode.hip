@@ -133,6 +133,7 @@ int enqueue_step(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr,
     sa.cond = e->cond; sa.x_next = e->xdec; sa.tokens = e->d_tokens; sa.prev_box = e->d_prev_box; sa.control_slot = e->d_control;
     sa.boxes = e->d_boxes; sa.n_boxes = e->d_nboxes; sa.seeds = e->d_seeds; sa.forced = e->d_forced; sa.counters = e->d_counters;
     sa.detail = e->d_detail;  // (likewise: OarState::want_detail)
+    sa.bias_rows = e->d_bias_rows; sa.logz = e->d_logz;   // (likewise: OarState::bias_classes / want_logz; the class table follows with the step's mod)
     sa.logp = e->d_logp;      // (always set: whether a step writes it is the device-side OarState::want_logp, so one captured graph serves both kinds of call)
     if (mod == 0) {
         launch_fixed_token(st, sa, B);
@@ -158,6 +159,7 @@ int enqueue_step(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr,
         }
         sa.mod = mod;
         sa.vocab = V;
+        sa.bias = e->d_bias + e->bias_offset(mod);
         launch_sample_token(st, sa, B);
     }
     return 0;
@@ -169,13 +171,13 @@ namespace umgen {
 
 DecView current_view(const umgen_engine* e) {
     return DecView{e->stream, e->xdec, e->qdec, e->logits, e->logits_tar, e->cond, e->xfrag, e->afrag, e->hfrag, e->kvcache,
-                   e->d_tokens, e->d_prev_box, e->d_nboxes, e->d_control, e->d_boxes, e->d_seeds, e->d_state, e->d_logp, e->d_detail};
+                   e->d_tokens, e->d_prev_box, e->d_nboxes, e->d_control, e->d_boxes, e->d_seeds, e->d_state, e->d_logp, e->d_detail, e->d_bias_rows, e->d_logz};
 }
 void apply_view(umgen_engine* e, const DecView& v) {
     e->stream = v.stream; e->xdec = v.xdec; e->qdec = v.qdec; e->logits = v.logits; e->logits_tar = v.logits_tar; e->cond = v.cond;
     e->xfrag = v.xfrag; e->afrag = v.afrag; e->hfrag = v.hfrag; e->kvcache = v.kvcache; e->d_tokens = v.d_tokens; e->d_prev_box = v.d_prev_box;
     e->d_nboxes = v.d_nboxes; e->d_control = v.d_control; e->d_boxes = v.d_boxes; e->d_seeds = v.d_seeds; e->d_state = v.d_state; e->d_logp = v.d_logp;
-    e->d_detail = v.d_detail;
+    e->d_detail = v.d_detail; e->d_bias_rows = v.d_bias_rows; e->d_logz = v.d_logz;
 }
 DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine::DecLane& ln, int b0) {
     const long E = e->E;
@@ -188,6 +190,7 @@ DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine:
     v.d_control = all.d_control + (long)b0 * kSlots; v.d_boxes = all.d_boxes + (long)b0 * 64 * 10; v.d_seeds = all.d_seeds + b0;
     v.d_logp = all.d_logp + (long)b0 * kTokPerFrame;
     v.d_detail = detail_at(all.d_detail, b0);
+    v.d_bias_rows = all.d_bias_rows + (long)b0 * kBiasRows * kBiasRowLen; v.d_logz = all.d_logz + (long)b0 * kTokPerFrame;
     return v;
 }
 

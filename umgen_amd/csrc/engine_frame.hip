@@ -154,6 +154,7 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     HIPCHK(e, hipMemsetAsync(e->d_nboxes, 0, (size_t)B * sizeof(int), st));
     // log-likelihoods of the new frame: NaN (all bits set) wherever no head is evaluated -- a given pose, given map / bbox3d positions
     if (io.out_logp) HIPCHK(e, hipMemsetAsync(e->d_logp, 0xFF, (size_t)B * kTokPerFrame * sizeof(float), st));
+    if (io.out_logz) HIPCHK(e, hipMemsetAsync(e->d_logz, 0xFF, (size_t)B * kTokPerFrame * sizeof(float), st));      // (NaN exactly where logp is)
     if (io.out_detail) {      // the same for the diagnostics: all bits set is -1 for rank and tokens, NaN for the floats
         const size_t n = (size_t)B * kTokPerFrame * 4;
         HIPCHK(e, hipMemsetAsync(e->d_detail.rank, 0xFF, n, st));
@@ -165,6 +166,12 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         }
     }
     return 0;
+}
+
+// what the ego sampler takes of a biased call: the pose table when the call has one, the scratch rows, logz when asked
+static EgoBias ego_bias(const umgen_engine* e, const FrameIO& io) {
+    const bool pose = ((io.bias_classes >> kBiasPose) & 1) != 0;
+    return EgoBias{pose ? e->d_bias + e->bias_offset(kBiasPose) : nullptr, pose ? e->d_bias_rows : nullptr, io.out_logz ? e->d_logz : nullptr};
 }
 
 int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
@@ -183,7 +190,7 @@ int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         for (int i = 0; i < B * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
         run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, io.out_logp ? e->d_logp : nullptr,
-                    io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0);
+                    io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0, ego_bias(e, io));
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }
@@ -321,7 +328,7 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         e->eng_epoch = 16u;
     }
     ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, io.out_logp ? 1 : 0, io.out_detail ? 1 : 0,
-                      io.out_detail ? io.out_detail->topk : 0};
+                      io.out_detail ? io.out_detail->topk : 0, io.bias_classes, io.out_logz ? 1 : 0};
     e->eng_epoch += (unsigned)(kImgEos + 1) * kEpochPerStep;
     HIPCHK(e, hipMemcpyAsync(e->d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     ctx.n_lanes = (sizeof(T) == 2 && !tr) ? e->lane_count(B) : 1;      // decode lanes: every lane steps its own copy of the state
@@ -554,6 +561,7 @@ int drain_and_download(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     HIPCHK(e, hipEventRecord(e->ev[3], st));
     HIPCHK(e, hipMemcpyAsync(io.out_tokens, e->d_tokens, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
     if (io.out_logp) HIPCHK(e, hipMemcpyAsync(io.out_logp, e->d_logp, (size_t)B * kTokPerFrame * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (io.out_logz) HIPCHK(e, hipMemcpyAsync(io.out_logz, e->d_logz, (size_t)B * kTokPerFrame * sizeof(float), hipMemcpyDeviceToHost, st));
     if (const FrameDetail* d = io.out_detail) {
         const size_t n = (size_t)B * kTokPerFrame * 4;
         HIPCHK(e, hipMemcpyAsync(d->rank, e->d_detail.rank, n, hipMemcpyDeviceToHost, st));
@@ -728,7 +736,7 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
         for (int i = 0; i < BN * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
         run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, io.out_logp ? e->d_logp : nullptr,
-                        io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0);
+                        io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0, ego_bias(e, io));
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)BN * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }

@@ -481,6 +481,10 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dalloc(e, &e->d_detail.entropy, Bm * kTokPerFrame)) return rc;
     if (int rc = dalloc(e, &e->d_detail.topk_tok, Bm * kTokPerFrame * kDetailTopK)) return rc;
     if (int rc = dalloc(e, &e->d_detail.topk_logp, Bm * kTokPerFrame * kDetailTopK)) return rc;
+    // constrained sampling: the call's bias tables, the samplers' scratch rows and logz (likewise with the engine)
+    if (int rc = dalloc(e, &e->d_bias, e->bias_floats())) return rc;
+    if (int rc = dalloc(e, &e->d_bias_rows, Bm * kBiasRows * kBiasRowLen)) return rc;
+    if (int rc = dalloc(e, &e->d_logz, Bm * kTokPerFrame)) return rc;
     return 0;
 }
 

@@ -83,6 +83,15 @@ struct umgen_engine {
     OarState* d_state = nullptr;
     float* d_logp = nullptr;             // [max_batch][2199] log-likelihoods of the frame being generated (umgen_rollout_logp / umgen_frame_logp; SampleArgs::logp)
     DetailOut d_detail{};                // [max_batch][2199] (x kDetailTopK) diagnostics of the frame being generated (umgen_rollout_detail / umgen_frame_detail; SampleArgs::detail)
+    // Constrained sampling (umgen_rollout_biased / umgen_frame_biased), allocated with the engine so that every captured step graph holds the final pointers:
+    // d_bias, the call's tables pose [3][pose_vocab] | map [map_vocab] | bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_table: a class's start);
+    // d_bias_rows [max_batch][kBiasRows][kBiasRowLen], the samplers' scratch rows (SampleArgs::bias_rows); d_logz [max_batch][2199] (SampleArgs::logz)
+    float *d_bias = nullptr, *d_bias_rows = nullptr, *d_logz = nullptr;
+    size_t bias_floats() const { return (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab + cfg.img_vocab; }
+    size_t bias_offset(int cls) const {
+        const size_t o[4] = {0, (size_t)3 * cfg.pose_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab};
+        return o[cls];
+    }
     // umgen_score (engine_score.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
@@ -309,6 +318,8 @@ struct FrameIO {
     int* out_tokens;                             // host [B][2199]
     float* out_logp = nullptr;                   // host [B][2199] or nullptr: log-likelihood of every content token of the new frame (NaN where no head ran)
     const FrameDetail* out_detail = nullptr;     // or nullptr: the diagnostics of every content token of the new frame (-1 / NaN where no head ran)
+    int bias_classes = 0;                        // bit c: the call uploaded a logit-bias table for class c into d_bias (OarState::bias_classes)
+    float* out_logz = nullptr;                   // host [B][2199] or nullptr: logz of every sampled position of the new frame (NaN where no head ran)
     int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
     bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
     bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed
@@ -379,9 +390,9 @@ void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vect
 void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
 void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
-                 float* logp = nullptr, const DetailOut* detail = nullptr, int detail_topk = 0);
+                 float* logp = nullptr, const DetailOut* detail = nullptr, int detail_topk = 0, const EgoBias& eb = EgoBias{});
 void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp,
-                     const DetailOut* detail = nullptr, int detail_topk = 0);
+                     const DetailOut* detail = nullptr, int detail_topk = 0, const EgoBias& eb = EgoBias{});
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
@@ -406,6 +417,7 @@ struct DecView {
     OarState* d_state;
     float* d_logp;
     DetailOut d_detail;
+    float *d_bias_rows, *d_logz;
 };
 // ---- engine_decode.hip ----------------------------------------------------------------------------------------------
 DecView current_view(const umgen_engine* e);

@@ -58,7 +58,17 @@ struct OarState {
     // At the end of the struct (the decode engines read step and epoch at the offsets they know; older initialisers leave both 0)
     int want_detail;
     int detail_topk;
+    // constrained sampling (umgen_rollout_biased / umgen_frame_biased), likewise at the end and 0 from older initialisers: bit c of bias_classes says
+    // that this call has a logit-bias table for class c (kBiasPose ..), want_logz that the samplers also write SampleArgs::logz
+    int bias_classes;
+    int want_logz;
 };
+
+// Logit-bias classes: the bit of a token class in OarState::bias_classes is 1 << class; map / bbox3d / image are SampleArgs::mod.  The tables of a call lie
+// back to back on the device: pose [3][pose_vocab] | map [map_vocab] | bbox3d [11][bbox3d_vocab] | image [img_vocab]
+enum { kBiasPose = 0, kBiasMap = 1, kBiasBox = 2, kBiasImg = 3 };
+constexpr int kBiasRowLen = 8192;   // a scratch row holds the largest vocabulary the samplers take
+constexpr int kBiasRows = 3;        // scratch rows per scene: the biased AR and TAR rows of the token sampler (0, 1), the three pose rows of the ego sampler
 
 // Diagnostics of a generated token (umgen_rollout_detail / umgen_frame_detail, block_detail in frame.hip), device buffers: rank, mass_above, entropy
 // [B][2199]; topk_tok, topk_logp [B][2199][kDetailTopK] -- a call that lists K < kDetailTopK tokens writes the first K entries of a position.
@@ -97,6 +107,16 @@ struct SampleArgs {
                                //     -, 7: unused since round 5 -- more than 64 ties at the k-th logit are sampled by an exhaustive walk, frame.hip)
     float* logp;               // [B][2199] or nullptr: log softmax(AR row over [0, vocab))[token the step settled on], written when st->want_logp
     DetailOut detail;          // the same token's diagnostics on the same row, written when st->want_detail
+    const float* bias;         // the bias table of this step's class: [vocab] (map, image) or [11][vocab] (bbox3d, row k % 11); read when bit `mod` of st->bias_classes is set
+    float* bias_rows;          // [B][kBiasRows][kBiasRowLen] scratch: w = v + r of the AR row (row 0) and of the TAR row of a resample (row 1), written and read by the scene's block
+    float* logz;               // [B][2199]: lse(w) - lse(v) of the AR row (+0.0 for a class without a table), written when st->want_logz
+};
+
+// what the ego sampler needs of a biased call (all null: the plain call)
+struct EgoBias {
+    const float* bias = nullptr;   // [3][vocab] or nullptr
+    float* rows = nullptr;         // [B][kBiasRows][kBiasRowLen] scratch, row jq of scene b
+    float* logz = nullptr;         // [B][2199] or nullptr: entry [b][jq]
 };
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);
@@ -127,7 +147,10 @@ void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts
 // logp: nullptr, or [B][2199] -- entry [b][jq] receives log softmax(head_ego row)[pose token jq of scene b]
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
                        const int* forced, int* out_tokens, int B, int* overflow, float* logp = nullptr, const DetailOut* detail = nullptr,
-                       int detail_topk = 0);   // detail (or nullptr): entry [b][jq] receives the diagnostics of pose token jq on its head_ego row
+                       int detail_topk = 0, const EgoBias& eb = EgoBias{});   // detail (or nullptr): entry [b][jq] receives the diagnostics of pose token jq on its head_ego row
+// test hook: block_sample on n rows w = logits + bias (their own bias rows [n][V], scratch rows [n][kBiasRowLen]) with given uniforms and one masked index
+void launch_sample_dbg_biased(hipStream_t s, const float* logits, const float* bias, float* rows, int V, const SamplerParams& sp, int k, float p, const float* u,
+                              int mask_idx, int* out, int* overflow, int n);
 // ego query rows: egoe[j] + spe[j] + tpe[T-1]; item_T [B] on the device (or nullptr): item i's own window length instead of T
 void launch_ego_queries(hipStream_t s, const EmbedTables& tb, int B, int T, float* x, const int* item_T = nullptr);
 

@@ -404,10 +404,15 @@ __device__ int block_sample_topp(const float* __restrict__ logits, int V, float 
         const float target = mul_rn(u, t2);
         float cc = 0.f;
         int res = sh.ix[n - 1];
+        bool hit = false;
         for (int i = 0; i < n; ++i) {
             cc = add_rn(cc, sh.pr[i]);
-            if (cc > target) { res = sh.ix[i]; break; }
+            if (cc > target) { res = sh.ix[i]; hit = true; break; }
         }
+        // no prefix sum exceeded the target: the last entry of the walk that may be drawn at all.  With p >= 1 the walk covers every entry, the banned
+        // (-inf) and the masked ones behind the others with probability 0; on a row of finite logits without a mask this is entry n - 1 as before
+        for (int i = n - 1; !hit && i >= 0; --i)
+            if (sh.ix[i] != mask_idx && logits[sh.ix[i]] > -INFINITY) { res = sh.ix[i]; break; }
         sh.result = res;
     }
     __syncthreads();
@@ -613,6 +618,56 @@ __device__ float block_logp(const float* __restrict__ row, int V, int tok) {
     return sub_rn(sub_rn(row[tok], mx), logf(total));
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// constrained sampling: the biased row w = v + r of a class with a logit-bias table, and logz = lse(w) - lse(v)
+// ---------------------------------------------------------------------------------------------------------
+// w[n] = v[n] + r[n] for n < V (one fp32 add, round to nearest; -inf where r[n] is -inf: a ban) into the block's scratch row, then a barrier: the row is
+// written and read by this workgroup only, and the samplers take it through the one row pointer they always took.  All 256 threads call.
+__device__ inline const float* biased_row(const float* __restrict__ v, const float* __restrict__ r, int V, float* w) {
+    for (int i = threadIdx.x; i < V; i += 256) {
+        const float ri = r[i];
+        w[i] = ri == -INFINITY ? -INFINITY : add_rn(v[i], ri);
+    }
+    __syncthreads();
+    return w;
+}
+
+// m + log S of row[0 .. V) with m and S formed exactly as block_logp forms them -- the same operations in the same order, columns >= V never read -- for
+// the samplers' 256-thread block (all threads call, all get the value).  red: the call's own reduction words (a second call takes another pair)
+__device__ float block_lse(const float* __restrict__ row, int V, float (*red)[4]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float v[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int idx = tid + 256 * i;
+        v[i] = idx < V ? row[idx] : -INFINITY;
+    }
+    float mx = v[0];
+#pragma unroll
+    for (int i = 1; i < 32; ++i) mx = fmaxf(mx, v[i]);
+    mx = wave_max(mx);
+    if (lane == 0) red[0][wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+        if (tid + 256 * i < V) s = add_rn(s, exp_det(sub_rn(v[i], mx)));
+    s = wave_sum(s);
+    if (lane == 0) red[1][wave] = s;
+    __syncthreads();
+    const float total = add_rn(add_rn(add_rn(red[1][0], red[1][1]), red[1][2]), red[1][3]);
+    return add_rn(mx, logf(total));
+}
+// logz = lse(w) - lse(v): the log of sum_n softmax(v)[n] exp(r[n]) -- for a table of bans the log of the model's mass on the allowed set.  Its bits are a
+// function of (v, r, V) alone; w == v (an all-zero table) gives exactly +0.0.  w holds at least one entry > -inf (the tables are checked on the host).
+__device__ float block_logz(const float* __restrict__ v, const float* __restrict__ w, int V) {
+    __shared__ float red[4][4];
+    const float lw = block_lse(w, V, red);
+    const float lv = block_lse(v, V, red + 2);
+    return sub_rn(lw, lv);
+}
+
 // The diagnostics of umgen_score_detail for the row a sampler drew from, for the samplers' 256-thread block (all threads call; thread 0 writes
 // entry `at` of the buffers): with t = row[tok], m the row maximum and S = sum exp(v - m),
 //   rank = #{n : v[n] > t};  mass_above = A / Z, A = sum over v > t of exp((v - m) / tau), Z = the same over all;
@@ -717,11 +772,21 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     const int topk = a.mod == 1 ? sp.top_k_map : (a.mod == 3 ? sp.topk_image : sp.top_k);
     // top-p: the image head receives topk_image as its "p" (UMGen.py:1133) => the whole distribution is kept
     const float topp = a.mod == 1 ? sp.p_map : (a.mod == 3 ? (float)sp.topk_image : sp.p);
-    int tok = block_sample(sp, lg, a.vocab, topk, topp, rng_uniform(seed, frame, pos1, DRAW_MAIN), -1, sh, a.counters + 7);
     int off, k;
     if (a.mod == 1) { off = kOffMap; k = j - kMapC0; }
     else if (a.mod == 2) { off = kOffBox; k = j - kBoxC0; }
     else { off = kOffImg; k = j - kImgC0; }
+    // Constrained sampling (OarState::bias_classes, block-uniform, 0 unless the call brought a table for this class): every sampler of this step reads
+    // w = v + r instead of v, r the class row of the position (bbox3d: attribute k % 11) -- the AR row here, the TAR row inside the two resamples.
+    // lp and the diagnostics below stay on v.
+    const bool biased = ((a.st->bias_classes >> a.mod) & 1) != 0, want_logz = a.st->want_logz != 0;
+    const float* rb = nullptr;
+    const float* lw = lg;
+    if (biased) {
+        rb = a.bias + (a.mod == 2 ? (long)(k % kSlotLen) * a.vocab : 0L);
+        lw = biased_row(lg, rb, a.vocab, a.bias_rows + (long)b * kBiasRows * kBiasRowLen);
+    }
+    int tok = block_sample(sp, lw, a.vocab, topk, topp, rng_uniform(seed, frame, pos1, DRAW_MAIN), -1, sh, a.counters + 7);
     int* toks = a.tokens + (long)b * kTokPerFrame;
     int prev = kBoxPad;
     if (a.mod == 2) {
@@ -730,14 +795,21 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
         if (use_control) {   // UMGen.py:1083-1089
             const int object_id = (pos1 - 1032) / kSlotLen;
             if (object_id < kSlots && a.control_slot[b * kSlots + object_id]) {
-                tok = block_sample(sp, lt, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_CONTROL), a.vocab - 1, sh, a.counters + 7);
+                const float* ltw = biased ? biased_row(lt, rb, a.vocab, a.bias_rows + ((long)b * kBiasRows + 1) * kBiasRowLen) : lt;
+                tok = block_sample(sp, ltw, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_CONTROL), a.vocab - 1, sh, a.counters + 7);
                 if (threadIdx.x == 0) atomicAdd(a.counters + 1, 1);
             }
         }
         if (tok == kBoxPad && sp.merge_ar_tar && prev != kBoxPad && !sp.only_ar) {   // UMGen.py:1092-1104
-            tok = block_sample(sp, lt, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_PAD_AVOID), -1, sh, a.counters + 7);
+            const float* ltw = biased ? biased_row(lt, rb, a.vocab, a.bias_rows + ((long)b * kBiasRows + 1) * kBiasRowLen) : lt;
+            tok = block_sample(sp, ltw, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_PAD_AVOID), -1, sh, a.counters + 7);
             if (threadIdx.x == 0) atomicAdd(a.counters + 0, 1);
         }
+    }
+    // logz of the AR row, also where the token came from the TAR head (like lp); +0.0 for a class without a table
+    if (want_logz) {
+        const float lz = biased ? block_logz(lg, lw, a.vocab) : 0.f;
+        if (threadIdx.x == 0) a.logz[(long)b * kTokPerFrame + off + k] = lz;
     }
     // The token is settled (main draw, control or pad-avoid resample; the forced token under teacher forcing): its log-likelihood under the
     // plain AR row -- also where the token came from the TAR head -- before the rule constraint may blank the slot: the drawn tokens are what
@@ -802,11 +874,18 @@ void launch_sample_token(hipStream_t s, const SampleArgs& a, int B) { hipLaunchK
 __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict__ logits, int vocab, SamplerParams sp,
                                                          const unsigned long long* __restrict__ seeds, int frame_idx,
                                                          const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow,
-                                                         float* __restrict__ logp, DetailOut detail, int detail_topk) {
+                                                         float* __restrict__ logp, DetailOut detail, int detail_topk, EgoBias eb) {
     __shared__ SamplerLds sh;
     const int b = blockIdx.x / 3, jq = blockIdx.x % 3;
-    int tok = block_sample(sp, logits + (long)blockIdx.x * vocab, vocab, sp.top_k, sp.p,
+    // a pose table (constrained sampling): the draw reads w = v + r[jq]; lp and the diagnostics stay on v
+    const float* lw = logits + (long)blockIdx.x * vocab;
+    if (eb.bias) lw = biased_row(lw, eb.bias + (long)jq * vocab, vocab, eb.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
+    int tok = block_sample(sp, lw, vocab, sp.top_k, sp.p,
                            rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN), -1, sh, overflow);
+    if (eb.logz) {
+        const float lz = eb.bias ? block_logz(logits + (long)blockIdx.x * vocab, lw, vocab) : 0.f;
+        if (threadIdx.x == 0) eb.logz[(long)b * kTokPerFrame + jq] = lz;
+    }
     if (forced) tok = forced[(long)b * kTokPerFrame + jq];
     if (threadIdx.x == 0) out_tokens[b * 3 + jq] = tok;
     if (logp) {
@@ -816,9 +895,9 @@ __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict
     if (detail.rank) block_detail(logits + (long)blockIdx.x * vocab, vocab, tok, detail_topk, sp.temperature, detail, (long)b * kTokPerFrame + jq);
 }
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow, float* logp, const DetailOut* detail, int detail_topk) {
+                       const int* forced, int* out_tokens, int B, int* overflow, float* logp, const DetailOut* detail, int detail_topk, const EgoBias& eb) {
     hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow, logp,
-                       detail ? *detail : DetailOut{}, detail_topk);
+                       detail ? *detail : DetailOut{}, detail_topk, eb);
 }
 
 // test hook (debug_gemm_attn.hip): the top-k sampler on n independent logit rows with given uniforms
@@ -843,6 +922,20 @@ __global__ __launch_bounds__(256) void sample_dbg_kernel(const float* __restrict
 void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerParams& sp, int k, float p, const float* u, int mask_idx, int* out,
                        int* overflow, int n) {
     hipLaunchKernelGGL(sample_dbg_kernel, dim3(n), dim3(256), 0, s, logits, V, sp, k, p, u, mask_idx, out, overflow);
+}
+
+// test hook (debug_decode.hip): the same on the rows w = logits + bias, formed in the block's scratch row as the samplers of a biased call form them
+__global__ __launch_bounds__(256) void sample_dbg_biased_kernel(const float* __restrict__ logits, const float* __restrict__ bias, float* __restrict__ rows, int V,
+                                                                SamplerParams sp, int k, float p, const float* __restrict__ u, int mask_idx,
+                                                                int* __restrict__ out, int* overflow) {
+    __shared__ SamplerLds sh;
+    const float* lw = biased_row(logits + (long)blockIdx.x * V, bias + (long)blockIdx.x * V, V, rows + (long)blockIdx.x * kBiasRowLen);
+    const int tok = block_sample(sp, lw, V, k, p, u[blockIdx.x], mask_idx, sh, overflow);
+    if (threadIdx.x == 0) out[blockIdx.x] = tok;
+}
+void launch_sample_dbg_biased(hipStream_t s, const float* logits, const float* bias, float* rows, int V, const SamplerParams& sp, int k, float p, const float* u,
+                              int mask_idx, int* out, int* overflow, int n) {
+    hipLaunchKernelGGL(sample_dbg_biased_kernel, dim3(n), dim3(256), 0, s, logits, bias, rows, V, sp, k, p, u, mask_idx, out, overflow);
 }
 
 // test hook (debug_decode.hip): check_collision_dev on box set b = boxes[b][0 .. counts[b]), one block per set; thread 0 evaluates it with

@@ -116,6 +116,49 @@ class Engine:
         logp = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
         return logp, _lib.LogpOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
 
+    @staticmethod
+    def _logz_out(lead: Tuple[int, ...]):
+        """(mod -> float32 [*lead, S_mod] filled with NaN, the umgen_logz_out that points at them)"""
+        logz = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
+        return logz, _lib.LogzOut(**{f"logz_{m}": logz[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
+
+    BIAS_ROWS = {"pose": 3, "map": 1, "bbox3d": 11, "image": 1}
+
+    def _bias_args(self, call: str, logit_bias):
+        """logit_bias of a rollout / frame -- class -> float array [vocab] (map, image), [3, vocab] (pose) or [11, vocab] (bbox3d); a [vocab] array for
+        pose / bbox3d is every row's -- checked before anything reaches the device: class names, shapes, dtype, NaN / +inf, a row without an allowed
+        token.  Returns (the umgen_logit_bias or None, the arrays it points at)."""
+        if logit_bias is None:
+            return None, None
+        if not hasattr(logit_bias, "items"):
+            raise UMGenError(f"{call}: logit_bias is a dict class -> array, not {type(logit_bias).__name__}")
+        vocab = {"pose": self.cfg.pose_vocab_size, "map": self.cfg.map_vocab_size, "bbox3d": self.cfg.bbox3d_vocab_size, "image": self.cfg.img_vocab_size}
+        keep = {}
+        for m, t in logit_bias.items():
+            if m not in vocab:
+                raise UMGenError(f"{call}: logit_bias has no class {m!r} (one of {MOD_ORDER})")
+            if t is None:
+                continue
+            a = np.asarray(t)
+            if a.dtype.kind != "f":
+                raise UMGenError(f"{call}: logit_bias[{m}] has dtype {a.dtype}, expected a float type")
+            rows, V = self.BIAS_ROWS[m], vocab[m]
+            if a.shape == (V,) and rows > 1:
+                a = np.broadcast_to(a, (rows, V))
+            if a.shape != ((rows, V) if rows > 1 else (V,)):
+                raise UMGenError(f"{call}: logit_bias[{m}] has shape {np.shape(t)}, expected {(rows, V) if rows > 1 else (V,)}" + (f" or {(V,)}" if rows > 1 else ""))
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            bad = np.flatnonzero(np.isnan(a.reshape(-1)) | np.isposinf(a.reshape(-1)))
+            if bad.size:
+                raise UMGenError(f"{call}: logit_bias[{m}] row {int(bad[0]) // V} index {int(bad[0]) % V} is {a.reshape(-1)[bad[0]]} (entries are finite or -inf)")
+            empty = np.flatnonzero(np.isneginf(a.reshape(rows, V)).all(axis=1))
+            if empty.size:
+                raise UMGenError(f"{call}: logit_bias[{m}] row {int(empty[0])} bans every token")
+            keep[m] = a
+        if not keep:
+            return None, None
+        return _lib.LogitBias(**{m: a.ctypes.data_as(C.POINTER(C.c_float)) for m, a in keep.items()}), keep
+
     # the diagnostics of score(detail=...) and of rollout / frame (return_detail): key -> (field stem of the C struct, dtype); the "topk_" keys are lists
     _DETAIL_FIELDS = {"rank": ("rank", np.int32), "mass_above": ("mass_above", np.float32), "entropy": ("entropy", np.float32),
                       "topk_tokens": ("topk_tok", np.int32), "topk_logp": ("topk_logp", np.float32)}
@@ -192,7 +235,7 @@ class Engine:
                 input_cond_frames: int = -1, init_tokens: Optional[Dict[str, np.ndarray]] = None,
                 control_test: bool = False, seeds: Optional[Sequence[int]] = None,
                 sampling: Optional[RolloutConfig] = None, return_logp: bool = False, samples: Optional[int] = None,
-                return_detail: bool = False, topk: int = 0):
+                return_detail: bool = False, topk: int = 0, logit_bias: Optional[Dict[str, np.ndarray]] = None, return_logz: bool = False):
         """tokens: mod -> int64 [B, T, S_mod].  Returns mod -> int64 [B, input_cond_frames + new_frames, S_mod].
         samples=N (umgen_rollout_fan): N sampled futures of every scene off one pass over its history.  seeds: [B, N] or flat B*N (default 0), branch
         (b, s) at b*N + s; init_tokens stay per scene, a scene's branches share them.  Returns mod -> int64 [B, N, input_cond_frames + new_frames, S_mod],
@@ -205,7 +248,14 @@ class Engine:
         return_detail (with topk <= 16): the result gains, as its last element, the diagnostics of every generated token (umgen_rollout_detail) keyed like
         score(detail=True)'s: "rank" int64, "mass_above" (at the rollout's own temperature), "entropy", and with topk > 0 "topk_tokens" int64 [.., S_mod, topk]
         and "topk_logp"; each mod -> [B, new_frames, S_mod] ([B, N, new_frames, S_mod] with samples).  They are taken from the fp32 row the decode step
-        sampled from, for the token logp scores; -1 / NaN where logp is NaN.  Tokens and logp are the same bits with or without them."""
+        sampled from, for the token logp scores; -1 / NaN where logp is NaN.  Tokens and logp are the same bits with or without them.
+        logit_bias (umgen_rollout_biased; umgen_amd.constraints builds the tables): class -> float array, "pose" [3, vocab], "map" [vocab], "bbox3d" [11, vocab]
+        (row = attribute, 10 the category token), "image" [vocab]; a [vocab] array for pose / bbox3d is every row's.  Every sampler of every decode step draws from
+        logits + bias of its class; -inf bans a token from every draw (not from control / given / forced tokens, nor from the rule constraint's pads).  One set of
+        tables per call.  logp and the diagnostics stay on the model's own logits.
+        return_logz: the result gains, behind logp, mod -> float32 shaped like logp: lse(logits + bias) - lse(logits) of the AR row per sampled position (+0.0 for
+        a class without a table, NaN where logp is NaN); for bans the log of the model's mass on the allowed tokens."""
+        bias_struct, bias_keep = self._bias_args("rollout", logit_bias)
         if return_detail or topk:
             topk = self._gen_detail_args("rollout", topk, sampling or self.cfg)
             return_detail = True
@@ -237,6 +287,19 @@ class Engine:
         args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
+        if bias_struct is not None or return_logz:
+            logp, lp = self._logp_out(lead + (new_frames,)) if return_logp else (None, None)
+            logz, lz = self._logz_out(lead + (new_frames,)) if return_logz else (None, None)
+            dbufs, det = self._gen_detail_out(lead + (new_frames,), topk) if return_detail else (None, None)
+            shared = C.c_int32(-1)
+            ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+            self._check(self.lib.umgen_rollout_biased(self._h, B, samples or 1, *args[2:], ref(lp), C.byref(shared), topk, ref(det), ref(bias_struct), ref(lz)),
+                        "rollout")
+            del keep, bias_keep
+            if samples is not None:
+                self.last_shared_slots = int(shared.value)
+            res = (outs,) + ((logp,) if return_logp else ()) + ((logz,) if return_logz else ()) + ((self._detail_result(dbufs),) if return_detail else ())
+            return res if len(res) > 1 else outs
         if samples is not None or return_detail:
             logp, lp = self._logp_out(lead + (new_frames,)) if return_logp else (None, None)
             shared = C.c_int32(-1)
@@ -263,14 +326,16 @@ class Engine:
     def frame(self, window: Dict[str, np.ndarray], frame_idx: int = 0, ctrl: Optional[Dict[str, np.ndarray]] = None,
               control_test: bool = False, seed: int = 0, sampling: Optional[RolloutConfig] = None,
               forced: Optional[Dict[str, np.ndarray]] = None, trace: bool = False, given: Optional[Dict[str, np.ndarray]] = None,
-              logp: bool = False, detail: bool = False, topk: int = 0):
+              logp: bool = False, detail: bool = False, topk: int = 0, logit_bias: Optional[Dict[str, np.ndarray]] = None, logz: bool = False):
         """One frame of one scene.  window: mod -> [T, S_mod].  Returns (tokens dict, trace dict or None).
         given: {"map": [1024]} or {"map": ..., "bbox3d": [660]}: the frame's GIVEN tokens (init_tokens of `rollout` for one frame).
         logp: the trace dict (created if need be) gains "logp": mod -> float32 [S_mod], `rollout(return_logp=True)` for this frame; under
         `forced` the values are those of the forced tokens: a step-by-step `score`.
         detail (with topk <= 16): the trace dict gains "detail", `rollout(return_detail=True, topk=topk)` for this frame: key -> mod -> [S_mod] (lists
-        [S_mod, topk])."""
+        [S_mod, topk]).
+        logit_bias / logz: `rollout(logit_bias=..., return_logz=True)` for this frame (umgen_frame_biased); the trace dict gains "logz": mod -> float32 [S_mod]."""
         cfg = self.cfg
+        bias_struct, bias_keep = self._bias_args("frame", logit_bias)
         if detail or topk:
             topk = self._gen_detail_args("frame", topk, sampling or cfg)
             detail = True
@@ -308,8 +373,15 @@ class Engine:
         args = (self._h, T, _p64(w["pose"]), _p64(w["map"]), _p64(w["bbox3d"]), _p64(w["image"]), _p64(cp), _p64(cb),
                 int(control_test), C.byref(smp), frame_idx, C.byref(tr) if tr is not None else None,
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
-        lpv = dbufs = None
-        if detail:
+        lpv = dbufs = lzv = None
+        if bias_struct is not None or logz:
+            lpv, lp = self._logp_out(()) if logp else (None, None)
+            lzv, lz = self._logz_out(()) if logz else (None, None)
+            dbufs, det = self._gen_detail_out((), topk) if detail else (None, None)
+            ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+            self._check(self.lib.umgen_frame_biased(*args, ref(lp), topk, ref(det), ref(bias_struct), ref(lz)), "frame")
+            del bias_keep
+        elif detail:
             lpv, lp = self._logp_out(()) if logp else (None, None)
             dbufs, det = self._gen_detail_out((), topk)
             self._check(self.lib.umgen_frame_detail(*args, C.byref(lp) if lp is not None else None, topk, C.byref(det)), "frame")
@@ -326,6 +398,9 @@ class Engine:
         if lpv is not None:
             tbuf = tbuf if tbuf is not None else {}
             tbuf["logp"] = lpv
+        if lzv is not None:
+            tbuf = tbuf if tbuf is not None else {}
+            tbuf["logz"] = lzv
         if dbufs is not None:
             tbuf = tbuf if tbuf is not None else {}
             tbuf["detail"] = self._detail_result(dbufs)

@@ -57,6 +57,8 @@ def build_parser():
                    help="bf16: production; fp16: the reference's own autocast arithmetic; fp32: exact parity mode")
     p.add_argument("--batch", type=int, default=1, help="scenes rolled out together per GPU")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--ban_category", action="append", default=[], metavar="NAME",
+                   help="constrained generation: no generated agent of this category (vehicle / bicycle / pedestrian); repeatable")
     return p
 
 
@@ -150,12 +152,16 @@ def main(argv=None):
         nf = new_frames if new_frames >= 0 else toks["pose"].shape[1] - icf
         key = (icf, nf, tuple(sorted((k, v.shape[1:]) for k, v in ctl.items())) if ctl else None)
         groups.setdefault(key, []).append(sid)
+    bias_kw = {}
+    if args.ban_category:
+        from .constraints import ban_categories
+        bias_kw["logit_bias"] = ban_categories(args.ban_category, vocab=cfg.bbox3d_vocab_size)
     for (icf, nf, _), sids in groups.items():
         def rollout_fn(toks, seeds, scene_ids):
             ctls = [scenes[s][2] for s in scene_ids]
             init = {k: np.concatenate([c[k] for c in ctls]) for k in ctls[0]} if ctls[0] else None
             return eng.rollout(toks, nf, cond_frames=T_hist, input_cond_frames=icf, init_tokens=init,
-                               control_test=control and init is not None and "bbox3d" in init, seeds=seeds)
+                               control_test=control and init is not None and "bbox3d" in init, seeds=seeds, **bias_kw)
         out = sharded_rollout(rollout_fn, [scenes[s][1] for s in sids], base_seed=args.seed, batch=args.batch,
                               device="cuda" if world > 1 else "cpu", scene_ids=sids, pass_ids=True)
         for pos in scene_partition(len(sids), world, rank):                   # every rank writes the scenes it rolled out

@@ -138,7 +138,7 @@ class UMGen(nn.Module):
                   input_cond_tokens: Optional[Dict[str, torch.Tensor]] = None,
                   init_tokens: Optional[Dict[str, torch.Tensor]] = None, cond_on_tar: bool = False,
                   test_map_affine: bool = False, max_objects=100, control_test=False, return_logp: bool = False,
-                  num_samples: Optional[int] = None, return_detail: bool = False, topk: int = 0, **kwargs):
+                  num_samples: Optional[int] = None, return_detail: bool = False, topk: int = 0, logit_bias=None, return_logz: bool = False, **kwargs):
         """UMGen.inference (UMGen.py:1542-1671).  ``cond_on_par`` / ``infer_from_gt`` are swallowed like the reference.
         return_logp (extension): returns (tokens, mod -> torch.float32 [B, new_frames, S_mod]), the log-likelihood of every generated token
         (Engine.rollout's return_logp; NaN on controlled / given positions), beside the tokens it returns today.
@@ -146,8 +146,17 @@ class UMGen(nn.Module):
         [B, N, T, S_mod]; with return_logp (tokens, logp) where logp holds mod -> torch.float32 [B, N, new_frames, S_mod] and "total", torch.float64
         [B, N, new_frames]: the host sum over a frame's finite entries, the ranking key for best-of-N.  seeds: [B, N] or flat B*N (default seed + i).
         return_detail=True, topk=K (extension): the result gains, as its last element, Engine.rollout's detail dict -- rank, mass_above, entropy and the K most
-        likely tokens of every generated token, from the decode step that sampled it -- as key -> mod -> torch tensor; combines with return_logp and num_samples."""
+        likely tokens of every generated token, from the decode step that sampled it -- as key -> mod -> torch tensor; combines with return_logp and num_samples.
+        logit_bias=tables, return_logz=True (extension): constrained generation (Engine.rollout's logit_bias / return_logz; umgen_amd.constraints builds the tables,
+        arrays or torch tensors).  logz follows logp in the result, mod -> torch.float32 shaped like logp; combines with return_logp, num_samples and return_detail."""
         return_detail = bool(return_detail) or bool(topk)
+        extra = {}      # (only what the call asks for reaches Engine.rollout: the plain calls stay the plain calls)
+        if logit_bias is not None:
+            if not hasattr(logit_bias, "items"):
+                raise UMGenError(f"logit_bias is a dict class -> array, not {type(logit_bias).__name__}")
+            extra["logit_bias"] = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in logit_bias.items()}
+        if return_logz:
+            extra["return_logz"] = True
         as_torch = lambda d: {k: {m: torch.from_numpy(v) for m, v in per.items()} for k, per in d.items()}      # noqa: E731
         if pred_task != "pose_map_bbox3d_image":
             raise UMGenError(f"pred_task={pred_task!r}: only 'pose_map_bbox3d_image' (the evaluation task) is implemented")
@@ -170,14 +179,16 @@ class UMGen(nn.Module):
             seeds = kwargs.get("seeds", [self.seed + i for i in range(B * N)])
             out = self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames, init_tokens=init,
                                       control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp), samples=N,
-                                      return_detail=return_detail, topk=topk)
-            if not return_logp and not return_detail:
+                                      return_detail=return_detail, topk=topk, **extra)
+            if not return_logp and not return_detail and not return_logz:
                 return {m: torch.from_numpy(v) for m, v in out.items()}
             res = [{m: torch.from_numpy(v) for m, v in out[0].items()}]
             if return_logp:
                 lp = {m: torch.from_numpy(v) for m, v in out[1].items()}
                 lp["total"] = torch.from_numpy(sum(np.where(np.isfinite(v), v, 0).astype(np.float64).sum(axis=-1) for v in out[1].values()))
                 res.append(lp)
+            if return_logz:
+                res.append({m: torch.from_numpy(v) for m, v in out[2 if return_logp else 1].items()})
             if return_detail:
                 res.append(as_torch(out[-1]))
             return tuple(res)
@@ -186,12 +197,14 @@ class UMGen(nn.Module):
         seeds = kwargs.get("seeds", [self.seed + i for i in range(B)])
         out = self.engine.rollout(toks, new_frames, cond_frames=cond_frames, input_cond_frames=input_cond_frames,
                                   init_tokens=init, control_test=bool(control_test), seeds=seeds, return_logp=bool(return_logp),
-                                  return_detail=return_detail, topk=topk)
-        if not return_logp and not return_detail:
+                                  return_detail=return_detail, topk=topk, **extra)
+        if not return_logp and not return_detail and not return_logz:
             return out
         res = [out[0]]
         if return_logp:
             res.append({m: torch.from_numpy(v) for m, v in out[1].items()})
+        if return_logz:
+            res.append({m: torch.from_numpy(v) for m, v in out[2 if return_logp else 1].items()})
         if return_detail:
             res.append(as_torch(out[-1]))
         return tuple(res)
