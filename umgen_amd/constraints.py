@@ -144,3 +144,37 @@ def pose_limits(dx: Optional[Tuple[float, float]] = None, dy: Optional[Tuple[flo
     except ValueError:
         raise ValueError("pose_limits: no pose token decodes into the envelope of one component") from None
     return {"pose": t}
+
+
+def log_importance_weight(tokens: Dict[str, np.ndarray], logz: Dict[str, np.ndarray], tables: Optional[Tables]) -> np.ndarray:
+    """The log importance weight of every generated frame of a constrained rollout against the model: the sum over the frame's sampled positions
+    of ``logz - r[tok]`` (include/umgen.h), float64 [..., new_frames].
+
+    ``tokens`` and ``logz`` are what ``Engine.rollout(clip, F, logit_bias=tables, return_logz=True)`` returned: mod -> int [..., T, S_mod] whose LAST
+    ``F`` frames are the generated ones (only those are read), and mod -> float [..., F, S_mod].  Positions whose logz is NaN (no sampler ran: a
+    controlled pose, given tokens) are skipped; a class without a table has r = 0.
+
+    Exact under these conditions only: the rollout drew with an UNTRUNCATED sampler (today: ``sample_method="topp"`` with p = p_map = 1) at temperature
+    1, and no token came from a control or pad-avoid resample (``only_ar`` and no control slots) -- then the proposal's density of a drawn token is
+    softmax(v + r)[tok] = exp(lp + r[tok] - logz), and model / proposal = exp(logz - r[tok]).  A truncated or tempered sampler renormalises
+    differently, and a resampled token was drawn from another head; neither is accounted for here."""
+    tables = merge(tables)
+    total = None
+    for mod in CLASSES:
+        lz = np.asarray(logz[mod], dtype=np.float64)
+        F = lz.shape[-2]
+        tok = np.asarray(tokens[mod])
+        if tok.shape[-1] != lz.shape[-1] or tok.shape[:-2] != lz.shape[:-2] or tok.shape[-2] < F:
+            raise ValueError(f"{mod}: tokens {tok.shape} and logz {lz.shape} do not belong together")
+        tok = tok[..., tok.shape[-2] - F:, :].astype(np.int64)
+        r = np.zeros(lz.shape, np.float64)
+        if mod in tables:
+            t = tables[mod].reshape(ROWS[mod], -1).astype(np.float64)
+            if tok.size and (tok.min() < 0 or tok.max() >= t.shape[1]):
+                raise ValueError(f"{mod}: token outside the table's [0, {t.shape[1]})")
+            row = np.arange(lz.shape[-1]) % ROWS[mod]      # pose component / bbox3d attribute of the position; 0 for the one-row classes
+            r = t[np.broadcast_to(row, tok.shape), tok]
+        skip = np.isnan(lz)
+        w = np.where(skip, 0.0, lz - np.where(skip, 0.0, r)).sum(axis=-1)
+        total = w if total is None else total + w
+    return total

@@ -35,6 +35,13 @@ def str2bool(v):   # evaluate.py declares these flags with type=bool (True for A
     return str(v).lower() not in ("0", "false", "no", "")
 
 
+def positive_int(v):
+    k = int(v)
+    if k < 1:
+        raise argparse.ArgumentTypeError(f"{v!r} is not a positive integer")
+    return k
+
+
 def build_parser():
     p = argparse.ArgumentParser("umgen_amd.evaluate")
     p.add_argument("--pred_task", type=str, default="pose_map_bbox3d_image")
@@ -47,7 +54,9 @@ def build_parser():
     p.add_argument("--output_path", default="output/UMGen/")
     p.add_argument("--launcher", type=str, default=None)
     # sampler (config.py:442-463 infer_task_config)
-    p.add_argument("--top_k", type=int, default=5)
+    p.add_argument("--top_k", type=positive_int, default=5, help="top-k of the pose and bbox3d heads (the engine takes 1 .. 16)")
+    p.add_argument("--top_k_map", type=positive_int, default=5, help="top-k of the map head")
+    p.add_argument("--topk_image", type=positive_int, default=16, help="top-k of the image head")
     p.add_argument("--top_p", type=float, default=0.4)
     p.add_argument("--sample_method", type=str, default="topk")
     # build-side additions
@@ -75,6 +84,7 @@ def resolve(args):
     else:
         cfg = large_config(n_tar_layer=36 if args.model_scale == "larger" else 24)
     cfg.top_k, cfg.p, cfg.sample_method, cfg.rule_constrain = args.top_k, args.top_p, args.sample_method, bool(args.rule_constrain)
+    cfg.top_k_map, cfg.topk_image = args.top_k_map, args.topk_image
     return cfg, new_frames, input_cond
 
 
