@@ -50,24 +50,31 @@ EmbedTables tables_in(Scratch& s, const umgen_dbg_tables& t) {
     tb.grid_posi = s.in(t.grid_posi, (size_t)kNMap * E * 2);
     return tb;
 }
-// The five arrays of a detail hook: on the host [n] and [n][topk] (in / out: a position no sampled step reaches keeps what it was handed), on the
-// device in the kernels' layout -- the lists kDetailTopK apart, the entries behind topk all bits set, and checked to come back that way
-struct DetailHook {
-    int topk;
+// The side outputs of a sampler hook for n = B * 2199 positions (all in / out: a position no sampled step reaches keeps what it was handed): logp, logz
+// [n] or NULL, and with `detail` the five arrays of the diagnostics, on the host [n] and [n][topk], on the device in the kernels' layout -- the lists
+// kDetailTopK apart, the entries behind topk all bits set, and checked to come back that way.  d: the device bundle, a member not asked for null
+struct SideHook {
     size_t n;
-    int32_t* rank; float *mass_above, *entropy; int32_t* topk_tok; float* topk_logp;
-    DetailOut d{};
-    std::vector<uint32_t> wt, wl;
-    bool sane() const { return rank && mass_above && entropy && topk >= 0 && topk <= kDetailTopK && (topk == 0 || (topk_tok && topk_logp)); }
+    float *logp = nullptr, *logz = nullptr;
+    bool detail = false;
+    int topk = 0;
+    int32_t* rank = nullptr; float *mass_above = nullptr, *entropy = nullptr; int32_t* topk_tok = nullptr; float* topk_logp = nullptr;
+    TokenSide d{};
+    std::vector<uint32_t> wt{}, wl{};
+    void ask_detail(int k, int32_t* r, float* ma, float* en, int32_t* tt, float* tl) { detail = true; topk = k; rank = r; mass_above = ma; entropy = en; topk_tok = tt; topk_logp = tl; }
+    bool sane() const { return !detail || (rank && mass_above && entropy && topk >= 0 && topk <= kDetailTopK && (topk == 0 || (topk_tok && topk_logp))); }
     void widen(const void* host, std::vector<uint32_t>& w) const {
         w.assign(n * kDetailTopK, 0xffffffffu);
         for (size_t i = 0; i < n; ++i) memcpy(&w[i * kDetailTopK], (const uint32_t*)host + i * topk, (size_t)topk * 4);
     }
     void to_device(Scratch& s) {
-        d.rank = s.inout(rank, n * 4); d.mass_above = s.inout(mass_above, n * 4); d.entropy = s.inout(entropy, n * 4);
+        if (logp) d.logp = s.inout(logp, n * 4);
+        if (logz) d.logz = s.inout(logz, n * 4);
+        if (!detail) return;
+        d.detail.rank = s.inout(rank, n * 4); d.detail.mass_above = s.inout(mass_above, n * 4); d.detail.entropy = s.inout(entropy, n * 4);
         if (!topk) return;
         widen(topk_tok, wt); widen(topk_logp, wl);
-        d.topk_tok = s.inout(wt.data(), wt.size() * 4); d.topk_logp = s.inout(wl.data(), wl.size() * 4);
+        d.detail.topk_tok = s.inout(wt.data(), wt.size() * 4); d.detail.topk_logp = s.inout(wl.data(), wl.size() * 4);
     }
     int narrow(void* host, const void* dev, std::vector<uint32_t>& w) const {
         if (down(w.data(), dev, w.size() * 4)) return UMGEN_E_HIP;
@@ -79,18 +86,21 @@ struct DetailHook {
         return UMGEN_OK;
     }
     int to_host() {
-        if (down(rank, d.rank, n * 4) || down(mass_above, d.mass_above, n * 4) || down(entropy, d.entropy, n * 4)) return UMGEN_E_HIP;
+        if ((logp && down(logp, d.logp, n * 4)) || (logz && down(logz, d.logz, n * 4))) return UMGEN_E_HIP;
+        if (!detail) return UMGEN_OK;
+        if (down(rank, d.detail.rank, n * 4) || down(mass_above, d.detail.mass_above, n * 4) || down(entropy, d.detail.entropy, n * 4)) return UMGEN_E_HIP;
         if (!topk) return UMGEN_OK;
-        if (int rc = narrow(topk_tok, d.topk_tok, wt)) return rc;
-        return narrow(topk_logp, d.topk_logp, wl);
+        if (int rc = narrow(topk_tok, d.detail.topk_tok, wt)) return rc;
+        return narrow(topk_logp, d.detail.topk_logp, wl);
     }
 };
-// what a biased token-step hook adds: the class tables on the host (any may be NULL: no bias for that class) and logz [B][2199] (in / out, or NULL)
+// the class tables of a biased token-step hook on the host (any may be NULL: no bias for that class)
 struct BiasHook {
     const float *map, *box /*[11][n_box]*/, *img;
-    float* logz;
 };
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh = nullptr, const BiasHook* bh = nullptr);
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh = nullptr);
+// a hook's positions: B * 2199 (0 for a B the hook refuses anyway)
+inline size_t side_n(int B) { return B < 1 ? 0 : (size_t)B * kTokPerFrame; }
 
 // the body of umgen_dbg_embed_warp and umgen_dbg_embed_warp_slots (warped_all: nullptr, or the host buffer of launch_warp_map's output of that name)
 int embed_warp(int stack, const umgen_dbg_tables* t, const int32_t* pose, const int32_t* map, const int32_t* box, const int32_t* img, int B, int T, int Tfull,
@@ -286,35 +296,42 @@ int umgen_dbg_prefix_kv_to_cache(int prec, const void* qk, const void* vt, int B
 // (logits [j1 - j0][B][ld_logits]).  logits_tar [B][660][n_box], prev_box [B][660], control_slot [B][60], forced [B][2199] (or NULL), seeds [B].
 // In / out: tokens [B][2199], counters [8], n_boxes [B], boxes [B][64][10].  Out: x_next [j1 - j0][B][E] (NaN before every step) and
 // state_log [j1 - j0][3] = OarState step, epoch, done behind every step.
-int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) { return token_steps(t, a, nullptr); }
-// The same with OarState::want_logp = 1 and SampleArgs::logp = logp [B][2199] (in / out: the sampled steps write their position, nothing else changes)
-int umgen_dbg_token_steps_logp(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp) {
-    return logp ? token_steps(t, a, logp) : UMGEN_E_INVALID;
+int umgen_dbg_token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a) {
+    SideHook sh{side_n(a ? a->B : 0)};
+    return token_steps(t, a, sh);
 }
-// ... and with OarState::want_detail = 1, detail_topk = topk and SampleArgs::detail = rank, mass_above, entropy [B][2199], topk_tok, topk_logp [B][2199][topk]
+// The same with OarState::want_logp = 1 and SampleArgs::side.logp = logp [B][2199] (in / out: the sampled steps write their position, nothing else changes)
+int umgen_dbg_token_steps_logp(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp) {
+    SideHook sh{side_n(a ? a->B : 0), logp};
+    return logp ? token_steps(t, a, sh) : UMGEN_E_INVALID;
+}
+// ... and with OarState::want_detail = 1, detail_topk = topk and SampleArgs::side.detail = rank, mass_above, entropy [B][2199], topk_tok, topk_logp [B][2199][topk]
 // (in / out like logp; the lists may be NULL when topk == 0)
 int umgen_dbg_token_steps_detail(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, int topk, int32_t* rank, float* mass_above,
                                  float* entropy, int32_t* topk_tok, float* topk_logp) {
     if (!logp || !a || a->B < 1) return UMGEN_E_INVALID;
-    DetailHook dh{topk, (size_t)a->B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
-    return dh.sane() ? token_steps(t, a, logp, &dh) : UMGEN_E_INVALID;
+    SideHook sh{side_n(a->B), logp};
+    sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
+    return sh.sane() ? token_steps(t, a, sh) : UMGEN_E_INVALID;
 }
 // ... and with the logit-bias tables of a biased call: bias_map [n_map], bias_box [11][n_box], bias_img [n_img] (any may be NULL; entries finite or -inf,
 // every row with an allowed entry) set the classes' bits of OarState::bias_classes, SampleArgs::bias follows the step's mod, bias_rows is the hook's
 // scratch; logz [B][2199] (in / out, or NULL) sets want_logz.  logp may be NULL
 int umgen_dbg_token_steps_biased(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, const float* bias_map, const float* bias_box,
                                  const float* bias_img, float* logz) {
-    const BiasHook bh{bias_map, bias_box, bias_img, logz};
-    return token_steps(t, a, logp, nullptr, &bh);
+    const BiasHook bh{bias_map, bias_box, bias_img};
+    SideHook sh{side_n(a ? a->B : 0), logp, logz};
+    return token_steps(t, a, sh, &bh);
 }
 // ... together with umgen_dbg_token_steps_detail's diagnostics (they stay on the unbiased row)
 int umgen_dbg_token_steps_biased_detail(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, const float* bias_map, const float* bias_box,
                                         const float* bias_img, float* logz, int topk, int32_t* rank, float* mass_above, float* entropy, int32_t* topk_tok,
                                         float* topk_logp) {
     if (!logp || !a || a->B < 1) return UMGEN_E_INVALID;
-    const BiasHook bh{bias_map, bias_box, bias_img, logz};
-    DetailHook dh{topk, (size_t)a->B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
-    return dh.sane() ? token_steps(t, a, logp, &dh, &bh) : UMGEN_E_INVALID;
+    const BiasHook bh{bias_map, bias_box, bias_img};
+    SideHook sh{side_n(a->B), logp, logz};
+    sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
+    return sh.sane() ? token_steps(t, a, sh, &bh) : UMGEN_E_INVALID;
 }
 
 }  // extern "C"
@@ -333,7 +350,7 @@ bool bias_rows_sane(const float* tab, int rows, int V) {
     }
     return true;
 }
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, DetailHook* dh, const BiasHook* bh) {
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh) {
     if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
     // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
     if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
@@ -361,12 +378,11 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     const size_t bn = (size_t)B * 64 * 10, xn = (size_t)B * E;
     OarState s0{};
     s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
-    s0.epoch = a->epoch0; s0.sp = a->sp; s0.want_logp = logp ? 1 : 0;
-    s0.want_detail = dh ? 1 : 0; s0.detail_topk = dh ? dh->topk : 0;
+    s0.epoch = a->epoch0; s0.sp = a->sp; s0.want_logp = sh.logp ? 1 : 0;
+    s0.want_detail = sh.detail ? 1 : 0; s0.detail_topk = sh.topk; s0.want_logz = sh.logz ? 1 : 0;
     if (bh) {
         if (!bias_rows_sane(bh->map, 1, t->n_map) || !bias_rows_sane(bh->box, kSlotLen, t->n_box) || !bias_rows_sane(bh->img, 1, t->n_img)) return UMGEN_E_INVALID;
         s0.bias_classes = (bh->map ? 1 << kBiasMap : 0) | (bh->box ? 1 << kBiasBox : 0) | (bh->img ? 1 << kBiasImg : 0);
-        s0.want_logz = bh->logz ? 1 : 0;
     }
     Scratch s;
     SampleArgs sa{};
@@ -379,14 +395,13 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     if (a->use_forced) sa.forced = s.in(a->forced, tn * 4); else sa.forced = s.raw(tn * 4);   // never read without use_forced
     sa.x_next = s.out(xn * 4); sa.tokens = s.inout(a->tokens, tn * 4); sa.counters = s.inout(a->counters, 8 * 4);
     sa.n_boxes = s.inout(a->n_boxes, (size_t)B * 4); sa.boxes = s.inout(a->boxes, bn * 8);
-    if (logp) sa.logp = s.inout(logp, tn * 4);
-    if (dh) { dh->to_device(s); sa.detail = dh->d; }
+    sh.to_device(s);
+    sa.side = sh.d;
     const float* dBias[4] = {nullptr, nullptr, nullptr, nullptr};
     if (bh) {
         dBias[kBiasMap] = s.in(bh->map, (size_t)t->n_map * 4); dBias[kBiasBox] = s.in(bh->box, (size_t)kSlotLen * t->n_box * 4);
         dBias[kBiasImg] = s.in(bh->img, (size_t)t->n_img * 4);
         sa.bias_rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
-        if (bh->logz) sa.logz = s.inout(bh->logz, tn * 4);
     }
     if (s.rc) return s.rc;
     for (int i = 0; i < n; ++i) {
@@ -408,9 +423,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp
     }
     if (!s.intact()) return UMGEN_E_STATE;
     if (down(a->tokens, sa.tokens, tn * 4) || down(a->counters, sa.counters, 8 * 4) || down(a->n_boxes, sa.n_boxes, (size_t)B * 4)) return UMGEN_E_HIP;
-    if (logp && down(logp, sa.logp, tn * 4)) return UMGEN_E_HIP;
-    if (bh && bh->logz && down(bh->logz, sa.logz, tn * 4)) return UMGEN_E_HIP;
-    if (dh) { if (int rc = dh->to_host()) return rc; }
+    if (int rc = sh.to_host()) return rc;
     return down(a->boxes, sa.boxes, bn * 8);
 }
 }  // namespace
@@ -421,11 +434,11 @@ extern "C" {
 // [B][2199] (or NULL) overrides with its pose tokens.  logp [B][2199] (in / out, or NULL): entry [b][jq] receives the log-likelihood of pose token jq
 // of scene b on its row
 static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
-                           int32_t* out_tokens, float* logp, DetailHook* dh, const float* bias = nullptr, float* logz = nullptr) {
+                           int32_t* out_tokens, SideHook& sh, const float* bias = nullptr) {
     if (bias && !bias_rows_sane(bias, 3, V)) return UMGEN_E_INVALID;
     if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
         return UMGEN_E_INVALID;
-    for (int b = 0; (logp || dh) && forced && b < B; ++b)      // the scored token indexes the row
+    for (int b = 0; (sh.logp || sh.detail) && forced && b < B; ++b)      // the scored token indexes the row
         if (!in_range(forced + (size_t)b * kTokPerFrame, kNPose, V)) return UMGEN_E_INVALID;
     const size_t ln = (size_t)B * 3 * V, tn = (size_t)B * kTokPerFrame, osz = (size_t)B * 3 * 4;
     Scratch s;
@@ -433,40 +446,38 @@ static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, 
     const unsigned long long* dS = s.in(seeds, (size_t)B * 8);
     const int* dF = s.in(forced, tn * 4);
     int *dOv = s.raw(4), *dT = s.out(osz);
-    float* dLp = logp ? (float*)s.inout(logp, tn * 4) : nullptr;
-    if (dh) dh->to_device(s);
-    EgoBias eb{};
-    eb.bias = s.in(bias, (size_t)3 * V * 4);
-    if (bias) eb.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
-    if (logz) eb.logz = s.inout(logz, tn * 4);
+    sh.to_device(s);
+    EgoSide es{sh.d, sh.topk, s.in(bias, (size_t)3 * V * 4)};
+    if (bias) es.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
     if (s.rc) return s.rc;
     if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
-    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, dLp, dh ? &dh->d : nullptr, dh ? dh->topk : 0, eb);
+    launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, es);
     if (int rc = finish()) return rc;
     int ovf = 0;
     if (down(&ovf, dOv, 4)) return UMGEN_E_HIP;
     if (!s.intact() || ovf != 0) return UMGEN_E_STATE;      // (the overflow word is unused since the exhaustive tie walk: it must stay 0)
-    if (logp && down(logp, dLp, tn * 4)) return UMGEN_E_HIP;
-    if (logz && down(logz, eb.logz, tn * 4)) return UMGEN_E_HIP;
-    if (dh) { if (int rc = dh->to_host()) return rc; }
+    if (int rc = sh.to_host()) return rc;
     return down(out_tokens, dT, osz);
 }
 // the same with a pose bias table bias [3][V] (or NULL) and logz [B][2199] (in / out, or NULL): entries [b][jq]
 int umgen_dbg_sample_ego_biased(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                                 int32_t* out_tokens, const float* bias, float* logp, float* logz) {
-    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, logp, nullptr, bias, logz);
+    SideHook sh{side_n(B), logp, logz};
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, bias);
 }
 int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                               int32_t* out_tokens, float* logp) {
-    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, logp, nullptr);
+    SideHook sh{side_n(B), logp};
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh);
 }
 // the same with the diagnostics of the three pose tokens: rank, mass_above, entropy [B][2199], topk_tok, topk_logp [B][2199][topk] (in / out, entries [b][jq])
 int umgen_dbg_sample_ego_detail(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                                 int32_t* out_tokens, float* logp, int topk, int32_t* rank, float* mass_above, float* entropy, int32_t* topk_tok,
                                 float* topk_logp) {
     if (B < 1) return UMGEN_E_INVALID;
-    DetailHook dh{topk, (size_t)B * kTokPerFrame, rank, mass_above, entropy, topk_tok, topk_logp};
-    return dh.sane() ? sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, logp, &dh) : UMGEN_E_INVALID;
+    SideHook sh{side_n(B), logp};
+    sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
+    return sh.sane() ? sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh) : UMGEN_E_INVALID;
 }
 int umgen_dbg_sample_ego(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                          int32_t* out_tokens) {

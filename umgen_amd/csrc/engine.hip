@@ -2,7 +2,9 @@
 // umgen_frame(_logp, _detail, _biased), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver
 // umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail / umgen_rollout_biased (UMGen.inference).  Every call narrows its int64 tokens once (narrow_tokens) and
 // hands them on as a TokenView (token_windows.h); the output structs become [4] arrays through MOD4; the driver keeps one conditioning sequence and
-// gathers a frame's window from it, and a frame's control / given tokens are one plan_frame, for the driver and for umgen_frame alike.  Creation,
+// gathers a frame's window from it, and a frame's control / given tokens are one plan_frame, for the driver and for umgen_frame alike.  Whatever a
+// generation call returns beside its tokens -- logp, logz, diagnostics -- is one GenSide (gen_side.h): checked and sized by gen_side_request, handed to
+// the frame as FrameIO::side, scattered to the caller's arrays by deliver.  Creation,
 // weights, the compute path, the frame itself and the scoring passes are in engine_setup.hip, engine_weights.hip, engine_stacks.hip,
 // engine_decode.hip, engine_frame.hip and engine_score.hip.
 #include "engine_state.h"
@@ -104,7 +106,6 @@ static int check_scene_tokens(umgen_engine* e, size_t frames, const int64_t* pos
     return 0;
 }
 
-static bool wants_logp(const umgen_logp_out* lp) { return lp && (lp->logp_pose || lp->logp_map || lp->logp_bbox3d || lp->logp_image); }
 static ScoreDst score_dst(const umgen_score_out* o) { return ScoreDst{MOD4(o, logp), MOD4(o, argmax)}; }
 static bool wants_lists(const ScoreDetailIO& d) {
     bool lists = false;
@@ -119,45 +120,15 @@ static int check_detail_request(umgen_engine* e, const ScoreDetailIO& d) {
     return 0;
 }
 
-// umgen_gen_detail_out behind its checks: a frame's host buffers in the device layout (FrameDetail) and their way into the caller's arrays
-struct GenDetail {
-    ScoreDetailIO dst{};      // the caller's arrays; topk is 0 when nobody receives a list (lists nobody receives are not formed)
-    bool on = false;
-    std::vector<int> f_rank, f_tok;
-    std::vector<float> f_mass, f_ent, f_tlp;
-    FrameDetail fd{};
-
-    // refuses what umgen_score_detail refuses; a NULL or all-NULL struct asks for nothing and is not checked further
-    int init(umgen_engine* e, const umgen_gen_detail_out* d, int32_t k, const umgen_sampling* s, size_t B) {
-        dst = detail_io(d, k, s->temperature);
-        for (int m = 0; m < 4; ++m) on = on || dst.rank[m] || dst.mass_above[m] || dst.entropy[m] || dst.topk_tok[m] || dst.topk_logp[m];
-        if (!on) return 0;
-        if (int rc = check_detail_request(e, dst)) return rc;
-        if (!wants_lists(dst)) dst.topk = 0;
-        const size_t n = B * kTokPerFrame;
-        f_rank.resize(n); f_mass.resize(n); f_ent.resize(n);
-        f_tok.resize(dst.topk ? n * kDetailTopK : 0); f_tlp.resize(dst.topk ? n * kDetailTopK : 0);
-        fd = FrameDetail{dst.topk, f_rank.data(), f_mass.data(), f_ent.data(), f_tok.data(), f_tlp.data()};
-        return 0;
-    }
-    const FrameDetail* frame() const { return on ? &fd : nullptr; }
-    // scene b of the frame just generated -> item `item` of the caller's arrays ([items][S_mod], the lists [items][S_mod][topk])
-    void deliver(size_t b, size_t item) const {
-        const size_t topk = (size_t)dst.topk;
-        for (int m = 0; on && m < 4; ++m) {
-            const size_t src = b * kTokPerFrame + kModOff[m], at = item * kModLen[m], len = (size_t)kModLen[m];
-            if (dst.rank[m]) memcpy(dst.rank[m] + at, &f_rank[src], len * sizeof(int));
-            if (dst.mass_above[m]) memcpy(dst.mass_above[m] + at, &f_mass[src], len * sizeof(float));
-            if (dst.entropy[m]) memcpy(dst.entropy[m] + at, &f_ent[src], len * sizeof(float));
-            for (size_t i = 0; i < len && topk; ++i) {
-                if (dst.topk_tok[m]) memcpy(dst.topk_tok[m] + (at + i) * topk, &f_tok[(src + i) * kDetailTopK], topk * sizeof(int));
-                if (dst.topk_logp[m]) memcpy(dst.topk_logp[m] + (at + i) * topk, &f_tlp[(src + i) * kDetailTopK], topk * sizeof(float));
-            }
-        }
-    }
-};
-
-static bool wants_logz(const umgen_logz_out* lz) { return lz && (lz->logz_pose || lz->logz_map || lz->logz_bbox3d || lz->logz_image); }
+// The side outputs of a generation call over `items` scenes: refuses of the diagnostics what umgen_score_detail refuses (a NULL or all-NULL struct asks for
+// nothing and is not checked further), then sizes gs from what the caller's structs ask for
+static int gen_side_request(umgen_engine* e, const umgen_logp_out* lp, const umgen_logz_out* lz, const umgen_gen_detail_out* d, int32_t k,
+                            const umgen_sampling* s, size_t items, GenSide& gs) {
+    const SideDst dst{MOD4(lp, logp), MOD4(lz, logz), MOD4(d, rank), MOD4(d, mass_above), MOD4(d, entropy), MOD4(d, topk_tok), MOD4(d, topk_logp), k};
+    if (dst.wants_detail()) { if (int rc = check_detail_request(e, detail_io(d, k, s->temperature))) return rc; }
+    gs.init(dst, items);
+    return 0;
+}
 
 // The logit-bias tables of a call (umgen_logit_bias) behind their checks, before anything reaches the device: entries are finite or -inf (a ban), every
 // row keeps an allowed entry, and with control slots a bbox3d row must allow more than vocab - 1 (the control resample masks that index).  -> the bit
@@ -209,8 +180,8 @@ int umgen_frame_biased(umgen_engine* e, int32_t T, const int64_t* pose, const in
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (T < 1 || T > e->cfg.max_cond_frames) return e->fail(UMGEN_E_INVALID, "T=%d out of range [1,%d]", T, e->cfg.max_cond_frames);
     if (int rc = check_sampling(e, sampling)) return rc;
-    GenDetail gd;
-    if (int rc = gd.init(e, detail, topk, sampling, 1)) return rc;
+    GenSide gs;
+    if (int rc = gen_side_request(e, lp, lz, detail, topk, sampling, 1, gs)) return rc;
     if (!pose || !map || !bbox3d || !image || !out_pose || !out_map || !out_bbox3d || !out_image) return e->fail(UMGEN_E_INVALID, "null token buffer");
     if (int rc = check_scene_tokens(e, (size_t)T, pose, map, bbox3d, image)) return rc;
     if (ctrl_pose) { if (int rc = check_tokens(e, "control pose", ctrl_pose, 3, e->cfg.pose_vocab, false)) return rc; }
@@ -232,29 +203,20 @@ int umgen_frame_biased(umgen_engine* e, int32_t T, const int64_t* pose, const in
     if (int rc = upload_bias(e, bias_host)) return rc;
     const int64_t* const in[4] = {pose, map, bbox3d, image};
     int64_t* const outp[4] = {out_pose, out_map, out_bbox3d, out_image};
-    float* const lp_out[4] = MOD4(lp, logp);
-    float* const lz_out[4] = MOD4(lz, logz);
     TokenSeqs win;
     narrow_tokens(in, 1, T, win);
     FramePlan plan;      // the rollout's plan for one scene and one frame of control / given tokens (the boxes overwrite window slot T - 1)
     plan_frame(1, 1, 1, 0, ctrl_pose, ctrl_bbox3d, given_map, given_bbox3d, win.at(2, 0, T - 1), 0, plan);
     std::vector<int> out(kTokPerFrame);
-    std::vector<float> flp(wants_logp(lp) ? (size_t)kTokPerFrame : 0);
     FrameIO io{1, T, win.view(), FramePlan::ptr(plan.cp), FramePlan::ptr(plan.cs), frame_idx, sampling, trace, out.data()};
     io.given_map = FramePlan::ptr(plan.gm);
     io.given_box = FramePlan::ptr(plan.gb);
-    std::vector<float> flz(wants_logz(lz) ? (size_t)kTokPerFrame : 0);
-    io.out_logp = flp.empty() ? nullptr : flp.data();
-    io.out_detail = gd.frame();
+    io.side = gs.frame();
     io.bias_classes = bias_classes;
-    io.out_logz = flz.empty() ? nullptr : flz.data();
     if (int rc = run_frame_any(e, io)) return rc;
-    gd.deliver(0, 0);
-    for (int m = 0; m < 4; ++m) {
+    gs.deliver(0, 0);
+    for (int m = 0; m < 4; ++m)
         for (int i = 0; i < kModLen[m]; ++i) outp[m][i] = out[kModOff[m] + i];
-        if (lp_out[m] && !flp.empty()) memcpy(lp_out[m], &flp[kModOff[m]], kModLen[m] * sizeof(float));
-        if (lz_out[m] && !flz.empty()) memcpy(lz_out[m], &flz[kModOff[m]], kModLen[m] * sizeof(float));
-    }
     return UMGEN_OK;
 }
 
@@ -407,13 +369,14 @@ int umgen_score_clip(umgen_engine* e, int32_t B, int32_t L, int32_t T_in, int32_
 // What every rollout call refuses, in this order, on the caller's arrays: B scenes, whatever the number of branches
 static int check_rollout(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* const in[4], int32_t T_ctl,
                          const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test, const int64_t* given_map, const int64_t* given_bbox3d,
-                         const umgen_sampling* sampling, int64_t* const out[4], GenDetail& gd, size_t branches, int32_t topk, const umgen_gen_detail_out* detail) {
+                         const umgen_sampling* sampling, int64_t* const out[4], GenSide& gs, size_t branches, const umgen_logp_out* lp, const umgen_logz_out* lz, int32_t topk,
+                         const umgen_gen_detail_out* detail) {
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
     if (B < 1 || B > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B=%d out of range [1,%d]", B, e->cfg.max_batch);
     if (T_in < 1 || new_frames < 0 || cond_frames < 1 || cond_frames > e->cfg.max_cond_frames)
         return e->fail(UMGEN_E_INVALID, "T_in=%d new_frames=%d cond_frames=%d (max %d)", T_in, new_frames, cond_frames, e->cfg.max_cond_frames);
     if (int rc = check_sampling(e, sampling)) return rc;
-    if (int rc = gd.init(e, detail, topk, sampling, branches)) return rc;
+    if (int rc = gen_side_request(e, lp, lz, detail, topk, sampling, branches, gs)) return rc;
     for (int m = 0; m < 4; ++m)
         if (!in[m] || !out[m]) return e->fail(UMGEN_E_INVALID, "null token buffer");
     if (int rc = check_scene_tokens(e, (size_t)B * T_in, in[0], in[1], in[2], in[3])) return rc;
@@ -446,12 +409,10 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
     if (!e) return UMGEN_E_INVALID;
     const int64_t* const in[4] = {pose, map, bbox3d, image};
     int64_t* const out[4] = {out_pose, out_map, out_bbox3d, out_image};
-    float* const lp_out[4] = MOD4(lp, logp);
-    float* const lz_out[4] = MOD4(lz, logz);
     const int BN = B * N, T_out = T_in + new_frames;
-    GenDetail gd;      // a frame's diagnostics and log-likelihoods are scattered to [B * N][new_frames][S_mod] below
-    if (int rc = check_rollout(e, B, T_in, new_frames, cond_frames, in, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d, sampling, out, gd,
-                               (size_t)BN, topk, detail))
+    GenSide gs;      // a frame's side outputs are scattered to [B * N][new_frames][S_mod] below
+    if (int rc = check_rollout(e, B, T_in, new_frames, cond_frames, in, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d, sampling, out, gs,
+                               (size_t)BN, lp, lz, topk, detail))
         return rc;
     std::vector<float> bias_host;      // one set of tables per call: scenes, branches and frames share it
     int bias_classes = 0;
@@ -468,8 +429,6 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
             for (size_t k = 0; k < len; ++k) { out[m][(size_t)i * T_out * kModLen[m] + k] = src[k]; seq.at(m, i, 0)[k] = (int)src[k]; }
         }
     std::vector<int> frame_out((size_t)BN * kTokPerFrame);
-    std::vector<float> frame_logp(wants_logp(lp) ? (size_t)BN * kTokPerFrame : 0);
-    std::vector<float> frame_logz(wants_logz(lz) ? (size_t)BN * kTokPerFrame : 0);
     for (int idx = 0; idx < new_frames; ++idx) {
         const int f = T_in + idx;
         const CondWindow w = cond_window(f, cond_frames);
@@ -485,10 +444,8 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
         io.next_has_ctrl_pose = ctrl_pose && idx + 1 < T_ctl;
         io.given_map = FramePlan::ptr(plan.gm);
         io.given_box = FramePlan::ptr(plan.gb);
-        io.out_logp = frame_logp.empty() ? nullptr : frame_logp.data();
-        io.out_detail = gd.frame();
+        io.side = gs.frame();
         io.bias_classes = bias_classes;
-        io.out_logz = frame_logz.empty() ? nullptr : frame_logz.data();
         const char* fse = getenv("UMGEN_FAN_SHARE");      // (read per call: the tests compare both forms in one process)
         const bool fan = idx == 0 && N >= 2 && w.n >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
         if (fan && shared_slots) *shared_slots = w.n - 1;
@@ -499,10 +456,8 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
                 const size_t src = (size_t)i * kTokPerFrame + kModOff[m], len = (size_t)kModLen[m];
                 memcpy(seq.at(m, i, f), &frame_out[src], len * sizeof(int));
                 for (size_t k = 0; k < len; ++k) out[m][((size_t)i * T_out + f) * len + k] = frame_out[src + k];
-                if (lp_out[m] && !frame_logp.empty()) memcpy(lp_out[m] + ((size_t)i * new_frames + idx) * len, &frame_logp[src], len * sizeof(float));
-                if (lz_out[m] && !frame_logz.empty()) memcpy(lz_out[m] + ((size_t)i * new_frames + idx) * len, &frame_logz[src], len * sizeof(float));
             }
-        for (int i = 0; i < BN; ++i) gd.deliver((size_t)i, (size_t)i * new_frames + idx);
+        for (int i = 0; i < BN; ++i) gs.deliver((size_t)i, (size_t)i * new_frames + idx);
     }
     return UMGEN_OK;
 }

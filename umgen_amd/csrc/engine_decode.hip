@@ -132,9 +132,8 @@ int enqueue_step(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr,
     sa.st = e->d_state; sa.tb = e->tb; sa.logits = e->logits; sa.logits_tar = e->logits_tar; sa.ld_logits = 8192; sa.ld_tar = e->cfg.bbox3d_vocab;
     sa.cond = e->cond; sa.x_next = e->xdec; sa.tokens = e->d_tokens; sa.prev_box = e->d_prev_box; sa.control_slot = e->d_control;
     sa.boxes = e->d_boxes; sa.n_boxes = e->d_nboxes; sa.seeds = e->d_seeds; sa.forced = e->d_forced; sa.counters = e->d_counters;
-    sa.detail = e->d_detail;  // (likewise: OarState::want_detail)
-    sa.bias_rows = e->d_bias_rows; sa.logz = e->d_logz;   // (likewise: OarState::bias_classes / want_logz; the class table follows with the step's mod)
-    sa.logp = e->d_logp;      // (always set: whether a step writes it is the device-side OarState::want_logp, so one captured graph serves both kinds of call)
+    sa.side = e->d_side;      // (always set: what a step writes of it are the device-side switches of OarState, so one captured graph serves every kind of call)
+    sa.bias_rows = e->d_bias_rows;   // (likewise: OarState::bias_classes; the class table follows with the step's mod)
     if (mod == 0) {
         launch_fixed_token(st, sa, B);
     } else {
@@ -171,13 +170,13 @@ namespace umgen {
 
 DecView current_view(const umgen_engine* e) {
     return DecView{e->stream, e->xdec, e->qdec, e->logits, e->logits_tar, e->cond, e->xfrag, e->afrag, e->hfrag, e->kvcache,
-                   e->d_tokens, e->d_prev_box, e->d_nboxes, e->d_control, e->d_boxes, e->d_seeds, e->d_state, e->d_logp, e->d_detail, e->d_bias_rows, e->d_logz};
+                   e->d_tokens, e->d_prev_box, e->d_nboxes, e->d_control, e->d_boxes, e->d_seeds, e->d_state, e->d_side, e->d_bias_rows};
 }
 void apply_view(umgen_engine* e, const DecView& v) {
     e->stream = v.stream; e->xdec = v.xdec; e->qdec = v.qdec; e->logits = v.logits; e->logits_tar = v.logits_tar; e->cond = v.cond;
     e->xfrag = v.xfrag; e->afrag = v.afrag; e->hfrag = v.hfrag; e->kvcache = v.kvcache; e->d_tokens = v.d_tokens; e->d_prev_box = v.d_prev_box;
-    e->d_nboxes = v.d_nboxes; e->d_control = v.d_control; e->d_boxes = v.d_boxes; e->d_seeds = v.d_seeds; e->d_state = v.d_state; e->d_logp = v.d_logp;
-    e->d_detail = v.d_detail; e->d_bias_rows = v.d_bias_rows; e->d_logz = v.d_logz;
+    e->d_nboxes = v.d_nboxes; e->d_control = v.d_control; e->d_boxes = v.d_boxes; e->d_seeds = v.d_seeds; e->d_state = v.d_state; e->d_side = v.d_side;
+    e->d_bias_rows = v.d_bias_rows;
 }
 DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine::DecLane& ln, int b0) {
     const long E = e->E;
@@ -188,9 +187,8 @@ DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine:
     v.kvcache = static_cast<unsigned char*>(all.kvcache) + (size_t)b0 * e->kv_scene_stride * e->tsz;
     v.d_tokens = all.d_tokens + (long)b0 * kTokPerFrame; v.d_prev_box = all.d_prev_box + (long)b0 * kNBox; v.d_nboxes = all.d_nboxes + b0;
     v.d_control = all.d_control + (long)b0 * kSlots; v.d_boxes = all.d_boxes + (long)b0 * 64 * 10; v.d_seeds = all.d_seeds + b0;
-    v.d_logp = all.d_logp + (long)b0 * kTokPerFrame;
-    v.d_detail = detail_at(all.d_detail, b0);
-    v.d_bias_rows = all.d_bias_rows + (long)b0 * kBiasRows * kBiasRowLen; v.d_logz = all.d_logz + (long)b0 * kTokPerFrame;
+    v.d_side = side_at(all.d_side, b0);
+    v.d_bias_rows = all.d_bias_rows + (long)b0 * kBiasRows * kBiasRowLen;
     return v;
 }
 

@@ -152,26 +152,21 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     }
     HIPCHK(e, hipMemsetAsync(e->d_counters, 0, 8 * sizeof(int), st));
     HIPCHK(e, hipMemsetAsync(e->d_nboxes, 0, (size_t)B * sizeof(int), st));
-    // log-likelihoods of the new frame: NaN (all bits set) wherever no head is evaluated -- a given pose, given map / bbox3d positions
-    if (io.out_logp) HIPCHK(e, hipMemsetAsync(e->d_logp, 0xFF, (size_t)B * kTokPerFrame * sizeof(float), st));
-    if (io.out_logz) HIPCHK(e, hipMemsetAsync(e->d_logz, 0xFF, (size_t)B * kTokPerFrame * sizeof(float), st));      // (NaN exactly where logp is)
-    if (io.out_detail) {      // the same for the diagnostics: all bits set is -1 for rank and tokens, NaN for the floats
-        const size_t n = (size_t)B * kTokPerFrame * 4;
-        HIPCHK(e, hipMemsetAsync(e->d_detail.rank, 0xFF, n, st));
-        HIPCHK(e, hipMemsetAsync(e->d_detail.mass_above, 0xFF, n, st));
-        HIPCHK(e, hipMemsetAsync(e->d_detail.entropy, 0xFF, n, st));
-        if (io.out_detail->topk > 0) {
-            HIPCHK(e, hipMemsetAsync(e->d_detail.topk_tok, 0xFF, n * kDetailTopK, st));
-            HIPCHK(e, hipMemsetAsync(e->d_detail.topk_logp, 0xFF, n * kDetailTopK, st));
-        }
-    }
+    // the side outputs of the new frame: all bits set -- NaN, -1 for rank and tokens -- wherever no head is evaluated: a given pose, given map / bbox3d positions
+    if (io.side)
+        for (const SideBuf& sb : side_buffers(e->d_side, *io.side, (size_t)B)) HIPCHK(e, hipMemsetAsync(sb.dev, 0xFF, sb.bytes, st));
     return 0;
 }
 
-// what the ego sampler takes of a biased call: the pose table when the call has one, the scratch rows, logz when asked
-static EgoBias ego_bias(const umgen_engine* e, const FrameIO& io) {
-    const bool pose = ((io.bias_classes >> kBiasPose) & 1) != 0;
-    return EgoBias{pose ? e->d_bias + e->bias_offset(kBiasPose) : nullptr, pose ? e->d_bias_rows : nullptr, io.out_logz ? e->d_logz : nullptr};
+// what the ego sampler writes of the call's side outputs, and of a biased call the pose table, when the call has one, with the scratch rows
+static EgoSide ego_side(const umgen_engine* e, const FrameIO& io) {
+    EgoSide es{};
+    if (const FrameSide* h = io.side) {
+        es.out = TokenSide{h->logp ? e->d_side.logp : nullptr, h->logz ? e->d_side.logz : nullptr, h->rank ? e->d_side.detail : DetailOut{}};
+        es.detail_topk = h->topk;
+    }
+    if ((io.bias_classes >> kBiasPose) & 1) { es.bias = e->d_bias + e->bias_offset(kBiasPose); es.rows = e->d_bias_rows; }
+    return es;
 }
 
 int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
@@ -189,8 +184,7 @@ int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if (io.ctrl_pose) {
         for (int i = 0; i < B * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, io.out_logp ? e->d_logp : nullptr,
-                    io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0, ego_bias(e, io));
+        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, ego_side(e, io));
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }
@@ -327,8 +321,9 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipMemset(e->eng_gloc, 0, e->eng_gloc_bytes));
         e->eng_epoch = 16u;
     }
-    ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, io.out_logp ? 1 : 0, io.out_detail ? 1 : 0,
-                      io.out_detail ? io.out_detail->topk : 0, io.bias_classes, io.out_logz ? 1 : 0};
+    const FrameSide sd = io.side ? *io.side : FrameSide{};      // (topk is 0 without the diagnostics)
+    ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, sd.logp ? 1 : 0, sd.rank ? 1 : 0, sd.topk,
+                      io.bias_classes, sd.logz ? 1 : 0};
     e->eng_epoch += (unsigned)(kImgEos + 1) * kEpochPerStep;
     HIPCHK(e, hipMemcpyAsync(e->d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     ctx.n_lanes = (sizeof(T) == 2 && !tr) ? e->lane_count(B) : 1;      // decode lanes: every lane steps its own copy of the state
@@ -560,18 +555,8 @@ int drain_and_download(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     }
     HIPCHK(e, hipEventRecord(e->ev[3], st));
     HIPCHK(e, hipMemcpyAsync(io.out_tokens, e->d_tokens, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
-    if (io.out_logp) HIPCHK(e, hipMemcpyAsync(io.out_logp, e->d_logp, (size_t)B * kTokPerFrame * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (io.out_logz) HIPCHK(e, hipMemcpyAsync(io.out_logz, e->d_logz, (size_t)B * kTokPerFrame * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (const FrameDetail* d = io.out_detail) {
-        const size_t n = (size_t)B * kTokPerFrame * 4;
-        HIPCHK(e, hipMemcpyAsync(d->rank, e->d_detail.rank, n, hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(d->mass_above, e->d_detail.mass_above, n, hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(d->entropy, e->d_detail.entropy, n, hipMemcpyDeviceToHost, st));
-        if (d->topk > 0) {
-            HIPCHK(e, hipMemcpyAsync(d->topk_tok, e->d_detail.topk_tok, n * kDetailTopK, hipMemcpyDeviceToHost, st));
-            HIPCHK(e, hipMemcpyAsync(d->topk_logp, e->d_detail.topk_logp, n * kDetailTopK, hipMemcpyDeviceToHost, st));
-        }
-    }
+    if (io.side)
+        for (const SideBuf& sb : side_buffers(e->d_side, *io.side, (size_t)B)) HIPCHK(e, hipMemcpyAsync(sb.host, sb.dev, sb.bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(ctx.counters, e->d_counters, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (eng) HIPCHK(e, hipMemcpyAsync(&ctx.eng_err, wide ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
@@ -735,8 +720,7 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     if (io.ctrl_pose) {
         for (int i = 0; i < BN * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, io.out_logp ? e->d_logp : nullptr,
-                        io.out_detail ? &e->d_detail : nullptr, io.out_detail ? io.out_detail->topk : 0, ego_bias(e, io));
+        run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, ego_side(e, io));
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)BN * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }

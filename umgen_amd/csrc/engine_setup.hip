@@ -474,17 +474,16 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dalloc(e, &e->d_boxes, Bm * 64 * 10)) return rc;
     if (int rc = dalloc(e, &e->d_seeds, Bm)) return rc;
     if (int rc = dalloc(e, &e->d_state, (size_t)1)) return rc;
-    if (int rc = dalloc(e, &e->d_logp, Bm * kTokPerFrame)) return rc;
-    // (with the engine, like d_logp: the step graphs captured later hold these pointers)
-    if (int rc = dalloc(e, &e->d_detail.rank, Bm * kTokPerFrame)) return rc;
-    if (int rc = dalloc(e, &e->d_detail.mass_above, Bm * kTokPerFrame)) return rc;
-    if (int rc = dalloc(e, &e->d_detail.entropy, Bm * kTokPerFrame)) return rc;
-    if (int rc = dalloc(e, &e->d_detail.topk_tok, Bm * kTokPerFrame * kDetailTopK)) return rc;
-    if (int rc = dalloc(e, &e->d_detail.topk_logp, Bm * kTokPerFrame * kDetailTopK)) return rc;
-    // constrained sampling: the call's bias tables, the samplers' scratch rows and logz (likewise with the engine)
+    // the side outputs of the frame being generated, the call's bias tables and the samplers' scratch rows: with the engine, so that the step graphs
+    // captured later hold these pointers
+    int rc = 0;
+    const auto side = [&](auto** p, size_t per_token) { if (!rc) rc = dalloc(e, p, Bm * kTokPerFrame * per_token); };
+    DetailOut& d = e->d_side.detail;
+    side(&e->d_side.logp, 1); side(&e->d_side.logz, 1); side(&d.rank, 1); side(&d.mass_above, 1); side(&d.entropy, 1);
+    side(&d.topk_tok, kDetailTopK); side(&d.topk_logp, kDetailTopK);
+    if (rc) return rc;
     if (int rc = dalloc(e, &e->d_bias, e->bias_floats())) return rc;
     if (int rc = dalloc(e, &e->d_bias_rows, Bm * kBiasRows * kBiasRowLen)) return rc;
-    if (int rc = dalloc(e, &e->d_logz, Bm * kTokPerFrame)) return rc;
     return 0;
 }
 

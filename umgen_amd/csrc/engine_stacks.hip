@@ -235,7 +235,7 @@ void ego_decoder(umgen_engine* e, int n, const long* frame_of, int Tq, const int
 // (UMGen.py:1002), so the 12 decoder blocks run on the last frame only -- identical outputs, 1/T of the work.
 template <typename T>
 void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits,
-             CacheMode cache_mode, float* logp = nullptr, const DetailOut* detail = nullptr, int detail_topk = 0, const EgoBias& eb = EgoBias{}) {
+             CacheMode cache_mode, const EgoSide& es) {
     const int B = w.B, Tn = w.T;   // Tn: slots in this pass (the last one is the window's last frame)
     run_stack<T>(e, STACK_EGO, w, cache_mode);
     std::vector<long> last(B);
@@ -243,7 +243,7 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
     ego_decoder<T>(e, B, last.data(), w.Tfull ? w.Tfull : Tn, nullptr);
     if (trace_logits) hipMemcpyAsync(trace_logits, e->logits, (size_t)3 * e->cfg.pose_vocab * 4, hipMemcpyDeviceToHost, e->stream);
     launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, forced ? e->d_forced : nullptr, e->d_ego_tok, B,
-                      e->d_counters + 7, logp, detail, detail_topk, eb);
+                      e->d_counters + 7, es);
 }
 
 // run_ego for the fan frame of umgen_rollout_fan: the ego stack and decoder once per scene (the w.B scenes' whole windows), then every branch (b, s) -- item
@@ -251,8 +251,7 @@ void run_ego(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, in
 // places in e->logits scene by scene in DESCENDING b: scene b's rows lie where item b's go, and every destination of scene b is >= b*N, above every lower scene
 // whose rows are still unread (b == 0, s == 0 is the self-copy that is skipped).  The sampler and its logp then read the rows the replicated call's would.
 template <typename T>
-void run_ego_fan(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp,
-                 const DetailOut* detail, int detail_topk, const EgoBias& eb) {
+void run_ego_fan(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, const EgoSide& es) {
     const int B = w.B, Tn = w.T;
     run_stack<T>(e, STACK_EGO, w, cache_mode);
     std::vector<long> last(B);
@@ -263,7 +262,7 @@ void run_ego_fan(umgen_engine* e, const WindowTokens& w, int N, const SamplerPar
         for (int s = N - 1; s >= 0; --s)
             if (b * N + s != b)
                 hipMemcpyAsync(e->logits + (size_t)(b * N + s) * row3, e->logits + (size_t)b * row3, row3 * sizeof(float), hipMemcpyDeviceToDevice, e->stream);
-    launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, nullptr, e->d_ego_tok, B * N, e->d_counters + 7, logp, detail, detail_topk, eb);
+    launch_sample_ego(e->stream, e->logits, e->cfg.pose_vocab, sp, e->d_seeds, frame_idx, nullptr, e->d_ego_tok, B * N, e->d_counters + 7, es);
 }
 
 // The GIVEN-token prefix of a frame as ONE forward pass (infer_oar_net's first iteration pushes the whole predefined prefix through the 36
@@ -437,12 +436,11 @@ void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const
     with_precision(e, [&](auto t) { ego_decoder<decltype(t)>(e, n, frame_of, Tq, d_item_T); });
 }
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
-                 float* logp, const DetailOut* detail, int detail_topk, const EgoBias& eb) {
-    with_precision(e, [&](auto t) { run_ego<decltype(t)>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, logp, detail, detail_topk, eb); });
+                 const EgoSide& es) {
+    with_precision(e, [&](auto t) { run_ego<decltype(t)>(e, w, sp, frame_idx, forced, trace_logits, cache_mode, es); });
 }
-void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp,
-                     const DetailOut* detail, int detail_topk, const EgoBias& eb) {
-    with_precision(e, [&](auto t) { run_ego_fan<decltype(t)>(e, w, N, sp, frame_idx, cache_mode, logp, detail, detail_topk, eb); });
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, const EgoSide& es) {
+    with_precision(e, [&](auto t) { run_ego_fan<decltype(t)>(e, w, N, sp, frame_idx, cache_mode, es); });
 }
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src) {
     return with_precision(e, [&](auto t) { return run_prefix_prefill<decltype(t)>(e, B, P, src); });

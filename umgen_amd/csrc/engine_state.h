@@ -1,6 +1,8 @@
 // State of the host engine, shared by the engine_*.hip files: the weight table and struct umgen_engine (one block of members per mechanism),
 // the per-frame call arguments (FrameIO) and the scoring calls' (ScoreIO ...), which carry their host tokens as a TokenView (token_windows.h),
-// a decode lane's view of the engine (DecView), and the declarations of the functions that cross files.
+// a decode lane's view of the engine (DecView), and the declarations of the functions that cross files.  A generated token's side outputs
+// (log-likelihood, logz, diagnostics) take one path: FrameIO::side (FrameSide, gen_side.h) says what a frame's call asked for, d_side (TokenSide,
+// frame.h) holds the device buffers, and side_buffers pairs the two for the 0xFF fill and the copy back.
 // No code that launches or decides anything lives here.
 #pragma once
 
@@ -21,6 +23,7 @@
 #include "../../include/umgen.h"
 #include "bg_queue.h"
 #include "frame.h"
+#include "gen_side.h"
 #include "kernels.h"
 #include "token_windows.h"
 
@@ -81,12 +84,13 @@ struct umgen_engine {
     double* d_boxes = nullptr;
     unsigned long long* d_seeds = nullptr;
     OarState* d_state = nullptr;
-    float* d_logp = nullptr;             // [max_batch][2199] log-likelihoods of the frame being generated (umgen_rollout_logp / umgen_frame_logp; SampleArgs::logp)
-    DetailOut d_detail{};                // [max_batch][2199] (x kDetailTopK) diagnostics of the frame being generated (umgen_rollout_detail / umgen_frame_detail; SampleArgs::detail)
-    // Constrained sampling (umgen_rollout_biased / umgen_frame_biased), allocated with the engine so that every captured step graph holds the final pointers:
-    // d_bias, the call's tables pose [3][pose_vocab] | map [map_vocab] | bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_table: a class's start);
-    // d_bias_rows [max_batch][kBiasRows][kBiasRowLen], the samplers' scratch rows (SampleArgs::bias_rows); d_logz [max_batch][2199] (SampleArgs::logz)
-    float *d_bias = nullptr, *d_bias_rows = nullptr, *d_logz = nullptr;
+    // [max_batch][2199] (the lists x kDetailTopK) side outputs of the frame being generated (SampleArgs::side), allocated with the engine -- like d_bias
+    // and d_bias_rows below -- so that every captured step graph holds the final pointers
+    TokenSide d_side{};
+    // Constrained sampling (umgen_rollout_biased / umgen_frame_biased): d_bias, the call's tables pose [3][pose_vocab] | map [map_vocab] |
+    // bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_offset: a class's start); d_bias_rows [max_batch][kBiasRows][kBiasRowLen], the samplers'
+    // scratch rows (SampleArgs::bias_rows)
+    float *d_bias = nullptr, *d_bias_rows = nullptr;
     size_t bias_floats() const { return (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab + cfg.img_vocab; }
     size_t bias_offset(int cls) const {
         const size_t o[4] = {0, (size_t)3 * cfg.pose_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab};
@@ -268,6 +272,7 @@ inline int rows_per_block_for(const umgen_engine* e, int M) { return e->rows_per
 
 static_assert(kModLen[0] == kNPose && kModLen[1] == kNMap && kModLen[2] == kNBox && kModLen[3] == kNImg && kModOff[1] == kOffMap && kModOff[2] == kOffBox &&
                   kModOff[3] == kOffImg && kFrameRowLen == kTokPerFrame, "token_windows.h states the frame layout of frame.h");
+static_assert(kSideTopK == kDetailTopK, "gen_side.h states the list length of frame.h");
 
 // f(T{}) for the engine's precision T: templates on T do not cross files, so every file dispatches its own through this
 template <typename F>
@@ -300,13 +305,6 @@ constexpr int cache_fan_form(CacheMode m) {                                     
     return m == CACHE_SHARED_ITEMS ? 1 : (m == CACHE_SHARED_ITEMS_APPEND ? 2 : (m == CACHE_SHARED_ITEMS_TAIL ? 3 : 0));
 }
 
-// host buffers of a frame's diagnostics in the device layout (DetailOut, frame.h): [B][2199], the lists [B][2199][kDetailTopK] with the first topk entries
-// of a position written
-struct FrameDetail {
-    int topk;
-    int* rank; float *mass_above, *entropy;
-    int* topk_tok; float* topk_logp;
-};
 struct FrameIO {
     int B, T;
     TokenView win;                               // host window tokens [B][T][S_mod] (box already control-overwritten)
@@ -316,10 +314,8 @@ struct FrameIO {
     const umgen_sampling* smp;
     const umgen_trace* trace;                    // B == 1 only
     int* out_tokens;                             // host [B][2199]
-    float* out_logp = nullptr;                   // host [B][2199] or nullptr: log-likelihood of every content token of the new frame (NaN where no head ran)
-    const FrameDetail* out_detail = nullptr;     // or nullptr: the diagnostics of every content token of the new frame (-1 / NaN where no head ran)
+    const FrameSide* side = nullptr;             // or nullptr: the side outputs the call asked for of every content token of the new frame (NaN / -1 where no head ran)
     int bias_classes = 0;                        // bit c: the call uploaded a logit-bias table for class c into d_bias (OarState::bias_classes)
-    float* out_logz = nullptr;                   // host [B][2199] or nullptr: logz of every sampled position of the new frame (NaN where no head ran)
     int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
     bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
     bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed
@@ -390,9 +386,8 @@ void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vect
 void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
 void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
 void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
-                 float* logp = nullptr, const DetailOut* detail = nullptr, int detail_topk = 0, const EgoBias& eb = EgoBias{});
-void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, float* logp,
-                     const DetailOut* detail = nullptr, int detail_topk = 0, const EgoBias& eb = EgoBias{});
+                 const EgoSide& es = EgoSide{});
+void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, const EgoSide& es);
 int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
@@ -415,9 +410,8 @@ struct DecView {
     double* d_boxes;
     unsigned long long* d_seeds;
     OarState* d_state;
-    float* d_logp;
-    DetailOut d_detail;
-    float *d_bias_rows, *d_logz;
+    TokenSide d_side;
+    float* d_bias_rows;
 };
 // ---- engine_decode.hip ----------------------------------------------------------------------------------------------
 DecView current_view(const umgen_engine* e);

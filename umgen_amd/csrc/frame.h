@@ -1,4 +1,7 @@
-// Per-frame data layout shared by the host engine (engine.hip) and the frame kernels (frame.hip).
+// Per-frame data layout shared by the host engine (engine.hip) and the frame kernels (frame.hip): scene positions, embedding tables, window tokens, the
+// device-resident decode state (OarState), and what a sampler touches (SampleArgs).  Whatever a sampler writes beside its token -- log-likelihood, logz,
+// diagnostics -- is ONE bundle, TokenSide: SampleArgs carries it, the ego sampler takes it inside EgoSide, the engine owns one (umgen_engine::d_side) and
+// decode lanes slice it with side_at.  Its host counterpart is FrameSide / GenSide (gen_side.h).
 #pragma once
 #include "common.h"
 
@@ -53,13 +56,14 @@ struct OarState {
     int done;        // blocks of the step's last kernel that have finished (the last one advances `step`)
     unsigned epoch;  // base of the decode engine's hand-off tags for this step (advanced with `step`, oar_engine.hip)
     SamplerParams sp;
-    int want_logp;   // the call asked for per-token log-likelihoods: sample_token_kernel also writes SampleArgs::logp (older initialisers leave it 0)
-    // the call asked for per-token diagnostics: sample_token_kernel also writes SampleArgs::detail, the detail_topk <= kDetailTopK most likely tokens among them.
-    // At the end of the struct (the decode engines read step and epoch at the offsets they know; older initialisers leave both 0)
+    // What the samplers write beside the token, into SampleArgs::side: every switch is per call and lives here, at the end of the struct (the decode engines
+    // read step and epoch at the offsets they know; an older initialiser leaves the switches it does not name 0), so one captured step graph serves every kind
+    // of call.  want_logp: the token's log-likelihood; want_detail: its diagnostics, the detail_topk <= kDetailTopK most likely tokens among them
+    int want_logp;
     int want_detail;
     int detail_topk;
-    // constrained sampling (umgen_rollout_biased / umgen_frame_biased), likewise at the end and 0 from older initialisers: bit c of bias_classes says
-    // that this call has a logit-bias table for class c (kBiasPose ..), want_logz that the samplers also write SampleArgs::logz
+    // constrained sampling (umgen_rollout_biased / umgen_frame_biased): bit c of bias_classes says that this call has a logit-bias table for class c
+    // (kBiasPose ..), want_logz that the samplers also write logz
     int bias_classes;
     int want_logz;
 };
@@ -79,9 +83,20 @@ struct DetailOut {
     int* topk_tok;
     float* topk_logp;
 };
-inline DetailOut detail_at(const DetailOut& d, long scene) {   // the buffers of scene `scene` on (decode lanes, like d_tokens)
+// The side outputs of a generated token, device buffers [B][2199] that the samplers write beside the token at the token's entry (block_token_side, frame.hip):
+// logp = log softmax(AR row over [0, vocab))[token the step settled on]; logz = lse(w) - lse(v) of the AR row (+0.0 for a class without a table); the same
+// token's diagnostics on the same row.  In SampleArgs every pointer is set and OarState's switches say what a step writes; in EgoSide a null member is
+// not asked for (detail: a null rank)
+struct TokenSide {
+    float* logp;
+    float* logz;
+    DetailOut detail;
+};
+inline TokenSide side_at(const TokenSide& s, long scene) {   // the buffers of scene `scene` on (decode lanes, like d_tokens)
     const long o = scene * kTokPerFrame;
-    return d.rank ? DetailOut{d.rank + o, d.mass_above + o, d.entropy + o, d.topk_tok + o * kDetailTopK, d.topk_logp + o * kDetailTopK} : d;
+    const auto at = [o](auto* p, long per_token) { return p ? p + o * per_token : p; };
+    const DetailOut& d = s.detail;
+    return TokenSide{at(s.logp, 1), at(s.logz, 1), DetailOut{at(d.rank, 1), at(d.mass_above, 1), at(d.entropy, 1), at(d.topk_tok, kDetailTopK), at(d.topk_logp, kDetailTopK)}};
 }
 
 // everything the per-token sampler kernel touches
@@ -105,18 +120,17 @@ struct SampleArgs {
     const int* forced;         // [B][2199] teacher forcing (valid when st->use_forced)
     int* counters;             // [8] per-frame event counters (pad_avoid, control, rule_checked, rule_collision, rule_blanked, sampled != forced,
                                //     -, 7: unused since round 5 -- more than 64 ties at the k-th logit are sampled by an exhaustive walk, frame.hip)
-    float* logp;               // [B][2199] or nullptr: log softmax(AR row over [0, vocab))[token the step settled on], written when st->want_logp
-    DetailOut detail;          // the same token's diagnostics on the same row, written when st->want_detail
+    TokenSide side;            // [B][2199] side outputs of the token at its entry: what a step writes of them is st->want_logp / want_detail / want_logz
     const float* bias;         // the bias table of this step's class: [vocab] (map, image) or [11][vocab] (bbox3d, row k % 11); read when bit `mod` of st->bias_classes is set
     float* bias_rows;          // [B][kBiasRows][kBiasRowLen] scratch: w = v + r of the AR row (row 0) and of the TAR row of a resample (row 1), written and read by the scene's block
-    float* logz;               // [B][2199]: lse(w) - lse(v) of the AR row (+0.0 for a class without a table), written when st->want_logz
 };
 
-// what the ego sampler needs of a biased call (all null: the plain call)
-struct EgoBias {
-    const float* bias = nullptr;   // [3][vocab] or nullptr
+// what the ego sampler writes beside its three pose tokens, entries [b][jq] of `out`, and what it needs of a biased call (all null: the plain call)
+struct EgoSide {
+    TokenSide out{};               // a null member is not asked for
+    int detail_topk = 0;           // entries of the diagnostics' lists
+    const float* bias = nullptr;   // the pose table [3][vocab] or nullptr
     float* rows = nullptr;         // [B][kBiasRows][kBiasRowLen] scratch, row jq of scene b
-    float* logz = nullptr;         // [B][2199] or nullptr: entry [b][jq]
 };
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);
@@ -144,10 +158,8 @@ void launch_sample_rows(hipStream_t s, const float* logits, int V, int k, float 
 void launch_sample_dbg(hipStream_t s, const float* logits, int V, const SamplerParams& sp, int k, float p, const float* u, int mask_idx, int* out,
                        int* overflow, int n);
 void launch_collision_rows(hipStream_t s, const double* boxes, const int* counts, int max_n, int* out, int n_sets);
-// logp: nullptr, or [B][2199] -- entry [b][jq] receives log softmax(head_ego row)[pose token jq of scene b]
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow, float* logp = nullptr, const DetailOut* detail = nullptr,
-                       int detail_topk = 0, const EgoBias& eb = EgoBias{});   // detail (or nullptr): entry [b][jq] receives the diagnostics of pose token jq on its head_ego row
+                       const int* forced, int* out_tokens, int B, int* overflow, const EgoSide& es = EgoSide{});
 // test hook: block_sample on n rows w = logits + bias (their own bias rows [n][V], scratch rows [n][kBiasRowLen]) with given uniforms and one masked index
 void launch_sample_dbg_biased(hipStream_t s, const float* logits, const float* bias, float* rows, int V, const SamplerParams& sp, int k, float p, const float* u,
                               int mask_idx, int* out, int* overflow, int n);

@@ -585,14 +585,13 @@ template void launch_prefix_kv_to_cache<float>(hipStream_t, const float*, const 
 template void launch_prefix_kv_to_cache<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, int, int, int, int, int, bf16_t*, long);
 template void launch_prefix_kv_to_cache<f16_t>(hipStream_t, const f16_t*, const f16_t*, int, int, int, int, int, f16_t*, long);
 
-// log softmax(row[0 .. V))[tok] at temperature 1 -- the measure of umgen_score -- for the 256-thread block of the samplers (all threads call, all
-// get the value; one call per kernel: the reduction words are not fenced behind it).  Columns >= V are never read (the rows are ld_logits
-// apart and stale past the head's vocabulary).  Maximum first, then the sum of exp_det(x - max) in a FIXED order -- a thread's columns
-// tid, tid + 256, ... ascending, the lanes of a wave by wave_sum's DPP schedule, waves 0..3 -- with separately rounded operations, so the
-// bits of the result are a function of the row and the token alone: not of the batch size, the scene's block or its launch neighbours.
+// The maximum m of row[0 .. V) and S = sum exp_det(x - m), for the 256-thread block of the samplers (all threads call, all get both; red: the call's own
+// reduction words, not fenced behind it).  Columns >= V are never read (the rows are ld_logits apart and stale past the head's vocabulary).  Maximum first,
+// then the sum in a FIXED order -- a thread's columns tid, tid + 256, ... ascending, the lanes of a wave by wave_sum's DPP schedule, waves 0..3 -- with
+// separately rounded operations, so the bits are a function of the row alone: not of the batch size, the scene's block or its launch neighbours.
 // V <= 8192 like the samplers.
-__device__ float block_logp(const float* __restrict__ row, int V, int tok) {
-    __shared__ float red[2][4];
+struct MaxSum { float mx, total; };
+__device__ __forceinline__ MaxSum block_max_sum(const float* __restrict__ row, int V, float (*red)[4]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float v[32];
 #pragma unroll
@@ -614,8 +613,13 @@ __device__ float block_logp(const float* __restrict__ row, int V, int tok) {
     s = wave_sum(s);
     if (lane == 0) red[1][wave] = s;
     __syncthreads();
-    const float total = add_rn(add_rn(add_rn(red[1][0], red[1][1]), red[1][2]), red[1][3]);
-    return sub_rn(sub_rn(row[tok], mx), logf(total));
+    return MaxSum{mx, add_rn(add_rn(add_rn(red[1][0], red[1][1]), red[1][2]), red[1][3])};
+}
+// log softmax(row[0 .. V))[tok] at temperature 1 -- the measure of umgen_score -- from block_max_sum's m and S (one call per kernel: its reduction words)
+__device__ float block_logp(const float* __restrict__ row, int V, int tok) {
+    __shared__ float red[2][4];
+    const MaxSum r = block_max_sum(row, V, red);
+    return sub_rn(sub_rn(row[tok], r.mx), logf(r.total));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -632,32 +636,10 @@ __device__ inline const float* biased_row(const float* __restrict__ v, const flo
     return w;
 }
 
-// m + log S of row[0 .. V) with m and S formed exactly as block_logp forms them -- the same operations in the same order, columns >= V never read -- for
-// the samplers' 256-thread block (all threads call, all get the value).  red: the call's own reduction words (a second call takes another pair)
+// m + log S of row[0 .. V), m and S being block_logp's (red: the call's own reduction words; a second call takes another pair)
 __device__ float block_lse(const float* __restrict__ row, int V, float (*red)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float v[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-        const int idx = tid + 256 * i;
-        v[i] = idx < V ? row[idx] : -INFINITY;
-    }
-    float mx = v[0];
-#pragma unroll
-    for (int i = 1; i < 32; ++i) mx = fmaxf(mx, v[i]);
-    mx = wave_max(mx);
-    if (lane == 0) red[0][wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (tid + 256 * i < V) s = add_rn(s, exp_det(sub_rn(v[i], mx)));
-    s = wave_sum(s);
-    if (lane == 0) red[1][wave] = s;
-    __syncthreads();
-    const float total = add_rn(add_rn(add_rn(red[1][0], red[1][1]), red[1][2]), red[1][3]);
-    return add_rn(mx, logf(total));
+    const MaxSum r = block_max_sum(row, V, red);
+    return add_rn(r.mx, logf(r.total));
 }
 // logz = lse(w) - lse(v): the log of sum_n softmax(v)[n] exp(r[n]) -- for a table of bans the log of the model's mass on the allowed set.  Its bits are a
 // function of (v, r, V) alone; w == v (an all-zero table) gives exactly +0.0.  w holds at least one entry > -inf (the tables are checked on the host).
@@ -757,6 +739,22 @@ __device__ void block_detail(const float* __restrict__ row, int V, int tok, int 
     }
 }
 
+// What a sampler leaves beside the token it settled on, for its 256-thread block (all threads call; thread 0 writes entry `at` of side): logz of the AR
+// row v against the row w the draw read (+0.0 without a table: w == v), then tok's log-likelihood and diagnostics, both on v.  Block-uniform switches, all
+// off on the default path: nothing of it runs there.
+__device__ __forceinline__ void block_token_side(const float* __restrict__ v, const float* __restrict__ w, int V, int tok, bool want_logz, bool biased,
+                                                 bool want_logp, bool want_detail, int K, float tau, const TokenSide& side, long at) {
+    if (want_logz) {
+        const float lz = biased ? block_logz(v, w, V) : 0.f;
+        if (threadIdx.x == 0) side.logz[at] = lz;
+    }
+    if (want_logp) {
+        const float lp = block_logp(v, V, tok);
+        if (threadIdx.x == 0) side.logp[at] = lp;
+    }
+    if (want_detail) block_detail(v, V, tok, K, tau, side.detail, at);
+}
+
 __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     __shared__ SamplerLds sh;
     __shared__ float cor[64][8];
@@ -806,23 +804,11 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
             if (threadIdx.x == 0) atomicAdd(a.counters + 0, 1);
         }
     }
-    // logz of the AR row, also where the token came from the TAR head (like lp); +0.0 for a class without a table
-    if (want_logz) {
-        const float lz = biased ? block_logz(lg, lw, a.vocab) : 0.f;
-        if (threadIdx.x == 0) a.logz[(long)b * kTokPerFrame + off + k] = lz;
-    }
-    // The token is settled (main draw, control or pad-avoid resample; the forced token under teacher forcing): its log-likelihood under the
-    // plain AR row -- also where the token came from the TAR head -- before the rule constraint may blank the slot: the drawn tokens are what
-    // the KV cache holds and what the sampled path's density is made of.  Block-uniform, off unless the call asked (OarState::want_logp).
-    if (want_logp) {
-        const float lp = block_logp(lg, a.vocab, use_forced ? a.forced[(long)b * kTokPerFrame + off + k] : tok);
-        if (threadIdx.x == 0) a.logp[(long)b * kTokPerFrame + off + k] = lp;
-    }
-    // ... and its diagnostics on the same row -- rank, mass above at the call's temperature, entropy, the most likely tokens (OarState::want_detail,
-    // off unless the call asked: nothing of it runs on the default path)
-    if (want_detail)
-        block_detail(lg, a.vocab, use_forced ? a.forced[(long)b * kTokPerFrame + off + k] : tok, a.st->detail_topk, sp.temperature, a.detail,
-                     (long)b * kTokPerFrame + off + k);
+    // The token is settled (main draw, control or pad-avoid resample; the forced token under teacher forcing): its side outputs on the plain AR row -- also
+    // where the token came from the TAR head -- before the rule constraint may blank the slot: the drawn tokens are what the KV cache holds and what the
+    // sampled path's density is made of.
+    block_token_side(lg, lw, a.vocab, use_forced ? a.forced[(long)b * kTokPerFrame + off + k] : tok, want_logz, biased, want_logp, want_detail,
+                     a.st->detail_topk, sp.temperature, a.side, (long)b * kTokPerFrame + off + k);
     if (a.mod == 2) {
         if (sp.rule_constrain && !use_forced && tok != kBoxPad && (pos1 - 1032) % kSlotLen == 0) {   // UMGen.py:1116-1123
             if (threadIdx.x == 0) {
@@ -873,31 +859,23 @@ void launch_sample_token(hipStream_t s, const SampleArgs& a, int B) { hipLaunchK
 
 __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict__ logits, int vocab, SamplerParams sp,
                                                          const unsigned long long* __restrict__ seeds, int frame_idx,
-                                                         const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow,
-                                                         float* __restrict__ logp, DetailOut detail, int detail_topk, EgoBias eb) {
+                                                         const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow, EgoSide es) {
     __shared__ SamplerLds sh;
     const int b = blockIdx.x / 3, jq = blockIdx.x % 3;
-    // a pose table (constrained sampling): the draw reads w = v + r[jq]; lp and the diagnostics stay on v
-    const float* lw = logits + (long)blockIdx.x * vocab;
-    if (eb.bias) lw = biased_row(lw, eb.bias + (long)jq * vocab, vocab, eb.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
+    // a pose table (constrained sampling): the draw reads w = v + r[jq]; the side outputs stay on v
+    const float* lg = logits + (long)blockIdx.x * vocab;
+    const float* lw = lg;
+    if (es.bias) lw = biased_row(lg, es.bias + (long)jq * vocab, vocab, es.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
     int tok = block_sample(sp, lw, vocab, sp.top_k, sp.p,
                            rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN), -1, sh, overflow);
-    if (eb.logz) {
-        const float lz = eb.bias ? block_logz(logits + (long)blockIdx.x * vocab, lw, vocab) : 0.f;
-        if (threadIdx.x == 0) eb.logz[(long)b * kTokPerFrame + jq] = lz;
-    }
     if (forced) tok = forced[(long)b * kTokPerFrame + jq];
     if (threadIdx.x == 0) out_tokens[b * 3 + jq] = tok;
-    if (logp) {
-        const float lp = block_logp(logits + (long)blockIdx.x * vocab, vocab, tok);
-        if (threadIdx.x == 0) logp[(long)b * kTokPerFrame + jq] = lp;
-    }
-    if (detail.rank) block_detail(logits + (long)blockIdx.x * vocab, vocab, tok, detail_topk, sp.temperature, detail, (long)b * kTokPerFrame + jq);
+    block_token_side(lg, lw, vocab, tok, es.out.logz != nullptr, es.bias != nullptr, es.out.logp != nullptr, es.out.detail.rank != nullptr, es.detail_topk,
+                     sp.temperature, es.out, (long)b * kTokPerFrame + jq);
 }
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,
-                       const int* forced, int* out_tokens, int B, int* overflow, float* logp, const DetailOut* detail, int detail_topk, const EgoBias& eb) {
-    hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow, logp,
-                       detail ? *detail : DetailOut{}, detail_topk, eb);
+                       const int* forced, int* out_tokens, int B, int* overflow, const EgoSide& es) {
+    hipLaunchKernelGGL(sample_ego_kernel, dim3(B * 3), dim3(256), 0, s, logits, vocab, sp, seeds, frame_idx, forced, out_tokens, overflow, es);
 }
 
 // test hook (debug_gemm_attn.hip): the top-k sampler on n independent logit rows with given uniforms

@@ -111,16 +111,11 @@ class Engine:
         return smp, s
 
     @staticmethod
-    def _logp_out(lead: Tuple[int, ...]):
-        """(mod -> float32 [*lead, S_mod] filled with NaN, the umgen_logp_out that points at them)"""
-        logp = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
-        return logp, _lib.LogpOut(**{f"logp_{m}": logp[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
-
-    @staticmethod
-    def _logz_out(lead: Tuple[int, ...]):
-        """(mod -> float32 [*lead, S_mod] filled with NaN, the umgen_logz_out that points at them)"""
-        logz = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
-        return logz, _lib.LogzOut(**{f"logz_{m}": logz[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
+    def _logp_out(lead: Tuple[int, ...], key: str = "logp"):
+        """(mod -> float32 [*lead, S_mod] filled with NaN, the umgen_logp_out (key "logp") or umgen_logz_out ("logz") that points at them)"""
+        bufs = {m: np.full(tuple(lead) + (CONTENT_LEN[m],), np.nan, np.float32) for m in MOD_ORDER}
+        struct = {"logp": _lib.LogpOut, "logz": _lib.LogzOut}[key]
+        return bufs, struct(**{f"{key}_{m}": bufs[m].ctypes.data_as(C.POINTER(C.c_float)) for m in MOD_ORDER})
 
     BIAS_ROWS = {"pose": 3, "map": 1, "bbox3d": 11, "image": 1}
 
@@ -287,41 +282,30 @@ class Engine:
         args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
+        # the optional structs once, then the narrowest entry point that takes what was asked for
+        side = lead + (new_frames,)
+        logp, lp = self._logp_out(side) if return_logp else (None, None)
+        logz, lz = self._logp_out(side, "logz") if return_logz else (None, None)
+        dbufs, det = self._gen_detail_out(side, topk) if return_detail else (None, None)
+        shared = C.c_int32(-1)
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
+        fan = (self._h, B, samples or 1) + args[2:] + (ref(lp), C.byref(shared))
         if bias_struct is not None or return_logz:
-            logp, lp = self._logp_out(lead + (new_frames,)) if return_logp else (None, None)
-            logz, lz = self._logz_out(lead + (new_frames,)) if return_logz else (None, None)
-            dbufs, det = self._gen_detail_out(lead + (new_frames,), topk) if return_detail else (None, None)
-            shared = C.c_int32(-1)
-            ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-            self._check(self.lib.umgen_rollout_biased(self._h, B, samples or 1, *args[2:], ref(lp), C.byref(shared), topk, ref(det), ref(bias_struct), ref(lz)),
-                        "rollout")
-            del keep, bias_keep
-            if samples is not None:
-                self.last_shared_slots = int(shared.value)
-            res = (outs,) + ((logp,) if return_logp else ()) + ((logz,) if return_logz else ()) + ((self._detail_result(dbufs),) if return_detail else ())
-            return res if len(res) > 1 else outs
-        if samples is not None or return_detail:
-            logp, lp = self._logp_out(lead + (new_frames,)) if return_logp else (None, None)
-            shared = C.c_int32(-1)
-            lpp = C.byref(lp) if lp is not None else None
-            if return_detail:
-                dbufs, det = self._gen_detail_out(lead + (new_frames,), topk)
-                self._check(self.lib.umgen_rollout_detail(self._h, B, samples or 1, *args[2:], lpp, C.byref(shared), topk, C.byref(det)), "rollout")
-            else:
-                self._check(self.lib.umgen_rollout_fan(self._h, B, samples, *args[2:], lpp, C.byref(shared)), "rollout")
-            del keep
-            if samples is not None:
-                self.last_shared_slots = int(shared.value)
-            res = (outs,) + ((logp,) if return_logp else ()) + ((self._detail_result(dbufs),) if return_detail else ())
-            return res if len(res) > 1 else outs
-        if not return_logp:
-            self._check(self.lib.umgen_rollout(*args), "rollout")
-            del keep
-            return outs
-        logp, lp = self._logp_out((B, new_frames))
-        self._check(self.lib.umgen_rollout_logp(*args, C.byref(lp)), "rollout")
-        del keep
-        return outs, logp
+            rc = self.lib.umgen_rollout_biased(*fan, topk, ref(det), ref(bias_struct), ref(lz))
+        elif return_detail:
+            rc = self.lib.umgen_rollout_detail(*fan, topk, ref(det))
+        elif samples is not None:
+            rc = self.lib.umgen_rollout_fan(*fan)
+        elif return_logp:
+            rc = self.lib.umgen_rollout_logp(*args, ref(lp))
+        else:
+            rc = self.lib.umgen_rollout(*args)
+        self._check(rc, "rollout")
+        del keep, bias_keep
+        if samples is not None:
+            self.last_shared_slots = int(shared.value)
+        res = (outs,) + tuple(x for x in (logp, logz, self._detail_result(dbufs) if return_detail else None) if x is not None)
+        return res if len(res) > 1 else outs
 
     def frame(self, window: Dict[str, np.ndarray], frame_idx: int = 0, ctrl: Optional[Dict[str, np.ndarray]] = None,
               control_test: bool = False, seed: int = 0, sampling: Optional[RolloutConfig] = None,
@@ -373,23 +357,20 @@ class Engine:
         args = (self._h, T, _p64(w["pose"]), _p64(w["map"]), _p64(w["bbox3d"]), _p64(w["image"]), _p64(cp), _p64(cb),
                 int(control_test), C.byref(smp), frame_idx, C.byref(tr) if tr is not None else None,
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
-        lpv = dbufs = lzv = None
+        lpv, lp = self._logp_out(()) if logp else (None, None)
+        lzv, lz = self._logp_out((), "logz") if logz else (None, None)
+        dbufs, det = self._gen_detail_out((), topk) if detail else (None, None)
+        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
         if bias_struct is not None or logz:
-            lpv, lp = self._logp_out(()) if logp else (None, None)
-            lzv, lz = self._logz_out(()) if logz else (None, None)
-            dbufs, det = self._gen_detail_out((), topk) if detail else (None, None)
-            ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-            self._check(self.lib.umgen_frame_biased(*args, ref(lp), topk, ref(det), ref(bias_struct), ref(lz)), "frame")
-            del bias_keep
+            rc = self.lib.umgen_frame_biased(*args, ref(lp), topk, ref(det), ref(bias_struct), ref(lz))
         elif detail:
-            lpv, lp = self._logp_out(()) if logp else (None, None)
-            dbufs, det = self._gen_detail_out((), topk)
-            self._check(self.lib.umgen_frame_detail(*args, C.byref(lp) if lp is not None else None, topk, C.byref(det)), "frame")
+            rc = self.lib.umgen_frame_detail(*args, ref(lp), topk, ref(det))
         elif logp:
-            lpv, lp = self._logp_out(())
-            self._check(self.lib.umgen_frame_logp(*args, C.byref(lp)), "frame")
+            rc = self.lib.umgen_frame_logp(*args, ref(lp))
         else:
-            self._check(self.lib.umgen_frame(*args), "frame")
+            rc = self.lib.umgen_frame(*args)
+        self._check(rc, "frame")
+        del bias_keep
         del keep, fz, gz
         if tr is not None:
             tbuf = tbuf if tbuf is not None else {}
