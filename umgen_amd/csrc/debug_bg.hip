@@ -52,7 +52,7 @@ int umgen_dbg_bg_begin(umgen_engine* e, int32_t T, int32_t cond_cap, const int32
     const BgPassDebug dbg{foreground ? 1 : 0, chunk, margin_ticks};
     const std::vector<int> ego(ego3, ego3 + 3);
     e->bg_pending = false;
-    if (int rc = launch_prefix_any(e, io, ego, &dbg)) return rc;
+    if (int rc = launch_prefix_any(e, Place{e->stream, &e->w_main}, io, ego, &dbg)) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));      // (the uploads read the handle's staging buffers; a decode launch may take another stream)
     const int n = foreground ? 0 : (int)e->bg_rec.ops.size();
     if (n_ops) *n_ops = n;

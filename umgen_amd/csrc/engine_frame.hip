@@ -73,20 +73,20 @@ int upload_pose_shift(umgen_engine* e, hipStream_t st, const int* pose, const in
     return 0;
 }
 
-void stacks_with_cond_rows(umgen_engine* e, hipStream_t st, const WindowTokens& w, CacheMode mode) {
+void stacks_with_cond_rows(umgen_engine* e, const Place& pl, const WindowTokens& w, CacheMode mode, int fan_scenes) {
     const int stack[3] = {STACK_MAP, STACK_BOX, STACK_TAR};
     const float* const ln[3] = {e->ln_map_tar, e->ln_box_tar, e->ln_tar};
     for (int i = 0; i < 3; ++i) {
-        run_stack_any(e, stack[i], w, mode);
-        launch_cond_rows(st, stack[i], w.B, w.T, e->E, e->X, ln[i], stack[i] == STACK_MAP ? e->warped_last : nullptr, e->cond);
+        run_stack_any(e, pl, stack[i], w, mode, TAIL_AUTO, nullptr, fan_scenes);
+        launch_cond_rows(pl.stream, stack[i], w.B, w.T, e->E, pl.work->X, ln[i], stack[i] == STACK_MAP ? e->warped_last : nullptr, e->dv.cond);
     }
 }
 
-int history_slots_once(umgen_engine* e, hipStream_t st, const int* pose, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff) {
+int history_slots_once(umgen_engine* e, const Place& pl, const int* pose, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff) {
     const std::vector<int> no_pose((size_t)B * 3, 0);
-    if (int rc = upload_pose_shift(e, st, pose, no_pose.data(), B, Tn, pshift, pdiff)) return rc;
+    if (int rc = upload_pose_shift(e, pl.stream, pose, no_pose.data(), B, Tn, pshift, pdiff)) return rc;
     const WindowTokens wh{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, Tn - 1, Tn, 0};
-    for (int stack : {STACK_MAP, STACK_BOX, STACK_TAR}) run_stack_any(e, stack, wh, CACHE_FILL_PREFIX);
+    for (int stack : {STACK_MAP, STACK_BOX, STACK_TAR}) run_stack_any(e, pl, stack, wh, CACHE_FILL_PREFIX);
     return 0;
 }
 
@@ -130,7 +130,6 @@ int settle_background_pass(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     ctx.pre = e->full_stream ? e->full_stream : fg;   // (the background stream is idle until this phase is over)
     ctx.dec = (e->full_stream && !ctx.ov_active) ? e->full_stream : fg;
     ctx.st = ctx.pre;
-    e->stream = ctx.pre;
     return 0;
 }
 
@@ -141,7 +140,7 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if (int rc = upload_tokens(e, st, io.win, (size_t)B * Tn)) return rc;
     ctx.seeds.resize(B);
     for (int b = 0; b < B; ++b) ctx.seeds[b] = io.smp->seeds ? io.smp->seeds[b] : 0ull;
-    HIPCHK(e, hipMemcpyAsync(e->d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->dv.d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
     if (ctx.forced) {
         ctx.forced_host.resize(kTokPerFrame);
         for (int i = 0; i < kNPose; ++i) ctx.forced_host[i] = (int)tr->forced_pose[i];
@@ -151,10 +150,10 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipMemcpyAsync(e->d_forced, ctx.forced_host.data(), (size_t)kTokPerFrame * 4, hipMemcpyHostToDevice, st));
     }
     HIPCHK(e, hipMemsetAsync(e->d_counters, 0, 8 * sizeof(int), st));
-    HIPCHK(e, hipMemsetAsync(e->d_nboxes, 0, (size_t)B * sizeof(int), st));
+    HIPCHK(e, hipMemsetAsync(e->dv.d_nboxes, 0, (size_t)B * sizeof(int), st));
     // the side outputs of the new frame: all bits set -- NaN, -1 for rank and tokens -- wherever no head is evaluated: a given pose, given map / bbox3d positions
     if (io.side)
-        for (const SideBuf& sb : side_buffers(e->d_side, *io.side, (size_t)B)) HIPCHK(e, hipMemsetAsync(sb.dev, 0xFF, sb.bytes, st));
+        for (const SideBuf& sb : side_buffers(e->dv.d_side, *io.side, (size_t)B)) HIPCHK(e, hipMemsetAsync(sb.dev, 0xFF, sb.bytes, st));
     return 0;
 }
 
@@ -162,10 +161,10 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
 static EgoSide ego_side(const umgen_engine* e, const FrameIO& io) {
     EgoSide es{};
     if (const FrameSide* h = io.side) {
-        es.out = TokenSide{h->logp ? e->d_side.logp : nullptr, h->logz ? e->d_side.logz : nullptr, h->rank ? e->d_side.detail : DetailOut{}};
+        es.out = TokenSide{h->logp ? e->dv.d_side.logp : nullptr, h->logz ? e->dv.d_side.logz : nullptr, h->rank ? e->dv.d_side.detail : DetailOut{}};
         es.detail_topk = h->topk;
     }
-    if ((io.bias_classes >> kBiasPose) & 1) { es.bias = e->d_bias + e->bias_offset(kBiasPose); es.rows = e->d_bias_rows; }
+    if ((io.bias_classes >> kBiasPose) & 1) { es.bias = e->d_bias + e->bias_offset(kBiasPose); es.rows = e->dv.d_bias_rows; }
     return es;
 }
 
@@ -184,7 +183,7 @@ int ego_and_pose_shift(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if (io.ctrl_pose) {
         for (int i = 0; i < B * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_any(e, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, ego_side(e, io));
+        run_ego_any(e, Place{st, &e->w_main}, w, ctx.sp, io.frame_idx, ctx.forced, tr ? tr->ego_logits : nullptr, ctx.cmode, ego_side(e, io));
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)B * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }
@@ -202,27 +201,23 @@ int run_stacks(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if ((ctx.use_px || (e->conc_stacks && !e->profiling)) && e->side_stream[0]) {
         // the three stacks are independent -- map and box run on side streams (own workspaces: 1 slot for the last-slot passes of the
         // overlapped path, where 2207 rows per scene leave most CUs idle; the whole window otherwise) beside the TAR stack
-        RestoreStream restore{e, st};
         HIPCHK(e, hipEventRecord(e->ev_side_in, st));
         const int side_stack[2] = {STACK_MAP, STACK_BOX};
         for (int i = 0; i < 2; ++i) {
-            HIPCHK(e, hipStreamWaitEvent(e->side_stream[i], e->ev_side_in, 0));
-            e->stream = e->side_stream[i];
-            e->set_work(e->w_side[i]);
-            run_stack_any(e, side_stack[i], ws, ctx.cmode);
-            launch_cond_rows(e->stream, side_stack[i], B, ctx.Tc, E, e->X, i == 0 ? e->ln_map_tar : e->ln_box_tar, i == 0 ? e->warped_last : nullptr,
-                             e->cond);
-            HIPCHK(e, hipEventRecord(e->ev_side_done[i], e->side_stream[i]));
+            const Place side{e->side_stream[i], &e->w_side[i]};
+            HIPCHK(e, hipStreamWaitEvent(side.stream, e->ev_side_in, 0));
+            run_stack_any(e, side, side_stack[i], ws, ctx.cmode);
+            launch_cond_rows(side.stream, side_stack[i], B, ctx.Tc, E, side.work->X, i == 0 ? e->ln_map_tar : e->ln_box_tar, i == 0 ? e->warped_last : nullptr,
+                             e->dv.cond);
+            HIPCHK(e, hipEventRecord(e->ev_side_done[i], side.stream));
         }
-        e->stream = st;
-        e->set_work(e->w_main);
-        run_stack_any(e, STACK_TAR, ws, ctx.cmode);
-        launch_cond_rows(st, STACK_TAR, B, ctx.Tc, E, e->X, e->ln_tar, nullptr, e->cond);
+        run_stack_any(e, Place{st, &e->w_main}, STACK_TAR, ws, ctx.cmode);
+        launch_cond_rows(st, STACK_TAR, B, ctx.Tc, E, e->w_main.X, e->ln_tar, nullptr, e->dv.cond);
         for (int i = 0; i < 2; ++i) HIPCHK(e, hipStreamWaitEvent(st, e->ev_side_done[i], 0));
     } else {
-        stacks_with_cond_rows(e, st, ws, ctx.cmode);
+        stacks_with_cond_rows(e, Place{st, &e->w_main}, ws, ctx.cmode);
     }
-    if (tr && tr->cond) HIPCHK(e, hipMemcpyAsync(tr->cond, e->cond, (size_t)kSeq * E * 4, hipMemcpyDeviceToHost, st));
+    if (tr && tr->cond) HIPCHK(e, hipMemcpyAsync(tr->cond, e->dv.cond, (size_t)kSeq * E * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipEventRecord(e->ev[2], st));
     if (ctx.fg_write) remember_window(e, io, ctx.ego);
     return 0;
@@ -297,9 +292,9 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     // scene positions whose tokens are GIVEN (UMGen.py:1184-1201): the pose prefix always; the map, or the map and the boxes, when the
     // caller provides them.  Their steps replay the token (fixed_token_kernel), the sampled steps start behind them.
     ctx.given_end = io.given_box ? kBoxEos + 1 : (io.given_map ? kMapEos + 1 : kPoseEos + 1);
-    HIPCHK(e, hipMemcpyAsync(e->d_tokens, ctx.tok0.data(), ctx.tok0.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(e->d_prev_box, ctx.prevbox.data(), ctx.prevbox.size() * 4, hipMemcpyHostToDevice, st));
-    if (io.control_slot) HIPCHK(e, hipMemcpyAsync(e->d_control, io.control_slot, (size_t)B * kSlots, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->dv.d_tokens, ctx.tok0.data(), ctx.tok0.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->dv.d_prev_box, ctx.prevbox.data(), ctx.prevbox.size() * 4, hipMemcpyHostToDevice, st));
+    if (io.control_slot) HIPCHK(e, hipMemcpyAsync(e->dv.d_control, io.control_slot, (size_t)B * kSlots, hipMemcpyHostToDevice, st));
     // measurement knob (never set in production): UMGEN_DEBUG_OAR_STEPS="a:b" runs only decode steps j in [a, b) so that
     // per-dispatch PMC collection (which serialises every kernel) stays bounded; results are meaningless then.
     ctx.j_begin = 0; ctx.j_end = kImgEos;
@@ -325,7 +320,7 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, sd.logp ? 1 : 0, sd.rank ? 1 : 0, sd.topk,
                       io.bias_classes, sd.logz ? 1 : 0};
     e->eng_epoch += (unsigned)(kImgEos + 1) * kEpochPerStep;
-    HIPCHK(e, hipMemcpyAsync(e->d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->dv.d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     ctx.n_lanes = (sizeof(T) == 2 && !tr) ? e->lane_count(B) : 1;      // decode lanes: every lane steps its own copy of the state
     for (int l = 0; l < ctx.n_lanes && ctx.n_lanes > 1; ++l) HIPCHK(e, hipMemcpyAsync(e->lane[l].st, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     return 0;
@@ -343,18 +338,17 @@ int begin_decode(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipStreamWaitEvent(ctx.dec, e->ev_pre_done, 0));
     }
     ctx.st = ctx.dec;
-    e->stream = ctx.dec;
-    launch_first_input(ctx.st, B, E, e->tb.tske + (long)e->cfg.task_id * E, e->cond, e->xdec);
+    launch_first_input(ctx.st, B, E, e->tb.tske + (long)e->cfg.task_id * E, e->dv.cond, e->dv.xdec);
     {   // tar_head_logits: logits_tar[b][k][:] = head_tar_bbox3d . cond[b][kBoxC0 + k][:]  (exact fp32 FMA chain, bf16 or fp32 weights)
         GemmArgs g{};
-        g.P = e->head_tar_box; g.Q = e->cond + (long)kBoxC0 * E; g.Mi = e->cfg.bbox3d_vocab; g.Nj = kNBox; g.K = E; g.ldp = E; g.ldq = E;
-        g.strideP = 0; g.strideQ = (long)kSeq * E; g.batch = B; g.mode = GEMM_STORE_F32; g.out = e->logits_tar; g.ldo = e->cfg.bbox3d_vocab;
+        g.P = e->head_tar_box; g.Q = e->dv.cond + (long)kBoxC0 * E; g.Mi = e->cfg.bbox3d_vocab; g.Nj = kNBox; g.K = E; g.ldp = E; g.ldq = E;
+        g.strideP = 0; g.strideQ = (long)kSeq * E; g.batch = B; g.mode = GEMM_STORE_F32; g.out = e->dv.logits_tar; g.ldo = e->cfg.bbox3d_vocab;
         g.strideO = (long)kNBox * e->cfg.bbox3d_vocab;
         launch_gemm_valu<T, float>(ctx.st, g);
     }
     if (ctx.ov_active && io.next_follows) {
         const auto tp0 = std::chrono::steady_clock::now();
-        if (int rc = launch_prefix_any(e, io, ctx.ego)) return rc;
+        if (int rc = launch_prefix_any(e, Place{ctx.st, &e->w_main}, io, ctx.ego)) return rc;
         if (getenv("UMGEN_DEBUG_TIMING"))
             fprintf(stderr, "[umgen] host time to enqueue the background pass: %.1f ms\n",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
@@ -375,27 +369,27 @@ int prefix_pass(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     const bool prefix_pass_off = ppe && ppe[0] == '0';
     ctx.s1 = ctx.s0;                                   // (function scope: the asynchronous uploads below read it until the stream is drained)
     if (ctx.given_end > kPoseEos + 1 && !prefix_pass_off && (!e->overlap || e->bg_engine) && ctx.j_begin == 0) {
-        if (int rc = run_prefix_prefill_any(e, B, ctx.given_end)) return rc;
+        if (int rc = run_prefix_prefill_any(e, Place{st, &e->w_main}, B, ctx.given_end)) return rc;
         ctx.j_begin = ctx.given_end - 1;
         ctx.s1.step = ctx.j_begin;
-        HIPCHK(e, hipMemcpyAsync(e->d_state, &ctx.s1, sizeof(ctx.s1), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->dv.d_state, &ctx.s1, sizeof(ctx.s1), hipMemcpyHostToDevice, st));
         for (int l = 0; l < ctx.n_lanes && ctx.n_lanes > 1; ++l) HIPCHK(e, hipMemcpyAsync(e->lane[l].st, &ctx.s1, sizeof(ctx.s1), hipMemcpyHostToDevice, st));
         e->tm.prefix_passes += 1;
     }
     return 0;
 }
 
-template <typename T>
 void plan_decode_steps(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     const int B = io.B;
     const umgen_trace* tr = io.trace;
     hipStream_t const st = ctx.st;
     ctx.steps_run = ctx.j_end - ctx.j_begin;             // decode steps of this frame (a prefix pass replaces the given positions' steps)
     ctx.graphs = e->cfg.use_graphs && !tr && !e->profiling;   // profiled frames time every decode step's layer kernel(s) with events
-    ctx.batched = sizeof(T) == 2 && e->use_batched(B);       // the batched decode layer takes the step (oar_layers)
-    ctx.wide = sizeof(T) == 2 && e->use_wide(B);           // the chip-wide engine of the wide layers: one launch per scene and step
+    const DecodePath path = decode_path(e, B, st, false);   // what oar_layers takes for the whole batch (a lane's sub-batch follows it: DecView::lane)
+    ctx.batched = path == PATH_BATCHED;
+    ctx.wide = path == PATH_WIDE;                            // the chip-wide engine of the wide layers: one launch per scene and step
     static const umgen_engine::EngStream wide_stream{true, 8, {}};
-    ctx.eng = ctx.wide ? &wide_stream : ((sizeof(T) == 2 && !ctx.batched) ? e->eng_for(st) : nullptr);
+    ctx.eng = ctx.wide ? &wide_stream : (path == PATH_ENGINE ? e->eng_for(st) : nullptr);
     const int eng_ng = ctx.wide ? -3 : (ctx.eng ? ctx.eng->NG + (e->bg_engine && B == 1 ? 100 : 0) : (ctx.batched ? -2 : 0));     // the engine's grid depends on the stream's XCDs: graphs are per (B, NG)
     if (ctx.graphs && (e->step_graph_B != B || e->step_graph_NG != eng_ng)) {
         for (auto& row : e->step_graph)
@@ -427,14 +421,12 @@ int run_lane_loop(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         e->lane_graph_B = B;
         e->lane_graph_n = n_lanes;
     }
-    const DecView all = current_view(e);
-    struct RestoreView { umgen_engine* e; DecView v; ~RestoreView() { apply_view(e, v); e->in_lanes = false; e->in_capture = false; } } restore_view{e, all};
-    e->in_lanes = true;
     HIPCHK(e, hipEventRecord(e->ev_lane_fork, st));
-    int b0s[umgen_engine::kMaxLanes], nbs[umgen_engine::kMaxLanes];
+    DecView view[umgen_engine::kMaxLanes];
+    int nbs[umgen_engine::kMaxLanes];
     for (int l = 0, b0 = 0; l < n_lanes; ++l) {
         nbs[l] = B / n_lanes + (l < B % n_lanes ? 1 : 0);
-        b0s[l] = b0;
+        view[l] = lane_view(e, e->lane[l], b0);
         b0 += nbs[l];
         HIPCHK(e, hipStreamWaitEvent(e->lane[l].s, e->ev_lane_fork, 0));
     }
@@ -446,7 +438,6 @@ int run_lane_loop(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         const int ri = run == 16 ? 2 : (run == 4 ? 1 : 0);
         for (int l = 0; l < n_lanes; ++l) {
             umgen_engine::DecLane& ln = e->lane[l];
-            apply_view(e, lane_view(e, all, ln, b0s[l]));
             const bool timed = e->profiling && l == 0;
             if (timed) {
                 if (e->layer_ev_used == e->layer_ev.size()) {
@@ -462,17 +453,17 @@ int run_lane_loop(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
                 if (!ge) {
                     hipGraph_t g;
                     HIPCHK(e, hipStreamBeginCapture(ln.s, hipStreamCaptureModeThreadLocal));
-                    e->in_capture = true;
+                    DecView cap = view[l];
+                    cap.capture = true;
                     int crc = 0;
-                    for (int r = 0; r < run && !crc; ++r) crc = enqueue_step_any(e, nbs[l], mod, 1, nullptr, 0);
-                    e->in_capture = false;
+                    for (int r = 0; r < run && !crc; ++r) crc = enqueue_step_any(e, cap, nbs[l], mod, 1, nullptr, 0);
                     if (crc) return crc;   // (run_frame_any ends the open capture)
                     HIPCHK(e, hipStreamEndCapture(ln.s, &g));
                     HIPCHK(e, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
                     HIPCHK(e, hipGraphDestroy(g));
                 }
                 HIPCHK(e, hipGraphLaunch(ge, ln.s));
-            } else if (int rc = enqueue_step_any(e, nbs[l], mod, 1, nullptr, j)) {
+            } else if (int rc = enqueue_step_any(e, view[l], nbs[l], mod, 1, nullptr, j)) {
                 return rc;
             }
             if (timed) {
@@ -497,6 +488,8 @@ int run_step_loop(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     const umgen_engine::EngStream* eng = ctx.eng;
     const umgen_trace* tr = io.trace;
     hipStream_t const st = ctx.st;
+    DecView view = e->dv;                      // the whole batch on the frame's decode stream
+    view.stream = st;
     for (int j = j_begin; j < j_end; ++j) {   // the img-eos step (j = 2206) produces nothing that is consumed
         const int mod = step_kind(j, given_end);
         const int ns = attn_nsplit(j + 1);          // key splits over the j cached keys + the new one
@@ -518,10 +511,10 @@ int run_step_loop(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
             if (!ge) {
                 hipGraph_t g;
                 HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                e->in_capture = true;
+                DecView cap = view;
+                cap.capture = true;
                 int crc = 0;
-                for (int r = 0; r < run && !crc; ++r) crc = enqueue_step_any(e, B, mod, ns, nullptr, 0);
-                e->in_capture = false;
+                for (int r = 0; r < run && !crc; ++r) crc = enqueue_step_any(e, cap, B, mod, ns, nullptr, 0);
                 if (crc) return crc;   // (run_frame_any ends the open capture)
                 HIPCHK(e, hipStreamEndCapture(st, &g));
                 HIPCHK(e, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
@@ -530,7 +523,7 @@ int run_step_loop(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
             HIPCHK(e, hipGraphLaunch(ge, st));
             e->tm.oar_kernels += (int64_t)(run - 1) * ((eng ? (wide ? B : 1) : 5 * (int64_t)e->oar.size()) + (mod == 0 ? 1 : (mod == 2 ? 3 : 2)));
             j += run - 1;
-        } else if (int rc = enqueue_step_any(e, B, mod, ns, tr, j)) {
+        } else if (int rc = enqueue_step_any(e, view, B, mod, ns, tr, j)) {
             return rc;
         }
         e->tm.oar_kernels += (eng ? (wide ? B : 1) : 5 * (int64_t)e->oar.size()) + (mod == 0 ? 1 : (mod == 2 ? 3 : 2));
@@ -554,9 +547,9 @@ int drain_and_download(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
         HIPCHK(e, hipMemcpyAsync(e->bg_state_host.data(), &e->d_bgq->state[0][0], sizeof(e->d_bgq->state), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(e, hipEventRecord(e->ev[3], st));
-    HIPCHK(e, hipMemcpyAsync(io.out_tokens, e->d_tokens, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(io.out_tokens, e->dv.d_tokens, (size_t)B * kTokPerFrame * 4, hipMemcpyDeviceToHost, st));
     if (io.side)
-        for (const SideBuf& sb : side_buffers(e->d_side, *io.side, (size_t)B)) HIPCHK(e, hipMemcpyAsync(sb.host, sb.dev, sb.bytes, hipMemcpyDeviceToHost, st));
+        for (const SideBuf& sb : side_buffers(e->dv.d_side, *io.side, (size_t)B)) HIPCHK(e, hipMemcpyAsync(sb.host, sb.dev, sb.bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(ctx.counters, e->d_counters, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (eng) HIPCHK(e, hipMemcpyAsync(&ctx.eng_err, wide ? e->wide_err : e->eng_err, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
@@ -656,7 +649,7 @@ template <typename T>
 int decode_and_finish(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     if (int rc = begin_decode<T>(e, io, ctx)) return rc;
     if (int rc = prefix_pass(e, io, ctx)) return rc;
-    plan_decode_steps<T>(e, io, ctx);
+    plan_decode_steps(e, io, ctx);
     if (ctx.n_lanes > 1) {
         if (int rc = run_lane_loop(e, io, ctx)) return rc;
     }
@@ -671,7 +664,6 @@ int decode_and_finish(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
 template <typename T>
 int run_frame(umgen_engine* e, const FrameIO& io) {
     FrameCtx ctx = begin_call(e, *io.smp);
-    RestoreStream restore{e, ctx.fg};
     ctx.forced = io.trace && io.trace->forced_map;
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
@@ -701,7 +693,6 @@ template <typename T>
 int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     const int BN = io.B, B = io.B / N, Tn = io.T, P = io.T - 1;
     FrameCtx ctx = begin_call(e, *io.smp);
-    RestoreStream restore{e, ctx.fg};
     e->px.valid = false;                 // the passes below overwrite the slot caches: nothing an earlier call left there covers this window
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     if (int rc = upload_frame_inputs(e, io, ctx)) return rc;      // seeds, counters and logp of the B * N branches; the token arrays follow below
@@ -720,7 +711,7 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     if (io.ctrl_pose) {
         for (int i = 0; i < BN * 3; ++i) ctx.ego[i] = io.ctrl_pose[i];
     } else {
-        run_ego_fan_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, ego_side(e, io));
+        run_ego_fan_any(e, Place{st, &e->w_main}, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, N, ctx.sp, io.frame_idx, ctx.cmode, ego_side(e, io));
         HIPCHK(e, hipMemcpyAsync(ctx.ego.data(), e->d_ego_tok, (size_t)BN * 3 * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
     }
@@ -728,14 +719,14 @@ int run_frame_fan(umgen_engine* e, const FrameIO& io, int N) {
     if (int rc = init_decode_state<T>(e, io, ctx)) return rc;
     // Step 2a: slots [0, T - 1) of the three stacks once per scene, their temporal k | v rows into the scenes' blocks of the slot caches (slot T - 1 of the
     // shifted pose is not read)
-    if (int rc = history_slots_once(e, st, win.view().pose(), B, Tn, hshift, hdiff)) return rc;
+    if (int rc = history_slots_once(e, Place{st, &e->w_main}, win.view().pose(), B, Tn, hshift, hdiff)) return rc;
     // Step 2b: slot T - 1 of every branch -- its own pose in the shift, its own window rows -- against its scene's caches, and the conditioning rows
     if (int rc = upload_pose_shift(e, st, io.win.pose(), ctx.ego.data(), BN, Tn, ctx.pshift, ctx.pdiff)) return rc;
     if (int rc = upload_tokens(e, st, io.win, (size_t)BN * Tn)) return rc;
     for (int i = 0; i < BN; ++i) item_scene[i] = i / N;
     HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)BN * 4, hipMemcpyHostToDevice, st));
-    e->fan_scenes = B;
-    stacks_with_cond_rows(e, st, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, BN, 1, Tn, P}, ctx.fg_write ? CACHE_SHARED_ITEMS_APPEND : CACHE_SHARED_ITEMS);
+    stacks_with_cond_rows(e, Place{st, &e->w_main}, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, BN, 1, Tn, P},
+                          ctx.fg_write ? CACHE_SHARED_ITEMS_APPEND : CACHE_SHARED_ITEMS, B);
     if (ctx.fg_write) {   // behind every read of the scene blocks: each branch's block gets its scene's slots; then the caches hold slots 0 .. T-1 of all B * N windows
         spread_tcaches(e, st, STACK_MAP, B, N, P);
         spread_tcaches(e, st, STACK_BOX, B, N, P);

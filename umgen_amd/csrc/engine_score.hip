@@ -84,9 +84,9 @@ int score_heads(umgen_engine* e, hipStream_t st, int B, const ScoreDetailIO* dt,
     const void* head[3] = {e->head_ar_map, e->head_ar_box, e->head_ar_img};
     for (int m = 0; m < 3; ++m) {
         HeadNllArgs a{};
-        a.x = e->X + (long)c0[m] * E; a.ldx = E; a.rows_per_group = n[m]; a.group_stride = (long)(kSeq - 1) * E;
+        a.x = e->w_main.X + (long)c0[m] * E; a.ldx = E; a.rows_per_group = n[m]; a.group_stride = (long)(kSeq - 1) * E;
         a.ln_w = e->ln_oar; a.W = head[m]; a.V = V[m]; a.K = E; a.M = B * n[m];
-        a.target = (sb ? sb->tokens : e->d_tokens) + off[m]; a.target_group_stride = kTokPerFrame;
+        a.target = (sb ? sb->tokens : e->dv.d_tokens) + off[m]; a.target_group_stride = kTokPerFrame;
         a.part = sb ? sb->part : e->score_part; a.logp = (sb ? sb->logp : e->score_logp) + (long)B * off[m];
         a.argmax = (sb ? sb->arg : e->score_arg) + (long)B * off[m];
         if (dt) {
@@ -108,7 +108,6 @@ template <typename T>
 int run_score(umgen_engine* e, const ScoreIO& sc) {
     if (sc.detail && sc.rows) return e->fail(UMGEN_E_INVALID, "score detail with scattered rows");      // the detail destinations take rows row0 + b only
     FrameCtx ctx = begin_call(e, kNoSampling);
-    RestoreStream restore{e, ctx.fg};
     const int B = sc.B;
     const size_t rows = (size_t)B * kTokPerFrame;
     const ScoreDetailIO* dt = sc.detail;
@@ -117,15 +116,16 @@ int run_score(umgen_engine* e, const ScoreIO& sc) {
     e->px.valid = false;                 // (before the stage below asks whether an earlier pass covers this window: the score is always a whole-window pass)
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
+    const Place pl{st, &e->w_main};      // every pass of a scoring call: one stream, the main workspaces
     if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
     HIPCHK(e, hipMemcpyAsync(e->d_forced, sc.next, rows * 4, hipMemcpyHostToDevice, st));
-    ctx.forced = true;                   // the ego net with the next pose forced: its logits stay in e->logits [3 B][pose_vocab]
+    ctx.forced = true;                   // the ego net with the next pose forced: its logits stay in e->dv.logits [3 B][pose_vocab]
     if (int rc = ego_and_pose_shift(e, io, ctx)) return rc;
-    launch_logits_nll(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, e->score_logp, e->score_arg, nullptr, nullptr);
-    if (dt) HIPCHK(e, launch_logits_detail(st, e->logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, score_detail_out(e, dt, 0)));
-    HIPCHK(e, hipMemcpyAsync(e->d_tokens, sc.next, rows * 4, hipMemcpyHostToDevice, st));
+    launch_logits_nll(st, e->dv.logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, e->score_logp, e->score_arg, nullptr, nullptr);
+    if (dt) HIPCHK(e, launch_logits_detail(st, e->dv.logits, e->cfg.pose_vocab, e->cfg.pose_vocab, 3 * B, e->d_forced, kNPose, kTokPerFrame, score_detail_out(e, dt, 0)));
+    HIPCHK(e, hipMemcpyAsync(e->dv.d_tokens, sc.next, rows * 4, hipMemcpyHostToDevice, st));
     if (int rc = run_stacks(e, io, ctx)) return rc;
-    if (int rc = run_prefix_prefill_any(e, B, kSeq)) return rc;      // rows 0 .. 2205 of every scene in X; row j predicts the token at position j
+    if (int rc = run_prefix_prefill_any(e, pl, B, kSeq)) return rc;      // rows 0 .. 2205 of every scene in X; row j predicts the token at position j
     if (int rc = score_heads<T>(e, st, B, dt)) return rc;
     // the device's blocks pose | map | bbox3d | image, each [B][S_mod], and behind the synchronisation block by block to the caller's rows
     std::vector<float> lp(rows), mass(dt ? rows : 0), ent(dt ? rows : 0), tlp(dt ? rows * dt->topk : 0);
@@ -185,21 +185,20 @@ int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
         return 0;
     }
     FrameCtx ctx = begin_call(e, kNoSampling);
-    RestoreStream restore{e, ctx.fg};
     const FrameIO io{B, Tn, sc.win, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
     e->px.valid = false;                 // the passes below overwrite the slot caches and the stacks' workspaces
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
+    const Place pl{st, &e->w_main};      // every pass of a scoring call: one stream, the main workspaces
     if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
     StageClock clock{e, st};
     clock.stage(nullptr);                // the uploads
-    // once per scene: the ego net on the whole window (its three head_ego rows stay in e->logits [3 B][pose_vocab]) ...
-    run_ego_any(e, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, ctx.sp, 0, false, nullptr, CACHE_NONE);
+    // once per scene: the ego net on the whole window (its three head_ego rows stay in e->dv.logits [3 B][pose_vocab]) ...
+    run_ego_any(e, pl, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, Tn, Tn, 0}, ctx.sp, 0, false, nullptr, CACHE_NONE);
     clock.stage(&e->tm.ego_ms);
     // ... and slots [0, T - 1) of the three stacks
-    if (int rc = history_slots_once(e, st, sc.win.pose(), B, Tn, ctx.pshift, ctx.pdiff)) return rc;
+    if (int rc = history_slots_once(e, pl, sc.win.pose(), B, Tn, ctx.pshift, ctx.pdiff)) return rc;
     clock.stage(&e->tm.tar_ms);
-    e->fan_scenes = B;
     for (long i0 = 0; i0 < N; i0 += Bm) {
         const int n = (int)std::min<long>(Bm, N - i0);
         const int* next = sc.next + (size_t)i0 * kTokPerFrame;
@@ -213,14 +212,14 @@ int run_score_candidates(umgen_engine* e, ScoreCandIO& sc) {
         if (int rc = upload_pose_shift(e, st, rep.view().pose(), cand_pose.data(), n, Tn, pshift, pdiff)) return rc;      // slot T - 1 of item (b, c): the candidate's pose
         if (int rc = upload_tokens(e, st, rep.view(), (size_t)n * Tn, false)) return rc;
         HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(e, hipMemcpyAsync(e->d_tokens, next, (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(e->dv.d_tokens, next, (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
         // a candidate's pose: a lookup in its scene's rows (the bits depend on the row and the target only)
         for (int i = 0; i < n; ++i)
-            launch_logits_nll(st, e->logits + (long)item_scene[i] * 3 * e->cfg.pose_vocab, e->cfg.pose_vocab, e->cfg.pose_vocab, 3, e->d_tokens + (long)i * kTokPerFrame,
+            launch_logits_nll(st, e->dv.logits + (long)item_scene[i] * 3 * e->cfg.pose_vocab, e->cfg.pose_vocab, e->cfg.pose_vocab, 3, e->dv.d_tokens + (long)i * kTokPerFrame,
                               kNPose, kTokPerFrame, e->score_logp + (long)i * 3, e->score_arg + (long)i * 3, nullptr, nullptr);
-        stacks_with_cond_rows(e, st, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, 1, Tn, P}, CACHE_SHARED_ITEMS);
+        stacks_with_cond_rows(e, pl, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, 1, Tn, P}, CACHE_SHARED_ITEMS, B);
         clock.stage(&e->tm.tar_ms);
-        if (int rc = run_prefix_prefill_any(e, n, kSeq)) return rc;
+        if (int rc = run_prefix_prefill_any(e, pl, n, kSeq)) return rc;
         if (int rc = score_heads<T>(e, st, n, nullptr)) return rc;
         lp.resize((size_t)n * kTokPerFrame);
         am.resize((size_t)n * kTokPerFrame);
@@ -293,16 +292,15 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
     const int B = sc.B, C = sc.C, Bm = e->cfg.max_batch, pv = e->cfg.pose_vocab;
     const long N = (long)B * C;
     FrameCtx ctx = begin_call(e, kNoSampling);
-    RestoreStream restore{e, ctx.fg};
     const FrameIO io{B, std::min(sc.T, sc.cond), sc.win, nullptr, nullptr, 0, &kNoSampling, nullptr, nullptr};
     e->px.valid = false;                 // the passes below overwrite the slot caches and the stacks' workspaces
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
+    const Place pl{st, &e->w_main};      // every pass of a scoring call: one stream, the main workspaces
     HIPCHK(e, hipMemsetAsync(e->d_counters, 0, 8 * sizeof(int), st));      // (what upload_frame_inputs clears ahead of the ego sampler)
     ctx.seeds.assign(B, 0ull);
-    HIPCHK(e, hipMemcpyAsync(e->d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->dv.d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
     StageClock clock{e, st};
-    e->fan_scenes = B;
     // host staging (the asynchronous copies read it until the next synchronisation: a chunk ends with one, and nothing is rewritten before it)
     TokenSeqs hist;                      // the scenes' history frames inside the window, [B][h][S_mod]
     std::vector<int> cand_pose, item_scene, pshift, am;
@@ -320,12 +318,12 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
             if (int rc = upload_tokens(e, st, hist.view(), (size_t)B * w.h)) return rc;
             clock.stage(nullptr);            // the uploads
             const WindowTokens we{e->d_pose, e->d_map, e->d_box, e->d_img, B, w.h, w.h, 0};
-            // k == 0: the whole window is history -- the ego net once per scene, its three head_ego rows in e->logits [3 B][pose_vocab], and the ego stack's
+            // k == 0: the whole window is history -- the ego net once per scene, its three head_ego rows in e->dv.logits [3 B][pose_vocab], and the ego stack's
             // k | v rows kept for the longer windows that follow; later: the ego stack's shared slots alone
-            if (k == 0) run_ego_any(e, we, ctx.sp, 0, false, nullptr, Ks > 1 ? CACHE_WINDOW_KEEP : CACHE_NONE);
-            else run_stack_any(e, STACK_EGO, we, CACHE_FILL_PREFIX);
+            if (k == 0) run_ego_any(e, pl, we, ctx.sp, 0, false, nullptr, Ks > 1 ? CACHE_WINDOW_KEEP : CACHE_NONE);
+            else run_stack_any(e, pl, STACK_EGO, we, CACHE_FILL_PREFIX);
             clock.stage(&e->tm.ego_ms);
-            if (int rc = history_slots_once(e, st, hist.view().pose(), B, w.h, ctx.pshift, ctx.pdiff)) return rc;
+            if (int rc = history_slots_once(e, pl, hist.view().pose(), B, w.h, ctx.pshift, ctx.pdiff)) return rc;
             clock.stage(&e->tm.tar_ms);
         }
         for (long i0 = 0; i0 < N; i0 += Bm) {
@@ -339,26 +337,26 @@ int score_futures_shared(umgen_engine* e, const ScoreFutIO& sc, int Ks) {
             }
             if (int rc = upload_tokens(e, st, ch.win.view(), (size_t)n * w.n, false)) return rc;
             HIPCHK(e, hipMemcpyAsync(e->d_item_scene, item_scene.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(e, hipMemcpyAsync(e->d_tokens, ch.next.data(), (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipMemcpyAsync(e->dv.d_tokens, ch.next.data(), (size_t)n * kTokPerFrame * 4, hipMemcpyHostToDevice, st));
             if (k == 0) {
                 // the pose of future frame 0: a lookup in the scene's rows (the bits depend on the row and the target only)
                 for (int i = 0; i < n; ++i)
-                    launch_logits_nll(st, e->logits + (long)item_scene[i] * 3 * pv, pv, pv, 3, e->d_tokens + (long)i * kTokPerFrame, kNPose, kTokPerFrame,
+                    launch_logits_nll(st, e->dv.logits + (long)item_scene[i] * 3 * pv, pv, pv, 3, e->dv.d_tokens + (long)i * kTokPerFrame, kNPose, kTokPerFrame,
                                       e->score_logp + (long)i * 3, e->score_arg + (long)i * 3, nullptr, nullptr);
             } else {
                 // the ego net reads the unshifted window: the item's k future slots behind the scene's h, the decoder and head_ego on its last slot
                 HIPCHK(e, hipMemcpyAsync(e->d_pose, ch.win.view().pose(), ch.win.mod[0].size() * 4, hipMemcpyHostToDevice, st));
-                run_stack_any(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, n, k, w.n, w.h}, CACHE_SHARED_ITEMS_TAIL);
+                run_stack_any(e, pl, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, n, k, w.n, w.h}, CACHE_SHARED_ITEMS_TAIL, TAIL_AUTO, nullptr, B);
                 frame_of.resize(n);
                 for (int i = 0; i < n; ++i) frame_of[i] = (long)i * k + (k - 1);
-                ego_decoder_any(e, n, frame_of.data(), w.n, nullptr);
-                launch_logits_nll(st, e->logits, pv, pv, 3 * n, e->d_tokens, kNPose, kTokPerFrame, e->score_logp, e->score_arg, nullptr, nullptr);
+                ego_decoder_any(e, pl, n, frame_of.data(), w.n, nullptr);
+                launch_logits_nll(st, e->dv.logits, pv, pv, 3 * n, e->dv.d_tokens, kNPose, kTokPerFrame, e->score_logp, e->score_arg, nullptr, nullptr);
                 clock.stage(&e->tm.ego_ms);
             }
             if (int rc = upload_pose_shift(e, st, ch.win.view().pose(), cand_pose.data(), n, w.n, pshift, pdiff)) return rc;      // slot n - 1: the pose of future frame k
-            stacks_with_cond_rows(e, st, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, Wt, w.n, w.P}, CACHE_SHARED_ITEMS_TAIL);
+            stacks_with_cond_rows(e, pl, WindowTokens{e->d_pose_shift, e->d_map, e->d_box, e->d_img, n, Wt, w.n, w.P}, CACHE_SHARED_ITEMS_TAIL, B);
             clock.stage(&e->tm.tar_ms);
-            if (int rc = run_prefix_prefill_any(e, n, kSeq)) return rc;
+            if (int rc = run_prefix_prefill_any(e, pl, n, kSeq)) return rc;
             if (int rc = score_heads<T>(e, st, n, nullptr)) return rc;
             lp.resize((size_t)n * kTokPerFrame);
             am.resize((size_t)n * kTokPerFrame);
@@ -451,7 +449,6 @@ template <typename T>
 int score_clip_shared(umgen_engine* e, const ScoreClipIO& sc, int P, int G) {
     const int E = e->E, B = sc.B, Bm = e->cfg.max_batch, n = B * G, pv = e->cfg.pose_vocab;
     FrameCtx ctx = begin_call(e, kNoSampling);
-    RestoreStream restore{e, ctx.fg};
     // the window [0, P) of every clip, [B][P][S_mod], and frame P's pose, which the shift hands to slot P - 1
     TokenSeqs win;
     std::vector<int> pose_P((size_t)B * 3), items((size_t)n * 2), item_T(n), next((size_t)n * kTokPerFrame);
@@ -469,6 +466,7 @@ int score_clip_shared(umgen_engine* e, const ScoreClipIO& sc, int P, int G) {
     e->px.valid = false;                 // the passes below overwrite the stacks' workspaces; nothing of them is for a later rollout
     if (int rc = settle_background_pass(e, io, ctx)) return rc;
     hipStream_t const st = ctx.st;
+    const Place pl{st, &e->w_main};      // every pass of a scoring call: one stream, the main workspaces
     if (int rc = upload_frame_inputs(e, io, ctx)) return rc;
     HIPCHK(e, hipMemcpyAsync(e->clip_items, items.data(), items.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(e->clip_item_T, item_T.data(), item_T.size() * 4, hipMemcpyHostToDevice, st));
@@ -476,29 +474,29 @@ int score_clip_shared(umgen_engine* e, const ScoreClipIO& sc, int P, int G) {
     StageClock clock{e, st};             // here ego_ms is the ego stack and decoder, tar_ms the three stacks and the conditioning rows
     clock.stage(nullptr);                // the uploads
     // the ego stack over [0, P), every block on every slot; the decoder and head_ego on the items, in chunks that fit the 3 * max_batch-row buffers
-    run_stack_any(e, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, P, 0}, CACHE_NONE, TAIL_NONE);
+    run_stack_any(e, pl, STACK_EGO, WindowTokens{e->d_pose, e->d_map, e->d_box, e->d_img, B, P, P, 0}, CACHE_NONE, TAIL_NONE);
     std::vector<long> frame_of(Bm);
     for (int i0 = 0; i0 < n; i0 += Bm) {
         const int nc = std::min(Bm, n - i0);
         for (int i = 0; i < nc; ++i) frame_of[i] = (long)items[2 * (i0 + i)] * P + items[2 * (i0 + i) + 1];
-        ego_decoder_any(e, nc, frame_of.data(), 0, e->clip_item_T + i0);
-        launch_logits_nll(st, e->logits, pv, pv, 3 * nc, e->clip_tokens + (long)i0 * kTokPerFrame, kNPose, kTokPerFrame, e->clip_logp + (long)i0 * 3,
+        ego_decoder_any(e, pl, nc, frame_of.data(), 0, e->clip_item_T + i0);
+        launch_logits_nll(st, e->dv.logits, pv, pv, 3 * nc, e->clip_tokens + (long)i0 * kTokPerFrame, kNPose, kTokPerFrame, e->clip_logp + (long)i0 * 3,
                           e->clip_arg + (long)i0 * 3, nullptr, nullptr);
     }
     clock.stage(&e->tm.ego_ms);
     // one pose shift for the window: slot t carries the pose of frame t + 1, slot P - 1 that of frame P
     if (int rc = upload_pose_shift(e, st, win.view().pose(), pose_P.data(), B, P, ctx.pshift, ctx.pdiff)) return rc;
     const WindowTokens ws{e->d_pose_shift, e->d_map, e->d_box, e->d_img, B, P, P, 0};
-    run_stack_any(e, STACK_MAP, ws, CACHE_NONE, TAIL_NONE, e->clip_warped);
-    launch_cond_rows_slots(st, STACK_MAP, P, E, e->X, e->ln_map_tar, e->clip_warped, e->clip_items, n, e->clip_cond);
-    run_stack_any(e, STACK_BOX, ws, CACHE_NONE, TAIL_NONE);
-    launch_cond_rows_slots(st, STACK_BOX, P, E, e->X, e->ln_box_tar, nullptr, e->clip_items, n, e->clip_cond);
-    run_stack_any(e, STACK_TAR, ws, CACHE_NONE, TAIL_NONE);
-    launch_cond_rows_slots(st, STACK_TAR, P, E, e->X, e->ln_tar, nullptr, e->clip_items, n, e->clip_cond);
+    run_stack_any(e, pl, STACK_MAP, ws, CACHE_NONE, TAIL_NONE, e->clip_warped);
+    launch_cond_rows_slots(st, STACK_MAP, P, E, pl.work->X, e->ln_map_tar, e->clip_warped, e->clip_items, n, e->clip_cond);
+    run_stack_any(e, pl, STACK_BOX, ws, CACHE_NONE, TAIL_NONE);
+    launch_cond_rows_slots(st, STACK_BOX, P, E, pl.work->X, e->ln_box_tar, nullptr, e->clip_items, n, e->clip_cond);
+    run_stack_any(e, pl, STACK_TAR, ws, CACHE_NONE, TAIL_NONE);
+    launch_cond_rows_slots(st, STACK_TAR, P, E, pl.work->X, e->ln_tar, nullptr, e->clip_items, n, e->clip_cond);
     clock.stage(&e->tm.tar_ms);
     // one BlockOAR pass and one head sweep for all items (n <= max_batch * max_cond_frames: the rows the stacks' workspaces hold)
     const PrefillSrc ps{e->clip_cond, e->clip_tokens, e->clip_xlast, true};
-    if (int rc = run_prefix_prefill_any(e, n, kSeq, &ps)) return rc;
+    if (int rc = run_prefix_prefill_any(e, pl, n, kSeq, &ps)) return rc;
     const ScoreBufs sb{e->clip_tokens, e->clip_part, e->clip_logp, e->clip_arg};
     if (int rc = score_heads<T>(e, st, n, nullptr, &sb)) return rc;
     std::vector<float> lp((size_t)n * kTokPerFrame);

@@ -358,14 +358,14 @@ int alloc_workspace(umgen_engine* e, const umgen_config* cfg) {
     const size_t Bm = cfg->max_batch, Tm = cfg->max_cond_frames;
     const size_t R = Bm * Tm * kSeq;
     e->S_pad = ((kSeq + 63) / 64) * 64;
-    if (int rc = dalloc(e, &e->X, R * E)) return rc;
-    if (int rc = dev_alloc(e, &e->A, R * E * e->tsz)) return rc;
-    if (int rc = dev_alloc(e, &e->QKV, R * 3 * E * e->tsz)) return rc;
-    if (int rc = dev_alloc(e, &e->VT, Bm * Tm * E * e->S_pad * e->tsz)) return rc;
-    HIPCHK(e, hipMemset(e->VT, 0, Bm * Tm * E * e->S_pad * e->tsz));   // pad columns stay zero forever
-    if (int rc = dev_alloc(e, &e->Hb, R * 4 * E * e->tsz)) return rc;
-    if (int rc = dalloc(e, &e->mapfeat, Bm * Tm * kNMap * E)) return rc;
-    e->w_main = umgen_engine::Work{e->X, e->A, e->QKV, e->VT, e->Hb, e->mapfeat};
+    umgen_engine::Work& wm = e->w_main;
+    if (int rc = dalloc(e, &wm.X, R * E)) return rc;
+    if (int rc = dev_alloc(e, &wm.A, R * E * e->tsz)) return rc;
+    if (int rc = dev_alloc(e, &wm.QKV, R * 3 * E * e->tsz)) return rc;
+    if (int rc = dev_alloc(e, &wm.VT, Bm * Tm * E * e->S_pad * e->tsz)) return rc;
+    HIPCHK(e, hipMemset(wm.VT, 0, Bm * Tm * E * e->S_pad * e->tsz));   // pad columns stay zero forever
+    if (int rc = dev_alloc(e, &wm.Hb, R * 4 * E * e->tsz)) return rc;
+    if (int rc = dalloc(e, &wm.mapfeat, Bm * Tm * kNMap * E)) return rc;
     if (int rc = dalloc(e, &e->score_part, Bm * kNMap * 8 * 4)) return rc;      // (head_nll_nsplit <= 8)
     if (int rc = dalloc(e, &e->score_logp, Bm * kTokPerFrame)) return rc;
     if (int rc = dalloc(e, &e->score_arg, Bm * kTokPerFrame)) return rc;
@@ -410,21 +410,21 @@ int alloc_workspace(umgen_engine* e, const umgen_config* cfg) {
         HIPCHK(e, hipEventCreate(&e->ev_side_in));
     }
     if (int rc = dalloc(e, &e->warped_last, Bm * kNMap * E)) return rc;
-    if (int rc = dalloc(e, &e->cond, Bm * kSeq * E)) return rc;
+    if (int rc = dalloc(e, &e->dv.cond, Bm * kSeq * E)) return rc;
     if (int rc = dalloc(e, &e->pego, Bm * kSeq * E)) return rc;
     if (int rc = dalloc(e, &e->pose_diff, Bm * Tm * 3)) return rc;
-    if (int rc = dalloc(e, &e->xdec, 3 * Bm * E)) return rc;
-    if (int rc = dalloc(e, &e->qdec, 3 * Bm * E)) return rc;
+    if (int rc = dalloc(e, &e->dv.xdec, 3 * Bm * E)) return rc;
+    if (int rc = dalloc(e, &e->dv.qdec, 3 * Bm * E)) return rc;
     if (int rc = dalloc(e, &e->qkv3, 3 * Bm * 3 * E)) return rc;
     if (int rc = dalloc(e, &e->part, 3 * Bm * e->H * kAttnRec)) return rc;
     HIPCHK(e, hipMemset(e->part, 0, 3 * Bm * e->H * kAttnRec * sizeof(float)));   // never-written split slots are read with weight 0
     if (int rc = dalloc(e, &e->hdec, 3 * Bm * 4 * E)) return rc;
-    if (int rc = dalloc(e, &e->xfrag, (size_t)kRowsMaxM * E)) return rc;
-    if (int rc = dalloc(e, &e->afrag, (size_t)kRowsMaxM * E)) return rc;
-    if (int rc = dalloc(e, &e->hfrag, (size_t)kRowsMaxM * 4 * E)) return rc;
-    HIPCHK(e, hipMemset(e->xfrag, 0, (size_t)kRowsMaxM * E * 4));       // (columns past the batch are computed, never stored: keep them finite)
-    HIPCHK(e, hipMemset(e->afrag, 0, (size_t)kRowsMaxM * E * 4));
-    HIPCHK(e, hipMemset(e->hfrag, 0, (size_t)kRowsMaxM * 4 * E * 4));
+    if (int rc = dalloc(e, &e->dv.xfrag, (size_t)kRowsMaxM * E)) return rc;
+    if (int rc = dalloc(e, &e->dv.afrag, (size_t)kRowsMaxM * E)) return rc;
+    if (int rc = dalloc(e, &e->dv.hfrag, (size_t)kRowsMaxM * 4 * E)) return rc;
+    HIPCHK(e, hipMemset(e->dv.xfrag, 0, (size_t)kRowsMaxM * E * 4));       // (columns past the batch are computed, never stored: keep them finite)
+    HIPCHK(e, hipMemset(e->dv.afrag, 0, (size_t)kRowsMaxM * E * 4));
+    HIPCHK(e, hipMemset(e->dv.hfrag, 0, (size_t)kRowsMaxM * 4 * E * 4));
     return 0;
 }
 
@@ -447,13 +447,13 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
         }
         HIPCHK(e, hipEventCreateWithFlags(&e->ev_lane_fork, hipEventDisableTiming));
     }
-    if (int rc = dalloc(e, &e->logits, 3 * Bm * 8192)) return rc;
-    if (int rc = dalloc(e, &e->logits_tar, Bm * kNBox * (size_t)cfg->bbox3d_vocab)) return rc;
+    if (int rc = dalloc(e, &e->dv.logits, 3 * Bm * 8192)) return rc;
+    if (int rc = dalloc(e, &e->dv.logits_tar, Bm * kNBox * (size_t)cfg->bbox3d_vocab)) return rc;
     e->kv_scene_stride = (long)e->Lmax * 2 * E;
     e->kv_layer_stride = (long)Bm * e->kv_scene_stride;
-    if (int rc = dev_alloc(e, &e->kvcache, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz)) return rc;
+    if (int rc = dev_alloc(e, &e->dv.kvcache, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz)) return rc;
     // (the engines' key loops request whole 16-key passes and mask the keys past the step: p = 0 times whatever bits lie there must be 0, not NaN)
-    HIPCHK(e, hipMemset(e->kvcache, 0, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz));
+    HIPCHK(e, hipMemset(e->dv.kvcache, 0, (size_t)cfg->n_oar_layer * e->kv_layer_stride * e->tsz));
     // slot caches of the overlapped TAR pass: k | v rows of every temporal sub-block, all history slots (the foreground's growing-window
     // reuse allocates the same caches on first use, run_frame)
     if (e->overlap && !ensure_tcache(e)) e->overlap = false;     // keep the plain path rather than crowding the KV caches out
@@ -463,27 +463,27 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     if (int rc = dalloc(e, &e->d_map, Bm * Tm * kNMap)) return rc;
     if (int rc = dalloc(e, &e->d_box, Bm * Tm * kNBox)) return rc;
     if (int rc = dalloc(e, &e->d_img, Bm * Tm * kNImg)) return rc;
-    if (int rc = dalloc(e, &e->d_tokens, Bm * kTokPerFrame)) return rc;
-    if (int rc = dalloc(e, &e->d_prev_box, Bm * kNBox)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_tokens, Bm * kTokPerFrame)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_prev_box, Bm * kNBox)) return rc;
     if (int rc = dalloc(e, &e->d_forced, Bm * kTokPerFrame)) return rc;
     if (int rc = dalloc(e, &e->d_counters, (size_t)8)) return rc;
-    if (int rc = dalloc(e, &e->d_nboxes, Bm)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_nboxes, Bm)) return rc;
     if (int rc = dalloc(e, &e->d_ego_tok, Bm * 3)) return rc;
     if (int rc = dalloc(e, &e->d_item_scene, Bm)) return rc;
-    if (int rc = dalloc(e, &e->d_control, Bm * kSlots)) return rc;
-    if (int rc = dalloc(e, &e->d_boxes, Bm * 64 * 10)) return rc;
-    if (int rc = dalloc(e, &e->d_seeds, Bm)) return rc;
-    if (int rc = dalloc(e, &e->d_state, (size_t)1)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_control, Bm * kSlots)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_boxes, Bm * 64 * 10)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_seeds, Bm)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_state, (size_t)1)) return rc;
     // the side outputs of the frame being generated, the call's bias tables and the samplers' scratch rows: with the engine, so that the step graphs
     // captured later hold these pointers
     int rc = 0;
     const auto side = [&](auto** p, size_t per_token) { if (!rc) rc = dalloc(e, p, Bm * kTokPerFrame * per_token); };
-    DetailOut& d = e->d_side.detail;
-    side(&e->d_side.logp, 1); side(&e->d_side.logz, 1); side(&d.rank, 1); side(&d.mass_above, 1); side(&d.entropy, 1);
+    DetailOut& d = e->dv.d_side.detail;
+    side(&e->dv.d_side.logp, 1); side(&e->dv.d_side.logz, 1); side(&d.rank, 1); side(&d.mass_above, 1); side(&d.entropy, 1);
     side(&d.topk_tok, kDetailTopK); side(&d.topk_logp, kDetailTopK);
     if (rc) return rc;
     if (int rc = dalloc(e, &e->d_bias, e->bias_floats())) return rc;
-    if (int rc = dalloc(e, &e->d_bias_rows, Bm * kBiasRows * kBiasRowLen)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_bias_rows, Bm * kBiasRows * kBiasRowLen)) return rc;
     return 0;
 }
 

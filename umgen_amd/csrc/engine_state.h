@@ -1,7 +1,9 @@
 // State of the host engine, shared by the engine_*.hip files: the weight table and struct umgen_engine (one block of members per mechanism),
 // the per-frame call arguments (FrameIO) and the scoring calls' (ScoreIO ...), which carry their host tokens as a TokenView (token_windows.h),
-// a decode lane's view of the engine (DecView), and the declarations of the functions that cross files.  A generated token's side outputs
-// (log-likelihood, logz, diagnostics) take one path: FrameIO::side (FrameSide, gen_side.h) says what a frame's call asked for, d_side (TokenSide,
+// where a stack pass runs (Place: stream and workspaces, an argument of every pass) and what a decode step reads and writes per scene (DecView: the engine
+// holds the whole batch's as `dv`, a decode lane gets its sub-batch's from lane_view; both are arguments, nothing is swapped into the engine around a
+// call), the path a decode step takes (DecodePath), and the declarations of the functions that cross files.  A generated token's side outputs
+// (log-likelihood, logz, diagnostics) take one path: FrameIO::side (FrameSide, gen_side.h) says what a frame's call asked for, dv.d_side (TokenSide,
 // frame.h) holds the device buffers, and side_buffers pairs the two for the 0xFF fill and the copy back.
 // No code that launches or decides anything lives here.
 #pragma once
@@ -51,13 +53,33 @@ struct Slot {            // destination of one state-dict entry
     bool optional;
 };
 
+// What a decode step reads and writes per scene, and how it is enqueued: the only home of these buffers.  umgen_engine::dv is the whole batch's
+// (engine_setup.hip allocates into it; its stream and flags stay unset); a step takes a copy with the call's stream and flags, a decode lane the view
+// of its sub-batch (lane_view: scenes b0 .. b0 + nb - 1 of every per-scene array, its own stream / step state / fragment buffers).
+struct DecView {
+    hipStream_t stream;      // the step's launches go here
+    bool lane;               // a lane's sub-batch of a batch that took the batched layer: so does the lane (use_batched); timed around its graph launches
+    bool capture;            // the step is being captured into a graph: no per-step events, no hipGetLastError
+    float *xdec, *qdec, *logits, *logits_tar, *cond, *xfrag, *afrag, *hfrag;   // (xfrag / afrag / hfrag: fragment-major x / attention output [64 E], gelu(c_fc) [64 x 4E] of the batched layer)
+    void* kvcache;
+    int *d_tokens, *d_prev_box, *d_nboxes;
+    unsigned char* d_control;
+    double* d_boxes;
+    unsigned long long* d_seeds;
+    OarState* d_state;
+    // [max_batch][2199] (the lists x kDetailTopK) side outputs of the frame being generated (SampleArgs::side), allocated with the engine -- like d_bias
+    // and d_bias_rows -- so that every captured step graph holds the final pointers
+    TokenSide d_side;
+    float* d_bias_rows;      // [max_batch][kBiasRows][kBiasRowLen], the samplers' scratch rows (SampleArgs::bias_rows)
+};
+
 }  // namespace umgen
 
 struct umgen_engine {
     umgen_config cfg{};
     int E = 0, H = 0;
     size_t tsz = 4;                      // sizeof(T)
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;        // the foreground stream (the decode stream of overlapped rollouts); assigned in engine_setup.hip only
     std::string err = "";
     std::map<std::string, Slot> slots;
     std::vector<void*> allocs;
@@ -72,25 +94,16 @@ struct umgen_engine {
     float *map_cb = nullptr, *img_cb = nullptr;
     EmbedTables tb{};
     // workspace
-    float *X = nullptr, *mapfeat = nullptr, *warped_last = nullptr, *cond = nullptr, *pose_diff = nullptr, *pego = nullptr;
-    void *A = nullptr, *QKV = nullptr, *VT = nullptr, *Hb = nullptr;
-    float *xdec = nullptr, *qdec = nullptr, *part = nullptr, *hdec = nullptr, *logits = nullptr, *logits_tar = nullptr, *qkv3 = nullptr;
-    void* kvcache = nullptr;
+    float *warped_last = nullptr, *pose_diff = nullptr, *pego = nullptr;
+    float *part = nullptr, *hdec = nullptr, *qkv3 = nullptr;
+    DecView dv{};                        // the per-scene decode buffers of the whole batch
     long kv_layer_stride = 0, kv_scene_stride = 0;
     int Lmax = kAttnSplit * kAttnChunk, S_pad = 2240;   // cache rows per head: every split's fixed key range is addressable
     int *d_pose = nullptr, *d_pose_shift = nullptr, *d_map = nullptr, *d_box = nullptr, *d_img = nullptr;
-    int *d_tokens = nullptr, *d_prev_box = nullptr, *d_forced = nullptr, *d_counters = nullptr, *d_nboxes = nullptr, *d_ego_tok = nullptr;
-    unsigned char* d_control = nullptr;
-    double* d_boxes = nullptr;
-    unsigned long long* d_seeds = nullptr;
-    OarState* d_state = nullptr;
-    // [max_batch][2199] (the lists x kDetailTopK) side outputs of the frame being generated (SampleArgs::side), allocated with the engine -- like d_bias
-    // and d_bias_rows below -- so that every captured step graph holds the final pointers
-    TokenSide d_side{};
+    int *d_forced = nullptr, *d_counters = nullptr, *d_ego_tok = nullptr;
     // Constrained sampling (umgen_rollout_biased / umgen_frame_biased): d_bias, the call's tables pose [3][pose_vocab] | map [map_vocab] |
-    // bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_offset: a class's start); d_bias_rows [max_batch][kBiasRows][kBiasRowLen], the samplers'
-    // scratch rows (SampleArgs::bias_rows)
-    float *d_bias = nullptr, *d_bias_rows = nullptr;
+    // bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_offset: a class's start); the samplers' scratch rows are dv.d_bias_rows
+    float* d_bias = nullptr;
     size_t bias_floats() const { return (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab + cfg.img_vocab; }
     size_t bias_offset(int cls) const {
         const size_t o[4] = {0, (size_t)3 * cfg.pose_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab};
@@ -101,10 +114,10 @@ struct umgen_engine {
     float *score_part = nullptr, *score_logp = nullptr;
     int* score_arg = nullptr;
     // umgen_score_candidates (engine_score.hip run_score_candidates): the scene of every item (b, c) of the chunk in flight, [max_batch], and the number of
-    // scenes whose slot caches the chunk's last-slot pass reads (CACHE_SHARED_ITEMS); umgen_rollout_fan's first frame (run_frame_fan) uses both the same way
-    // for its B * N branches (CACHE_SHARED_ITEMS / CACHE_SHARED_ITEMS_APPEND), umgen_score_futures for its B * C items (CACHE_SHARED_ITEMS_TAIL)
+    // scenes whose slot caches the chunk's last-slot pass reads travels with the pass (run_stack's fan_scenes; CACHE_SHARED_ITEMS); umgen_rollout_fan's first
+    // frame (run_frame_fan) uses both the same way for its B * N branches (CACHE_SHARED_ITEMS / CACHE_SHARED_ITEMS_APPEND), umgen_score_futures for its B * C
+    // items (CACHE_SHARED_ITEMS_TAIL)
     int* d_item_scene = nullptr;
-    int fan_scenes = 0;
     // umgen_score_futures (engine_score.hip run_score_futures): per-scene history passes of the last call (read by the test hook umgen_dbg_score_futures_passes)
     int fut_history_passes = 0;
     // umgen_score_clip (engine_score.hip run_score_clip): allocated by its first call (ensure_score_clip), for max_batch * max_cond_frames items (b, slot) of one
@@ -128,12 +141,11 @@ struct umgen_engine {
     float last_full_pre_ms = 0.f, last_oar_ms = 0.f;   // ego + TAR phase of the last whole-window frame / decode loop of the last frame
     int overlap_mode = 1;                // UMGEN_OVERLAP: 0 off, 1 on for one scene per GPU (default), 2 always
     hipStream_t bg_stream = nullptr;
-    // the last-slot passes of the map / box stacks run beside the TAR stack's on their own streams and 1-slot workspaces
+    // the stacks' workspaces: w_main, and w_side for the last-slot passes of the map / box stacks, which run beside the TAR stack's on their own streams
     struct Work { float* X; void *A, *QKV, *VT, *Hb; float* mapfeat; };
     Work w_main{}, w_side[2] = {};
     hipStream_t side_stream[2] = {nullptr, nullptr};
     hipEvent_t ev_side_in = nullptr, ev_side_done[2] = {nullptr, nullptr};
-    void set_work(const Work& w) { X = w.X; A = w.A; QKV = w.QKV; VT = w.VT; Hb = w.Hb; mapfeat = w.mapfeat; }
     hipStream_t full_stream = nullptr;   // unmasked: whole-window passes, profiling frames and rollouts that do not overlap use all CUs
     hipEvent_t ev_pre_done = nullptr;
     hipEvent_t ev_tar_done = nullptr, ev_bg_done = nullptr, ev_bg0 = nullptr;
@@ -201,7 +213,6 @@ struct umgen_engine {
     int fg_xcds = 8;
     unsigned eng_epoch = 16u;             // first hand-off tag of the next frame (see run_frame)
     int step_graph_NG = -1;
-    bool in_capture = false;
     const EngStream* eng_for(hipStream_t s) const {
         if (!eng_enabled) return nullptr;
         const EngStream* es = (full_stream && s == full_stream) ? &eng_full : &eng_fg;
@@ -211,9 +222,8 @@ struct umgen_engine {
     // Batched decode layer (decode_batched.hip) from `batched_min` scenes per launch on (UMGEN_DECODE_BATCHED=n; 0 = never): the weights
     // once per step for the whole batch, the scenes as the matrix-core instruction's B-columns
     int batched_min = 24;               // measured crossover with the engine (profiles/r04_lanes_sweep.txt): 20 scenes 1546 (engine) vs 1674 us per step, 24: 1843 vs 1708, 28: 2104 vs 1775
-    float *xfrag = nullptr, *afrag = nullptr, *hfrag = nullptr;   // fragment-major x / attention output [64 E], gelu(c_fc) [64 x 4E] of the batched layer
-    bool use_batched(int B) const {      // (in_lanes: a lane's sub-batch of a batch that qualified)
-        return tsz == 2 && (in_lanes || (batched_min > 0 && B >= batched_min)) && B <= kRowsMaxM && E % 32 == 0 && E <= 768;
+    bool use_batched(int B, bool lane = false) const {      // (lane: a lane's sub-batch of a batch that qualified, DecView::lane)
+        return tsz == 2 && (lane || (batched_min > 0 && B >= batched_min)) && B <= kRowsMaxM && E % 32 == 0 && E <= 768;
     }
     // Decode LANES: the scenes of a batch are independent until the frame is complete (own K/V rows, own sampler state, own RNG
     // stream), and a batched layer launch for <= 16 scenes is latency-bound (5 dependent launches per layer, 48 - 96 workgroups each,
@@ -233,7 +243,6 @@ struct umgen_engine {
     hipEvent_t ev_lane_fork = nullptr;
     int lanes_env = -1;                  // UMGEN_DECODE_LANES=n: n lanes whenever the batched layer runs (1 = off); -1: by batch size
     int lane_graph_B = 0, lane_graph_n = 0;
-    bool in_lanes = false;               // enqueueing a lane's steps (a profiled frame times them around the graph launches, not inside enqueue_step)
     int lane_count(int B) const {
         if (!use_batched(B) || !lane[0].s) return 1;
         // measured (profiles/r04_lanes_sweep.txt): lanes of 16 scenes (one full column block of the matrix-core instruction) are best --
@@ -287,13 +296,13 @@ enum CacheMode {
     CACHE_LAST_SLOT = 2,           // last-slot pass: slots [w.t0, w.t0 + w.T) against the caches
     CACHE_WINDOW_KEEP = 3,         // whole window like CACHE_NONE, and its k | v rows are left in the slot caches for a longer window that follows
     CACHE_LAST_SLOT_APPEND = 4,    // last-slot pass like CACHE_LAST_SLOT that appends its own k | v rows (the window keeps growing)
-    // last-slot pass of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of e->fan_scenes scenes: item i reads the slots [0, P) of scene
+    // last-slot pass of w.B ITEMS (w.T == 1, w.t0 = P) that share the caches of fan_scenes scenes (run_stack's argument): item i reads the slots [0, P) of scene
     // e->d_item_scene[i] (umgen_score_candidates; the token arrays and pose_diff hold every item's own window)
     CACHE_SHARED_ITEMS = 5,
     // ... and item i appends its own k | v rows to block i of the caches (umgen_rollout_fan ahead of a longer window: spread_tcaches then hands every
     // item its scene's slots [0, P))
     CACHE_SHARED_ITEMS_APPEND = 6,
-    // tail pass of w.B ITEMS that share the caches of e->fan_scenes scenes like CACHE_SHARED_ITEMS, with w.T >= 1 slots [w.t0, w.t0 + w.T) of their own each
+    // tail pass of w.B ITEMS that share the caches of fan_scenes scenes like CACHE_SHARED_ITEMS, with w.T >= 1 slots [w.t0, w.t0 + w.T) of their own each
     // (umgen_score_futures: future frame k of a candidate brings k + 1 slots); nothing is written to the caches.  The final block's last-frame shortcut
     // applies to the tail (w.T > 1), as it does to a whole window
     CACHE_SHARED_ITEMS_TAIL = 7,
@@ -382,42 +391,37 @@ enum { TAIL_AUTO = -1, TAIL_NONE = 0 };
 // ---- engine_weights.hip ---------------------------------------------------------------------------------------------
 void decode_pose_shift(const int* pose, const int* ego, int B, int Tn, std::vector<int>& pshift, std::vector<float>& pdiff);
 
+// Where a stack pass runs: its stream and the workspaces it owns (umgen_engine::w_main, or a side stream's w_side[i]).  An argument of every pass:
+// the engine keeps no "current" stream or workspace.  capture: the launches are being captured into a graph (gemm_timed then leaves hipGetLastError alone)
+struct Place { hipStream_t stream; const umgen_engine::Work* work; bool capture = false; };
+
 // ---- engine_stacks.hip: by-precision entry points of the templated compute path ------------------------------------
-void run_stack_any(umgen_engine* e, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr);
-void ego_decoder_any(umgen_engine* e, int n, const long* frame_of, int Tq, const int* d_item_T);
-void run_ego_any(umgen_engine* e, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits, CacheMode cache_mode,
-                 const EgoSide& es = EgoSide{});
-void run_ego_fan_any(umgen_engine* e, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, const EgoSide& es);
-int run_prefix_prefill_any(umgen_engine* e, int B, int P, const PrefillSrc* src = nullptr);
+// fan_scenes (the CACHE_SHARED_ITEMS modes): the scenes whose slot caches the pass's items share through e->d_item_scene
+void run_stack_any(umgen_engine* e, const Place& pl, int stack, const WindowTokens& w, CacheMode cache_mode, int tail = TAIL_AUTO, float* warped_all = nullptr,
+                   int fan_scenes = 0);
+void ego_decoder_any(umgen_engine* e, const Place& pl, int n, const long* frame_of, int Tq, const int* d_item_T);
+void run_ego_any(umgen_engine* e, const Place& pl, const WindowTokens& w, const SamplerParams& sp, int frame_idx, bool forced, float* trace_logits,
+                 CacheMode cache_mode, const EgoSide& es = EgoSide{});
+void run_ego_fan_any(umgen_engine* e, const Place& pl, const WindowTokens& w, int N, const SamplerParams& sp, int frame_idx, CacheMode cache_mode, const EgoSide& es);
+int run_prefix_prefill_any(umgen_engine* e, const Place& pl, int B, int P, const PrefillSrc* src = nullptr);
 // what the test hooks of debug_bg.hip change about a background pass (launch_prefix)
 struct BgPassDebug {
-    int foreground;                              // 1: the pass as stand-alone launches on the engine's stream, synchronised; 0: recorded and uploaded, nothing runs
+    int foreground;                              // 1: the pass as stand-alone launches on the caller's stream, synchronised; 0: recorded and uploaded, nothing runs
     int chunk;                                   // > 0: BgOpHead::chunk of every uploaded op
     int margin_ticks;                            // >= 0: BgQueue::margin_ticks
 };
-int launch_prefix_any(umgen_engine* e, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg = nullptr);
-void gemv_any(umgen_engine* e, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out, long ldo);
-int build_tables_any(umgen_engine* e);
+// fg: the frame's decode stream and the main workspaces
+int launch_prefix_any(umgen_engine* e, const Place& fg, const FrameIO& io, const std::vector<int>& ego, const BgPassDebug* dbg = nullptr);
+void gemv_any(umgen_engine* e, const Place& pl, const float* x, long ldx, const float* ln_w, const void* W, const float* bias, int N, int K, int M, int mode, float* out,
+              long ldo);
+int build_tables_any(umgen_engine* e, const Place& pl);
 
-// What a decode step reads and writes per scene, as the engine's members: a decode lane swaps in the view of its sub-batch (scenes
-// b0 .. b0 + nb - 1 of every per-scene array, its own stream / step state / fragment buffers) around enqueue_step.
-struct DecView {
-    hipStream_t stream;
-    float *xdec, *qdec, *logits, *logits_tar, *cond, *xfrag, *afrag, *hfrag;
-    void* kvcache;
-    int *d_tokens, *d_prev_box, *d_nboxes;
-    unsigned char* d_control;
-    double* d_boxes;
-    unsigned long long* d_seeds;
-    OarState* d_state;
-    TokenSide d_side;
-    float* d_bias_rows;
-};
 // ---- engine_decode.hip ----------------------------------------------------------------------------------------------
-DecView current_view(const umgen_engine* e);
-void apply_view(umgen_engine* e, const DecView& v);
-DecView lane_view(const umgen_engine* e, const DecView& all, const umgen_engine::DecLane& ln, int b0);
-int enqueue_step_any(umgen_engine* e, int B, int mod, int ns, const umgen_trace* tr, int j);
+// The path that takes a decode step of B scenes (umgen_dbg_oar_step's numbering)
+enum DecodePath { PATH_LAUNCHES = 0, PATH_ENGINE = 1, PATH_BATCHED = 2, PATH_WIDE = 3 };   // five launches per layer, XCD-resident engine, batched layer, chip-wide engine
+DecodePath decode_path(const umgen_engine* e, int B, hipStream_t st, bool lane);
+DecView lane_view(const umgen_engine* e, const umgen_engine::DecLane& ln, int b0);
+int enqueue_step_any(umgen_engine* e, const DecView& v, int B, int mod, int ns, const umgen_trace* tr, int j);
 int launch_bg_drain(umgen_engine* e, hipStream_t st);   // the launch without an engine part that runs what is left of the background workers' op list
 
 // ---- engine_frame.hip -----------------------------------------------------------------------------------------------

@@ -258,7 +258,7 @@ int umgen_finalize_weights(umgen_engine* e) {
                     gp[((size_t)i * 32 + j) * E + c] = f32_to_bf16(bf16_to_f32(posi[(size_t)tok[i] * E + c]) + bf16_to_f32(posi[(size_t)tok[j] * E + c]));
         HIPCHK(e, hipMemcpy(const_cast<bf16_t*>(e->tb.grid_posi), gp.data(), gp.size() * 2, hipMemcpyHostToDevice));
     }
-    const int rc = build_tables_any(e);
+    const int rc = build_tables_any(e, Place{e->stream, &e->w_main});
     if (rc) return rc;
     if (e->eng_enabled) { if (int rc2 = repack_mlp_proj(e)) return rc2; }
     if (e->wide_enabled) { if (int rc2 = repack_wide(e)) return rc2; }
