@@ -330,7 +330,8 @@ int umgen_frame_detail(umgen_engine *e, int32_t T, const int64_t *pose, const in
  *   - Refused with UMGEN_E_INVALID before anything reaches the device, the message naming class, row and index: a NaN or +inf entry; a row without an
  *     allowed entry; a bbox3d row whose only allowed entry is vocab - 1 when the call has control slots (control_test with ctrl_bbox3d: the control
  *     resample masks that index); a table of a class whose vocabulary exceeds 8192.
- *   - One set of tables per call: scenes, fan-out branches and frames share it.  lz without a bias is allowed (+0.0 / NaN).
+ *   - One set of tables per call: scenes, fan-out branches and frames share it (umgen_rollout_planned below lifts this).  lz without a bias is
+ *     allowed (+0.0 / NaN).
  * The scoring entry points take no bias: they describe the model, not a sampler. */
 typedef struct umgen_logit_bias { const float *pose, *map, *bbox3d, *image; } umgen_logit_bias;   /* host; any may be NULL = no bias for that class */
 typedef struct umgen_logz_out   { float *logz_pose, *logz_map, *logz_bbox3d, *logz_image; } umgen_logz_out; /* shapes of umgen_logp_out */
@@ -347,6 +348,45 @@ int umgen_frame_biased(umgen_engine *e, int32_t T, const int64_t *pose, const in
                        const umgen_sampling *sampling, int32_t frame_idx, const umgen_trace *trace,
                        int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image, const umgen_logp_out *lp,
                        int32_t topk, const umgen_gen_detail_out *detail, const umgen_logit_bias *bias, const umgen_logz_out *lz);
+
+/* ---- sampling plans: per-scene sampler settings, per-scene and per-frame table sets --------------------------------------------------------
+ * umgen_rollout_planned is umgen_rollout_biased with a plan in the place of `bias`: every scene / fan-out branch i = b*N + s of the call may draw
+ * under its own sampler settings, per_scene[i], and, in every NEW frame f, under its own set of logit-bias tables, bias_sets[bias_of[i][f]] (-1 = no
+ * bias).  umgen_rollout_biased is this call with per_scene = NULL and, when it has a `bias`, one set with bias_of = NULL; plan = NULL is the unbiased
+ * call.  There is no umgen_frame_planned: a frame call is one scene and one frame, so its caller has already resolved the plan.
+ * Contract.  Take a planned call on B*N scenes.  The tokens, lp, lz and diagnostics of scene i in new frame f are, bit for bit, what scene i of
+ * umgen_rollout_biased returns when that call has the same B, N, arrays and seeds, sampling = per_scene[i] (the call's `sampling` when per_scene is
+ * NULL), bias = bias_sets[bias_of[i][f]] (no bias for -1), and a history up to frame f that is the same bits.  In particular:
+ *   - a plan whose per_scene entries all equal `sampling`, and whose bias_of is constant, returns the bytes of the unplanned call;
+ *   - the plan does not enter the RNG: draws stay a function of (seed, frame, position, draw kind); the `seeds` members of per_scene are ignored,
+ *     the seeds are `sampling`'s;
+ *   - mass_above of the diagnostics is taken at the scene's own temperature;
+ *   - lp and the diagnostics stay on the model's row v; logz is formed against the scene's own table;
+ *   - a class without a table in a scene's set is not biased and its logz is +0.0: the "class without a table" path, not a table of zeros.
+ * rule_constrain, merge_ar_tar and only_ar stay PER CALL: the host decides per call whether head_tar_bbox3d runs, so every per_scene entry must
+ * carry the values of `sampling`.
+ * Refused with UMGEN_E_INVALID before anything reaches the device, the message naming scene, frame, set, class, row and index as applicable:
+ *   - a per_scene[i] that the call would refuse as its `sampling`, or whose rule_constrain / merge_ar_tar / only_ar differ from `sampling`'s;
+ *   - n_bias_sets outside [0, UMGEN_BIAS_SETS_MAX], or bias_of given with n_bias_sets == 0; a bias_of entry outside [-1, n_bias_sets);
+ *   - in ANY set, used by a scene or not, a table that umgen_rollout_biased refuses; the "bbox3d row that allows only vocab - 1 under control slots"
+ *     rule applies to every set that some scene uses.
+ * A set whose tables are all NULL is an empty set: its scenes are unbiased. */
+#define UMGEN_BIAS_SETS_MAX 16
+typedef struct umgen_sample_plan {
+    const umgen_sampling   *per_scene;   /* NULL, or [B*N]: the sampler settings of scene / branch b*N + s; their `seeds` members are ignored */
+    int32_t                 n_bias_sets; /* 0 .. UMGEN_BIAS_SETS_MAX */
+    const umgen_logit_bias *bias_sets;   /* [n_bias_sets]; every set is what umgen_rollout_biased takes as `bias` */
+    const int32_t          *bias_of;     /* NULL (every scene and frame uses set 0 when n_bias_sets >= 1), or [B*N][new_frames]: the set of scene i
+                                            in NEW frame f, -1 = unbiased */
+} umgen_sample_plan;
+int umgen_rollout_planned(umgen_engine *e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames,
+                          const int64_t *pose, const int64_t *map, const int64_t *bbox3d, const int64_t *image,
+                          int32_t T_ctl, const int64_t *ctrl_pose, const int64_t *ctrl_bbox3d, int32_t control_test,
+                          const int64_t *given_map, const int64_t *given_bbox3d,
+                          const umgen_sampling *sampling,
+                          int64_t *out_pose, int64_t *out_map, int64_t *out_bbox3d, int64_t *out_image,
+                          const umgen_logp_out *lp, int32_t *shared_slots, int32_t topk, const umgen_gen_detail_out *detail,
+                          const umgen_sample_plan *plan, const umgen_logz_out *lz);
 
 /* Ranking futures: C given next frames per scene against ONE history.  Entry (b, c) of every output is bit for bit what
  *     umgen_score(e, 1, T, window b, candidate (b, c))

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("UMGEN_LIB_PATH") or os.path.join(HERE, "libumgen_hip.
 SOURCES = ["engine.hip", "engine_setup.hip", "engine_weights.hip", "engine_stacks.hip", "engine_decode.hip", "engine_frame.hip", "engine_score.hip", "gemm.hip", "gemm256.hip", "attn.hip", "gemv.hip", "oar_engine.hip", "oar_engine_wide.hip", "decode_batched.hip", "score.hip", "rowops.hip", "frame.hip", "tokenizers.hip", "vqdec.hip", "vqenc.hip",
            "debug_gemm_attn.hip", "debug_decode.hip", "debug_frame.hip", "debug_score.hip", "debug_bg.hip", "debug_vq.hip"]
 EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen_rollout", "umgen_frame", "umgen_score", "umgen_score_detail", "umgen_score_candidates", "umgen_score_futures", "umgen_score_clip", "umgen_rollout_logp", "umgen_frame_logp", "umgen_rollout_fan",
-           "umgen_rollout_detail", "umgen_frame_detail", "umgen_rollout_biased", "umgen_frame_biased",
+           "umgen_rollout_detail", "umgen_frame_detail", "umgen_rollout_biased", "umgen_frame_biased", "umgen_rollout_planned",
            "umgen_set_profiling", "umgen_get_timings", "umgen_last_error", "umgen_version", "umgen_destroy",
            "umgen_tokenize_ego", "umgen_detokenize_ego", "umgen_tokenize_boxes", "umgen_detokenize_boxes",
            "umgen_vq_create", "umgen_vq_load_tensor", "umgen_vq_finalize", "umgen_vq_decode", "umgen_vq_last_error", "umgen_vq_destroy",
@@ -30,12 +30,13 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_prefix_rows", "umgen_dbg_prefix_kv_to_cache", "umgen_dbg_token_steps", "umgen_dbg_sample_ego", "umgen_dbg_token_steps_logp", "umgen_dbg_sample_ego_logp",
            "umgen_dbg_token_steps_detail", "umgen_dbg_sample_ego_detail",
            "umgen_dbg_token_steps_biased", "umgen_dbg_token_steps_biased_detail", "umgen_dbg_sample_ego_biased", "umgen_dbg_sample_biased",
+           "umgen_dbg_token_steps_planned", "umgen_dbg_sample_ego_planned",
            "umgen_dbg_head_nll", "umgen_dbg_head_nll_split", "umgen_dbg_head_detail", "umgen_dbg_logits_detail",
            "umgen_dbg_bg_begin", "umgen_dbg_bg_est", "umgen_dbg_bg_state", "umgen_dbg_bg_steps", "umgen_dbg_bg_drain", "umgen_dbg_bg_end", "umgen_dbg_tcache", "umgen_dbg_score_futures_passes",
            "umgen_dbg_vq_quantize", "umgen_dbg_vq_quant_tile", "umgen_dbg_vq_im2col", "umgen_dbg_vq_im2col_s2", "umgen_dbg_vq_upsample", "umgen_dbg_vq_from_nchw", "umgen_dbg_vq_to_nchw",
            "umgen_dbg_vq_group_norm", "umgen_dbg_vq_softmax"]
 
-HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "engine_frame.h", "token_windows.h", "gen_side.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
+HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "engine_frame.h", "token_windows.h", "gen_side.h", "sample_plan.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
 
 PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DT_F32, DT_BF16, DT_F16, DT_F64 = 0, 1, 2, 3
@@ -102,6 +103,14 @@ class LogpOut(C.Structure):
 class LogitBias(C.Structure):
     """umgen_logit_bias (include/umgen.h): host float32 tables pose [3][pose_vocab], map [map_vocab], bbox3d [11][bbox3d_vocab], image [img_vocab]; any may be NULL"""
     _fields_ = [(m, C.POINTER(C.c_float)) for m in ("pose", "map", "bbox3d", "image")]
+
+
+BIAS_SETS_MAX = 16
+
+
+class SamplePlan(C.Structure):
+    """umgen_sample_plan (include/umgen.h): per_scene [B*N] settings or NULL; n_bias_sets table sets; bias_of [B*N][new_frames] (-1 = unbiased) or NULL"""
+    _fields_ = [("per_scene", C.POINTER(Sampling)), ("n_bias_sets", C.c_int32), ("bias_sets", C.POINTER(LogitBias)), ("bias_of", C.POINTER(C.c_int32))]
 
 
 class LogzOut(C.Structure):
@@ -299,6 +308,7 @@ def load_library() -> C.CDLL:
     lib.umgen_frame_detail.argtypes = lib.umgen_frame_logp.argtypes + [i32, C.POINTER(GenDetailOut)]
     lib.umgen_rollout_biased.argtypes = lib.umgen_rollout_detail.argtypes + [C.POINTER(LogitBias), C.POINTER(LogzOut)]
     lib.umgen_frame_biased.argtypes = lib.umgen_frame_detail.argtypes + [C.POINTER(LogitBias), C.POINTER(LogzOut)]
+    lib.umgen_rollout_planned.argtypes = lib.umgen_rollout_detail.argtypes + [C.POINTER(SamplePlan), C.POINTER(LogzOut)]
     lib.umgen_score.argtypes = [vp, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut)]
     lib.umgen_score_detail.argtypes = lib.umgen_score.argtypes[:-1] + [i32, C.c_float, C.POINTER(ScoreOut), C.POINTER(ScoreDetailOut)]
     lib.umgen_score_candidates.argtypes = [vp, i32, i32, i32, i64p, i64p, i64p, i64p, i64p, i64p, i64p, i64p, C.POINTER(ScoreOut), C.POINTER(C.c_int32)]
@@ -368,6 +378,9 @@ def load_library() -> C.CDLL:
     lib.umgen_dbg_token_steps_biased_detail.argtypes = lib.umgen_dbg_token_steps_biased.argtypes + [i32, i32p, fp, fp, i32p, fp]
     lib.umgen_dbg_sample_ego_biased.argtypes = lib.umgen_dbg_sample_ego.argtypes + [fp, fp, fp]
     lib.umgen_dbg_sample_biased.argtypes = [i32, fp, fp, i32, i32, i32, C.c_float, C.c_float, i32, fp, i32p]
+    plan_args = [C.POINTER(DbgSamplerParams), fp, i32, i32p, i32p]      # sp_of [B], pool, n_sets, set_classes [n_sets], bias_set_of [B]
+    lib.umgen_dbg_token_steps_planned.argtypes = [tp, C.POINTER(DbgSteps), fp, fp, i32, i32p, fp, fp, i32p, fp] + plan_args
+    lib.umgen_dbg_sample_ego_planned.argtypes = lib.umgen_dbg_sample_ego.argtypes + [fp, fp, i32, i32p, fp, fp, i32p, fp] + plan_args
     lib.umgen_dbg_head_nll.argtypes = [i32, i32, i32, i32, fp, C.c_long, fp, vp, i32p, fp, i32p, fp, fp]
     lib.umgen_dbg_head_nll_split.argtypes = [i32]
     lib.umgen_dbg_head_detail.argtypes = [i32, i32, i32, i32, fp, C.c_long, fp, vp, i32p, i32, C.c_float, i32p, fp, fp, i32p, fp]

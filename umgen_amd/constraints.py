@@ -146,7 +146,80 @@ def pose_limits(dx: Optional[Tuple[float, float]] = None, dy: Optional[Tuple[flo
     return {"pose": t}
 
 
-def log_importance_weight(tokens: Dict[str, np.ndarray], logz: Dict[str, np.ndarray], tables: Optional[Tables]) -> np.ndarray:
+BIAS_SETS_MAX = 16      # UMGEN_BIAS_SETS_MAX (include/umgen.h): table sets of one call
+
+
+class Schedule:
+    """Which set of tables a scene / branch draws under in every new frame of ``Engine.rollout(logit_bias=schedule)`` (include/umgen.h:
+    umgen_rollout_planned).  ``sets``: the table sets, each a (merged) dict class -> array, ``{}`` for an empty set; ``index``: int array of set numbers,
+    -1 = unbiased, with the axes it was given over (``axes``: a subset of ("scene", "branch", "frame") in that order).  Build one with ``schedule`` or
+    ``per_frame``."""
+
+    def __init__(self, sets: Sequence[Tables], index: np.ndarray, axes: Tuple[str, ...]):
+        self.sets, self.index, self.axes = list(sets), index, tuple(axes)
+
+    def resolve(self, B: int, N: int, new_frames: int) -> np.ndarray:
+        """the index of a call over B scenes of N branches and new_frames new frames: int32 [B*N, new_frames]"""
+        want = {"scene": B, "branch": N, "frame": new_frames}
+        for ax, n in zip(self.axes, self.index.shape):
+            if n != want[ax]:
+                raise ValueError(f"schedule: the index has {n} entries along its {ax} axis, the call has {want[ax]}")
+        shape = tuple(self.index.shape[self.axes.index(ax)] if ax in self.axes else 1 for ax in ("scene", "branch", "frame"))
+        full = np.broadcast_to(self.index.reshape(shape), (B, N, new_frames))
+        return np.ascontiguousarray(full.reshape(B * N, new_frames), dtype=np.int32)
+
+
+def schedule(sets: Sequence[Optional[Tables]], index, axis: Optional[str] = None) -> Schedule:
+    """A schedule of table sets.  ``sets``: a list of table dicts (``None``: an empty set -- its scenes are unbiased), at most 16.  ``index``: integers in
+    [-1, len(sets)), -1 = unbiased, broadcast to [B*N, new_frames] by its SHAPE, never by the sizes that happen to match:
+
+        a scalar                       every scene, branch and frame
+        [B]                            per scene (a scene's branches and all frames share it)      -- the default for one dimension
+        [new_frames], axis="frame"     per new frame (all scenes and branches share it)
+        [B, N]                         per branch
+        [B, N, new_frames]             the full index (N = 1 without ``samples``)
+
+    Two dimensions always mean [B, N]: a [B, new_frames] array would be indistinguishable, so per-scene-and-frame indices are given in full, as
+    [B, N, new_frames].  Refused: more than three dimensions, ``axis`` with anything but one dimension, an ``axis`` other than "scene" / "frame", entries
+    outside [-1, len(sets)), more than 16 sets; a shape that does not fit the call is refused by the call (``Schedule.resolve``)."""
+    sets = [merge(t) for t in sets]
+    if len(sets) > BIAS_SETS_MAX:
+        raise ValueError(f"schedule: {len(sets)} table sets, a call takes at most {BIAS_SETS_MAX}")
+    idx = np.asarray(index)
+    if idx.dtype.kind not in "iu":
+        raise ValueError(f"schedule: the index has dtype {idx.dtype}, expected integers")
+    if axis not in (None, "scene", "frame"):
+        raise ValueError(f"schedule: axis={axis!r} (one of None, 'scene', 'frame')")
+    if axis is not None and idx.ndim != 1:
+        raise ValueError(f"schedule: axis={axis!r} names the axis of a one-dimensional index, this one has shape {idx.shape}")
+    if idx.ndim > 3:
+        raise ValueError(f"schedule: the index has shape {idx.shape}; accepted are a scalar, [B], [new_frames] with axis='frame', [B, N] and [B, N, new_frames]")
+    axes = {0: (), 1: ("frame",) if axis == "frame" else ("scene",), 2: ("scene", "branch"), 3: ("scene", "branch", "frame")}[idx.ndim]
+    if idx.size and (idx.min() < -1 or idx.max() >= len(sets)):
+        raise ValueError(f"schedule: index entries lie in [-1, {len(sets)}), found {int(idx.min())} .. {int(idx.max())}")
+    return Schedule(sets, idx.astype(np.int32), axes)
+
+
+def per_frame(tables_by_frame: Sequence[Optional[Tables]]) -> Schedule:
+    """One set of tables per new frame, for every scene and branch: ``tables_by_frame[f]`` applies in new frame f (``None``: unbiased).  Frames that hand over
+    the SAME dict object share a set (deduplicated by identity, not by value), so a long rollout that switches between a few constraints fits the call's 16
+    sets; more distinct objects are refused."""
+    sets, seen, index = [], {}, []
+    for t in tables_by_frame:
+        if t is None:
+            index.append(-1)
+            continue
+        if id(t) not in seen:
+            seen[id(t)] = len(sets)
+            sets.append(t)
+        index.append(seen[id(t)])
+    if len(sets) > BIAS_SETS_MAX:
+        raise ValueError(f"per_frame: {len(sets)} distinct table sets over {len(index)} frames, a call takes at most {BIAS_SETS_MAX} (reuse one dict object for "
+                         "frames that share their tables)")
+    return schedule(sets, np.asarray(index, dtype=np.int32), axis="frame")
+
+
+def log_importance_weight(tokens: Dict[str, np.ndarray], logz: Dict[str, np.ndarray], tables) -> np.ndarray:
     """The log importance weight of every generated frame of a constrained rollout against the model: the sum over the frame's sampled positions
     of ``logz - r[tok]`` (include/umgen.h), float64 [..., new_frames].
 
@@ -157,7 +230,12 @@ def log_importance_weight(tokens: Dict[str, np.ndarray], logz: Dict[str, np.ndar
     Exact under these conditions only: the rollout drew with an UNTRUNCATED sampler (today: ``sample_method="topp"`` with p = p_map = 1) at temperature
     1, and no token came from a control or pad-avoid resample (``only_ar`` and no control slots) -- then the proposal's density of a drawn token is
     softmax(v + r)[tok] = exp(lp + r[tok] - logz), and model / proposal = exp(logz - r[tok]).  A truncated or tempered sampler renormalises
-    differently, and a resampled token was drawn from another head; neither is accounted for here."""
+    differently, and a resampled token was drawn from another head; neither is accounted for here.
+
+    ``tables`` may be the ``Schedule`` of a planned rollout: every position then reads the row of ITS OWN set -- branch i in new frame f the set
+    ``schedule.resolve(B, N, F)[i, f]``, r = 0 for -1 and for a class without a table in that set; the leading axes of logz are then [B] or [B, N]."""
+    if isinstance(tables, Schedule):
+        return _scheduled_weight(tokens, logz, tables)
     tables = merge(tables)
     total = None
     for mod in CLASSES:
@@ -177,4 +255,19 @@ def log_importance_weight(tokens: Dict[str, np.ndarray], logz: Dict[str, np.ndar
         skip = np.isnan(lz)
         w = np.where(skip, 0.0, lz - np.where(skip, 0.0, r)).sum(axis=-1)
         total = w if total is None else total + w
+    return total
+
+
+def _scheduled_weight(tokens: Dict[str, np.ndarray], logz: Dict[str, np.ndarray], sch: Schedule) -> np.ndarray:
+    """log_importance_weight under a Schedule: the per-set weights, picked per (branch, frame) by the resolved index"""
+    lead = np.asarray(logz[CLASSES[0]]).shape[:-2]
+    F = np.asarray(logz[CLASSES[0]]).shape[-2]
+    if len(lead) not in (1, 2):
+        raise ValueError(f"logz has leading axes {lead}; a scheduled rollout returns [B, F, S_mod] or [B, N, F, S_mod]")
+    B, N = lead[0], (lead[1] if len(lead) == 2 else 1)
+    of = sch.resolve(B, N, F).reshape(lead + (F,))
+    total = log_importance_weight(tokens, logz, None)      # r = 0: unbiased positions and NaN skipping
+    for q, tabs in enumerate(sch.sets):
+        if tabs and (of == q).any():
+            total = np.where(of == q, log_importance_weight(tokens, logz, tabs), total)
     return total

@@ -98,7 +98,28 @@ struct SideHook {
 struct BiasHook {
     const float *map, *box /*[11][n_box]*/, *img;
 };
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh = nullptr);
+// The sampling plan of a planned hook on the host: sp_of [B] per-scene settings (NULL: OarState::plan bit 0 stays off); bias_set_of [B] (NULL: bit 1 stays
+// off) with the pool of n_sets table sets, `stride` floats apart, and set_classes [n_sets], the class bits (1 << kBiasPose ..) of every set.  A set of the
+// token-step hook lies like the engine's: pose [3][n_pose] | map [n_map] | bbox3d [11][n_box] | image [n_img]; a set of the ego hook is pose [3][V]
+struct PlanHook {
+    const SamplerParams* sp_of;
+    const float* pool;
+    int n_sets;
+    const int32_t* set_classes;
+    const int32_t* bias_set_of;
+};
+inline bool sampler_params_sane(const SamplerParams& sp) {
+    return sp.method >= 0 && sp.method <= 1 && sp.top_k >= 1 && sp.top_k_map >= 1 && sp.topk_image >= 1 && sp.temperature > 0.f;
+}
+// the index arrays of a plan: sets within the pool, scenes within the sets
+inline bool plan_index_sane(const PlanHook& ph, int B) {
+    if (!ph.bias_set_of) return true;
+    if (ph.n_sets < 0 || ph.n_sets > kBiasSetsMax || (ph.n_sets > 0 && (!ph.pool || !ph.set_classes))) return false;
+    for (int b = 0; b < B; ++b)
+        if (ph.bias_set_of[b] < -1 || ph.bias_set_of[b] >= ph.n_sets) return false;
+    return true;
+}
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh = nullptr, const PlanHook* ph = nullptr);
 // a hook's positions: B * 2199 (0 for a B the hook refuses anyway)
 inline size_t side_n(int B) { return B < 1 ? 0 : (size_t)B * kTokPerFrame; }
 
@@ -333,6 +354,18 @@ int umgen_dbg_token_steps_biased_detail(const umgen_dbg_tables* t, const umgen_d
     sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
     return sh.sane() ? token_steps(t, a, sh, &bh) : UMGEN_E_INVALID;
 }
+// ... and under a sampling plan (OarState::plan) in the place of the three tables: sp_of [B] per-scene settings (or NULL: a->sp for every scene), and
+// bias_set_of [B] (or NULL: no tables), scene b's set in the pool of n_sets sets (-1: none), with set_classes [n_sets]; a set lies like the engine's,
+// pose [3][n_pose] | map [n_map] | bbox3d [11][n_box] | image [n_img], the sets back to back.  Both NULL: the switch stays 0
+int umgen_dbg_token_steps_planned(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, float* logz, int topk, int32_t* rank, float* mass_above,
+                                  float* entropy, int32_t* topk_tok, float* topk_logp, const SamplerParams* sp_of, const float* pool, int n_sets,
+                                  const int32_t* set_classes, const int32_t* bias_set_of) {
+    if (!logp || !a || a->B < 1) return UMGEN_E_INVALID;
+    const PlanHook ph{sp_of, pool, n_sets, set_classes, bias_set_of};
+    SideHook sh{side_n(a->B), logp, logz};
+    sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
+    return sh.sane() ? token_steps(t, a, sh, nullptr, &ph) : UMGEN_E_INVALID;
+}
 
 }  // extern "C"
 
@@ -350,7 +383,7 @@ bool bias_rows_sane(const float* tab, int rows, int V) {
     }
     return true;
 }
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh) {
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh, const PlanHook* ph) {
     if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
     // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
     if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
@@ -384,6 +417,24 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& s
         if (!bias_rows_sane(bh->map, 1, t->n_map) || !bias_rows_sane(bh->box, kSlotLen, t->n_box) || !bias_rows_sane(bh->img, 1, t->n_img)) return UMGEN_E_INVALID;
         s0.bias_classes = (bh->map ? 1 << kBiasMap : 0) | (bh->box ? 1 << kBiasBox : 0) | (bh->img ? 1 << kBiasImg : 0);
     }
+    // a plan: the pool in the engine's layout, every table of every set checked like a biased hook's
+    const size_t pool_off[4] = {0, (size_t)3 * t->n_pose, (size_t)3 * t->n_pose + t->n_map, (size_t)3 * t->n_pose + t->n_map + (size_t)kSlotLen * t->n_box};
+    const size_t pool_stride = pool_off[kBiasImg] + (size_t)t->n_img;
+    if (ph) {
+        if (bh || !plan_index_sane(*ph, a->B)) return UMGEN_E_INVALID;
+        for (int b = 0; ph->sp_of && b < a->B; ++b)
+            if (!sampler_params_sane(ph->sp_of[b])) return UMGEN_E_INVALID;
+        for (int q = 0; ph->bias_set_of && q < ph->n_sets; ++q) {
+            const float* set = ph->pool + (size_t)q * pool_stride;
+            const int cl = ph->set_classes[q];
+            if (cl < 0 || cl >= 16) return UMGEN_E_INVALID;
+            if (((cl >> kBiasMap) & 1 && !bias_rows_sane(set + pool_off[kBiasMap], 1, t->n_map)) ||
+                ((cl >> kBiasBox) & 1 && !bias_rows_sane(set + pool_off[kBiasBox], kSlotLen, t->n_box)) ||
+                ((cl >> kBiasImg) & 1 && !bias_rows_sane(set + pool_off[kBiasImg], 1, t->n_img)))
+                return UMGEN_E_INVALID;
+        }
+        s0.plan = (ph->sp_of ? kPlanSettings : 0) | (ph->bias_set_of ? kPlanSets : 0);
+    }
     Scratch s;
     SampleArgs sa{};
     sa.tb = tables_in(s, *t);
@@ -401,6 +452,17 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& s
     if (bh) {
         dBias[kBiasMap] = s.in(bh->map, (size_t)t->n_map * 4); dBias[kBiasBox] = s.in(bh->box, (size_t)kSlotLen * t->n_box * 4);
         dBias[kBiasImg] = s.in(bh->img, (size_t)t->n_img * 4);
+        sa.bias_rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
+    }
+    if (ph && ph->sp_of) sa.sp_of = s.in(ph->sp_of, (size_t)B * sizeof(SamplerParams));
+    if (ph && ph->bias_set_of) {
+        int32_t classes[kBiasSetsMax] = {};
+        for (int q = 0; q < ph->n_sets; ++q) classes[q] = ph->set_classes[q];
+        sa.set_classes = s.in(classes, sizeof(classes));
+        sa.bias_set_of = s.in(ph->bias_set_of, (size_t)B * 4);
+        sa.bias_stride = (long)pool_stride;
+        const float* dPool = s.in(ph->pool, (size_t)ph->n_sets * pool_stride * 4);      // (no set: nullptr, and no scene reads it)
+        for (int c = kBiasMap; c <= kBiasImg; ++c) dBias[c] = dPool ? dPool + pool_off[c] : nullptr;
         sa.bias_rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
     }
     if (s.rc) return s.rc;
@@ -434,8 +496,15 @@ extern "C" {
 // [B][2199] (or NULL) overrides with its pose tokens.  logp [B][2199] (in / out, or NULL): entry [b][jq] receives the log-likelihood of pose token jq
 // of scene b on its row
 static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
-                           int32_t* out_tokens, SideHook& sh, const float* bias = nullptr) {
+                           int32_t* out_tokens, SideHook& sh, const float* bias = nullptr, const PlanHook* ph = nullptr) {
     if (bias && !bias_rows_sane(bias, 3, V)) return UMGEN_E_INVALID;
+    if (ph) {
+        if (bias || B < 1 || V < 1 || !plan_index_sane(*ph, B)) return UMGEN_E_INVALID;
+        for (int b = 0; ph->sp_of && b < B; ++b)
+            if (!sampler_params_sane(ph->sp_of[b])) return UMGEN_E_INVALID;
+        for (int q = 0; ph->bias_set_of && q < ph->n_sets; ++q)
+            if ((ph->set_classes[q] & ~1) || ((ph->set_classes[q] & 1) && !bias_rows_sane(ph->pool + (size_t)q * 3 * V, 3, V))) return UMGEN_E_INVALID;
+    }
     if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
         return UMGEN_E_INVALID;
     for (int b = 0; (sh.logp || sh.detail) && forced && b < B; ++b)      // the scored token indexes the row
@@ -449,6 +518,19 @@ static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, 
     sh.to_device(s);
     EgoSide es{sh.d, sh.topk, s.in(bias, (size_t)3 * V * 4)};
     if (bias) es.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
+    if (ph) {
+        es.plan = (ph->sp_of ? kPlanSettings : 0) | (ph->bias_set_of ? kPlanSets : 0);
+        if (ph->sp_of) es.sp_of = s.in(ph->sp_of, (size_t)B * sizeof(SamplerParams));
+        if (ph->bias_set_of) {
+            int32_t classes[kBiasSetsMax] = {};
+            for (int q = 0; q < ph->n_sets; ++q) classes[q] = ph->set_classes[q];
+            es.set_classes = s.in(classes, sizeof(classes));
+            es.bias_set_of = s.in(ph->bias_set_of, (size_t)B * 4);
+            es.bias_stride = (long)3 * V;
+            es.bias = s.in(ph->pool, (size_t)ph->n_sets * 3 * V * 4);
+            es.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
+        }
+    }
     if (s.rc) return s.rc;
     if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
     launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, es);
@@ -464,6 +546,19 @@ int umgen_dbg_sample_ego_biased(const float* logits, int V, const SamplerParams*
                                 int32_t* out_tokens, const float* bias, float* logp, float* logz) {
     SideHook sh{side_n(B), logp, logz};
     return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, bias);
+}
+// the same under a sampling plan: sp_of [B] (or NULL: *sp for every scene); bias_set_of [B] (or NULL) into a pool of n_sets pose tables [n_sets][3][V] with
+// set_classes [n_sets] (bit kBiasPose: the set has its table); rank .. topk_logp: umgen_dbg_sample_ego_detail's diagnostics (rank NULL: none), every
+// scene's mass_above at its own temperature
+int umgen_dbg_sample_ego_planned(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
+                                 int32_t* out_tokens, float* logp, float* logz, int topk, int32_t* rank, float* mass_above, float* entropy,
+                                 int32_t* topk_tok, float* topk_logp, const SamplerParams* sp_of, const float* pool, int n_sets,
+                                 const int32_t* set_classes, const int32_t* bias_set_of) {
+    const PlanHook ph{sp_of, pool, n_sets, set_classes, bias_set_of};
+    SideHook sh{side_n(B), logp, logz};
+    if (rank) sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);      // (rank NULL: no diagnostics, like umgen_dbg_sample_ego_biased)
+    if (!sh.sane() || (sh.detail && !logp)) return UMGEN_E_INVALID;
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, nullptr, &ph);
 }
 int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                               int32_t* out_tokens, float* logp) {

@@ -1,6 +1,6 @@
 // The C ABI of include/umgen.h that drives frames: version and error text, profiling and timings, the argument checks at the ABI boundary,
 // umgen_frame(_logp, _detail, _biased), umgen_score(_detail), umgen_score_candidates, umgen_score_futures, umgen_score_clip and the rollout driver
-// umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail / umgen_rollout_biased (UMGen.inference).  Every call narrows its int64 tokens once (narrow_tokens) and
+// umgen_rollout(_logp) / umgen_rollout_fan / umgen_rollout_detail / umgen_rollout_biased / umgen_rollout_planned (UMGen.inference).  Every call narrows its int64 tokens once (narrow_tokens) and
 // hands them on as a TokenView (token_windows.h); the output structs become [4] arrays through MOD4; the driver keeps one conditioning sequence and
 // gathers a frame's window from it, and a frame's control / given tokens are one plan_frame, for the driver and for umgen_frame alike.  Whatever a
 // generation call returns beside its tokens -- logp, logz, diagnostics -- is one GenSide (gen_side.h): checked and sized by gen_side_request, handed to
@@ -77,12 +77,8 @@ int umgen_get_timings(umgen_engine* e, umgen_timings* out) {
 
 static int check_sampling(umgen_engine* e, const umgen_sampling* s) {
     if (!s) return e->fail(UMGEN_E_INVALID, "sampling is null");
-    if (s->method != UMGEN_SAMPLE_TOPK && s->method != UMGEN_SAMPLE_TOPP) return e->fail(UMGEN_E_INVALID, "sample method %d", s->method);
-    if (s->method == UMGEN_SAMPLE_TOPP && !(s->p > 0.f && s->p_map > 0.f)) return e->fail(UMGEN_E_INVALID, "top-p mass must be > 0");
-    if (s->top_k < 1 || s->top_k > 16 || s->top_k_map < 1 || s->top_k_map > 16 || s->topk_image < 1 || s->topk_image > 16)
-        return e->fail(UMGEN_E_INVALID, "top-k values must be in [1, 16] (reference: 5 / 5 / 16)");
-    if (!(s->temperature > 0.f)) return e->fail(UMGEN_E_INVALID, "temperature must be > 0");
-    return 0;
+    const std::string m = sampling_error(*s);      // (sample_plan.h: the same check serves every per_scene entry of a planned call)
+    return m.empty() ? 0 : e->fail(UMGEN_E_INVALID, "%s", m.c_str());
 }
 
 // Every token that becomes a gather index is checked at the ABI boundary (history: embed_stack_kernel's table rows; control
@@ -137,37 +133,74 @@ static int check_bias(umgen_engine* e, const umgen_logit_bias* bias, bool contro
     *classes = 0;
     if (!bias) return 0;
     const float* const tab[4] = {bias->pose, bias->map, bias->bbox3d, bias->image};
-    const char* const name[4] = {"pose", "map", "bbox3d", "image"};
-    const int rows[4] = {3, 1, kSlotLen, 1}, vocab[4] = {e->cfg.pose_vocab, e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
-    for (int c = 0; c < 4; ++c) {
-        if (!tab[c]) continue;
-        if (vocab[c] > kBiasRowLen)
-            return e->fail(UMGEN_E_INVALID, "logit bias: class %s has a vocabulary of %d, the samplers' scratch row holds %d", name[c], vocab[c], kBiasRowLen);
-        for (int r = 0; r < rows[c]; ++r) {
-            const float* row = tab[c] + (size_t)r * vocab[c];
-            int allowed = 0, last = -1;
-            for (int n = 0; n < vocab[c]; ++n) {
-                const float v = row[n];
-                if (v != v || v == INFINITY)
-                    return e->fail(UMGEN_E_INVALID, "logit bias: class %s row %d index %d is %s (entries are finite or -inf)", name[c], r, n, v != v ? "NaN" : "+inf");
-                if (v != -INFINITY) { ++allowed; last = n; }
-            }
-            if (!allowed) return e->fail(UMGEN_E_INVALID, "logit bias: class %s row %d bans every token (index 0 .. %d are all -inf)", name[c], r, vocab[c] - 1);
-            if (c == kBiasBox && control_slots && allowed == 1 && last == vocab[c] - 1)
-                return e->fail(UMGEN_E_INVALID, "logit bias: class %s row %d allows only index %d, which the control resample of a controlled slot masks", name[c], r, last);
-        }
-        *classes |= 1 << c;
-    }
+    const int vocab[4] = {e->cfg.pose_vocab, e->cfg.map_vocab, e->cfg.bbox3d_vocab, e->cfg.img_vocab};
+    const std::string m = bias_tables_error(tab, vocab, kBiasRowLen, control_slots, classes);      // (sample_plan.h)
+    if (!m.empty()) return e->fail(UMGEN_E_INVALID, "%s", m.c_str());
     if (!*classes) return 0;
     host.assign(e->bias_floats(), 0.f);
     for (int c = 0; c < 4; ++c)
-        if (tab[c]) memcpy(host.data() + e->bias_offset(c), tab[c], (size_t)rows[c] * vocab[c] * sizeof(float));
+        if (tab[c]) memcpy(host.data() + e->bias_offset(c), tab[c], (size_t)kPlanTableRows[c] * vocab[c] * sizeof(float));
     return 0;
 }
 // ... and onto the device, on the engine's stream and finished before the call's first frame starts (a frame may run on another stream of the engine)
 static int upload_bias(umgen_engine* e, const std::vector<float>& host) {
     if (host.empty()) return 0;
     HIPCHK(e, hipMemcpyAsync(e->d_bias, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// What a planned call (umgen_sample_plan) brings, behind its checks and before anything reaches the device.  plan == NULL, or a plan without per_scene
+// entries and without an index array, resolves to the unplanned call: bits 0, its one set (if any) in set 0 of the pool.
+struct PlanHost {
+    int bits = 0;                      // OarState::plan
+    int classes0 = 0;                  // the class bits of set 0 (OarState::bias_classes of the unplanned form)
+    std::vector<SamplerParams> sp;     // [items] with kPlanSettings
+    PlanIndex idx;                     // [items][new_frames] with kPlanSets
+    std::vector<float> pool;           // [n_sets][bias_floats()], absent classes 0 (never read)
+    int set_classes[kBiasSetsMax] = {};
+};
+static SamplerParams sampler_params(const umgen_sampling& s) {
+    return SamplerParams{s.method, s.top_k, s.top_k_map, s.topk_image, s.p, s.p_map, s.temperature, s.rule_constrain, s.merge_ar_tar, s.only_ar};
+}
+static int check_plan(umgen_engine* e, const umgen_sample_plan* plan, const umgen_sampling* sampling, int items, int new_frames, bool control_slots,
+                      bool wants_detail, PlanHost& ph) {
+    if (!plan) return 0;
+    if (plan->per_scene) {
+        const std::string m = plan_settings_error(*sampling, plan->per_scene, items);
+        if (!m.empty()) return e->fail(UMGEN_E_INVALID, "%s", m.c_str());
+        for (int i = 0; wants_detail && i < items; ++i)      // (check_detail_request's bar on the call's temperature, per scene)
+            if (!(plan->per_scene[i].temperature <= 3.0e38f)) return e->fail(UMGEN_E_INVALID, "sample plan: per_scene[%d]: temperature must be > 0 and finite", i);
+        ph.sp.resize((size_t)items);
+        for (int i = 0; i < items; ++i) ph.sp[(size_t)i] = sampler_params(plan->per_scene[i]);
+        ph.bits |= kPlanSettings;
+    }
+    {
+        const std::string m = plan_index_error(items, new_frames, plan->n_bias_sets, plan->bias_of, ph.idx);
+        if (!m.empty()) return e->fail(UMGEN_E_INVALID, "%s", m.c_str());
+    }
+    if (plan->n_bias_sets > 0 && !plan->bias_sets) return e->fail(UMGEN_E_INVALID, "sample plan: n_bias_sets=%d with bias_sets = NULL", plan->n_bias_sets);
+    // every set is validated, used or not; the control-slot rule holds for the sets some scene uses
+    const bool named = plan->bias_of != nullptr || plan->n_bias_sets > 1;      // (umgen_rollout_biased's one set keeps its messages)
+    ph.pool.assign((size_t)plan->n_bias_sets * e->bias_floats(), 0.f);
+    for (int s = 0; s < plan->n_bias_sets; ++s) {
+        std::vector<float> host;
+        if (int rc = check_bias(e, &plan->bias_sets[s], control_slots && ph.idx.uses(s), host, &ph.set_classes[s])) {
+            if (named) e->err = "sample plan: bias set " + std::to_string(s) + ": " + e->err;
+            return rc;
+        }
+        if (!host.empty()) memcpy(ph.pool.data() + (size_t)s * e->bias_floats(), host.data(), host.size() * sizeof(float));
+    }
+    ph.classes0 = ph.set_classes[0];
+    if (plan->bias_of) ph.bits |= kPlanSets;
+    return 0;
+}
+// ... and onto the device like upload_bias: the pool, the sets' class bits and the per-scene settings, once per call
+static int upload_plan(umgen_engine* e, const PlanHost& ph) {
+    if (ph.bits == 0 && ph.classes0 == 0) return 0;      // nothing a sampler of this call reads
+    if (!ph.pool.empty()) HIPCHK(e, hipMemcpyAsync(e->d_bias, ph.pool.data(), ph.pool.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (ph.bits & kPlanSets) HIPCHK(e, hipMemcpyAsync(e->d_set_classes, ph.set_classes, sizeof(ph.set_classes), hipMemcpyHostToDevice, e->stream));
+    if (ph.bits & kPlanSettings) HIPCHK(e, hipMemcpyAsync(e->dv.d_sp_of, ph.sp.data(), ph.sp.size() * sizeof(SamplerParams), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return 0;
 }
@@ -405,7 +438,7 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
                           const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
                           const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
                           int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
-                          const umgen_gen_detail_out* detail, const umgen_logit_bias* bias, const umgen_logz_out* lz) {
+                          const umgen_gen_detail_out* detail, const umgen_sample_plan* splan, const umgen_logz_out* lz) {
     if (!e) return UMGEN_E_INVALID;
     const int64_t* const in[4] = {pose, map, bbox3d, image};
     int64_t* const out[4] = {out_pose, out_map, out_bbox3d, out_image};
@@ -414,10 +447,13 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
     if (int rc = check_rollout(e, B, T_in, new_frames, cond_frames, in, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d, sampling, out, gs,
                                (size_t)BN, lp, lz, topk, detail))
         return rc;
-    std::vector<float> bias_host;      // one set of tables per call: scenes, branches and frames share it
-    int bias_classes = 0;
-    if (int rc = check_bias(e, bias, ctrl_bbox3d && control_test, bias_host, &bias_classes)) return rc;
-    if (int rc = upload_bias(e, bias_host)) return rc;
+    // the call's plan: per-scene settings, the pool of table sets and which set scene i draws under in new frame f.  An unplanned call (one set of tables, or
+    // none, for every scene, branch and frame) leaves ph.bits 0 and takes the path it always took
+    PlanHost ph;
+    const SideDst want{MOD4(lp, logp), MOD4(lz, logz), MOD4(detail, rank), MOD4(detail, mass_above), MOD4(detail, entropy), MOD4(detail, topk_tok), MOD4(detail, topk_logp), topk};
+    if (int rc = check_plan(e, splan, sampling, BN, new_frames, ctrl_bbox3d && control_test, want.wants_detail(), ph)) return rc;
+    if (int rc = upload_plan(e, ph)) return rc;
+    std::vector<int> set_of((size_t)BN, -1);      // column idx of the plan's index (the frame's upload reads it until the frame's synchronisation)
     e->tm = umgen_timings{};
     e->overlap_suspended = false;
     TokenSeqs seq, win;      // (win: the frame's asynchronous uploads read it until the frame's synchronisation)
@@ -445,7 +481,13 @@ static int rollout_driver(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, i
         io.given_map = FramePlan::ptr(plan.gm);
         io.given_box = FramePlan::ptr(plan.gb);
         io.side = gs.frame();
-        io.bias_classes = bias_classes;
+        io.plan = ph.bits;
+        if (ph.bits & kPlanSets) {
+            ph.idx.column(idx, set_of.data());
+            io.bias_set_of = set_of.data();
+        } else {
+            io.bias_classes = ph.classes0;
+        }
         const char* fse = getenv("UMGEN_FAN_SHARE");      // (read per call: the tests compare both forms in one process)
         const bool fan = idx == 0 && N >= 2 && w.n >= 2 && !(fse && fse[0] == '0') && ensure_tcache(e);
         if (fan && shared_slots) *shared_slots = w.n - 1;
@@ -474,12 +516,12 @@ int umgen_rollout_logp(umgen_engine* e, int32_t B, int32_t T_in, int32_t new_fra
 // umgen_rollout_fan: N sampled futures per scene, the driver above with N branches per scene, whose first frame shares the history between a scene's branches
 // (engine_frame.hip run_frame_fan).  Every argument is checked once, on the caller's arrays: an error that names a flat index names it there.
 // umgen_rollout_detail: the same with the diagnostics of every generated token ([B][N][..] likewise)
-// umgen_rollout_biased: the same with the call's logit-bias tables and logz of every sampled position
-int umgen_rollout_biased(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
-                         const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
-                         const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
-                         int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
-                         const umgen_gen_detail_out* detail, const umgen_logit_bias* bias, const umgen_logz_out* lz) {
+// umgen_rollout_planned: the same with the call's sampling plan (per-scene settings, per-scene and per-frame table sets) and logz of every sampled position
+int umgen_rollout_planned(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                          const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                          const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                          int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
+                          const umgen_gen_detail_out* detail, const umgen_sample_plan* plan, const umgen_logz_out* lz) {
     if (!e) return UMGEN_E_INVALID;
     if (shared_slots) *shared_slots = 0;
     if (!e->finalized) return e->fail(UMGEN_E_STATE, "umgen_finalize_weights has not been called");
@@ -487,7 +529,18 @@ int umgen_rollout_biased(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, in
     if (N < 1) return e->fail(UMGEN_E_INVALID, "N=%d: at least one sample per scene", N);
     if ((int64_t)B * N > e->cfg.max_batch) return e->fail(UMGEN_E_INVALID, "B*N=%lld (B=%d, N=%d) exceeds max_batch=%d", (long long)B * N, B, N, e->cfg.max_batch);
     return rollout_driver(e, B, N, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map, given_bbox3d,
-                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail, bias, lz);
+                          sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail, plan, lz);
+}
+
+// umgen_rollout_biased: the plan of one set for every scene, branch and frame (none without a bias)
+int umgen_rollout_biased(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,
+                         const int64_t* bbox3d, const int64_t* image, int32_t T_ctl, const int64_t* ctrl_pose, const int64_t* ctrl_bbox3d, int32_t control_test,
+                         const int64_t* given_map, const int64_t* given_bbox3d, const umgen_sampling* sampling, int64_t* out_pose, int64_t* out_map,
+                         int64_t* out_bbox3d, int64_t* out_image, const umgen_logp_out* lp, int32_t* shared_slots, int32_t topk,
+                         const umgen_gen_detail_out* detail, const umgen_logit_bias* bias, const umgen_logz_out* lz) {
+    const umgen_sample_plan one{nullptr, 1, bias, nullptr};
+    return umgen_rollout_planned(e, B, N, T_in, new_frames, cond_frames, pose, map, bbox3d, image, T_ctl, ctrl_pose, ctrl_bbox3d, control_test, given_map,
+                                 given_bbox3d, sampling, out_pose, out_map, out_bbox3d, out_image, lp, shared_slots, topk, detail, bias ? &one : nullptr, lz);
 }
 
 int umgen_rollout_detail(umgen_engine* e, int32_t B, int32_t N, int32_t T_in, int32_t new_frames, int32_t cond_frames, const int64_t* pose, const int64_t* map,

@@ -482,8 +482,14 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     side(&e->dv.d_side.logp, 1); side(&e->dv.d_side.logz, 1); side(&d.rank, 1); side(&d.mass_above, 1); side(&d.entropy, 1);
     side(&d.topk_tok, kDetailTopK); side(&d.topk_logp, kDetailTopK);
     if (rc) return rc;
-    if (int rc = dalloc(e, &e->d_bias, e->bias_floats())) return rc;
+    // (d_bias is the pool of kBiasSetsMax table sets of a planned call; an unplanned call's one set is set 0 of it)
+    if (int rc = dalloc(e, &e->d_bias, (size_t)kBiasSetsMax * e->bias_floats())) return rc;
     if (int rc = dalloc(e, &e->dv.d_bias_rows, Bm * kBiasRows * kBiasRowLen)) return rc;
+    if (int rc = dalloc(e, &e->d_set_classes, (size_t)kBiasSetsMax)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_sp_of, Bm)) return rc;
+    if (int rc = dalloc(e, &e->dv.d_bias_set_of, Bm)) return rc;
+    HIPCHK(e, hipMemset(e->d_set_classes, 0, (size_t)kBiasSetsMax * sizeof(int)));
+    HIPCHK(e, hipMemset(e->dv.d_bias_set_of, 0xFF, Bm * sizeof(int)));
     return 0;
 }
 

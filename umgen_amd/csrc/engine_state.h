@@ -27,7 +27,10 @@
 #include "frame.h"
 #include "gen_side.h"
 #include "kernels.h"
+#include "sample_plan.h"
 #include "token_windows.h"
+
+static_assert(umgen::kBiasSetsMax == UMGEN_BIAS_SETS_MAX && umgen::kPlanSetsMax == UMGEN_BIAS_SETS_MAX, "one limit on the table sets of a sampling plan");
 
 using namespace umgen;
 
@@ -71,6 +74,10 @@ struct DecView {
     // and d_bias_rows -- so that every captured step graph holds the final pointers
     TokenSide d_side;
     float* d_bias_rows;      // [max_batch][kBiasRows][kBiasRowLen], the samplers' scratch rows (SampleArgs::bias_rows)
+    // sampling plan (umgen_rollout_planned): [max_batch] per-scene settings, uploaded once per call, and the scenes' table sets in the frame being generated
+    // (-1 = none), uploaded per frame; read under OarState::plan only (SampleArgs::sp_of / bias_set_of)
+    SamplerParams* d_sp_of;
+    int* d_bias_set_of;
 };
 
 }  // namespace umgen
@@ -103,7 +110,10 @@ struct umgen_engine {
     int *d_forced = nullptr, *d_counters = nullptr, *d_ego_tok = nullptr;
     // Constrained sampling (umgen_rollout_biased / umgen_frame_biased): d_bias, the call's tables pose [3][pose_vocab] | map [map_vocab] |
     // bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_offset: a class's start); the samplers' scratch rows are dv.d_bias_rows
+    // A planned call (umgen_rollout_planned) brings up to kBiasSetsMax sets: d_bias is the pool [kBiasSetsMax][bias_floats()], set 0 of it the tables of an
+    // unplanned call; d_set_classes [kBiasSetsMax] holds every set's class bits
     float* d_bias = nullptr;
+    int* d_set_classes = nullptr;
     size_t bias_floats() const { return (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab + cfg.img_vocab; }
     size_t bias_offset(int cls) const {
         const size_t o[4] = {0, (size_t)3 * cfg.pose_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab};
@@ -325,6 +335,8 @@ struct FrameIO {
     int* out_tokens;                             // host [B][2199]
     const FrameSide* side = nullptr;             // or nullptr: the side outputs the call asked for of every content token of the new frame (NaN / -1 where no head ran)
     int bias_classes = 0;                        // bit c: the call uploaded a logit-bias table for class c into d_bias (OarState::bias_classes)
+    int plan = 0;                                // OarState::plan of a planned call: kPlanSettings (dv.d_sp_of is uploaded), kPlanSets (bias_set_of below)
+    const int* bias_set_of = nullptr;            // host [B] with kPlanSets: the scenes' table sets in this frame, -1 = none (column f of the plan's index)
     int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
     bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
     bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed

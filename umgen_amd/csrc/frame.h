@@ -66,7 +66,13 @@ struct OarState {
     // (kBiasPose ..), want_logz that the samplers also write logz
     int bias_classes;
     int want_logz;
+    // sampling plan (umgen_rollout_planned), the last switch: bit 0 (kPlanSettings) -- scene b draws under SampleArgs::sp_of[b] instead of sp; bit 1
+    // (kPlanSets) -- scene b's tables are set SampleArgs::bias_set_of[b] of the table pool (-1: none) and bias_classes is not read.  0: neither sampler
+    // executes anything new beyond testing the word
+    int plan;
 };
+enum { kPlanSettings = 1, kPlanSets = 2 };
+constexpr int kBiasSetsMax = 16;    // == UMGEN_BIAS_SETS_MAX: table sets of the pool
 
 // Logit-bias classes: the bit of a token class in OarState::bias_classes is 1 << class; map / bbox3d / image are SampleArgs::mod.  The tables of a call lie
 // back to back on the device: pose [3][pose_vocab] | map [map_vocab] | bbox3d [11][bbox3d_vocab] | image [img_vocab]
@@ -123,6 +129,12 @@ struct SampleArgs {
     TokenSide side;            // [B][2199] side outputs of the token at its entry: what a step writes of them is st->want_logp / want_detail / want_logz
     const float* bias;         // the bias table of this step's class: [vocab] (map, image) or [11][vocab] (bbox3d, row k % 11); read when bit `mod` of st->bias_classes is set
     float* bias_rows;          // [B][kBiasRows][kBiasRowLen] scratch: w = v + r of the AR row (row 0) and of the TAR row of a resample (row 1), written and read by the scene's block
+    // sampling plan (OarState::plan; fixed at engine creation like every pointer here).  `bias` is the class table of set 0 of the pool: set s lies
+    // bias_stride floats behind it per set
+    const SamplerParams* sp_of;   // [B] per-scene settings (kPlanSettings)
+    const int* bias_set_of;       // [B] the scene's table set in the frame being generated, -1 = none (kPlanSets)
+    const int* set_classes;       // [kBiasSetsMax] the class bits of every set
+    long bias_stride;             // floats per set of the pool
 };
 
 // what the ego sampler writes beside its three pose tokens, entries [b][jq] of `out`, and what it needs of a biased call (all null: the plain call)
@@ -131,6 +143,12 @@ struct EgoSide {
     int detail_topk = 0;           // entries of the diagnostics' lists
     const float* bias = nullptr;   // the pose table [3][vocab] or nullptr
     float* rows = nullptr;         // [B][kBiasRows][kBiasRowLen] scratch, row jq of scene b
+    // sampling plan: OarState::plan's bits and SampleArgs' four plan members; with kPlanSets `bias` is the pose table of set 0 of the pool (never null)
+    int plan = 0;
+    const SamplerParams* sp_of = nullptr;
+    const int* bias_set_of = nullptr;
+    const int* set_classes = nullptr;
+    long bias_stride = 0;
 };
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);

@@ -760,7 +760,9 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     __shared__ float cor[64][8];
     __shared__ int s_tok;
     const int b = blockIdx.x, j = a.st->step, frame = a.st->frame_idx, E = a.tb.E;
-    const SamplerParams sp = a.st->sp;
+    // sampling plan (OarState::plan, 0 on every unplanned call): the block is a scene, so its own settings and its own table set stay block-uniform
+    const int plan = a.st->plan;
+    const SamplerParams sp = (plan & kPlanSettings) ? a.sp_of[b] : a.st->sp;
     const bool use_forced = a.st->use_forced != 0, use_control = a.st->use_control != 0, want_logp = a.st->want_logp != 0;
     const bool want_detail = a.st->want_detail != 0;
     const int pos1 = j + 1;   // the reference's 1-based curr_seq_len
@@ -777,11 +779,19 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     // Constrained sampling (OarState::bias_classes, block-uniform, 0 unless the call brought a table for this class): every sampler of this step reads
     // w = v + r instead of v, r the class row of the position (bbox3d: attribute k % 11) -- the AR row here, the TAR row inside the two resamples.
     // lp and the diagnostics below stay on v.
-    const bool biased = ((a.st->bias_classes >> a.mod) & 1) != 0, want_logz = a.st->want_logz != 0;
+    // Under kPlanSets the scene's set decides: no set (-1), or a set without a table for this class, is the unbiased path (logz +0.0)
+    bool biased = ((a.st->bias_classes >> a.mod) & 1) != 0;
+    const bool want_logz = a.st->want_logz != 0;
+    const float* tab = a.bias;
+    if (plan & kPlanSets) {
+        const int set = a.bias_set_of[b];
+        biased = set >= 0 && ((a.set_classes[set] >> a.mod) & 1) != 0;
+        if (biased) tab += (long)set * a.bias_stride;
+    }
     const float* rb = nullptr;
     const float* lw = lg;
     if (biased) {
-        rb = a.bias + (a.mod == 2 ? (long)(k % kSlotLen) * a.vocab : 0L);
+        rb = tab + (a.mod == 2 ? (long)(k % kSlotLen) * a.vocab : 0L);
         lw = biased_row(lg, rb, a.vocab, a.bias_rows + (long)b * kBiasRows * kBiasRowLen);
     }
     int tok = block_sample(sp, lw, a.vocab, topk, topp, rng_uniform(seed, frame, pos1, DRAW_MAIN), -1, sh, a.counters + 7);
@@ -862,15 +872,24 @@ __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict
                                                          const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow, EgoSide es) {
     __shared__ SamplerLds sh;
     const int b = blockIdx.x / 3, jq = blockIdx.x % 3;
+    // sampling plan (EgoSide::plan, 0 on every unplanned call): scene b's own settings, and the pose table of scene b's own set
+    if (es.plan & kPlanSettings) sp = es.sp_of[b];
+    bool biased = es.bias != nullptr;
+    const float* tab = es.bias;
+    if (es.plan & kPlanSets) {
+        const int set = es.bias_set_of[b];
+        biased = set >= 0 && ((es.set_classes[set] >> kBiasPose) & 1) != 0;
+        if (biased) tab += (long)set * es.bias_stride;
+    }
     // a pose table (constrained sampling): the draw reads w = v + r[jq]; the side outputs stay on v
     const float* lg = logits + (long)blockIdx.x * vocab;
     const float* lw = lg;
-    if (es.bias) lw = biased_row(lg, es.bias + (long)jq * vocab, vocab, es.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
+    if (biased) lw = biased_row(lg, tab + (long)jq * vocab, vocab, es.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
     int tok = block_sample(sp, lw, vocab, sp.top_k, sp.p,
                            rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN), -1, sh, overflow);
     if (forced) tok = forced[(long)b * kTokPerFrame + jq];
     if (threadIdx.x == 0) out_tokens[b * 3 + jq] = tok;
-    block_token_side(lg, lw, vocab, tok, es.out.logz != nullptr, es.bias != nullptr, es.out.logp != nullptr, es.out.detail.rank != nullptr, es.detail_topk,
+    block_token_side(lg, lw, vocab, tok, es.out.logz != nullptr, biased, es.out.logp != nullptr, es.out.detail.rank != nullptr, es.detail_topk,
                      sp.temperature, es.out, (long)b * kTokPerFrame + jq);
 }
 void launch_sample_ego(hipStream_t s, const float* logits, int vocab, SamplerParams sp, const unsigned long long* seeds, int frame_idx,

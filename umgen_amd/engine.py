@@ -154,6 +154,75 @@ class Engine:
             return None, None
         return _lib.LogitBias(**{m: a.ctypes.data_as(C.POINTER(C.c_float)) for m, a in keep.items()}), keep
 
+    def _plan_args(self, call: str, sampling, logit_bias, B: int, N: int, new_frames: int, seeds):
+        """The umgen_sample_plan of a rollout whose `sampling` is a sequence of RolloutConfig and / or whose `logit_bias` is a constraints.Schedule, checked
+        before anything reaches the device with the messages of the C call: -> (the call's umgen_sampling, the plan, whatever both point at).  per-scene
+        settings: B entries (a scene's branches share theirs), B*N flat, or [B][N] nested; rule_constrain / merage_ar_tar / only_ar are per call."""
+        from .constraints import Schedule
+        items = B * N
+        keep = []
+        cfgs = None
+        if isinstance(sampling, RolloutConfig) or sampling is None:
+            base = sampling or self.cfg
+        else:
+            rows = list(sampling)
+            if rows and all(not isinstance(r, RolloutConfig) and hasattr(r, "__len__") for r in rows):      # [B][N]
+                if len(rows) != B or any(len(r) != N for r in rows):
+                    raise UMGenError(f"{call}: sampling has shape [{len(rows)}][{', '.join(str(len(r)) for r in rows)}], expected [{B}][{N}]")
+                cfgs = [c for r in rows for c in r]
+            elif len(rows) == items:
+                cfgs = rows
+            elif len(rows) == B:
+                cfgs = [c for c in rows for _ in range(N)]
+            else:
+                raise UMGenError(f"{call}: sampling has {len(rows)} entries, expected {B} (one per scene)" + (f", {items} or [{B}][{N}] (one per branch)" if N > 1 else ""))
+            for i, c in enumerate(cfgs):
+                if not isinstance(c, RolloutConfig):
+                    raise UMGenError(f"{call}: sampling[{i}] is {type(c).__name__}, expected a RolloutConfig")
+            base = cfgs[0]
+            for i, c in enumerate(cfgs):
+                if (bool(c.rule_constrain), bool(c.merage_ar_tar), bool(c.only_ar)) != (bool(base.rule_constrain), bool(base.merage_ar_tar), bool(base.only_ar)):
+                    raise UMGenError(f"{call}: sample plan: per_scene[{i}] has rule_constrain / merge_ar_tar / only_ar = {int(c.rule_constrain)} / {int(c.merage_ar_tar)} / "
+                                     f"{int(c.only_ar)}, the call's sampling {int(base.rule_constrain)} / {int(base.merage_ar_tar)} / {int(base.only_ar)} (these are per call)")
+        smp, skeep = self._sampling(base, seeds)
+        keep.append(skeep)
+        plan = _lib.SamplePlan()
+        if cfgs is not None:
+            per = (_lib.Sampling * items)()
+            for i, c in enumerate(cfgs):
+                per[i] = self._sampling(c, [])[0]
+                per[i].seeds = None
+            plan.per_scene = C.cast(per, C.POINTER(_lib.Sampling))
+            keep.append(per)
+        if isinstance(logit_bias, Schedule):
+            if len(logit_bias.sets) > _lib.BIAS_SETS_MAX:
+                raise UMGenError(f"{call}: sample plan: n_bias_sets={len(logit_bias.sets)} out of range [0,{_lib.BIAS_SETS_MAX}]")
+            sets = (_lib.LogitBias * max(1, len(logit_bias.sets)))()
+            for q, tabs in enumerate(logit_bias.sets):
+                st, k = self._bias_args(f"{call}: sample plan: bias set {q}", tabs or None)
+                if st is not None:
+                    sets[q] = st
+                    keep.append(k)
+            try:
+                of = logit_bias.resolve(B, N, new_frames)      # int32 [B*N, new_frames]
+            except ValueError as err:
+                raise UMGenError(f"{call}: {err}") from None
+            bad = np.argwhere((of < -1) | (of >= len(logit_bias.sets)))
+            if bad.size:
+                i, f = (int(x) for x in bad[0])
+                raise UMGenError(f"{call}: sample plan: bias_of of scene {i} in new frame {f} is {int(of[i, f])}, outside [-1, {len(logit_bias.sets)})")
+            if logit_bias.sets:      # (a schedule without sets constrains nothing: every entry is -1)
+                plan.n_bias_sets, plan.bias_sets = len(logit_bias.sets), C.cast(sets, C.POINTER(_lib.LogitBias))
+                plan.bias_of = of.ctypes.data_as(C.POINTER(C.c_int32))
+                keep += [sets, of]
+        else:
+            st, k = self._bias_args(call, logit_bias)
+            if st is not None:
+                one = (_lib.LogitBias * 1)(st)
+                plan.n_bias_sets, plan.bias_sets = 1, C.cast(one, C.POINTER(_lib.LogitBias))
+                keep += [one, k]
+        return smp, plan, keep
+
     # the diagnostics of score(detail=...) and of rollout / frame (return_detail): key -> (field stem of the C struct, dtype); the "topk_" keys are lists
     _DETAIL_FIELDS = {"rank": ("rank", np.int32), "mass_above": ("mass_above", np.float32), "entropy": ("entropy", np.float32),
                       "topk_tokens": ("topk_tok", np.int32), "topk_logp": ("topk_logp", np.float32)}
@@ -229,8 +298,8 @@ class Engine:
     def rollout(self, tokens: Dict[str, np.ndarray], new_frames: int, cond_frames: int = 20,
                 input_cond_frames: int = -1, init_tokens: Optional[Dict[str, np.ndarray]] = None,
                 control_test: bool = False, seeds: Optional[Sequence[int]] = None,
-                sampling: Optional[RolloutConfig] = None, return_logp: bool = False, samples: Optional[int] = None,
-                return_detail: bool = False, topk: int = 0, logit_bias: Optional[Dict[str, np.ndarray]] = None, return_logz: bool = False):
+                sampling=None, return_logp: bool = False, samples: Optional[int] = None,
+                return_detail: bool = False, topk: int = 0, logit_bias=None, return_logz: bool = False):
         """tokens: mod -> int64 [B, T, S_mod].  Returns mod -> int64 [B, input_cond_frames + new_frames, S_mod].
         samples=N (umgen_rollout_fan): N sampled futures of every scene off one pass over its history.  seeds: [B, N] or flat B*N (default 0), branch
         (b, s) at b*N + s; init_tokens stay per scene, a scene's branches share them.  Returns mod -> int64 [B, N, input_cond_frames + new_frames, S_mod],
@@ -249,10 +318,18 @@ class Engine:
         logits + bias of its class; -inf bans a token from every draw (not from control / given / forced tokens, nor from the rule constraint's pads).  One set of
         tables per call.  logp and the diagnostics stay on the model's own logits.
         return_logz: the result gains, behind logp, mod -> float32 shaped like logp: lse(logits + bias) - lse(logits) of the AR row per sampled position (+0.0 for
-        a class without a table, NaN where logp is NaN); for bans the log of the model's mass on the allowed tokens."""
-        bias_struct, bias_keep = self._bias_args("rollout", logit_bias)
+        a class without a table, NaN where logp is NaN); for bans the log of the model's mass on the allowed tokens.
+        Sampling plans (umgen_rollout_planned): sampling may be a sequence of RolloutConfig -- B entries (one per scene; a scene's branches share it), or with
+        samples=N also B*N flat / [B][N] nested (one per branch) -- and logit_bias a constraints.Schedule (constraints.schedule / per_frame: which set of tables
+        scene / branch i draws under in new frame f, -1 = none).  Branch i in frame f returns the bits of the unplanned call that applies its settings and its set
+        to everyone; seeds stay per branch; rule_constrain / merage_ar_tar / only_ar must agree across the entries."""
+        from .constraints import Schedule
+        planned = isinstance(logit_bias, Schedule) or not (sampling is None or isinstance(sampling, RolloutConfig))
+        bias_struct, bias_keep = (None, None) if planned else self._bias_args("rollout", logit_bias)
         if return_detail or topk:
-            topk = self._gen_detail_args("rollout", topk, sampling or self.cfg)
+            one = sampling is None or isinstance(sampling, RolloutConfig)
+            for c in ([sampling or self.cfg] if one else [c for r in sampling for c in ([r] if isinstance(r, RolloutConfig) else r)]):      # (every entry of a plan)
+                topk = self._gen_detail_args("rollout", topk, c)
             return_detail = True
         if new_frames < 0:
             raise UMGenError(f"new_frames={new_frames}")
@@ -278,7 +355,10 @@ class Engine:
             seeds = sd.reshape(-1)
         outs = {m: np.empty(lead + (T_in + new_frames, CONTENT_LEN[m]), dtype=np.int64) for m in MOD_ORDER}
         T_ctl, cp, cb, gm, gb = self._init_token_args(init_tokens, control_test, B)
-        smp, keep = self._sampling(sampling or self.cfg, seeds if seeds is not None else [0] * B)
+        if planned:
+            smp, plan_struct, keep = self._plan_args("rollout", sampling, logit_bias, B, samples or 1, new_frames, seeds if seeds is not None else [0] * B)
+        else:
+            smp, keep = self._sampling(sampling or self.cfg, seeds if seeds is not None else [0] * B)
         args = (self._h, B, T_in, new_frames, cond_frames, _p64(arrs["pose"]), _p64(arrs["map"]), _p64(arrs["bbox3d"]),
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
@@ -290,7 +370,9 @@ class Engine:
         shared = C.c_int32(-1)
         ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
         fan = (self._h, B, samples or 1) + args[2:] + (ref(lp), C.byref(shared))
-        if bias_struct is not None or return_logz:
+        if planned:
+            rc = self.lib.umgen_rollout_planned(*fan, topk, ref(det), C.byref(plan_struct), ref(lz))
+        elif bias_struct is not None or return_logz:
             rc = self.lib.umgen_rollout_biased(*fan, topk, ref(det), ref(bias_struct), ref(lz))
         elif return_detail:
             rc = self.lib.umgen_rollout_detail(*fan, topk, ref(det))
@@ -302,7 +384,7 @@ class Engine:
             rc = self.lib.umgen_rollout(*args)
         self._check(rc, "rollout")
         del keep, bias_keep
-        if samples is not None:
+        if samples is not None or planned:
             self.last_shared_slots = int(shared.value)
         res = (outs,) + tuple(x for x in (logp, logz, self._detail_result(dbufs) if return_detail else None) if x is not None)
         return res if len(res) > 1 else outs

@@ -18,6 +18,7 @@ control_bbox3d), or generated with ``--synthetic N``.  Under ``torchrun`` the sc
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import glob
 import os
 import pickle
@@ -40,6 +41,16 @@ def positive_int(v):
     if k < 1:
         raise argparse.ArgumentTypeError(f"{v!r} is not a positive integer")
     return k
+
+
+def temperature_list(v):
+    try:
+        ts = [float(x) for x in str(v).split(",") if x.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{v!r} is not a comma-separated list of temperatures") from None
+    if not ts or any(not (t > 0 and np.isfinite(t)) for t in ts):
+        raise argparse.ArgumentTypeError(f"{v!r}: temperatures are finite and > 0")
+    return ts
 
 
 def build_parser():
@@ -68,7 +79,33 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ban_category", action="append", default=[], metavar="NAME",
                    help="constrained generation: no generated agent of this category (vehicle / bicycle / pedestrian); repeatable")
+    p.add_argument("--ban_from_frame", type=int, default=0, metavar="F",
+                   help="the tables of --ban_category apply from generated frame F on (0: every generated frame); a per-frame schedule inside ONE rollout call")
+    p.add_argument("--num_samples", type=positive_int, default=1, help="sampled futures per scene (saved as <scene>_s<k>)")
+    p.add_argument("--temperatures", type=temperature_list, default=None, metavar="T1,T2,...",
+                   help="sampling temperature per future: sample s draws at temperatures[s %% len]; one call for all of them")
     return p
+
+
+def plan_kwargs(args, cfg, n_scenes, new_frames):
+    """What --num_samples / --temperatures / --ban_category / --ban_from_frame add to Engine.rollout for a batch of n_scenes scenes: samples, per-branch sampling
+    (a sampling plan only when the temperatures differ), and the tables -- one set for the call, or a per-frame schedule when they start at a later frame"""
+    kw = {}
+    N = args.num_samples
+    if N > 1:
+        kw["samples"] = N
+    if args.temperatures:
+        temps = [args.temperatures[s % len(args.temperatures)] for s in range(N)]
+        per = [dataclasses.replace(cfg, sfmx_temp=t) for t in temps]
+        kw["sampling"] = per[0] if len(set(temps)) == 1 else [list(per) for _ in range(n_scenes)]
+    if args.ban_from_frame < 0:
+        raise ValueError(f"--ban_from_frame {args.ban_from_frame}: a generated frame index >= 0")
+    if args.ban_category:
+        from .constraints import ban_categories, per_frame
+        tables = ban_categories(args.ban_category, vocab=cfg.bbox3d_vocab_size)
+        F = min(args.ban_from_frame, new_frames)
+        kw["logit_bias"] = tables if F == 0 else per_frame([None] * F + [tables] * (new_frames - F))
+    return kw
 
 
 def resolve(args):
@@ -131,7 +168,7 @@ def main(argv=None):
     # skip-if-exists stays per scene (model_pl.py:215-216); every rank takes the same decision before anybody writes
     todo = []
     for sid, (name, _, _) in enumerate(scenes):
-        if os.path.exists(os.path.join(save_dir, name + "_tokens.pkl")):
+        if os.path.exists(os.path.join(save_dir, (name if args.num_samples == 1 else f"{name}_s{args.num_samples - 1}") + "_tokens.pkl")):
             if rank == 0:
                 print(name, " has been processed")
         else:
@@ -142,7 +179,7 @@ def main(argv=None):
         if world > 1:
             dist.destroy_process_group()
         return
-    eng = Engine(cfg, precision=args.precision, max_batch=args.batch, max_cond_frames=T_hist, device=local_rank)
+    eng = Engine(cfg, precision=args.precision, max_batch=args.batch * args.num_samples, max_cond_frames=T_hist, device=local_rank)
     if args.debug:
         for key, shape in expected_keys(cfg).items():
             eng.load_tensor(key, synth_tensor(key, shape, seed=0))
@@ -162,21 +199,24 @@ def main(argv=None):
         nf = new_frames if new_frames >= 0 else toks["pose"].shape[1] - icf
         key = (icf, nf, tuple(sorted((k, v.shape[1:]) for k, v in ctl.items())) if ctl else None)
         groups.setdefault(key, []).append(sid)
-    bias_kw = {}
-    if args.ban_category:
-        from .constraints import ban_categories
-        bias_kw["logit_bias"] = ban_categories(args.ban_category, vocab=cfg.bbox3d_vocab_size)
+    N = args.num_samples
     for (icf, nf, _), sids in groups.items():
         def rollout_fn(toks, seeds, scene_ids):
             ctls = [scenes[s][2] for s in scene_ids]
             init = {k: np.concatenate([c[k] for c in ctls]) for k in ctls[0]} if ctls[0] else None
-            return eng.rollout(toks, nf, cond_frames=T_hist, input_cond_frames=icf, init_tokens=init,
-                               control_test=control and init is not None and "bbox3d" in init, seeds=seeds, **bias_kw)
+            if N > 1:      # a seed per future; the futures of a scene travel through the gather as one [N * T] sequence
+                seeds = np.array([[(int(sd) + 0x9E3779B97F4A7C15 * k) % 2 ** 64 for k in range(N)] for sd in seeds], dtype=np.uint64)
+            out = eng.rollout(toks, nf, cond_frames=T_hist, input_cond_frames=icf, init_tokens=init,
+                              control_test=control and init is not None and "bbox3d" in init, seeds=seeds, **plan_kwargs(args, cfg, len(scene_ids), nf))
+            return {m: out[m].reshape(out[m].shape[0], -1, out[m].shape[-1]) for m in MOD_ORDER} if N > 1 else out
         out = sharded_rollout(rollout_fn, [scenes[s][1] for s in sids], base_seed=args.seed, batch=args.batch,
                               device="cuda" if world > 1 else "cpu", scene_ids=sids, pass_ids=True)
         for pos in scene_partition(len(sids), world, rank):                   # every rank writes the scenes it rolled out
             name = scenes[sids[pos]][0]
-            print("saved", save_tokens({m: out[m][pos:pos + 1] for m in MOD_ORDER}, args.output_path, name))
+            for k in range(N):
+                T = out["pose"].shape[1] // N
+                one = {m: out[m][pos:pos + 1, k * T:(k + 1) * T] for m in MOD_ORDER}
+                print("saved", save_tokens(one, args.output_path, name if N == 1 else f"{name}_s{k}"))
     eng.close()
     if world > 1:
         dist.barrier()

@@ -148,13 +148,19 @@ class UMGen(nn.Module):
         return_detail=True, topk=K (extension): the result gains, as its last element, Engine.rollout's detail dict -- rank, mass_above, entropy and the K most
         likely tokens of every generated token, from the decode step that sampled it -- as key -> mod -> torch tensor; combines with return_logp and num_samples.
         logit_bias=tables, return_logz=True (extension): constrained generation (Engine.rollout's logit_bias / return_logz; umgen_amd.constraints builds the tables,
-        arrays or torch tensors).  logz follows logp in the result, mod -> torch.float32 shaped like logp; combines with return_logp, num_samples and return_detail."""
+        arrays or torch tensors).  logz follows logp in the result, mod -> torch.float32 shaped like logp; combines with return_logp, num_samples and return_detail.
+        Sampling plans (extension): logit_bias may be a constraints.Schedule and sampling= a sequence of RolloutConfig, as Engine.rollout takes them."""
         return_detail = bool(return_detail) or bool(topk)
         extra = {}      # (only what the call asks for reaches Engine.rollout: the plain calls stay the plain calls)
-        if logit_bias is not None:
+        from .constraints import Schedule
+        if isinstance(logit_bias, Schedule):      # a sampling plan's table sets (constraints.schedule / per_frame), handed on as it is
+            extra["logit_bias"] = logit_bias
+        elif logit_bias is not None:
             if not hasattr(logit_bias, "items"):
-                raise UMGenError(f"logit_bias is a dict class -> array, not {type(logit_bias).__name__}")
+                raise UMGenError(f"logit_bias is a dict class -> array or a constraints.Schedule, not {type(logit_bias).__name__}")
             extra["logit_bias"] = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in logit_bias.items()}
+        if kwargs.get("sampling") is not None:    # one RolloutConfig, or a sequence of them: per-scene / per-branch settings (Engine.rollout)
+            extra["sampling"] = kwargs["sampling"]
         if return_logz:
             extra["return_logz"] = True
         as_torch = lambda d: {k: {m: torch.from_numpy(v) for m, v in per.items()} for k, per in d.items()}      # noqa: E731
