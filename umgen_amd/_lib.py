@@ -36,7 +36,7 @@ EXPORTS = ["umgen_create", "umgen_load_tensor", "umgen_finalize_weights", "umgen
            "umgen_dbg_vq_quantize", "umgen_dbg_vq_quant_tile", "umgen_dbg_vq_im2col", "umgen_dbg_vq_im2col_s2", "umgen_dbg_vq_upsample", "umgen_dbg_vq_from_nchw", "umgen_dbg_vq_to_nchw",
            "umgen_dbg_vq_group_norm", "umgen_dbg_vq_softmax"]
 
-HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "engine_frame.h", "token_windows.h", "gen_side.h", "sample_plan.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
+HEADERS = ("common.h", "kernels.h", "frame.h", "engine_state.h", "engine_frame.h", "token_windows.h", "gen_side.h", "sample_plan.h", "gen_call.h", "oar_common.h", "bg_queue.h", "bg_worker.h", "gemm256_body.h", "attn_body.h", "rowops_body.h", "frame_body.h", "vq_common.h", "debug_util.h")
 
 PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DT_F32, DT_BF16, DT_F16, DT_F64 = 0, 1, 2, 3

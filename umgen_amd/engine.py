@@ -258,6 +258,25 @@ class Engine:
         keys = [k for k in cls.DETAIL_KEYS if topk > 0 or not k.startswith("topk_")]
         return cls._detail_out(_lib.GenDetailOut, keys, lead, topk, {np.int32: -1, np.float32: np.nan})
 
+    @classmethod
+    def _side_out(cls, lead: Tuple[int, ...], logp: bool, logz: bool, detail: bool, topk: int):
+        """The optional side outputs of a generation call for a leading shape: (logp buffers, logz buffers, diagnostics buffers, the pointers to their
+        umgen_logp_out / umgen_logz_out / umgen_gen_detail_out); None for whatever was not asked for"""
+        made = [cls._logp_out(lead) if logp else (None, None), cls._logp_out(lead, "logz") if logz else (None, None),
+                cls._gen_detail_out(lead, topk) if detail else (None, None)]
+        return tuple(b for b, _ in made) + (tuple(C.byref(s) if s is not None else None for _, s in made),)
+
+    # the two ladders of include/umgen.h, widest rung first: (entry point, what it is the narrowest rung for, how many of the optional arguments it takes) --
+    # of (lp, shared_slots, topk, detail, bias | plan, lz) for a rollout, of (lp, topk, detail, bias, lz) for a frame
+    _RUNGS = {"rollout": (("umgen_rollout_planned", "plan", 6), ("umgen_rollout_biased", "bias", 6), ("umgen_rollout_detail", "detail", 4),
+                          ("umgen_rollout_fan", "fan", 2), ("umgen_rollout_logp", "logp", 1), ("umgen_rollout", None, 0)),
+              "frame": (("umgen_frame_biased", "bias", 5), ("umgen_frame_detail", "detail", 3), ("umgen_frame_logp", "logp", 1), ("umgen_frame", None, 0))}
+
+    def _narrowest(self, ladder: str, tail: tuple, **asked):
+        """(the narrowest entry point of `ladder` that takes everything asked for, the optional arguments of `tail` it takes)"""
+        name, _, n = next(r for r in self._RUNGS[ladder] if r[1] is None or asked.get(r[1]))
+        return getattr(self.lib, name), tail[:n]
+
     @staticmethod
     def _init_token_args(init_tokens: Optional[Dict[str, np.ndarray]], control_test: bool, B: int):
         """init_tokens of a rollout as the arrays of the C call: (T_ctl, control pose, control bbox3d, given map, given bbox3d), int64 [B, T_ctl, S_mod] or
@@ -363,25 +382,12 @@ class Engine:
                 _p64(arrs["image"]), T_ctl, _p64(cp), _p64(cb), int(control_test), _p64(gm), _p64(gb), C.byref(smp),
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
         # the optional structs once, then the narrowest entry point that takes what was asked for
-        side = lead + (new_frames,)
-        logp, lp = self._logp_out(side) if return_logp else (None, None)
-        logz, lz = self._logp_out(side, "logz") if return_logz else (None, None)
-        dbufs, det = self._gen_detail_out(side, topk) if return_detail else (None, None)
+        logp, logz, dbufs, (lp, lz, det) = self._side_out(lead + (new_frames,), return_logp, return_logz, return_detail, topk)
         shared = C.c_int32(-1)
-        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        fan = (self._h, B, samples or 1) + args[2:] + (ref(lp), C.byref(shared))
-        if planned:
-            rc = self.lib.umgen_rollout_planned(*fan, topk, ref(det), C.byref(plan_struct), ref(lz))
-        elif bias_struct is not None or return_logz:
-            rc = self.lib.umgen_rollout_biased(*fan, topk, ref(det), ref(bias_struct), ref(lz))
-        elif return_detail:
-            rc = self.lib.umgen_rollout_detail(*fan, topk, ref(det))
-        elif samples is not None:
-            rc = self.lib.umgen_rollout_fan(*fan)
-        elif return_logp:
-            rc = self.lib.umgen_rollout_logp(*args, ref(lp))
-        else:
-            rc = self.lib.umgen_rollout(*args)
+        last = C.byref(plan_struct) if planned else C.byref(bias_struct) if bias_struct is not None else None
+        fn, tail = self._narrowest("rollout", (lp, C.byref(shared), topk, det, last, lz), plan=planned, bias=bias_struct is not None or return_logz,
+                                   detail=return_detail, fan=samples is not None, logp=return_logp)
+        rc = fn(*(args if len(tail) < 2 else (self._h, B, samples or 1) + args[2:]), *tail)      # (from umgen_rollout_fan on: B, N)
         self._check(rc, "rollout")
         del keep, bias_keep
         if samples is not None or planned:
@@ -439,18 +445,10 @@ class Engine:
         args = (self._h, T, _p64(w["pose"]), _p64(w["map"]), _p64(w["bbox3d"]), _p64(w["image"]), _p64(cp), _p64(cb),
                 int(control_test), C.byref(smp), frame_idx, C.byref(tr) if tr is not None else None,
                 _p64(outs["pose"]), _p64(outs["map"]), _p64(outs["bbox3d"]), _p64(outs["image"]))
-        lpv, lp = self._logp_out(()) if logp else (None, None)
-        lzv, lz = self._logp_out((), "logz") if logz else (None, None)
-        dbufs, det = self._gen_detail_out((), topk) if detail else (None, None)
-        ref = lambda s: C.byref(s) if s is not None else None  # noqa: E731
-        if bias_struct is not None or logz:
-            rc = self.lib.umgen_frame_biased(*args, ref(lp), topk, ref(det), ref(bias_struct), ref(lz))
-        elif detail:
-            rc = self.lib.umgen_frame_detail(*args, ref(lp), topk, ref(det))
-        elif logp:
-            rc = self.lib.umgen_frame_logp(*args, ref(lp))
-        else:
-            rc = self.lib.umgen_frame(*args)
+        lpv, lzv, dbufs, (lp, lz, det) = self._side_out((), logp, logz, detail, topk)
+        fn, tail = self._narrowest("frame", (lp, topk, det, C.byref(bias_struct) if bias_struct is not None else None, lz),
+                                   bias=bias_struct is not None or logz, detail=detail, logp=logp)
+        rc = fn(*args, *tail)
         self._check(rc, "frame")
         del bias_keep
         del keep, fz, gz
@@ -458,15 +456,10 @@ class Engine:
             tbuf = tbuf if tbuf is not None else {}
             tbuf["counters"] = dict(zip(("pad_avoid", "control_resample", "rule_checked", "rule_collision", "rule_blanked",
                                          "sampled_ne_forced"), counters[:6].tolist()))
-        if lpv is not None:
-            tbuf = tbuf if tbuf is not None else {}
-            tbuf["logp"] = lpv
-        if lzv is not None:
-            tbuf = tbuf if tbuf is not None else {}
-            tbuf["logz"] = lzv
-        if dbufs is not None:
-            tbuf = tbuf if tbuf is not None else {}
-            tbuf["detail"] = self._detail_result(dbufs)
+        for key, val in (("logp", lpv), ("logz", lzv), ("detail", self._detail_result(dbufs) if dbufs is not None else None)):
+            if val is not None:
+                tbuf = tbuf if tbuf is not None else {}
+                tbuf[key] = val
         return outs, tbuf
 
     # -- scoring -------------------------------------------------------------------------------
