@@ -1,5 +1,5 @@
 """Constrained sampling inside the samplers (csrc/frame.hip), through umgen_dbg_token_steps_biased(_detail), umgen_dbg_sample_ego_biased and
-umgen_dbg_sample_biased: with a class's bit of OarState::bias_classes set, every sampler of a step draws from w = v + r -- the AR row, and the
+umgen_dbg_sample_biased: with a table for the step's class in the call's one set, every sampler of a step draws from w = v + r -- the AR row, and the
 head_tar_bbox3d row inside the control and pad-avoid resamples -- while lp and the diagnostics stay on v, and want_logz adds lse(w) - lse(v).
 
 References (none measured on the code under test):

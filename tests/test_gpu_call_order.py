@@ -87,6 +87,39 @@ def test_call_kinds_in_any_order_leave_the_handle_as_they_found_it(setup, overla
         np.testing.assert_array_equal(first[m], ref[m], err_msg=f"R vs a fresh handle, {m}")
 
 
+def test_a_biased_call_reads_no_set_index_an_earlier_plan_left(setup):
+    """A call with one set of tables is the plan that puts every scene on set 0, and its samplers read the per-scene set index.  A planned rollout that leaves
+    scene 0 on set 1 and scene 1 on no set, the biased call, a plain rollout and the biased call again, on one handle: both biased calls have the tokens and
+    logz of the biased call on a fresh handle, bit for bit, and the plain rollout the tokens of a fresh handle's.  Two scenes and one new frame are the
+    smallest case in which the index the plan leaves differs from "set 0 for everyone"."""
+    from tests.test_gpu_rollout_bias import random_tables
+    from umgen_amd import constraints
+    cfg, sd = setup
+    toks = cat([synthetic_scene(80 + i, n_frames=1) for i in range(2)])
+    tabs, others = random_tables(cfg, 3), [random_tables(cfg, 4), random_tables(cfg, 5)]
+    kw = dict(cond_frames=3, input_cond_frames=1, seeds=[21, 22])
+    biased = lambda h: h.rollout(toks, 1, logit_bias=tabs, return_logz=True, **kw)  # noqa: E731
+    h = make(cfg, sd, max_batch=2)
+    planned = h.rollout(toks, 1, logit_bias=constraints.schedule(others, [1, -1]), return_logz=True, **kw)
+    b = biased(h)
+    c = h.rollout(toks, 1, **kw)
+    d = biased(h)
+    h.close()
+    fresh = make(cfg, sd, max_batch=2)
+    b_ref = biased(fresh)
+    fresh.close()
+    fresh = make(cfg, sd, max_batch=2)
+    c_ref = fresh.rollout(toks, 1, **kw)
+    fresh.close()
+    assert any((planned[0][m] != b_ref[0][m]).any() for m in MOD_ORDER), "premise: the plan's sets generate other tokens than the call's one set"
+    assert any((c_ref[m] != b_ref[0][m]).any() for m in MOD_ORDER), "premise: the tables change what is generated"
+    for m in MOD_ORDER:
+        for name, got in (("first", b), ("second", d)):
+            np.testing.assert_array_equal(got[0][m], b_ref[0][m], err_msg=f"{name} biased call vs a fresh handle, tokens of {m}")
+            assert got[1][m].tobytes() == b_ref[1][m].tobytes(), f"{name} biased call vs a fresh handle, logz of {m}"
+        np.testing.assert_array_equal(c[m], c_ref[m], err_msg=f"plain rollout vs a fresh handle, {m}")
+
+
 def test_uneven_lanes_give_the_one_stream_bits_of_every_side_output(setup):
     """3 scenes on 2 lanes are lanes of 2 and 1: the smallest batch in which a lane has a non-zero base offset and the lanes differ in size.  Tokens,
     logp and every diagnostic array of two frames equal the one-stream batched layer's, bit for bit."""

@@ -22,7 +22,7 @@ from tests.test_gpu_bias_kernel import NEG, RUNS, ZERO_BITS, BiasSteps, biased, 
 from tests.test_gpu_detail_kernel import ABS_BAR, reference
 from tests.test_gpu_frame_kernels import (DRAW_MAIN, IMG_BOS, IMG_C0, KSEQ, MAP_C0, MAP_EOS, OFF_BOX, PAD, TOK, Steps, Tables, Walk, at_box, frame_tokens,
                                           i32p, kind_of, nan32, rng_uniform, sampler_params, u64p)
-from tests.test_gpu_logp_kernel import BAR, is_nan_bits, slot_of
+from tests.test_gpu_logp_kernel import BAR, LogpSteps, is_nan_bits, slot_of
 from tests.test_gpu_score import log_softmax_at
 from umgen_amd._lib import DbgSamplerParams
 
@@ -234,6 +234,23 @@ def test_uniform_plan_gives_the_bytes_of_the_unplanned_hooks(method):
         got = s.run(j0, j1, lg, want_logz=False)
         for k in OUT_KEYS:
             assert getattr(got, k).tobytes() == getattr(plain, k).tobytes(), k
+
+
+def test_one_set_without_the_steps_class_is_the_unbiased_step():
+    """umgen_dbg_token_steps_biased with a bbox3d table alone is the plan of one set that has no map and no image table: on a two-step walk of map
+    positions and one of image positions, tokens and x_next have the bytes of umgen_dbg_token_steps_logp on the same rows, and logz is +0.0"""
+    s = PlanSteps(E, 1, seed=3, top_k=3, top_k_map=4, topk_image=7)
+    box = np.ascontiguousarray(random_table(s.rng, 11, s.V[2]))
+    for j0 in (MAP_C0, IMG_C0):
+        lg = s.random_logits(j0, j0 + 2)
+        plain = LogpSteps.run(s, j0, j0 + 2, lg)
+        got = s.blank(2)
+        check(lib().umgen_dbg_token_steps_biased(s.tb.ref, C.byref(s.args(got, lg, j0, j0 + 2)), fp(got.logp), None, fp(box), None, fp(got.logz)))
+        for k in ("tokens", "x_next", "logp"):
+            assert getattr(got, k).tobytes() == getattr(plain, k).tobytes(), (j0, k)
+        at = [slot_of(j0), slot_of(j0 + 1)]
+        assert (got.logz[0, at].view(np.uint32) == ZERO_BITS).all(), f"logz at positions {j0}, {j0 + 1}: a class without a table in the one set is not +0.0"
+        assert is_nan_bits(np.delete(got.logz[0], at)).all(), "a position without a sampled step lost its NaN"
 
 
 # ---- 5. edges: vocabularies, one scene, the last scene --------------------------------------------------------------------------------------------

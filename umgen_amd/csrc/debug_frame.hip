@@ -94,32 +94,34 @@ struct SideHook {
         return narrow(topk_logp, d.detail.topk_logp, wl);
     }
 };
-// the class tables of a biased token-step hook on the host (any may be NULL: no bias for that class)
-struct BiasHook {
-    const float *map, *box /*[11][n_box]*/, *img;
-};
-// The sampling plan of a planned hook on the host: sp_of [B] per-scene settings (NULL: OarState::plan bit 0 stays off); bias_set_of [B] (NULL: bit 1 stays
-// off) with the pool of n_sets table sets, `stride` floats apart, and set_classes [n_sets], the class bits (1 << kBiasPose ..) of every set.  A set of the
-// token-step hook lies like the engine's: pose [3][n_pose] | map [n_map] | bbox3d [11][n_box] | image [n_img]; a set of the ego hook is pose [3][V]
+// The sampling plan of a hook on the host: sp_of [B] per-scene settings (NULL: OarState::plan bit 0 stays off); bias_set_of [B] (NULL: bit 1 stays off)
+// with the pool of n_sets table sets and set_classes [n_sets], the class bits (1 << kBiasPose ..) of every set.  The tables of a biased hook are the plan
+// of one set with bias_set_of all 0.
 struct PlanHook {
     const SamplerParams* sp_of;
     const float* pool;
     int n_sets;
     const int32_t* set_classes;
     const int32_t* bias_set_of;
+    int bits() const { return (sp_of ? kPlanSettings : 0) | (bias_set_of ? kPlanSets : 0); }
 };
+// How a set of a hook's pool lies (stride and class_off, by the engine's lay_out_sets), the class bits a set may carry, and the vocabularies of the classes
+// the hook's sampler reads (0: not this sampler's class, its table is never checked).  The token-step hooks: the engine's layout, pose [3][n_pose] | map
+// [n_map] | bbox3d [11][n_box] | image [n_img]; the ego hooks: pose [3][V]
+struct SetLayout { long stride, class_off[4]; int classes, vocab[4]; };
+inline SetLayout layout_of(const int (&vocab)[4], int classes, int read) {
+    DrawPlan p{};
+    lay_out_sets(p, vocab);
+    SetLayout lay{p.stride, {}, classes, {}};
+    for (int c = 0; c < 4; ++c) { lay.class_off[c] = p.class_off[c]; lay.vocab[c] = ((read >> c) & 1) ? vocab[c] : 0; }
+    return lay;
+}
+inline SetLayout token_layout(const umgen_dbg_tables& t) { return layout_of({t.n_pose, t.n_map, t.n_box, t.n_img}, 15, 14); }
+inline SetLayout ego_layout(int V) { return layout_of({V, 0, 0, 0}, 1 << kBiasPose, 1 << kBiasPose); }
 inline bool sampler_params_sane(const SamplerParams& sp) {
     return sp.method >= 0 && sp.method <= 1 && sp.top_k >= 1 && sp.top_k_map >= 1 && sp.topk_image >= 1 && sp.temperature > 0.f;
 }
-// the index arrays of a plan: sets within the pool, scenes within the sets
-inline bool plan_index_sane(const PlanHook& ph, int B) {
-    if (!ph.bias_set_of) return true;
-    if (ph.n_sets < 0 || ph.n_sets > kBiasSetsMax || (ph.n_sets > 0 && (!ph.pool || !ph.set_classes))) return false;
-    for (int b = 0; b < B; ++b)
-        if (ph.bias_set_of[b] < -1 || ph.bias_set_of[b] >= ph.n_sets) return false;
-    return true;
-}
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh = nullptr, const PlanHook* ph = nullptr);
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const PlanHook* ph = nullptr);
 // a hook's positions: B * 2199 (0 for a B the hook refuses anyway)
 inline size_t side_n(int B) { return B < 1 ? 0 : (size_t)B * kTokPerFrame; }
 
@@ -336,23 +338,34 @@ int umgen_dbg_token_steps_detail(const umgen_dbg_tables* t, const umgen_dbg_step
     return sh.sane() ? token_steps(t, a, sh) : UMGEN_E_INVALID;
 }
 // ... and with the logit-bias tables of a biased call: bias_map [n_map], bias_box [11][n_box], bias_img [n_img] (any may be NULL; entries finite or -inf,
-// every row with an allowed entry) set the classes' bits of OarState::bias_classes, SampleArgs::bias follows the step's mod, bias_rows is the hook's
+// every row with an allowed entry) are the one set of a plan that puts every scene on set 0 (OarState::plan = kPlanSets), DrawPlan::rows is the hook's
 // scratch; logz [B][2199] (in / out, or NULL) sets want_logz.  logp may be NULL
+static int token_steps_biased(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const float* bias_map, const float* bias_box,
+                              const float* bias_img) {
+    if (!tables_sane(t) || !a || a->B < 1 || std::max(t->n_map, std::max(t->n_box, t->n_img)) > 8192) return UMGEN_E_INVALID;
+    const SetLayout lay = token_layout(*t);
+    const float* const tab[4] = {nullptr, bias_map, bias_box, bias_img};
+    std::vector<float> pool((size_t)lay.stride, NAN);      // (a class without a table is never read: NaN would show)
+    const std::vector<int32_t> set_of((size_t)a->B, 0);
+    int32_t classes = 0;
+    for (int c = kBiasMap; c <= kBiasImg; ++c)
+        if (tab[c]) { memcpy(pool.data() + lay.class_off[c], tab[c], (size_t)kPlanTableRows[c] * lay.vocab[c] * 4); classes |= 1 << c; }
+    const PlanHook ph{nullptr, pool.data(), 1, &classes, set_of.data()};
+    return token_steps(t, a, sh, &ph);
+}
 int umgen_dbg_token_steps_biased(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, const float* bias_map, const float* bias_box,
                                  const float* bias_img, float* logz) {
-    const BiasHook bh{bias_map, bias_box, bias_img};
     SideHook sh{side_n(a ? a->B : 0), logp, logz};
-    return token_steps(t, a, sh, &bh);
+    return token_steps_biased(t, a, sh, bias_map, bias_box, bias_img);
 }
 // ... together with umgen_dbg_token_steps_detail's diagnostics (they stay on the unbiased row)
 int umgen_dbg_token_steps_biased_detail(const umgen_dbg_tables* t, const umgen_dbg_steps* a, float* logp, const float* bias_map, const float* bias_box,
                                         const float* bias_img, float* logz, int topk, int32_t* rank, float* mass_above, float* entropy, int32_t* topk_tok,
                                         float* topk_logp) {
     if (!logp || !a || a->B < 1) return UMGEN_E_INVALID;
-    const BiasHook bh{bias_map, bias_box, bias_img};
     SideHook sh{side_n(a->B), logp, logz};
     sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
-    return sh.sane() ? token_steps(t, a, sh, &bh) : UMGEN_E_INVALID;
+    return sh.sane() ? token_steps_biased(t, a, sh, bias_map, bias_box, bias_img) : UMGEN_E_INVALID;
 }
 // ... and under a sampling plan (OarState::plan) in the place of the three tables: sp_of [B] per-scene settings (or NULL: a->sp for every scene), and
 // bias_set_of [B] (or NULL: no tables), scene b's set in the pool of n_sets sets (-1: none), with set_classes [n_sets]; a set lies like the engine's,
@@ -364,7 +377,7 @@ int umgen_dbg_token_steps_planned(const umgen_dbg_tables* t, const umgen_dbg_ste
     const PlanHook ph{sp_of, pool, n_sets, set_classes, bias_set_of};
     SideHook sh{side_n(a->B), logp, logz};
     sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);
-    return sh.sane() ? token_steps(t, a, sh, nullptr, &ph) : UMGEN_E_INVALID;
+    return sh.sane() ? token_steps(t, a, sh, &ph) : UMGEN_E_INVALID;
 }
 
 }  // extern "C"
@@ -383,7 +396,39 @@ bool bias_rows_sane(const float* tab, int rows, int V) {
     }
     return true;
 }
-int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const BiasHook* bh, const PlanHook* ph) {
+// a hook's plan: settings a sampler takes, sets within the pool, scenes within the sets, every set's bits among lay.classes and its tables of the hook's
+// classes like bias_rows_sane
+bool plan_sane(const PlanHook& ph, int B, const SetLayout& lay) {
+    for (int b = 0; ph.sp_of && b < B; ++b)
+        if (!sampler_params_sane(ph.sp_of[b])) return false;
+    if (!ph.bias_set_of) return true;
+    if (ph.n_sets < 0 || ph.n_sets > kBiasSetsMax || (ph.n_sets > 0 && (!ph.pool || !ph.set_classes))) return false;
+    for (int b = 0; b < B; ++b)
+        if (ph.bias_set_of[b] < -1 || ph.bias_set_of[b] >= ph.n_sets) return false;
+    for (int q = 0; q < ph.n_sets; ++q) {
+        const int cl = ph.set_classes[q];
+        if (cl & ~lay.classes) return false;
+        for (int c = 0; c < 4; ++c)
+            if (((cl >> c) & 1) && lay.vocab[c] && !bias_rows_sane(ph.pool + (size_t)q * lay.stride + lay.class_off[c], kPlanTableRows[c], lay.vocab[c])) return false;
+    }
+    return true;
+}
+// ... on the device: the samplers' DrawPlan, with scratch rows when it has sets
+DrawPlan plan_to_device(Scratch& s, const PlanHook& ph, int B, const SetLayout& lay) {
+    DrawPlan p{};
+    p.sp_of = s.in(ph.sp_of, (size_t)B * sizeof(SamplerParams));
+    if (!ph.bias_set_of) return p;
+    int32_t classes[kBiasSetsMax] = {};
+    for (int q = 0; q < ph.n_sets; ++q) classes[q] = ph.set_classes[q];
+    p.set_classes = s.in(classes, sizeof(classes));
+    p.set_of = s.in(ph.bias_set_of, (size_t)B * 4);
+    p.pool = s.in(ph.pool, (size_t)ph.n_sets * lay.stride * 4);      // (no set: nullptr, and no scene reads it)
+    p.stride = lay.stride;
+    for (int c = 0; c < 4; ++c) p.class_off[c] = lay.class_off[c];
+    p.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
+    return p;
+}
+int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& sh, const PlanHook* ph) {
     if (!tables_sane(t) || !a || a->B < 1 || a->j0 < 0 || a->j1 <= a->j0 || a->j1 > kImgEos) return UMGEN_E_INVALID;
     // given tokens end behind the pose prefix, the map or the boxes (umgen_frame's given_end): fixed_token_kernel knows no given image token
     if (a->given_end != kPoseEos + 1 && a->given_end != kMapEos + 1 && a->given_end != kBoxEos + 1) return UMGEN_E_INVALID;
@@ -413,27 +458,11 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& s
     s0.step = a->j0; s0.frame_idx = a->frame_idx; s0.use_forced = a->use_forced ? 1 : 0; s0.use_control = a->use_control ? 1 : 0; s0.done = 0;
     s0.epoch = a->epoch0; s0.sp = a->sp; s0.want_logp = sh.logp ? 1 : 0;
     s0.want_detail = sh.detail ? 1 : 0; s0.detail_topk = sh.topk; s0.want_logz = sh.logz ? 1 : 0;
-    if (bh) {
-        if (!bias_rows_sane(bh->map, 1, t->n_map) || !bias_rows_sane(bh->box, kSlotLen, t->n_box) || !bias_rows_sane(bh->img, 1, t->n_img)) return UMGEN_E_INVALID;
-        s0.bias_classes = (bh->map ? 1 << kBiasMap : 0) | (bh->box ? 1 << kBiasBox : 0) | (bh->img ? 1 << kBiasImg : 0);
-    }
-    // a plan: the pool in the engine's layout, every table of every set checked like a biased hook's
-    const size_t pool_off[4] = {0, (size_t)3 * t->n_pose, (size_t)3 * t->n_pose + t->n_map, (size_t)3 * t->n_pose + t->n_map + (size_t)kSlotLen * t->n_box};
-    const size_t pool_stride = pool_off[kBiasImg] + (size_t)t->n_img;
+    // a plan: the pool in the engine's layout
+    const SetLayout lay = token_layout(*t);
     if (ph) {
-        if (bh || !plan_index_sane(*ph, a->B)) return UMGEN_E_INVALID;
-        for (int b = 0; ph->sp_of && b < a->B; ++b)
-            if (!sampler_params_sane(ph->sp_of[b])) return UMGEN_E_INVALID;
-        for (int q = 0; ph->bias_set_of && q < ph->n_sets; ++q) {
-            const float* set = ph->pool + (size_t)q * pool_stride;
-            const int cl = ph->set_classes[q];
-            if (cl < 0 || cl >= 16) return UMGEN_E_INVALID;
-            if (((cl >> kBiasMap) & 1 && !bias_rows_sane(set + pool_off[kBiasMap], 1, t->n_map)) ||
-                ((cl >> kBiasBox) & 1 && !bias_rows_sane(set + pool_off[kBiasBox], kSlotLen, t->n_box)) ||
-                ((cl >> kBiasImg) & 1 && !bias_rows_sane(set + pool_off[kBiasImg], 1, t->n_img)))
-                return UMGEN_E_INVALID;
-        }
-        s0.plan = (ph->sp_of ? kPlanSettings : 0) | (ph->bias_set_of ? kPlanSets : 0);
+        if (!plan_sane(*ph, B, lay)) return UMGEN_E_INVALID;
+        s0.plan = ph->bits();
     }
     Scratch s;
     SampleArgs sa{};
@@ -448,23 +477,7 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& s
     sa.n_boxes = s.inout(a->n_boxes, (size_t)B * 4); sa.boxes = s.inout(a->boxes, bn * 8);
     sh.to_device(s);
     sa.side = sh.d;
-    const float* dBias[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (bh) {
-        dBias[kBiasMap] = s.in(bh->map, (size_t)t->n_map * 4); dBias[kBiasBox] = s.in(bh->box, (size_t)kSlotLen * t->n_box * 4);
-        dBias[kBiasImg] = s.in(bh->img, (size_t)t->n_img * 4);
-        sa.bias_rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
-    }
-    if (ph && ph->sp_of) sa.sp_of = s.in(ph->sp_of, (size_t)B * sizeof(SamplerParams));
-    if (ph && ph->bias_set_of) {
-        int32_t classes[kBiasSetsMax] = {};
-        for (int q = 0; q < ph->n_sets; ++q) classes[q] = ph->set_classes[q];
-        sa.set_classes = s.in(classes, sizeof(classes));
-        sa.bias_set_of = s.in(ph->bias_set_of, (size_t)B * 4);
-        sa.bias_stride = (long)pool_stride;
-        const float* dPool = s.in(ph->pool, (size_t)ph->n_sets * pool_stride * 4);      // (no set: nullptr, and no scene reads it)
-        for (int c = kBiasMap; c <= kBiasImg; ++c) dBias[c] = dPool ? dPool + pool_off[c] : nullptr;
-        sa.bias_rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
-    }
+    if (ph) sa.plan = plan_to_device(s, *ph, B, lay);
     if (s.rc) return s.rc;
     for (int i = 0; i < n; ++i) {
         const int j = a->j0 + i, mod = kind_of_pos(j, a->given_end);
@@ -475,7 +488,6 @@ int token_steps(const umgen_dbg_tables* t, const umgen_dbg_steps* a, SideHook& s
             if (up(dLg, a->logits + (size_t)i * ln, ln * 4)) return UMGEN_E_HIP;
             sa.mod = mod;
             sa.vocab = mod == 1 ? t->n_map : (mod == 2 ? t->n_box : t->n_img);
-            sa.bias = dBias[mod];
             launch_sample_token(nullptr, sa, B);
         }
         if (int rc = finish()) return rc;
@@ -496,15 +508,9 @@ extern "C" {
 // [B][2199] (or NULL) overrides with its pose tokens.  logp [B][2199] (in / out, or NULL): entry [b][jq] receives the log-likelihood of pose token jq
 // of scene b on its row
 static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
-                           int32_t* out_tokens, SideHook& sh, const float* bias = nullptr, const PlanHook* ph = nullptr) {
-    if (bias && !bias_rows_sane(bias, 3, V)) return UMGEN_E_INVALID;
-    if (ph) {
-        if (bias || B < 1 || V < 1 || !plan_index_sane(*ph, B)) return UMGEN_E_INVALID;
-        for (int b = 0; ph->sp_of && b < B; ++b)
-            if (!sampler_params_sane(ph->sp_of[b])) return UMGEN_E_INVALID;
-        for (int q = 0; ph->bias_set_of && q < ph->n_sets; ++q)
-            if ((ph->set_classes[q] & ~1) || ((ph->set_classes[q] & 1) && !bias_rows_sane(ph->pool + (size_t)q * 3 * V, 3, V))) return UMGEN_E_INVALID;
-    }
+                           int32_t* out_tokens, SideHook& sh, const PlanHook* ph = nullptr) {
+    const SetLayout lay = ego_layout(V);
+    if (ph && (B < 1 || V < 1 || !plan_sane(*ph, B, lay))) return UMGEN_E_INVALID;
     if (!logits || !sp || !seeds || !out_tokens || B < 1 || V < 1 || V > 8192 || sp->method < 0 || sp->method > 1 || sp->top_k < 1 || !(sp->temperature > 0.f))
         return UMGEN_E_INVALID;
     for (int b = 0; (sh.logp || sh.detail) && forced && b < B; ++b)      // the scored token indexes the row
@@ -516,21 +522,8 @@ static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, 
     const int* dF = s.in(forced, tn * 4);
     int *dOv = s.raw(4), *dT = s.out(osz);
     sh.to_device(s);
-    EgoSide es{sh.d, sh.topk, s.in(bias, (size_t)3 * V * 4)};
-    if (bias) es.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
-    if (ph) {
-        es.plan = (ph->sp_of ? kPlanSettings : 0) | (ph->bias_set_of ? kPlanSets : 0);
-        if (ph->sp_of) es.sp_of = s.in(ph->sp_of, (size_t)B * sizeof(SamplerParams));
-        if (ph->bias_set_of) {
-            int32_t classes[kBiasSetsMax] = {};
-            for (int q = 0; q < ph->n_sets; ++q) classes[q] = ph->set_classes[q];
-            es.set_classes = s.in(classes, sizeof(classes));
-            es.bias_set_of = s.in(ph->bias_set_of, (size_t)B * 4);
-            es.bias_stride = (long)3 * V;
-            es.bias = s.in(ph->pool, (size_t)ph->n_sets * 3 * V * 4);
-            es.rows = s.out((size_t)B * kBiasRows * kBiasRowLen * 4);
-        }
-    }
+    EgoSide es{sh.d, sh.topk};
+    if (ph) { es.plan_bits = ph->bits(); es.plan = plan_to_device(s, *ph, B, lay); }
     if (s.rc) return s.rc;
     if (hipMemset(dOv, 0, 4) != hipSuccess || hipMemset(dT, 0xff, osz) != hipSuccess) return UMGEN_E_HIP;
     launch_sample_ego(nullptr, dL, V, *sp, dS, frame_idx, dF, dT, B, dOv, es);
@@ -541,11 +534,17 @@ static int sample_ego_hook(const float* logits, int V, const SamplerParams* sp, 
     if (int rc = sh.to_host()) return rc;
     return down(out_tokens, dT, osz);
 }
-// the same with a pose bias table bias [3][V] (or NULL) and logz [B][2199] (in / out, or NULL): entries [b][jq]
+// the same with a pose bias table bias [3][V] (or NULL) and logz [B][2199] (in / out, or NULL): entries [b][jq].  The table is the one set of a plan that
+// puts every scene on set 0; no table, no plan
 int umgen_dbg_sample_ego_biased(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                                 int32_t* out_tokens, const float* bias, float* logp, float* logz) {
     SideHook sh{side_n(B), logp, logz};
-    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, bias);
+    if (!bias) return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh);
+    if (B < 1) return UMGEN_E_INVALID;
+    const std::vector<int32_t> set_of((size_t)B, 0);
+    const int32_t classes = 1 << kBiasPose;
+    const PlanHook ph{nullptr, bias, 1, &classes, set_of.data()};
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, &ph);
 }
 // the same under a sampling plan: sp_of [B] (or NULL: *sp for every scene); bias_set_of [B] (or NULL) into a pool of n_sets pose tables [n_sets][3][V] with
 // set_classes [n_sets] (bit kBiasPose: the set has its table); rank .. topk_logp: umgen_dbg_sample_ego_detail's diagnostics (rank NULL: none), every
@@ -558,7 +557,7 @@ int umgen_dbg_sample_ego_planned(const float* logits, int V, const SamplerParams
     SideHook sh{side_n(B), logp, logz};
     if (rank) sh.ask_detail(topk, rank, mass_above, entropy, topk_tok, topk_logp);      // (rank NULL: no diagnostics, like umgen_dbg_sample_ego_biased)
     if (!sh.sane() || (sh.detail && !logp)) return UMGEN_E_INVALID;
-    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, nullptr, &ph);
+    return sample_ego_hook(logits, V, sp, seeds, frame_idx, forced, B, out_tokens, sh, &ph);
 }
 int umgen_dbg_sample_ego_logp(const float* logits, int V, const SamplerParams* sp, const uint64_t* seeds, int frame_idx, const int32_t* forced, int B,
                               int32_t* out_tokens, float* logp) {

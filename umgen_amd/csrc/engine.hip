@@ -3,8 +3,8 @@
 // umgen_rollout_planned (UMGen.inference).  Each of the ten generation entry points fills one GenCall (gen_call.h) -- no rung calls another -- and hands it
 // to rollout_call or frame_call.  Both admit the call the same way (admit_call): the argument checks of gen_call.h against the engine's GenLimits; the
 // side outputs the caller asked for -- logp, logz, diagnostics: one SideDst per call (side_dst), sized into one GenSide (gen_side.h), handed to the frame
-// as FrameIO::side, scattered to the caller's arrays by deliver; and the call's plan behind check_plan / upload_plan, a frame call's tables being the
-// one-set plan of umgen_rollout_biased.  The driver keeps one conditioning sequence and gathers a frame's window from it; a frame's control / given
+// as FrameIO::side, scattered to the caller's arrays by deliver; and the call's plan behind check_plan / upload_plan: the tables of umgen_rollout_biased /
+// umgen_frame_biased are the plan of one set that every scene draws under in every frame, and run as that plan (OarState::plan, DrawPlan).  The driver keeps one conditioning sequence and gathers a frame's window from it; a frame's control / given
 // tokens are one plan_frame and its FrameIO one frame_io, for the driver and for the frame call alike.  The scoring calls narrow their int64 tokens once
 // (narrow_tokens) and hand them on as a TokenView (token_windows.h).  Creation, weights, the compute path, the frame itself and the scoring passes are in
 // engine_setup.hip, engine_weights.hip, engine_stacks.hip, engine_decode.hip, engine_frame.hip and engine_score.hip.
@@ -70,28 +70,28 @@ static void plan_frame(const GenCall& c, int idx, int* box_last, size_t box_stri
 }
 
 // What a call's plan (umgen_sample_plan) brings, behind its checks and before anything reaches the device.  plan == NULL, or a plan without per_scene
-// entries and without an index array, resolves to the unplanned call: bits 0, its one set (if any) in set 0 of the pool.
+// entries and without sets, resolves to bits 0.  One set without an index array (umgen_rollout_biased / umgen_frame_biased) is the plan whose index is 0
+// everywhere: its set lands in set 0 of the pool.
 struct PlanHost {
     int bits = 0;                      // OarState::plan
-    int classes0 = 0;                  // the class bits of set 0 (OarState::bias_classes of the unplanned form)
     std::vector<SamplerParams> sp;     // [items] with kPlanSettings
     PlanIndex idx;                     // [items][new_frames] with kPlanSets
-    std::vector<float> pool;           // [n_sets][bias_floats()], absent classes 0 (never read)
+    std::vector<float> pool;           // [n_sets][DrawPlan::stride], absent classes 0 (never read)
     int set_classes[kBiasSetsMax] = {};
 };
 static SamplerParams sampler_params(const umgen_sampling& s) {
     return SamplerParams{s.method, s.top_k, s.top_k_map, s.topk_image, s.p, s.p_map, s.temperature, s.rule_constrain, s.merge_ar_tar, s.only_ar};
 }
 // One set of logit-bias tables (umgen_logit_bias) behind its checks: entries are finite or -inf (a ban), every row keeps an allowed entry, and with control
-// slots a bbox3d row must allow more than vocab - 1 (the control resample masks that index).  -> the bit per class with a table (OarState::bias_classes);
-// dst, a zeroed set of the pool, receives the tables in d_bias' layout (absent classes stay 0 and are never read)
+// slots a bbox3d row must allow more than vocab - 1 (the control resample masks that index).  -> the bit per class with a table (DrawPlan::set_classes);
+// dst, a zeroed set of the pool, receives the tables in the pool's layout (absent classes stay 0 and are never read)
 static int check_bias(umgen_engine* e, const umgen_logit_bias& bias, bool control_slots, float* dst, int* classes) {
     const float* const tab[4] = {bias.pose, bias.map, bias.bbox3d, bias.image};
     const GenLimits lim = limits_of(e);
     const std::string m = bias_tables_error(tab, lim.vocab, kBiasRowLen, control_slots, classes);      // (sample_plan.h)
     if (!m.empty()) return e->fail(UMGEN_E_INVALID, "%s", m.c_str());
     for (int c = 0; c < 4; ++c)
-        if (tab[c]) memcpy(dst + e->bias_offset(c), tab[c], (size_t)kPlanTableRows[c] * lim.vocab[c] * sizeof(float));
+        if (tab[c]) memcpy(dst + e->dv.d_plan.class_off[c], tab[c], (size_t)kPlanTableRows[c] * lim.vocab[c] * sizeof(float));
     return 0;
 }
 static int check_plan(umgen_engine* e, const GenCall& c, PlanHost& ph) {
@@ -114,24 +114,26 @@ static int check_plan(umgen_engine* e, const GenCall& c, PlanHost& ph) {
     if (plan->n_bias_sets > 0 && !plan->bias_sets) return e->fail(UMGEN_E_INVALID, "sample plan: n_bias_sets=%d with bias_sets = NULL", plan->n_bias_sets);
     // every set is validated, used or not; the control-slot rule holds for the sets some scene uses
     const bool named = plan->bias_of != nullptr || plan->n_bias_sets > 1;      // (the one set of umgen_rollout_biased / umgen_frame_biased keeps its messages)
-    const size_t set_len = e->bias_floats();
+    const size_t set_len = (size_t)e->dv.d_plan.stride;
     ph.pool.assign((size_t)plan->n_bias_sets * set_len, 0.f);
     for (int s = 0; s < plan->n_bias_sets; ++s)
         if (int rc = check_bias(e, plan->bias_sets[s], c.control_slots() && ph.idx.uses(s), ph.pool.data() + (size_t)s * set_len, &ph.set_classes[s])) {
             if (named) e->err = "sample plan: bias set " + std::to_string(s) + ": " + e->err;
             return rc;
         }
-    ph.classes0 = ph.set_classes[0];
-    if (plan->bias_of) ph.bits |= kPlanSets;
+    if (plan->n_bias_sets >= 1) ph.bits |= kPlanSets;
     return 0;
 }
 // ... and onto the device, on the engine's stream and finished before the call's first frame starts (a frame may run on another stream of the engine): the
 // pool, the sets' class bits and the per-scene settings, once per call
 static int upload_plan(umgen_engine* e, const PlanHost& ph) {
-    if (ph.bits == 0 && ph.classes0 == 0) return 0;      // nothing a sampler of this call reads
-    if (!ph.pool.empty()) HIPCHK(e, hipMemcpyAsync(e->d_bias, ph.pool.data(), ph.pool.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    if (ph.bits & kPlanSets) HIPCHK(e, hipMemcpyAsync(e->d_set_classes, ph.set_classes, sizeof(ph.set_classes), hipMemcpyHostToDevice, e->stream));
-    if (ph.bits & kPlanSettings) HIPCHK(e, hipMemcpyAsync(e->dv.d_sp_of, ph.sp.data(), ph.sp.size() * sizeof(SamplerParams), hipMemcpyHostToDevice, e->stream));
+    if (ph.bits == 0) return 0;      // nothing a sampler of this call reads
+    const DrawPlan& dp = e->dv.d_plan;
+    if (ph.bits & kPlanSets) {
+        HIPCHK(e, hipMemcpyAsync(dp.pool, ph.pool.data(), ph.pool.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(dp.set_classes, ph.set_classes, sizeof(ph.set_classes), hipMemcpyHostToDevice, e->stream));
+    }
+    if (ph.bits & kPlanSettings) HIPCHK(e, hipMemcpyAsync(dp.sp_of, ph.sp.data(), ph.sp.size() * sizeof(SamplerParams), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return 0;
 }
@@ -145,8 +147,8 @@ struct CallHost {
     std::vector<int> set_of;     // [items]: the frame's column of the plan's index
     std::vector<int> out;        // [items][2199]: the frame's tokens
 };
-// Everything a generation call is refused for -- the checks of gen_call.h, then the plan -- and what it uploads once: the plan.  An unplanned call (one
-// set of tables, or none, for every scene, branch and frame) leaves ph.bits 0 and takes the path it always took
+// Everything a generation call is refused for -- the checks of gen_call.h, then the plan -- and what it uploads once: the plan.  A call without a
+// plan leaves ph.bits 0: its samplers read nothing of it
 static int admit_call(umgen_engine* e, const GenCall& c, CallHost& h) {
     if (int rc = refuse(e, check_gen_call(limits_of(e), c))) return rc;
     if (int rc = check_plan(e, c, h.ph)) return rc;
@@ -162,8 +164,8 @@ static FrameIO frame_io(const GenCall& c, CallHost& h, int idx, int T) {
     io.given_box = FramePlan::ptr(h.fp.gb);
     io.side = h.gs.frame();
     io.plan = h.ph.bits;
-    if (h.ph.bits & kPlanSets) { h.ph.idx.column(idx, h.set_of.data()); io.bias_set_of = h.set_of.data(); }
-    else io.bias_classes = h.ph.classes0;
+    h.ph.idx.column(idx, h.set_of.data());
+    io.set_of = h.set_of.data();
     return io;
 }
 

@@ -137,8 +137,7 @@ int enqueue_step(umgen_engine* e, const DecView& v, int B, int mod, int ns, cons
     sa.cond = v.cond; sa.x_next = v.xdec; sa.tokens = v.d_tokens; sa.prev_box = v.d_prev_box; sa.control_slot = v.d_control;
     sa.boxes = v.d_boxes; sa.n_boxes = v.d_nboxes; sa.seeds = v.d_seeds; sa.forced = e->d_forced; sa.counters = e->d_counters;
     sa.side = v.d_side;      // (always set: what a step writes of it are the device-side switches of OarState, so one captured graph serves every kind of call)
-    sa.bias_rows = v.d_bias_rows;   // (likewise: OarState::bias_classes; the class table follows with the step's mod)
-    sa.sp_of = v.d_sp_of; sa.bias_set_of = v.d_bias_set_of; sa.set_classes = e->d_set_classes; sa.bias_stride = (long)e->bias_floats();   // (likewise: OarState::plan)
+    sa.plan = v.d_plan;      // (likewise: OarState::plan)
     if (mod == 0) {
         launch_fixed_token(st, sa, B);
     } else {
@@ -163,7 +162,6 @@ int enqueue_step(umgen_engine* e, const DecView& v, int B, int mod, int ns, cons
         }
         sa.mod = mod;
         sa.vocab = V;
-        sa.bias = e->d_bias + e->bias_offset(mod);
         launch_sample_token(st, sa, B);
     }
     return 0;
@@ -190,8 +188,7 @@ DecView lane_view(const umgen_engine* e, const umgen_engine::DecLane& ln, int b0
     v.d_tokens += (long)b0 * kTokPerFrame; v.d_prev_box += (long)b0 * kNBox; v.d_nboxes += b0;
     v.d_control += (long)b0 * kSlots; v.d_boxes += (long)b0 * 64 * 10; v.d_seeds += b0;
     v.d_side = side_at(v.d_side, b0);
-    v.d_bias_rows += (long)b0 * kBiasRows * kBiasRowLen;
-    v.d_sp_of += b0; v.d_bias_set_of += b0;
+    v.d_plan = plan_at(v.d_plan, b0);
     return v;
 }
 

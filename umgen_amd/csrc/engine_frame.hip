@@ -141,10 +141,10 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     ctx.seeds.resize(B);
     for (int b = 0; b < B; ++b) ctx.seeds[b] = io.smp->seeds ? io.smp->seeds[b] : 0ull;
     HIPCHK(e, hipMemcpyAsync(e->dv.d_seeds, ctx.seeds.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-    // a planned call's table sets of this frame, beside the seeds and like them read by the ego sampler and by every token sampler of the frame: both are
+    // the scenes' table sets of this frame (a call with one set: 0 for every scene, so nothing an earlier call left is read), beside the seeds and like them read by the ego sampler and by every token sampler of the frame: both are
     // launched behind this copy in stream order (the ego sampler on this stream; the decode stream and the lanes wait for this stream's events), and the
     // previous frame's last sampler finished before that frame's token download returned
-    if (io.plan & kPlanSets) HIPCHK(e, hipMemcpyAsync(e->dv.d_bias_set_of, io.bias_set_of, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    if (io.plan & kPlanSets) HIPCHK(e, hipMemcpyAsync(e->dv.d_plan.set_of, io.set_of, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
     if (ctx.forced) {
         ctx.forced_host.resize(kTokPerFrame);
         for (int i = 0; i < kNPose; ++i) ctx.forced_host[i] = (int)tr->forced_pose[i];
@@ -161,17 +161,12 @@ int upload_frame_inputs(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     return 0;
 }
 
-// what the ego sampler writes of the call's side outputs, and of a biased call the pose table, when the call has one, with the scratch rows
+// what the ego sampler writes of the call's side outputs, and what constrains its draws
 static EgoSide ego_side(const umgen_engine* e, const FrameIO& io) {
-    EgoSide es{};
+    EgoSide es{{}, 0, io.plan, e->dv.d_plan};
     if (const FrameSide* h = io.side) {
         es.out = TokenSide{h->logp ? e->dv.d_side.logp : nullptr, h->logz ? e->dv.d_side.logz : nullptr, h->rank ? e->dv.d_side.detail : DetailOut{}};
         es.detail_topk = h->topk;
-    }
-    if ((io.bias_classes >> kBiasPose) & 1) { es.bias = e->d_bias + e->bias_offset(kBiasPose); es.rows = e->dv.d_bias_rows; }
-    if (io.plan) {      // a planned call: the scenes' own settings / sets (the pose table of set 0 of the pool, the scene's set behind it)
-        es.plan = io.plan; es.sp_of = e->dv.d_sp_of; es.bias_set_of = e->dv.d_bias_set_of; es.set_classes = e->d_set_classes; es.bias_stride = (long)e->bias_floats();
-        if (io.plan & kPlanSets) { es.bias = e->d_bias + e->bias_offset(kBiasPose); es.rows = e->dv.d_bias_rows; }
     }
     return es;
 }
@@ -326,7 +321,7 @@ int init_decode_state(umgen_engine* e, const FrameIO& io, FrameCtx& ctx) {
     }
     const FrameSide sd = io.side ? *io.side : FrameSide{};      // (topk is 0 without the diagnostics)
     ctx.s0 = OarState{ctx.j_begin, io.frame_idx, ctx.forced ? 1 : 0, io.control_slot ? 1 : 0, 0, e->eng_epoch, ctx.sp, sd.logp ? 1 : 0, sd.rank ? 1 : 0, sd.topk,
-                      io.bias_classes, sd.logz ? 1 : 0, io.plan};
+                      sd.logz ? 1 : 0, io.plan};
     e->eng_epoch += (unsigned)(kImgEos + 1) * kEpochPerStep;
     HIPCHK(e, hipMemcpyAsync(e->dv.d_state, &ctx.s0, sizeof(ctx.s0), hipMemcpyHostToDevice, st));
     ctx.n_lanes = (sizeof(T) == 2 && !tr) ? e->lane_count(B) : 1;      // decode lanes: every lane steps its own copy of the state

@@ -482,14 +482,16 @@ int alloc_decode_buffers(umgen_engine* e, const umgen_config* cfg) {
     side(&e->dv.d_side.logp, 1); side(&e->dv.d_side.logz, 1); side(&d.rank, 1); side(&d.mass_above, 1); side(&d.entropy, 1);
     side(&d.topk_tok, kDetailTopK); side(&d.topk_logp, kDetailTopK);
     if (rc) return rc;
-    // (d_bias is the pool of kBiasSetsMax table sets of a planned call; an unplanned call's one set is set 0 of it)
-    if (int rc = dalloc(e, &e->d_bias, (size_t)kBiasSetsMax * e->bias_floats())) return rc;
-    if (int rc = dalloc(e, &e->dv.d_bias_rows, Bm * kBiasRows * kBiasRowLen)) return rc;
-    if (int rc = dalloc(e, &e->d_set_classes, (size_t)kBiasSetsMax)) return rc;
-    if (int rc = dalloc(e, &e->dv.d_sp_of, Bm)) return rc;
-    if (int rc = dalloc(e, &e->dv.d_bias_set_of, Bm)) return rc;
-    HIPCHK(e, hipMemset(e->d_set_classes, 0, (size_t)kBiasSetsMax * sizeof(int)));
-    HIPCHK(e, hipMemset(e->dv.d_bias_set_of, 0xFF, Bm * sizeof(int)));
+    // (the pool holds the kBiasSetsMax table sets of a planned call; a call's one set is set 0 of it)
+    DrawPlan& dp = e->dv.d_plan;
+    lay_out_sets(dp, {cfg->pose_vocab, cfg->map_vocab, cfg->bbox3d_vocab, cfg->img_vocab});
+    if (int rc = dalloc(e, &dp.pool, (size_t)kBiasSetsMax * dp.stride)) return rc;
+    if (int rc = dalloc(e, &dp.rows, Bm * kBiasRows * kBiasRowLen)) return rc;
+    if (int rc = dalloc(e, &dp.set_classes, (size_t)kBiasSetsMax)) return rc;
+    if (int rc = dalloc(e, &dp.sp_of, Bm)) return rc;
+    if (int rc = dalloc(e, &dp.set_of, Bm)) return rc;
+    HIPCHK(e, hipMemset(dp.set_classes, 0, (size_t)kBiasSetsMax * sizeof(int)));
+    HIPCHK(e, hipMemset(dp.set_of, 0xFF, Bm * sizeof(int)));
     return 0;
 }
 

@@ -4,7 +4,9 @@
 // holds the whole batch's as `dv`, a decode lane gets its sub-batch's from lane_view; both are arguments, nothing is swapped into the engine around a
 // call), the path a decode step takes (DecodePath), and the declarations of the functions that cross files.  A generated token's side outputs
 // (log-likelihood, logz, diagnostics) take one path: FrameIO::side (FrameSide, gen_side.h) says what a frame's call asked for, dv.d_side (TokenSide,
-// frame.h) holds the device buffers, and side_buffers pairs the two for the 0xFF fill and the copy back.
+// frame.h) holds the device buffers, and side_buffers pairs the two for the 0xFF fill and the copy back.  What constrains a draw takes one path too:
+// FrameIO::plan / set_of say what a frame's call brought, dv.d_plan (DrawPlan, frame.h) holds the device side -- per-scene settings, the pool of table
+// sets, the scenes' sets of the frame, the scratch rows -- whether the call came with one set of tables or with a plan.
 // No code that launches or decides anything lives here.
 #pragma once
 
@@ -70,14 +72,14 @@ struct DecView {
     double* d_boxes;
     unsigned long long* d_seeds;
     OarState* d_state;
-    // [max_batch][2199] (the lists x kDetailTopK) side outputs of the frame being generated (SampleArgs::side), allocated with the engine -- like d_bias
-    // and d_bias_rows -- so that every captured step graph holds the final pointers
+    // [max_batch][2199] (the lists x kDetailTopK) side outputs of the frame being generated (SampleArgs::side), allocated with the engine -- like d_plan
+    // -- so that every captured step graph holds the final pointers
     TokenSide d_side;
-    float* d_bias_rows;      // [max_batch][kBiasRows][kBiasRowLen], the samplers' scratch rows (SampleArgs::bias_rows)
-    // sampling plan (umgen_rollout_planned): [max_batch] per-scene settings, uploaded once per call, and the scenes' table sets in the frame being generated
-    // (-1 = none), uploaded per frame; read under OarState::plan only (SampleArgs::sp_of / bias_set_of)
-    SamplerParams* d_sp_of;
-    int* d_bias_set_of;
+    // Constrained sampling (SampleArgs::plan; umgen_rollout_biased / umgen_frame_biased / umgen_rollout_planned), read under OarState::plan only: sp_of
+    // [max_batch] per-scene settings and set_classes, uploaded once per call with the pool [kBiasSetsMax] sets of pose [3][pose_vocab] | map [map_vocab] |
+    // bbox3d [11][bbox3d_vocab] | image [img_vocab] (a call's one set is set 0); set_of [max_batch], the scenes' table sets in the frame being generated
+    // (-1 = none), uploaded per frame; rows [max_batch][kBiasRows][kBiasRowLen], the samplers' scratch
+    DrawPlan d_plan;
 };
 
 }  // namespace umgen
@@ -108,17 +110,6 @@ struct umgen_engine {
     int Lmax = kAttnSplit * kAttnChunk, S_pad = 2240;   // cache rows per head: every split's fixed key range is addressable
     int *d_pose = nullptr, *d_pose_shift = nullptr, *d_map = nullptr, *d_box = nullptr, *d_img = nullptr;
     int *d_forced = nullptr, *d_counters = nullptr, *d_ego_tok = nullptr;
-    // Constrained sampling (umgen_rollout_biased / umgen_frame_biased): d_bias, the call's tables pose [3][pose_vocab] | map [map_vocab] |
-    // bbox3d [11][bbox3d_vocab] | image [img_vocab] (bias_offset: a class's start); the samplers' scratch rows are dv.d_bias_rows
-    // A planned call (umgen_rollout_planned) brings up to kBiasSetsMax sets: d_bias is the pool [kBiasSetsMax][bias_floats()], set 0 of it the tables of an
-    // unplanned call; d_set_classes [kBiasSetsMax] holds every set's class bits
-    float* d_bias = nullptr;
-    int* d_set_classes = nullptr;
-    size_t bias_floats() const { return (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab + cfg.img_vocab; }
-    size_t bias_offset(int cls) const {
-        const size_t o[4] = {0, (size_t)3 * cfg.pose_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab, (size_t)3 * cfg.pose_vocab + cfg.map_vocab + (size_t)11 * cfg.bbox3d_vocab};
-        return o[cls];
-    }
     // umgen_score (engine_score.hip run_score): per (row, vocabulary split) records of the scoring head, and its results pose | map | bbox3d | image,
     // each block [max_batch][S_mod]
     float *score_part = nullptr, *score_logp = nullptr;
@@ -334,9 +325,8 @@ struct FrameIO {
     const umgen_trace* trace;                    // B == 1 only
     int* out_tokens;                             // host [B][2199]
     const FrameSide* side = nullptr;             // or nullptr: the side outputs the call asked for of every content token of the new frame (NaN / -1 where no head ran)
-    int bias_classes = 0;                        // bit c: the call uploaded a logit-bias table for class c into d_bias (OarState::bias_classes)
-    int plan = 0;                                // OarState::plan of a planned call: kPlanSettings (dv.d_sp_of is uploaded), kPlanSets (bias_set_of below)
-    const int* bias_set_of = nullptr;            // host [B] with kPlanSets: the scenes' table sets in this frame, -1 = none (column f of the plan's index)
+    int plan = 0;                                // OarState::plan of the call: kPlanSettings (dv.d_plan.sp_of is uploaded), kPlanSets (the pool is, and set_of below)
+    const int* set_of = nullptr;                 // host [B] with kPlanSets: the scenes' table sets in this frame, -1 = none (column f of the plan's index)
     int cond_cap = 0;                            // window cap (cond_frames) of the rollout; 0 = single frame, nothing follows
     bool next_follows = false;                   // another frame of the same rollout follows: run its prefix pass beside the decode
     bool next_has_ctrl_pose = false;             // ... and its pose is given, so the ego net's prefix is not needed

@@ -1,9 +1,13 @@
 // Per-frame data layout shared by the host engine (engine.hip) and the frame kernels (frame.hip): scene positions, embedding tables, window tokens, the
 // device-resident decode state (OarState), and what a sampler touches (SampleArgs).  Whatever a sampler writes beside its token -- log-likelihood, logz,
 // diagnostics -- is ONE bundle, TokenSide: SampleArgs carries it, the ego sampler takes it inside EgoSide, the engine owns one (umgen_engine::d_side) and
-// decode lanes slice it with side_at.  Its host counterpart is FrameSide / GenSide (gen_side.h).
+// decode lanes slice it with side_at.  Its host counterpart is FrameSide / GenSide (gen_side.h).  Whatever constrains a draw -- per-scene settings, logit-bias
+// table sets -- is one bundle too, DrawPlan, behind the one switch OarState::plan: SampleArgs and EgoSide carry it, lanes slice it with plan_at.
 #pragma once
+#include <cstddef>
+
 #include "common.h"
+#include "sample_plan.h"
 
 namespace umgen {
 
@@ -62,20 +66,19 @@ struct OarState {
     int want_logp;
     int want_detail;
     int detail_topk;
-    // constrained sampling (umgen_rollout_biased / umgen_frame_biased): bit c of bias_classes says that this call has a logit-bias table for class c
-    // (kBiasPose ..), want_logz that the samplers also write logz
-    int bias_classes;
-    int want_logz;
-    // sampling plan (umgen_rollout_planned), the last switch: bit 0 (kPlanSettings) -- scene b draws under SampleArgs::sp_of[b] instead of sp; bit 1
-    // (kPlanSets) -- scene b's tables are set SampleArgs::bias_set_of[b] of the table pool (-1: none) and bias_classes is not read.  0: neither sampler
-    // executes anything new beyond testing the word
+    int want_logz;   // the samplers also write logz (constrained sampling)
+    // The one switch of constrained sampling, the last word: what the samplers read of SampleArgs::plan (DrawPlan).  Bit 0 (kPlanSettings) -- scene b draws
+    // under plan.sp_of[b] instead of sp (umgen_rollout_planned); bit 1 (kPlanSets) -- the call has table sets, one (umgen_rollout_biased /
+    // umgen_frame_biased) or several, and scene b's tables are set plan.set_of[b] of the pool (-1: none).  0: neither sampler executes anything beyond
+    // testing the word
     int plan;
 };
+static_assert(offsetof(OarState, step) == 0 && offsetof(OarState, epoch) == 20, "the decode engines read step and epoch in front of the per-call switches");
 enum { kPlanSettings = 1, kPlanSets = 2 };
 constexpr int kBiasSetsMax = 16;    // == UMGEN_BIAS_SETS_MAX: table sets of the pool
 
-// Logit-bias classes: the bit of a token class in OarState::bias_classes is 1 << class; map / bbox3d / image are SampleArgs::mod.  The tables of a call lie
-// back to back on the device: pose [3][pose_vocab] | map [map_vocab] | bbox3d [11][bbox3d_vocab] | image [img_vocab]
+// Logit-bias classes: the bit of a token class in a set's class word (DrawPlan::set_classes) is 1 << class; map / bbox3d / image are SampleArgs::mod.  The
+// tables of a set lie back to back on the device: pose [3][pose_vocab] | map [map_vocab] | bbox3d [11][bbox3d_vocab] | image [img_vocab]
 enum { kBiasPose = 0, kBiasMap = 1, kBiasBox = 2, kBiasImg = 3 };
 constexpr int kBiasRowLen = 8192;   // a scratch row holds the largest vocabulary the samplers take
 constexpr int kBiasRows = 3;        // scratch rows per scene: the biased AR and TAR rows of the token sampler (0, 1), the three pose rows of the ego sampler
@@ -105,6 +108,29 @@ inline TokenSide side_at(const TokenSide& s, long scene) {   // the buffers of s
     return TokenSide{at(s.logp, 1), at(s.logz, 1), DetailOut{at(d.rank, 1), at(d.mass_above, 1), at(d.entropy, 1), at(d.topk_tok, kDetailTopK), at(d.topk_logp, kDetailTopK)}};
 }
 
+// What constrains a draw, ONE bundle like TokenSide: device pointers fixed at engine creation, read by the samplers under OarState::plan's bits (the ego
+// sampler: EgoSide::plan_bits) and never otherwise.  SampleArgs and EgoSide carry it, the engine owns one (DecView::d_plan) and uploads through it, and
+// decode lanes slice it with plan_at.  A call with one set of tables for every scene is the plan whose set_of is 0 everywhere.
+struct DrawPlan {
+    SamplerParams* sp_of;    // [B] per-scene settings (kPlanSettings)
+    int* set_of;             // [B] the scene's table set in the frame being generated, -1 = none (kPlanSets)
+    int* set_classes;        // [kBiasSetsMax] the class bits of every set
+    float* pool;             // set 0 of the table pool; set s lies s * stride floats behind it
+    long stride;             // floats per set
+    long class_off[4];       // where pose / map / bbox3d / image start inside a set
+    float* rows;             // [B][kBiasRows][kBiasRowLen] scratch of the scene's block: w = v + r of the AR / TAR row (token sampler: rows 0 / 1), of pose row jq (ego sampler)
+};
+// stride and class_off for the classes' vocabularies: the tables of a set back to back, pose [3][V] | map [V] | bbox3d [11][V] | image [V]
+inline void lay_out_sets(DrawPlan& p, const int (&vocab)[4]) {
+    p.stride = 0;
+    for (int c = 0; c < 4; ++c) { p.class_off[c] = p.stride; p.stride += (long)kPlanTableRows[c] * vocab[c]; }
+}
+inline DrawPlan plan_at(const DrawPlan& p, long scene) {   // the plan of scene `scene` on (decode lanes)
+    DrawPlan q = p;
+    q.sp_of += scene; q.set_of += scene; q.rows += scene * kBiasRows * kBiasRowLen;
+    return q;
+}
+
 // everything the per-token sampler kernel touches
 struct SampleArgs {
     OarState* st;
@@ -127,28 +153,15 @@ struct SampleArgs {
     int* counters;             // [8] per-frame event counters (pad_avoid, control, rule_checked, rule_collision, rule_blanked, sampled != forced,
                                //     -, 7: unused since round 5 -- more than 64 ties at the k-th logit are sampled by an exhaustive walk, frame.hip)
     TokenSide side;            // [B][2199] side outputs of the token at its entry: what a step writes of them is st->want_logp / want_detail / want_logz
-    const float* bias;         // the bias table of this step's class: [vocab] (map, image) or [11][vocab] (bbox3d, row k % 11); read when bit `mod` of st->bias_classes is set
-    float* bias_rows;          // [B][kBiasRows][kBiasRowLen] scratch: w = v + r of the AR row (row 0) and of the TAR row of a resample (row 1), written and read by the scene's block
-    // sampling plan (OarState::plan; fixed at engine creation like every pointer here).  `bias` is the class table of set 0 of the pool: set s lies
-    // bias_stride floats behind it per set
-    const SamplerParams* sp_of;   // [B] per-scene settings (kPlanSettings)
-    const int* bias_set_of;       // [B] the scene's table set in the frame being generated, -1 = none (kPlanSets)
-    const int* set_classes;       // [kBiasSetsMax] the class bits of every set
-    long bias_stride;             // floats per set of the pool
+    DrawPlan plan;             // the scenes' own settings and table sets: what a step reads of them is st->plan
 };
 
-// what the ego sampler writes beside its three pose tokens, entries [b][jq] of `out`, and what it needs of a biased call (all null: the plain call)
+// what the ego sampler writes beside its three pose tokens, entries [b][jq] of `out`, and what constrains its draws (plan_bits 0: the plain call)
 struct EgoSide {
-    TokenSide out{};               // a null member is not asked for
-    int detail_topk = 0;           // entries of the diagnostics' lists
-    const float* bias = nullptr;   // the pose table [3][vocab] or nullptr
-    float* rows = nullptr;         // [B][kBiasRows][kBiasRowLen] scratch, row jq of scene b
-    // sampling plan: OarState::plan's bits and SampleArgs' four plan members; with kPlanSets `bias` is the pose table of set 0 of the pool (never null)
-    int plan = 0;
-    const SamplerParams* sp_of = nullptr;
-    const int* bias_set_of = nullptr;
-    const int* set_classes = nullptr;
-    long bias_stride = 0;
+    TokenSide out{};       // a null member is not asked for
+    int detail_topk = 0;   // entries of the diagnostics' lists
+    int plan_bits = 0;     // OarState::plan of the call
+    DrawPlan plan{};       // the pose class of the scene's set, rows jq of scene b
 };
 
 void launch_embed_stack(hipStream_t s, int stack, const EmbedTables& tb, const WindowTokens& w, float* X, float* mapfeat);

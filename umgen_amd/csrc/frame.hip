@@ -755,14 +755,26 @@ __device__ __forceinline__ void block_token_side(const float* __restrict__ v, co
     if (want_detail) block_detail(v, V, tok, K, tau, side.detail, at);
 }
 
+// What constrains the draws of scene b in class cls (kBiasPose ..) under the call's switch `bits` (OarState::plan; 0 reads nothing of p): the scene's own
+// settings, or the call's, and the class table of the scene's set -- null without sets, for set -1 and for a set without that class: the unbiased path
+// (logz +0.0).  The block is a scene, so both stay block-uniform.
+struct Draw { SamplerParams sp; const float* tab; };
+__device__ __forceinline__ Draw resolve_draw(const DrawPlan& p, int bits, const SamplerParams& call_sp, int b, int cls) {
+    Draw d{(bits & kPlanSettings) ? p.sp_of[b] : call_sp, nullptr};
+    if (bits & kPlanSets) {
+        const int set = p.set_of[b];
+        if (set >= 0 && ((p.set_classes[set] >> cls) & 1) != 0) d.tab = p.pool + (long)set * p.stride + p.class_off[cls];
+    }
+    return d;
+}
+
 __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     __shared__ SamplerLds sh;
     __shared__ float cor[64][8];
     __shared__ int s_tok;
     const int b = blockIdx.x, j = a.st->step, frame = a.st->frame_idx, E = a.tb.E;
-    // sampling plan (OarState::plan, 0 on every unplanned call): the block is a scene, so its own settings and its own table set stay block-uniform
-    const int plan = a.st->plan;
-    const SamplerParams sp = (plan & kPlanSettings) ? a.sp_of[b] : a.st->sp;
+    const Draw draw = resolve_draw(a.plan, a.st->plan, a.st->sp, b, a.mod);
+    const SamplerParams& sp = draw.sp;
     const bool use_forced = a.st->use_forced != 0, use_control = a.st->use_control != 0, want_logp = a.st->want_logp != 0;
     const bool want_detail = a.st->want_detail != 0;
     const int pos1 = j + 1;   // the reference's 1-based curr_seq_len
@@ -776,23 +788,16 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
     if (a.mod == 1) { off = kOffMap; k = j - kMapC0; }
     else if (a.mod == 2) { off = kOffBox; k = j - kBoxC0; }
     else { off = kOffImg; k = j - kImgC0; }
-    // Constrained sampling (OarState::bias_classes, block-uniform, 0 unless the call brought a table for this class): every sampler of this step reads
-    // w = v + r instead of v, r the class row of the position (bbox3d: attribute k % 11) -- the AR row here, the TAR row inside the two resamples.
+    // Constrained sampling (block-uniform; no table unless the scene's set brought one for this class): every sampler of this step reads w = v + r
+    // instead of v, r the class row of the position (bbox3d: attribute k % 11) -- the AR row here, the TAR row inside the two resamples.
     // lp and the diagnostics below stay on v.
-    // Under kPlanSets the scene's set decides: no set (-1), or a set without a table for this class, is the unbiased path (logz +0.0)
-    bool biased = ((a.st->bias_classes >> a.mod) & 1) != 0;
+    const bool biased = draw.tab != nullptr;
     const bool want_logz = a.st->want_logz != 0;
-    const float* tab = a.bias;
-    if (plan & kPlanSets) {
-        const int set = a.bias_set_of[b];
-        biased = set >= 0 && ((a.set_classes[set] >> a.mod) & 1) != 0;
-        if (biased) tab += (long)set * a.bias_stride;
-    }
     const float* rb = nullptr;
     const float* lw = lg;
     if (biased) {
-        rb = tab + (a.mod == 2 ? (long)(k % kSlotLen) * a.vocab : 0L);
-        lw = biased_row(lg, rb, a.vocab, a.bias_rows + (long)b * kBiasRows * kBiasRowLen);
+        rb = draw.tab + (a.mod == 2 ? (long)(k % kSlotLen) * a.vocab : 0L);
+        lw = biased_row(lg, rb, a.vocab, a.plan.rows + (long)b * kBiasRows * kBiasRowLen);
     }
     int tok = block_sample(sp, lw, a.vocab, topk, topp, rng_uniform(seed, frame, pos1, DRAW_MAIN), -1, sh, a.counters + 7);
     int* toks = a.tokens + (long)b * kTokPerFrame;
@@ -803,13 +808,13 @@ __global__ __launch_bounds__(256) void sample_token_kernel(SampleArgs a) {
         if (use_control) {   // UMGen.py:1083-1089
             const int object_id = (pos1 - 1032) / kSlotLen;
             if (object_id < kSlots && a.control_slot[b * kSlots + object_id]) {
-                const float* ltw = biased ? biased_row(lt, rb, a.vocab, a.bias_rows + ((long)b * kBiasRows + 1) * kBiasRowLen) : lt;
+                const float* ltw = biased ? biased_row(lt, rb, a.vocab, a.plan.rows + ((long)b * kBiasRows + 1) * kBiasRowLen) : lt;
                 tok = block_sample(sp, ltw, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_CONTROL), a.vocab - 1, sh, a.counters + 7);
                 if (threadIdx.x == 0) atomicAdd(a.counters + 1, 1);
             }
         }
         if (tok == kBoxPad && sp.merge_ar_tar && prev != kBoxPad && !sp.only_ar) {   // UMGen.py:1092-1104
-            const float* ltw = biased ? biased_row(lt, rb, a.vocab, a.bias_rows + ((long)b * kBiasRows + 1) * kBiasRowLen) : lt;
+            const float* ltw = biased ? biased_row(lt, rb, a.vocab, a.plan.rows + ((long)b * kBiasRows + 1) * kBiasRowLen) : lt;
             tok = block_sample(sp, ltw, a.vocab, sp.top_k, sp.p, rng_uniform(seed, frame, pos1, DRAW_PAD_AVOID), -1, sh, a.counters + 7);
             if (threadIdx.x == 0) atomicAdd(a.counters + 0, 1);
         }
@@ -872,19 +877,13 @@ __global__ __launch_bounds__(256) void sample_ego_kernel(const float* __restrict
                                                          const int* __restrict__ forced, int* __restrict__ out_tokens, int* overflow, EgoSide es) {
     __shared__ SamplerLds sh;
     const int b = blockIdx.x / 3, jq = blockIdx.x % 3;
-    // sampling plan (EgoSide::plan, 0 on every unplanned call): scene b's own settings, and the pose table of scene b's own set
-    if (es.plan & kPlanSettings) sp = es.sp_of[b];
-    bool biased = es.bias != nullptr;
-    const float* tab = es.bias;
-    if (es.plan & kPlanSets) {
-        const int set = es.bias_set_of[b];
-        biased = set >= 0 && ((es.set_classes[set] >> kBiasPose) & 1) != 0;
-        if (biased) tab += (long)set * es.bias_stride;
-    }
+    const Draw draw = resolve_draw(es.plan, es.plan_bits, sp, b, kBiasPose);
+    sp = draw.sp;
+    const bool biased = draw.tab != nullptr;
     // a pose table (constrained sampling): the draw reads w = v + r[jq]; the side outputs stay on v
     const float* lg = logits + (long)blockIdx.x * vocab;
     const float* lw = lg;
-    if (biased) lw = biased_row(lg, tab + (long)jq * vocab, vocab, es.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
+    if (biased) lw = biased_row(lg, draw.tab + (long)jq * vocab, vocab, es.plan.rows + ((long)b * kBiasRows + jq) * kBiasRowLen);
     int tok = block_sample(sp, lw, vocab, sp.top_k, sp.p,
                            rng_uniform(seeds[b], frame_idx, kSeq + jq, DRAW_MAIN), -1, sh, overflow);
     if (forced) tok = forced[(long)b * kTokPerFrame + jq];
